@@ -2,7 +2,7 @@
 """Benchmark of the FastMOT per-frame hot path on MI355X (BASELINE.json metric:
 "end-to-end tracker FPS @1080p/50 dets").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,4}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,4}] [--full] [--dump-outputs DIR]
 
 A step = one MOT.step() on one synthetic BGR frame that lies in page-locked HOST memory: the H2D copy of the
 frame (6.2 MB at 1080p) is INSIDE the timed region ("includes H2D of each frame"), then
@@ -11,8 +11,14 @@ FAST, LK, RANSAC) -> OSNet on the crops -> batched Kalman -> association (cost k
 
 `value` is measured with the next frame handed to MOT.step (a capture queue that already holds it: the
 detector of frame t+1 overlaps the ReID / association stages of frame t; results are bit-identical).
-`variants` reports, on shorter runs of the same build in the same process, the strictly sequential rate
-(no next-frame prefetch) and the rate with the frames already resident in HBM (round-1 definition).
+A plain run measures the headline figure only.  `--full` adds the side measurements: `variants` reports, on
+shorter runs of the same build in the same process, the strictly sequential rate (no next-frame prefetch) and the rate
+with the frames already resident in HBM (round-1 definition); `stage_roofline` the per-stage rates of traced steps;
+`cpu_baseline` / `parity` the CPU ports of the tracker timed on the same clip and checked against the HIP pipeline.
+
+After the adaptive settle phase the tracker restarts from a fixed number of steps of the clip (N = 1), so the warm-up
+and the timed steps see the same state in every run.  `--dump-outputs DIR` writes what the last timed step computed
+(visible tracks with their Kalman states and ReID features, the detector's own detections) as DIR/<name>.npy.
 
 For N > 1 every rank tracks its own stream on its own GPU (weak scaling); the only collective is the opt-out
 ReID-gallery all-gather (RCCL) on a side stream.  value = total frames / max-over-ranks time.
@@ -105,6 +111,42 @@ def ping_pong(s, n):
     p = 2 * (n - 1)
     s %= p
     return s if s < n else p - s
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(mot):
+    """What the last step computed, as a caller of MOT.step receives it: the visible tracks (ID, label, box) with their
+    Kalman states and averaged ReID features read back from the device, and the detections of the detector's last pass
+    (network on the seeded weights, decode, DIoU-NMS, box filters; the tracker itself is fed the scripted detections)."""
+    ctx = mot.tracker.ctx
+    tracks = sorted(mot.visible_tracks(), key=lambda t: t.trk_id)
+    slots = [t.slot for t in tracks]
+    if slots:
+        mean, cov = ctx.trk_get_state(slots)
+        feat, count = ctx.feat_read(slots)
+    else:
+        mean, cov = np.zeros((0, 8)), np.zeros((0, 8, 8))
+        feat, count = np.zeros((0, ctx.feat_dim), np.float32), np.zeros(0)
+    dets = mot.detector.last_real
+    return {'track_id': np.array([t.trk_id for t in tracks], np.float64),
+            'track_label': np.array([t.label for t in tracks], np.float64),
+            'track_tlbr': np.array([t.tlbr for t in tracks], np.float64).reshape(-1, 4),
+            'track_kalman_mean': np.asarray(mean, np.float64), 'track_kalman_cov': np.asarray(cov, np.float64),
+            'track_feature': np.asarray(feat, np.float32), 'track_feature_count': np.asarray(count, np.float64),
+            'det_tlbr': np.asarray(dets.tlbr, np.float64).reshape(-1, 4),
+            'det_label': np.asarray(dets.label, np.float64), 'det_conf': np.asarray(dets.conf, np.float64)}
+
+
+def write_outputs(out_dir, outputs):
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the limit of {DUMP_MAX_BYTES}')
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(out_dir / f'{name}.npy', a)
 
 
 def cpu_leg(cfg, video, mot, budget_s=20.0):
@@ -461,6 +503,11 @@ def main():
                     help='candidate boxes per frame the scripted YOLO heads let through conf_thresh (0: purely random heads, none)')
     ap.add_argument('--no-gallery-sync', dest='gallery', action='store_false',
                     help='N > 1: disable the cross-stream ReID-gallery all-gather (RCCL)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the side measurements (N = 1): sequential / resident-frame variants, per-stage roofline, '
+                         'CPU baselines and their parity check; a plain run measures the headline figure only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
 
@@ -528,15 +575,26 @@ def main():
     hs = Harness(run, ctx.synchronize, comm=ctl)
     pos = hs.settle(0, frames)
     settle_steps = pos
+    if world == 1:
+        # the settle phase stops on the clock, so the tracker state it leaves differs from run to run: start the tracker
+        # afresh and rebuild its state over the shortest settle phase, from the first frame of the clip -- the warm-up
+        # and the timed steps then compute the same results in every run (and in every build that computes the same).
+        # (N > 1 keeps its state: the gallery exchange between the ranks refers to track IDs a restart would reuse.)
+        Track._count = 0
+        mot.reset(1 / 30.)
+        run(SETTLE_MIN, 0, frames, False)
+        pos = SETTLE_MIN
+        settle_steps += SETTLE_MIN
     hs.fence()                             # every rank enters warm-up and timed region at the same exchange index
     run(args.warmup, pos, frames, args.prefetch)
     pos += args.warmup
     elapsed, net_ms = hs.timed(args.steps, pos, frames, args.prefetch)
     elapsed = hs.max_over_ranks(elapsed)
     pos += args.steps
+    outputs = step_outputs(mot) if args.dump_outputs and rank == 0 else None     # before any side run moves the state
 
     variants = None
-    if world == 1 and not args.no_variants:
+    if world == 1 and args.full and not args.no_variants:
         nv = 100
         variants = {'steps_each': nv}
         for key, fr, pf in (('h2d_sequential_fps', pinned, False), ('resident_prefetch_fps', resident, True),
@@ -547,7 +605,7 @@ def main():
             variants[key] = round(nv / dt, 2)
 
     stages_roof = None
-    if world == 1 and not args.no_variants:
+    if world == 1 and args.full and not args.no_variants:
         def traced(n):
             nonlocal pos
             run(n, pos, pinned, args.prefetch)
@@ -618,7 +676,7 @@ def main():
             out['variants'] = variants
             # what the UNMODIFIED reference app.py gets (it calls mot.step(frame), no next_frame): first-class number
             out['sequential_fps'] = variants['h2d_sequential_fps']
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             port, out['parity'] = cpu_leg(cfg, video, mot)
             comp = compiled_baseline(cfg, video)
             # the mandatory baseline is the compiled port (1 thread + all usable cores); the numpy port -- the parity
@@ -628,6 +686,8 @@ def main():
             ref = reference_numba_constant()
             if ref is not None and args.config == 1:
                 out['reference_numba_tracker_stage'] = ref
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         print('stage ms (Profiler, incl. warmup):', stages, file=sys.stderr)
         print(json.dumps(out), flush=True)
     if sync is not None:

@@ -36,7 +36,15 @@ REF_ROOT = Path('/root/reference')
 
 
 def reference_available():
-    return (REF_ROOT / 'fastmot' / 'tracker.py').exists()
+    return ref_path_exists('fastmot/tracker.py')
+
+
+def ref_path_exists(rel=''):
+    """True when REF_ROOT / rel exists and can be read (a tree this user may not enter counts as absent)."""
+    try:
+        return (REF_ROOT / rel).exists()
+    except OSError:
+        return False
 
 
 def _numba_semantics(fn):

@@ -24,7 +24,10 @@ _lib = None
 
 
 def available():
-    return REF.exists()
+    try:
+        return REF.exists()
+    except OSError:                  # a reference tree this user may not enter counts as absent
+        return False
 
 
 def build(force=False):

@@ -11,11 +11,11 @@ O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -q --durations=15 2>&1 | tail -30 > $O/pytest_gpu.txt; tail -3 $O/pytest_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; cut -c1-180 $O/bench_n1.json
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_cmdline.json 2> $O/bench_driver.err; cut -c1-180 $O/bench_driver_cmdline.json
+timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; cut -c1-180 $O/bench_n1.json
+timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --full > $O/bench_driver_cmdline.json 2> $O/bench_driver.err; cut -c1-180 $O/bench_driver_cmdline.json
 NOCPU=; [ -z "$QUICK" ] || NOCPU=--no-cpu-baseline
-timeout 900 python bench.py --config 2 $NOCPU > $O/bench_config2.json 2> $O/bench_config2.err; cut -c1-230 $O/bench_config2.json
-timeout 900 python bench.py --config 4 --steps 60 --warmup 10 $NOCPU > $O/bench_config4.json 2> $O/bench_config4.err; cut -c1-230 $O/bench_config4.json
+timeout 900 python bench.py --config 2 --full $NOCPU > $O/bench_config2.json 2> $O/bench_config2.err; cut -c1-230 $O/bench_config2.json
+timeout 900 python bench.py --config 4 --steps 60 --warmup 10 --full $NOCPU > $O/bench_config4.json 2> $O/bench_config4.err; cut -c1-230 $O/bench_config4.json
 # stage boundaries of the pipelined step on the GPU's clock, hipGraph replays included (fm_trace_*)
 timeout 300 python scripts/trace_pipeline.py --show 3 > $O/pipeline_trace.txt 2> /dev/null; head -1 $O/pipeline_trace.txt
 # kernel stats of the bench command itself (the durations roofline.achieved must agree with).  FASTMOT_GRAPHS=0: the layers

@@ -3,5 +3,5 @@
 . scripts/ab_lib.sh r06n
 ab_tests tests/test_detect_gpu.py tests/test_mot_gpu.py tests/test_e2e_parity_gpu.py tests/test_two_process_gpu.py tests/test_app_gpu.py
 ab_bench 4 --steps 300 --warmup 10 -- "new:" 
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver.json 2>/dev/null; python -c "
+timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --full > $O/bench_driver.json 2>/dev/null; python -c "
 import json; d=json.load(open('$O/bench_driver.json')); print('driver cmdline: value', d['value'], 'seq', d.get('sequential_fps'), 'frac', d['roofline']['frac'], 'samples', d['roofline']['net_ms_samples'])"

@@ -83,6 +83,7 @@ class InjectedYOLODetector(YOLODetector):
             self._label = labels[0]
         self._frame_idx = 0
         self.last_real_count = self.last_candidates = 0
+        self.last_real = np.zeros(0, DET_DTYPE).view(np.recarray)   # the detector's own output of its last pass
         self.net_ms = []          # HIP-event time of the detector's layer sequence, one entry per timed pass
         self.ctx.set_option('net_timing', NET_TIMING_EVERY)
 
@@ -91,6 +92,7 @@ class InjectedYOLODetector(YOLODetector):
 
     def postprocess(self):
         real = super().postprocess()
+        self.last_real = real
         self.last_real_count = len(real)
         self.last_candidates = self.ctx.detect_last_counts()[0]
         ms = self.ctx.detect_net_ms()                      # (None: this pass carried no timing events, option 'net_timing')

@@ -28,3 +28,18 @@ def test_stage_durations_pairs_repeated_marks():
     # an end without a start since the previous end is dropped; unsorted input is accepted
     np.testing.assert_allclose(bench.stage_durations([30., 0.], [5., 20, 35]), [5, 5])
     assert len(bench.stage_durations([], [1.])) == 0 and len(bench.stage_durations([1.], [])) == 0
+
+
+def test_write_outputs_keeps_arrays_and_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per array, values and dtypes as given; more than the limit is refused."""
+    import numpy as np
+    import pytest
+    outs = {'track_tlbr': np.arange(8, dtype=np.float64).reshape(2, 4), 'track_feature': np.ones((2, 3), np.float32)}
+    bench.write_outputs(tmp_path / 'dump', outs)
+    for name, a in outs.items():
+        b = np.load(tmp_path / 'dump' / f'{name}.npy')
+        assert b.dtype == a.dtype and np.array_equal(a, b)
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 64)
+    with pytest.raises(SystemExit):
+        bench.write_outputs(tmp_path / 'big', outs)
+    assert not (tmp_path / 'big').exists()

@@ -11,8 +11,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import ref_shim
+
 ROOT = Path(__file__).resolve().parents[1]
-REF_APP = Path('/root/reference/app.py')
+REF_APP = ref_shim.REF_ROOT / 'app.py'
+NO_REF_APP = 'needs the reference implementation\'s own app.py, which is not part of this repository'
 
 RUNNER = r'''
 import sys, types, runpy, json, inspect
@@ -83,7 +86,7 @@ def _run(tmp_path, argv, fake_mot):
     return json.loads(log.read_text()), res
 
 
-@pytest.mark.skipif(not REF_APP.exists(), reason='/root/reference only exists in the build container')
+@pytest.mark.skipif(not ref_shim.ref_path_exists('app.py'), reason=NO_REF_APP)
 def test_reference_app_runs_unmodified_capture_and_write(tmp_path):
     """Reference app.py, no tracker: VideoIO reads the sequence and writes every frame back unchanged."""
     from PIL import Image
@@ -97,7 +100,7 @@ def test_reference_app_runs_unmodified_capture_and_write(tmp_path):
         np.testing.assert_array_equal(np.asarray(Image.open(path))[:, :, ::-1], f)
 
 
-@pytest.mark.skipif(not REF_APP.exists(), reason='/root/reference only exists in the build container')
+@pytest.mark.skipif(not ref_shim.ref_path_exists('app.py'), reason=NO_REF_APP)
 def test_reference_app_drives_mot_with_reference_config(tmp_path):
     """Reference app.py -m with the reference's own cfg/mot.json: the constructor call binds against
     fastmot_amd.MOT's signature (every mot_cfg key is accepted), reset/step/visible_tracks/print_timing_info are

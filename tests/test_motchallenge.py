@@ -1,15 +1,12 @@
-"""MOTChallenge I/O: PublicDetector against the reference's own class (imported under the
-shim, build container only), the result-row format of app.py:91-97, and the CLEAR-MOT / IDF1 scorer on
-hand-checkable cases."""
-import importlib.util
+"""MOTChallenge I/O: PublicDetector against the reference's own class (its results stored in
+tests/golden/public_detector_ref.npz by oracle/make_golden_refcheck.py), the result-row format of app.py:91-97, and
+the CLEAR-MOT / IDF1 scorer on hand-checkable cases."""
 import io
-import sys
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-import ref_shim
 from fastmot_amd.detector import PublicDetector
 from fastmot_amd.utils import motchallenge as mc
 
@@ -28,30 +25,25 @@ def make_sequence(root, n_frames=12, seed=0):
     (root / 'det' / 'det.txt').write_text('\n'.join(rows) + '\n')
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason='reference tree only exists in the build container')
-@pytest.mark.parametrize('size,frame_skip', [((1280, 720), 1), ((1920, 1080), 3), ((640, 360), 2)])
-def test_public_detector_equals_reference(tmp_path, size, frame_skip):
+PUBLIC_CASES = [((1280, 720), 1), ((1920, 1080), 3), ((640, 360), 2)]
+PUBLIC_STEPS = 6
+
+
+@pytest.mark.parametrize('size,frame_skip', PUBLIC_CASES)
+def test_public_detector_equals_reference(tmp_path, golden_dir, size, frame_skip):
+    """PublicDetector against the reference's own class on the same sequence: what the reference returned in each of
+    the steps is tests/golden/public_detector_ref.npz (oracle/make_golden_refcheck.py)."""
     make_sequence(tmp_path / 'seq')
-    ns = ref_shim.load_reference()
-    try:
-        sys.modules['fastmot.utils'].TRTInference = object
-        for mod, rel in (('utils.decoder', 'utils/decoder.py'), ('detector', 'detector.py')):
-            spec = importlib.util.spec_from_file_location('fastmot.' + mod, ref_shim.REF_ROOT / 'fastmot' / rel)
-            m = importlib.util.module_from_spec(spec)
-            sys.modules['fastmot.' + mod] = m
-            spec.loader.exec_module(m)
-        ref = m.PublicDetector(size, (1,), frame_skip, sequence_path=str(tmp_path / 'seq'), max_area=400000)
-        ours = PublicDetector(size, (1,), frame_skip, sequence_path=str(tmp_path / 'seq'), max_area=400000)
-        for _ in range(6):
-            ref.detect_async(None)
-            ours.detect_async(None)
-            a, b = ref.postprocess(), ours.postprocess()
-            assert len(a) == len(b)
-            np.testing.assert_array_equal(a.tlbr, b.tlbr)
-            np.testing.assert_array_equal(a.label, b.label)
-            np.testing.assert_array_equal(a.conf, b.conf)
-    finally:
-        ref_shim.unload_reference(ns)
+    ref = np.load(golden_dir / 'public_detector_ref.npz')
+    ours = PublicDetector(size, (1,), frame_skip, sequence_path=str(tmp_path / 'seq'), max_area=400000)
+    for step in range(PUBLIC_STEPS):
+        ours.detect_async(None)
+        b = ours.postprocess()
+        key = f'{size[0]}x{size[1]}_skip{frame_skip}_{step}'
+        assert len(ref[key + '_label']) == len(b)
+        np.testing.assert_array_equal(ref[key + '_tlbr'], np.asarray(b.tlbr).reshape(-1, 4))
+        np.testing.assert_array_equal(ref[key + '_label'], b.label)
+        np.testing.assert_array_equal(ref[key + '_conf'], b.conf)
 
 
 def test_result_rows_format():
@@ -97,10 +89,9 @@ def test_scorer_hand_cases(tmp_path):
     assert mc.evaluate(gt, back) == r or mc.evaluate(gt, back)['idsw'] == 1
 
 
-@pytest.mark.skipif(not (ref_shim.REF_ROOT / 'eval' / 'results' / 'MOT20-01.txt').exists(),
-                    reason='reference artefact only exists in the build container')
-def test_reference_result_file_parses_and_self_scores():
-    res = mc.read_txt(ref_shim.REF_ROOT / 'eval' / 'results' / 'MOT20-01.txt')
+def test_reference_result_file_parses_and_self_scores(golden_dir):
+    """The first frames of the reference's own result file eval/results/MOT20-01.txt (tests/golden/MOT20-01_head.txt)."""
+    res = mc.read_txt(golden_dir / 'MOT20-01_head.txt')
     assert len(res) > 100 and all(len(v) > 0 for v in res.values())
     sub = {f: res[f] for f in sorted(res)[:60]}
     r = mc.evaluate(sub, sub)

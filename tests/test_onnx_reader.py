@@ -19,11 +19,11 @@ import pytest
 
 import darknet_cases as dc
 import onnx_writer as ow
+import ref_shim
 from fastmot_amd.models import YOLO, ReID, darknet, onnx_reader
 from fastmot_amd.models.torchreid_weights import TorchreidWeights
 
 GOLDEN = Path(__file__).parent / 'golden'
-REF_SCRIPT = Path('/root/reference/scripts/yolo2onnx.py')
 CASES = {'mini_v4': dc.MINI_V4, 'mini_tiny': dc.MINI_TINY}
 
 
@@ -53,7 +53,7 @@ def test_reference_converter_output_reads_back(name, tmp_path):
     blob = dc.random_weights_file(cfg, seed=11)
     g0, heads0, meta = darknet.darknet_graph(cfg, darknet.DarknetWeights(blob))
     files = [GOLDEN / f'yolo2onnx_{name}.onnx']
-    if REF_SCRIPT.is_file():                       # build container: run the reference converter again, live
+    if ref_shim.ref_path_exists('scripts/yolo2onnx.py'):     # where the reference is: run its converter again, live
         sys.path.insert(0, str(Path(__file__).parents[1] / 'oracle'))
         import make_golden_onnx
         (tmp_path / f'yolo2onnx_{name}.cfg').write_text(CASES[name])
