@@ -395,6 +395,7 @@ SOLVER_GREEDY = 1
 
 # ---------------------------------------------------------------------- detector / extractor
 FM_MAX_HEADS, FM_MAX_ANCHORS = 4, 6
+FM_MAX_DET_BATCH = 4         # frames of one batched detector pass (fastmot_hip.h)
 
 
 class YoloCfg(C.Structure):
@@ -486,6 +487,21 @@ def _bind_device_io(cls):
     def detect_async_next(self):
         check(self.lib.fm_detect_async_next(self._ctx))
 
+    def frame_upload_ahead(self, k, frame):
+        """Host frame for the step k steps ahead (look-ahead slot k, 1 <= k <= FM_MAX_DET_BATCH; k = 1: frame_upload_next)."""
+        w, h = self.frame_size
+        if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
+            raise ValueError(f'frame must be uint8 {h}x{w}x3')
+        f = np.ascontiguousarray(frame)
+        check(self.lib.fm_frame_upload_ahead(self._ctx, C.c_int(k), _ptr(f)))
+
+    def frame_ring_select_ahead(self, k, index):
+        check(self.lib.fm_frame_ring_select_ahead(self._ctx, C.c_int(k), C.c_int(index)))
+
+    def detect_async_ahead(self, n):
+        """One detector pass at batch n over look-ahead slots 1..n; each of the next n detect_sync calls returns one frame."""
+        check(self.lib.fm_detect_async_ahead(self._ctx, C.c_int(n)))
+
     def frame_read(self):
         w, h = self.frame_size
         out = np.empty((h, w, 3), np.uint8)
@@ -554,7 +570,8 @@ def _bind_device_io(cls):
         return out
 
     for fn in (frame_configure, frame_upload, pinned_frames, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
-               frame_ring_select_next, frame_promote_next, detect_async_next,
+               frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
+               detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,
                detect_raw_candidates, detect_last_counts, extract_configure, extract_async, extract_sync, extract_read_input):
         setattr(cls, fn.__name__, fn)

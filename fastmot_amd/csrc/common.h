@@ -160,6 +160,12 @@ struct fm_ctx {
     uint8_t* frame_next = nullptr;         // frame the detector was prefetched on (fm_frame_*_next)
     uint8_t* frame_pinned2 = nullptr;
     hipEvent_t ev_next_upload = nullptr;   // completion of the prefetched frame's H2D copy (enqueued on the ReID stream)
+    // look-ahead slots k = 2..FM_MAX_DET_BATCH (fm_frame_*_ahead; slot 1 is frame_next / frame_own2 / frame_pinned2 /
+    // ev_next_upload): the frame of slot k, and upload slot k with its staging buffer and copy event (allocated on first use)
+    uint8_t* frame_ahead[FM_MAX_DET_BATCH + 1] = {};
+    uint8_t* frame_up[FM_MAX_DET_BATCH + 1] = {};
+    uint8_t* frame_up_pinned[FM_MAX_DET_BATCH + 1] = {};
+    hipEvent_t ev_up[FM_MAX_DET_BATCH + 1] = {};
     uint8_t* frame_ring = nullptr;
     uint8_t* frame_pinned = nullptr;
 

@@ -457,7 +457,8 @@ int launch_conv(const ConvParams& p, float* ws, size_t ws_floats, hipStream_t s)
     };
     constexpr int minb = 2;
     if (cout_pad <= 32) return launch_cfg<1, 4, 1, 1, 2>(p, 1, ws, s);                   //  32c x 128p
-    const long t = tiles(64, 64);
+    // (batch_inv: the split count -- the order of an output's partial sums -- follows one sample's tile count)
+    const long t = p.batch_inv ? (long)((p.Ho * p.Wo + 63) / 64) * ((cout_pad + 63) / 64) : tiles(64, 64);
     // many short workgroups (early, memory-bound layers): 128 VGPRs -> 4 workgroups per CU
     if (minb == 4 || (minb == 3 && t >= 1024)) return launch_cfg<2, 2, 1, 1, 4>(p, split_for(t), ws, s);
     return launch_cfg<2, 2, 1, 1, 2>(p, split_for(t), ws, s);                            //  64c x  64p

@@ -538,6 +538,21 @@ int launch_convd(const ConvParams& p, hipStream_t s) {
     FM_CHECK_ARG(((long)p.N * p.H * p.W + (long)(p.KH + p.pad) * p.W + p.KW + p.pad) * p.in_cs * 2 < (1L << 31));
     FM_CHECK_ARG((long)((p.Cout + 31) & ~31) * p.Kpad * 2 < (1L << 31));
     Cfg c = choose(p);
+    if (p.batch_inv && p.N > 1) {
+        // the K-group count fixes the order in which an output's partial sums are added: take the batch-1 layer's
+        // configuration whenever its count differs (tile shape, loader waves and ring depth do not change that order, so
+        // otherwise the tile follows the real tile count)
+        ConvParams q = p;
+        q.N = 1;
+        q.P = p.Ho * p.Wo;
+        const Cfg c1 = choose(q);
+        if (c1.kg != c.kg) {
+            const int cout_pad = (p.Cout + 31) & ~31, nk = p.Kpad >> 6;
+            const long nt = (long)((p.P + c1.bn - 1) / c1.bn) * ((cout_pad + c1.bm - 1) / c1.bm);
+            c = c1;
+            c.ns = stages_for(c.bm, c.bn, c.kg, c.spb, ((nk + c.kg - 1) / c.kg + c.spb - 1) / c.spb, nt > 256 ? LDS_MAX / 2 : LDS_MAX);
+        }
+    }
     if (g_convd_cfg) {      // forced: bm | bn << 8 | kg << 16 | ns << 20 | role << 24 | (spb == 2) << 25 (ns 0: as deep as LDS allows)
         Cfg f{g_convd_cfg & 255, (g_convd_cfg >> 8) & 255, (g_convd_cfg >> 16) & 15, (g_convd_cfg >> 20) & 15, (g_convd_cfg >> 24) & 1,
               1 + ((g_convd_cfg >> 25) & 1)};

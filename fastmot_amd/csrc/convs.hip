@@ -279,7 +279,7 @@ __global__ __launch_bounds__(NW * 64) void convs_halo_kernel(const ConvParams p,
     {   // halo tile -> LDS (zero outside the image = the layer's padding)
         const int segs = p.Cin >> 3;
         const float inv_segs = 1.f / (float)segs;
-        const f16* src = p.in + p.in_coff;
+        const f16* src = p.in + p.in_coff + (size_t)blockIdx.y * p.H * p.W * p.in_cs;     // (blockIdx.y: the image)
         for (int i = tid; i < NPOS * segs; i += NW * 64) {
             const int pos = idiv_small(i, segs, inv_segs), sg = i - pos * segs;
             const int py = pos / HWT, px = pos - py * HWT;
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(NW * 64) void convs_halo_kernel(const ConvParams p,
             const int pl = t * 32 + (ln & 31);
             const int oy = ty0 + (pl >> 3), ox = tx0 + (pl & 7);
             if (oy >= p.Ho || ox >= p.Wo || co >= p.cout_store) continue;
-            const long opix = (long)oy * p.Wo + ox;
+            const long opix = ((long)blockIdx.y * p.Ho + oy) * p.Wo + ox;
             const float4 b = *reinterpret_cast<const float4*>(p.bias + co);
             float v[4] = {a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w};
             float r[4] = {0.f, 0.f, 0.f, 0.f};
@@ -405,7 +405,7 @@ int convs_halo_launch(const ConvParams& p, int ntiles_c, hipStream_t s) {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
         configured = shmem;
     }
-    hipLaunchKernelGGL((convs_halo_kernel<CT, NW>), dim3(((total + 7) / 8) * 8), dim3(NW * 64), shmem, s, p, tiles_x,
+    hipLaunchKernelGGL((convs_halo_kernel<CT, NW>), dim3(((total + 7) / 8) * 8, p.N), dim3(NW * 64), shmem, s, p, tiles_x,
                        tiles_y, ncg);
     FM_HIP(hipGetLastError());
     return 0;
@@ -440,7 +440,8 @@ int launch_conv_streamed(const ConvParams& p_in, hipStream_t s) {
     FM_CHECK_ARG(p.out_cs % 4 == 0 && p.out_coff % 4 == 0 && p.cout_store % 4 == 0 && p.Cin <= 4096);
     FM_CHECK_ARG(p.res_mode == RES_NONE || (p.res_cs % 4 == 0 && p.res_coff % 4 == 0));
     FM_CHECK_ARG(p.P < (1 << 22));                  // idiv_small in the prologue
-    const int ntiles_c = (p.Cout + 31) / 32, npt = (p.P + 31) / 32, nq = p.K / 64;
+    // (batch_inv: the instance -- waves splitting K, halo or not -- is chosen on one sample's pixels; the grid follows p.P)
+    const int ntiles_c = (p.Cout + 31) / 32, npt = ((p.batch_inv ? p.Ho * p.Wo : p.P) + 31) / 32, nq = p.K / 64;
     // two cout tiles per workgroup halve the pixel-fragment traffic; only when that still fills the chip
     const bool ct2 = ntiles_c % 2 == 0 && (ntiles_c / 2) * npt >= 192;
     const bool nw8 = nq >= 16;                      // >= 2 chunks per wave
@@ -449,9 +450,9 @@ int launch_conv_streamed(const ConvParams& p_in, hipStream_t s) {
     // reproducing its results while they ran; round 3 found the cause in the LK kernel's own packed-fp32 code, flow.hip)
     constexpr int pt2_mode = 1;
     const int wgs1 = (ntiles_c / 2) * npt;
-    // 3x3 / stride 1 / pad 1 on one image: input halo staged in LDS once (convs_halo_kernel)
+    // 3x3 / stride 1 / pad 1 on one image (or each image of a batch_inv launch): input halo staged in LDS once (convs_halo_kernel)
     constexpr int halo_mode = 1;
-    if (halo_mode && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.N == 1 && p.Ho == p.H && p.Wo == p.W &&
+    if (halo_mode && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && (p.N == 1 || p.batch_inv) && p.Ho == p.H && p.Wo == p.W &&
         p.up != 2 && (size_t)100 * (p.Cin + 8) * 2 <= 150 * 1024 && nq >= 8) {
         // only where the 8 x 8 tiles waste little (38 x 38: 90 % of the tile pixels exist, 15.2 -> 12.5 us per layer; at
         // 19 x 19 = 3 x 3 tiles for 361 pixels, 63 %, it measured 12.5 -> 16.5 us)

@@ -169,6 +169,11 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
         if (p) (void)hipFree(p);
     if (ctx->frame_pinned) (void)hipHostFree(ctx->frame_pinned);
     if (ctx->frame_pinned2) (void)hipHostFree(ctx->frame_pinned2);
+    for (int k = 2; k <= FM_MAX_DET_BATCH; ++k) {
+        if (ctx->frame_up[k]) (void)hipFree(ctx->frame_up[k]);
+        if (ctx->frame_up_pinned[k]) (void)hipHostFree(ctx->frame_up_pinned[k]);
+        if (ctx->ev_up[k]) (void)hipEventDestroy(ctx->ev_up[k]);
+    }
     if (ctx->det_net) fm_net_free(ctx->det_net);
     if (ctx->ext_net) fm_net_free(ctx->ext_net);
     for (NetState* x : ctx->ext_net_x)

@@ -27,31 +27,34 @@ struct DetState {
     fm_yolo_cfg cfg{};
     bool configured = false;
     int cap = 8192;
-    // Results and the post-processing buffers are double buffered and completed by events: the pass on the NEXT frame
-    // can be queued behind this one (MOT.step with next_frame: the detector stream never idles) while the host still
-    // has to collect this frame's detections.  Passes are collected in enqueue order.
-    static constexpr int NSLOT = 2;
-    float* cand[NSLOT] = {nullptr, nullptr};        // [cap][8] : x y w h box_conf class cls_prob orig_idx(as float bits)
-    float* sorted[NSLOT] = {nullptr, nullptr};      // [cap][8]
-    int32_t* counters[NSLOT] = {nullptr, nullptr};  // [0]=n_cand [1]=overflow [2]=n_det
-    uint64_t* mask[NSLOT] = {nullptr, nullptr};     // [cap/64][cap]
-    fm_det48* dets[NSLOT] = {nullptr, nullptr};     // [cap]
-    bool used[NSLOT] = {false, false};
-    hipEvent_t ev_dec[NSLOT] = {nullptr, nullptr};  // candidates of the pass complete (stream that produced them)
-    int post_pending = -1;                          // slot whose sort + NMS has not been enqueued yet (flush_post)
+    // Results and the post-processing buffers form a ring of slots, one per frame, completed by events: the pass on the
+    // NEXT frame(s) can be queued behind this one (MOT.step with next_frame / detector look-ahead: the detector stream never
+    // idles) while the host still has to collect this frame's detections.  Frames are collected in enqueue order.  A
+    // batched pass (fm_detect_async_ahead) fills FM_MAX_DET_BATCH consecutive slots at most; the ring holds such a pass,
+    // the frame being collected and a stale prefetch.
+    static constexpr int NSLOT = FM_MAX_DET_BATCH + 2;
+    float* cand[NSLOT] = {};        // [cap][8] : x y w h box_conf class cls_prob orig_idx(as float bits)
+    float* sorted[NSLOT] = {};      // [cap][8]
+    int32_t* counters[NSLOT] = {};  // [0]=n_cand [1]=overflow [2]=n_det
+    uint64_t* mask[NSLOT] = {};     // [cap/64][cap]
+    fm_det48* dets[NSLOT] = {};     // [cap]
+    bool used[NSLOT] = {};
+    hipEvent_t ev_dec[NSLOT] = {};  // candidates of the pass complete (stream that produced them; first slot of a pass)
+    int post_pending = -1;          // first slot of the pass whose sort + NMS has not been enqueued yet (flush_post) ...
+    int post_pending_n = 0;         // ... and its number of slots (images)
     bool general_post = false;                      // the three-kernel sort / bit matrix / scan path (more than 4096 candidates,
                                                     // fm_ctx option "nms_path" = 1); default: nms_greedy_kernel
     static constexpr int GREEDY_RETRY = 1024;       // passes on the general path before the greedy kernel gets another try
     int general_passes = 0;
     int greedy_kmax = 2048, greedy_shrink = 0;      // LDS capacity (candidates) of the next greedy launches; passes since it was too large
-    bool sorted_valid[NSLOT] = {false, false};      // d->sorted[slot] holds the pass's sorted rows (general path / test hook)
+    bool sorted_valid[NSLOT] = {};      // d->sorted[slot] holds the pass's sorted rows (general path / test hook)
     static constexpr int PREFIX = 2048;        // detections copied back with the pass (more: synchronous fallback)
-    fm_det48* dets_host[NSLOT] = {nullptr, nullptr};
-    int32_t* counters_host[NSLOT] = {nullptr, nullptr};
-    hipEvent_t ev_done[NSLOT] = {nullptr, nullptr};
+    fm_det48* dets_host[NSLOT] = {};
+    int32_t* counters_host[NSLOT] = {};
+    hipEvent_t ev_done[NSLOT] = {};
     hipStream_t s_fallback = nullptr;          // redo of a pass the greedy kernel declined (collect): NOT s_up, see there
-    hipEvent_t ev0[NSLOT] = {nullptr, nullptr}, ev1[NSLOT] = {nullptr, nullptr};   // bracket the network launches
-    bool timed[NSLOT] = {false, false};        // ... of the passes that were timed (fm_ctx option "net_timing")
+    hipEvent_t ev0[NSLOT] = {}, ev1[NSLOT] = {};   // bracket the network launches (first slot of a pass)
+    bool timed[NSLOT] = {};                        // ... of the passes that were timed (fm_ctx option "net_timing")
     long n_passes = 0;
     int wr = 0, rd = 0, pending = 0, last = -1;   // slot written next / collected next / passes in flight / last collected
     uint8_t* label_mask = nullptr;
@@ -84,22 +87,23 @@ namespace {
 // grid_mode=True: src = (dst + 0.5) * (in/out) - 0.5; affine_transform order=1, mode='nearest'),
 // result rounded to uint8 (rint), then BGR->RGB, * 1/255 (fp32) and stored as fp16 NHWC with the
 // channel dimension padded to 8 (zeros).  Outside the letterbox ROI the input is 0.5.
-__global__ void preprocess_kernel(const uint8_t* __restrict__ frame, int fw, int fh,
-                                  f16* __restrict__ inp, int in_w, int in_h, int cs, int roi_x, int roi_y,
-                                  int roi_w, int roi_h, int32_t* __restrict__ counters) {
+// One launch for the n images of a batched pass: blockIdx.z = the image (frame src.frame[z], input sample z).
+__global__ void preprocess_kernel(const StemSrc src, f16* __restrict__ inp, int in_w, int in_h, int cs) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
+    const int y = blockIdx.y, n = blockIdx.z;
     // candidate counters of this frame's decode (one memset node fewer on the detector stream; the previous
     // frame's counters were copied to the host earlier on the same stream)
+    int32_t* counters = pick_sample(src.zero4, n);
     if (counters && x < 4 && y == 0) counters[x] = 0;
     if (x >= in_w || y >= in_h) return;
     float rgb[3];
-    det_input_pixel(frame, fw, fh, x, y, roi_x, roi_y, roi_w, roi_h, rgb);      // (pixel_source.h: shared with the fused stem)
+    det_input_pixel(pick_sample(src.frame, n), src.fw, src.fh, x, y, src.roi_x, src.roi_y, src.roi_w, src.roi_h,
+                    rgb);      // (pixel_source.h: shared with the fused stem)
     f16x8 o;
     o[0] = (f16)rgb[0]; o[1] = (f16)rgb[1]; o[2] = (f16)rgb[2];
 #pragma unroll
     for (int e = 3; e < 8; ++e) o[e] = (f16)0.f;
-    *reinterpret_cast<f16x8*>(inp + ((size_t)y * in_w + x) * cs) = o;
+    *reinterpret_cast<f16x8*>(inp + (((size_t)n * in_h + y) * in_w + x) * cs) = o;
 }
 
 // ------------------------------------------------------------------------------------ decode
@@ -150,10 +154,13 @@ __device__ __forceinline__ void emit_candidate(const FilterArgs& fa, float bx, f
 struct HeadSet {
     HeadArgs h[FM_MAX_HEADS];
     int first_block[FM_MAX_HEADS + 1];   // head i owns blocks [first_block[i], first_block[i + 1])
+    float* cand[FM_MAX_DET_BATCH];       // image z (blockIdx.y) of a batched pass: its slot's candidate list ...
+    int32_t* counters[FM_MAX_DET_BATCH]; // ... and counters (FilterArgs.cand / counters are image 0's)
 };
 
 // one thread per (head, anchor, cell), all heads in one launch: plugins/yolo_layer.cu:127-173 (classic) /
 // :185-230 (new_coords)
+// (blockIdx.y: the image of a batched pass -- its sample of the head tensors, its slot's candidate list)
 __global__ void decode_kernel(HeadSet hs, FilterArgs fa, int in_w, int in_h, int new_coords) {
     int hi = 0;
 #pragma unroll
@@ -162,10 +169,13 @@ __global__ void decode_kernel(HeadSet hs, FilterArgs fa, int in_w, int in_h, int
     const int idx = ((int)blockIdx.x - hs.first_block[hi]) * blockDim.x + threadIdx.x;
     const int cells = h.gw * h.gh;
     if (idx >= cells * h.na) return;
+    const int img = blockIdx.y;
+    fa.cand = pick_sample(hs.cand, img);
+    fa.counters = pick_sample(hs.counters, img);
     const int a = idx / cells, cell = idx - a * cells;
     const int row = cell / h.gw, col = cell - row * h.gw;
     const int info = 5 + fa.num_classes;
-    const float* p = h.data + (size_t)cell * h.cs + a * info;
+    const float* p = h.data + ((size_t)img * cells + cell) * h.cs + a * info;
     int cls = 0;
     float best = -INFINITY;
     // four class logits per (4-byte aligned) 16-byte load, scanned in ascending order with the strict comparison of the
@@ -853,6 +863,7 @@ int alloc_post(DetState* d, int cap) {
     d->wr = d->rd = d->pending = 0;
     d->last = -1;
     d->post_pending = -1;
+    d->post_pending_n = 0;
     for (int i = 0; i < DetState::NSLOT; ++i) {
         FM_HIP(hipMalloc(&d->cand[i], sizeof(float) * 8 * cap));
         FM_HIP(hipMalloc(&d->sorted[i], sizeof(float) * 8 * cap));
@@ -955,54 +966,69 @@ static int enqueue_greedy_post(fm_ctx* ctx, DetState* d, int slot, hipStream_t s
 // context drives more streams than the runtime has queues): one more stream for this work measured 612 -> 430, the
 // idle streams of the extra ReID instances 400 / 215 / 215, the ReID stream itself 480, s_up at high priority 450
 // (profiles/r03_pipeline_order_ab.txt).
+// A batched pass leaves its n images pending together: one wait for the pass's decode, then each image's post-processing.
 static int flush_post(fm_ctx* ctx, DetState* d) {
-    const int slot = d->post_pending;
-    if (slot < 0) return 0;
+    const int first = d->post_pending, n = d->post_pending_n;
+    if (first < 0) return 0;
     d->post_pending = -1;
-    const int cap = d->cap;
+    d->post_pending_n = 0;
     hipStream_t sp = ctx->s_up;
-    FM_HIP(hipStreamWaitEvent(sp, d->ev_dec[slot], 0));
-    fm_trace_mark(ctx, sp, 20);
-    int rc_p = (d->general_post || ctx->opt_nms_general) ? enqueue_general_post(ctx, d, slot, sp) : enqueue_greedy_post(ctx, d, slot, sp);
-    if (rc_p) return rc_p;
-    // (The counters and a bounded prefix of the detections -- they are few; the rest, rare, is fetched at collection
-    // time -- are written to page-locked host memory by the scan kernel itself.  As two hipMemcpyAsync they were handed
-    // to a copy engine as soon as they were enqueued, i.e. while the pass they wait for still had a millisecond to run,
-    // and every later device-to-host copy that landed on that engine -- the embeddings of the frame being tracked, the
-    // KLT results -- waited behind them: scripts/trace_pipeline.py showed the main thread receiving its embeddings
-    // 0.6 ms after the ReID network had finished, exactly when the NEXT pass's post-processing ended.  Whether it
-    // happened depended on the engine the runtime picked: runs of the same binary fell into 650 or 860 frames/s.)
-    FM_HIP(hipEventRecord(d->ev_done[slot], sp));
-    fm_trace_mark(ctx, sp, 21);
+    FM_HIP(hipStreamWaitEvent(sp, d->ev_dec[first], 0));
+    for (int i = 0; i < n; ++i) {
+        const int slot = (first + i) % DetState::NSLOT;
+        fm_trace_mark(ctx, sp, 20);
+        int rc_p = (d->general_post || ctx->opt_nms_general) ? enqueue_general_post(ctx, d, slot, sp) : enqueue_greedy_post(ctx, d, slot, sp);
+        if (rc_p) return rc_p;
+        // (The counters and a bounded prefix of the detections -- they are few; the rest, rare, is fetched at collection
+        // time -- are written to page-locked host memory by the scan kernel itself.  As two hipMemcpyAsync they were handed
+        // to a copy engine as soon as they were enqueued, i.e. while the pass they wait for still had a millisecond to run,
+        // and every later device-to-host copy that landed on that engine -- the embeddings of the frame being tracked, the
+        // KLT results -- waited behind them: scripts/trace_pipeline.py showed the main thread receiving its embeddings
+        // 0.6 ms after the ReID network had finished, exactly when the NEXT pass's post-processing ended.  Whether it
+        // happened depended on the engine the runtime picked: runs of the same binary fell into 650 or 860 frames/s.)
+        FM_HIP(hipEventRecord(d->ev_done[slot], sp));
+        fm_trace_mark(ctx, sp, 21);
+    }
     return 0;
 }
 
-// the candidates of slot d->wr are complete on stream `s` (real path: decode on the detector stream; test hook: the
-// row filter): book the pass and leave its post-processing pending
-int enqueue_post(fm_ctx* ctx, DetState* d, hipStream_t s) {
+// the candidates of the n slots from d->wr on are complete on stream `s` (real path: decode on the detector stream; test
+// hook: the row filter): book the pass and leave its post-processing pending
+int enqueue_post(fm_ctx* ctx, DetState* d, hipStream_t s, int n = 1) {
     int rc = flush_post(ctx, d);              // (a pass whose post-processing nobody flushed yet: keep the order)
     if (rc) return rc;
-    if (d->pending >= DetState::NSLOT) {      // never collected (a caller that only ever enqueues): drop the oldest
+    while (d->pending + n > DetState::NSLOT) {      // never collected (a caller that only ever enqueues): drop the oldest
         d->rd = (d->rd + 1) % DetState::NSLOT;
         --d->pending;
     }
     const int slot = d->wr;
     FM_HIP(hipEventRecord(d->ev_dec[slot], s));
     d->post_pending = slot;
-    d->used[slot] = true;
-    d->wr = (slot + 1) % DetState::NSLOT;
-    ++d->pending;
+    d->post_pending_n = n;
+    for (int i = 0; i < n; ++i) d->used[(slot + i) % DetState::NSLOT] = true;
+    d->wr = (slot + n) % DetState::NSLOT;
+    d->pending += n;
     return 0;
 }
 
-// a pass is about to write the candidate buffers of slot d->wr on stream `s`: the post-processing of the pass that
-// used the slot before (two passes ago) must be through with them
-static int acquire_slot(DetState* d, hipStream_t s) {
-    // (in steady state that post-processing ended a step ago: the host can see it, and a wait that is not enqueued is one
-    // packet fewer on the stream whose period is the step -- every packet there costs microseconds, r06_net_timing_events_ab.txt)
-    if (d->used[d->wr] && hipEventQuery(d->ev_done[d->wr]) != hipSuccess) {
-        (void)hipGetLastError();                     // (hipErrorNotReady is not an error)
-        FM_HIP(hipStreamWaitEvent(s, d->ev_done[d->wr], 0));
+// a pass is about to write the candidate buffers of the n slots from d->wr on, on stream `s`: the post-processing of
+// the passes that used them before must be through with them
+static int acquire_slots(fm_ctx* ctx, DetState* d, hipStream_t s, int n = 1) {
+    // (a pending pass among them -- only when a batched pass follows a batched pass nobody collected: enqueue its
+    // post-processing first, so that its ev_done is the event waited for below)
+    if (d->post_pending >= 0 && d->post_pending_n + n > DetState::NSLOT) {
+        int rc = flush_post(ctx, d);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int slot = (d->wr + i) % DetState::NSLOT;
+        // (in steady state that post-processing ended a step ago: the host can see it, and a wait that is not enqueued is
+        // one packet fewer on the stream whose period is the step -- every packet there costs microseconds,
+        // r06_net_timing_events_ab.txt)
+        if (d->used[slot] && hipEventQuery(d->ev_done[slot]) != hipSuccess) {
+            (void)hipGetLastError();                     // (hipErrorNotReady is not an error)
+            FM_HIP(hipStreamWaitEvent(s, d->ev_done[slot], 0));
+        }
     }
     return 0;
 }
@@ -1079,6 +1105,11 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         if (p) (void)hipHostFree(p);
     ctx->frame_own = ctx->frame_own2 = ctx->frame_ring = ctx->frame_pinned = ctx->frame_pinned2 = nullptr;
     ctx->frame_next = nullptr;
+    for (int k = 2; k <= FM_MAX_DET_BATCH; ++k) {      // look-ahead slots: allocated again on first use at the new size
+        if (ctx->frame_up[k]) (void)hipFree(ctx->frame_up[k]);
+        if (ctx->frame_up_pinned[k]) (void)hipHostFree(ctx->frame_up_pinned[k]);
+        ctx->frame_up[k] = ctx->frame_up_pinned[k] = ctx->frame_ahead[k] = nullptr;
+    }
     const size_t bytes = (size_t)width * height * 3;
     FM_HIP(hipMalloc(&ctx->frame_own, bytes + FM_FRAME_SLACK));        // (pixel_source.h load_px2 reads 8 bytes at a pixel)
     FM_HIP(hipMalloc(&ctx->frame_own2, bytes + FM_FRAME_SLACK));
@@ -1160,18 +1191,36 @@ extern "C" int fm_frame_upload(fm_ctx* ctx, const uint8_t* bgr) {
 // ---- next-frame prefetch: the detector may be started on frame t+1 while frame t is still being tracked
 // (MOT.step(frame, next_frame)).  The next frame lives in the second upload slot (or the ring) and becomes
 // the current one with fm_frame_promote_next -- no second upload.
-extern "C" int fm_frame_upload_next(fm_ctx* ctx, const uint8_t* bgr) {
-    FM_CHECK_ARG(ctx && bgr && ctx->frame_own2);
+// Look-ahead slot k: the frame the step k steps ahead receives.  Slot 1 is the fields of the next-frame prefetch
+// (frame_next, upload slot frame_own2 / frame_pinned2 / ev_next_upload), slots 2.. those of fm_ctx::frame_ahead /
+// frame_up / frame_up_pinned / ev_up.  An upload slot's buffers move with its frame when fm_frame_promote_next shifts the
+// slots, so that slot 1's frame always lies in frame_own2 when it was uploaded.
+static uint8_t*& ahead_frame(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_next : ctx->frame_ahead[k]; }
+static uint8_t*& ahead_buf(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_own2 : ctx->frame_up[k]; }
+static uint8_t*& ahead_pinned(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_pinned2 : ctx->frame_up_pinned[k]; }
+static hipEvent_t& ahead_event(fm_ctx* ctx, int k) { return k == 1 ? ctx->ev_next_upload : ctx->ev_up[k]; }
+
+extern "C" int fm_frame_upload_next(fm_ctx* ctx, const uint8_t* bgr) { return fm_frame_upload_ahead(ctx, 1, bgr); }
+
+extern "C" int fm_frame_upload_ahead(fm_ctx* ctx, int k, const uint8_t* bgr) {
+    FM_CHECK_ARG(ctx && bgr && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH);
     const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
     const uint8_t* src = bgr;
     if (!is_pinned_range(bgr, bytes)) {
         // previous H2D copy out of a staging buffer: its event, not the stream (a detector pass may be running)
-        if (ctx->ev_next_upload) FM_HIP(hipEventSynchronize(ctx->ev_next_upload));
-        memcpy(ctx->frame_pinned2, bgr, bytes);
-        src = ctx->frame_pinned2;
+        if (ev) FM_HIP(hipEventSynchronize(ev));
+        memcpy(ahead_pinned(ctx, k), bgr, bytes);
+        src = ahead_pinned(ctx, k);
     }
-    // The previous readers of frame_own2 -- every stage of the step before the last promote, its detector pass
-    // included -- are done (fm_frame_promote_next synchronised the ReID / KLT streams, that pass was collected).  The
+    // The previous readers of the slot's buffer -- every stage of the step before the last promote, its detector pass
+    // included -- are done (fm_frame_promote_next synchronised the ReID / KLT streams, that pass was collected; a batched
+    // pass is complete once any of its frames was collected).  The
     // copy goes to the ReID stream: that stream is idle at this point of a step (its network starts once this frame's
     // detections have been collected, long after a 6 MB copy), it is a high-priority stream, and the pass on the new
     // frame waits for the copy's event only.  On the low-priority stream that carries the post-processing the copy was
@@ -1182,19 +1231,21 @@ extern "C" int fm_frame_upload_next(fm_ctx* ctx, const uint8_t* bgr) {
     // included: 550-600 and 450).
     hipStream_t cs = ctx->s_ext;
     fm_trace_mark(ctx, cs, 30);
-    int rc_copy = enqueue_frame_copy(ctx->frame_own2, src, bytes, cs);
+    int rc_copy = enqueue_frame_copy(buf, src, bytes, cs);
     if (rc_copy) return rc_copy;
     fm_trace_mark(ctx, cs, 31);
-    if (!ctx->ev_next_upload) FM_HIP(hipEventCreateWithFlags(&ctx->ev_next_upload, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ctx->ev_next_upload, cs));
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
     if (ctx->det && (rc_copy = flush_post(ctx, ctx->det))) return rc_copy;   // see flush_post
-    ctx->frame_next = ctx->frame_own2;
+    ahead_frame(ctx, k) = buf;
     return 0;
 }
 
-extern "C" int fm_frame_ring_select_next(fm_ctx* ctx, int index) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size);
-    ctx->frame_next = ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index;
+extern "C" int fm_frame_ring_select_next(fm_ctx* ctx, int index) { return fm_frame_ring_select_ahead(ctx, 1, index); }
+
+extern "C" int fm_frame_ring_select_ahead(fm_ctx* ctx, int k, int index) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && k >= 1 && k <= FM_MAX_DET_BATCH);
+    ahead_frame(ctx, k) = ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index;
     return 0;
 }
 
@@ -1222,6 +1273,18 @@ extern "C" int fm_frame_promote_next(fm_ctx* ctx) {
         ctx->frame_cur = ctx->frame_next;
     }
     ctx->frame_next = nullptr;
+    // look-ahead: slot k becomes slot k - 1; a frame in its upload slot takes that slot's buffers along (the free buffer
+    // -- the previous frame's -- moves up in exchange)
+    for (int k = 2; k <= FM_MAX_DET_BATCH; ++k) {
+        uint8_t* f = ctx->frame_ahead[k];
+        if (f && f == ctx->frame_up[k]) {
+            std::swap(ahead_buf(ctx, k - 1), ahead_buf(ctx, k));
+            std::swap(ahead_pinned(ctx, k - 1), ahead_pinned(ctx, k));
+            std::swap(ahead_event(ctx, k - 1), ahead_event(ctx, k));
+        }
+        ahead_frame(ctx, k - 1) = f;
+        ctx->frame_ahead[k] = nullptr;
+    }
     return 0;
 }
 
@@ -1264,6 +1327,7 @@ extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_up));
     d->post_pending = -1;
+    d->post_pending_n = 0;
     d->rd = d->wr;            // a new detector: nothing of the previous one is collected any more
     d->pending = 0;
     d->cfg = *cfg;
@@ -1274,48 +1338,88 @@ extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
     return 0;
 }
 
-static int enqueue_preprocess(fm_ctx* ctx, DetState* d, NetState* net, const uint8_t* frame) {
+// the detector's frame source for the n images of a pass: frame i, the candidate counters of slot d->wr + i
+static StemSrc det_source(fm_ctx* ctx, DetState* d, const uint8_t* const* frames, int n) {
     const fm_yolo_cfg& c = d->cfg;
-    FM_CHECK_ARG(frame != nullptr);
+    StemSrc src{};
+    src.kind = 1; src.fw = ctx->frame_w; src.fh = ctx->frame_h;
+    src.roi_x = c.roi_x; src.roi_y = c.roi_y; src.roi_w = c.roi_w; src.roi_h = c.roi_h;
+    for (int i = 0; i < n; ++i) {
+        src.frame[i] = frames[i];
+        src.zero4[i] = d->counters[(d->wr + i) % DetState::NSLOT];
+    }
+    return src;
+}
+
+static int enqueue_preprocess(fm_ctx* ctx, DetState* d, NetState* net, const StemSrc& src, int n) {
+    const fm_yolo_cfg& c = d->cfg;
+    for (int i = 0; i < n; ++i) FM_CHECK_ARG(src.frame[i] != nullptr);
     FM_CHECK_ARG(c.input_tensor >= 0 && c.input_tensor < (int)net->tensors.size());
     const fm_tensor& t = net->tensors[c.input_tensor];
     FM_CHECK_ARG(t.h == c.in_h && t.w == c.in_w && !t.f32);
-    hipLaunchKernelGGL(preprocess_kernel, dim3((c.in_w + 255) / 256, c.in_h), dim3(256), 0, ctx->s_det,
-                       frame, ctx->frame_w, ctx->frame_h, (f16*)net->bufs[c.input_tensor], c.in_w,
-                       c.in_h, t.c, c.roi_x, c.roi_y, c.roi_w, c.roi_h, filter_args(d, d->wr).counters);
+    hipLaunchKernelGGL(preprocess_kernel, dim3((c.in_w + 255) / 256, c.in_h, n), dim3(256), 0, ctx->s_det,
+                       src, (f16*)net->bufs[c.input_tensor], c.in_w, c.in_h, t.c);
     FM_HIP(hipGetLastError());
     return 0;
 }
 
 extern "C" int fm_detect_preprocess_only(fm_ctx* ctx) {
     FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured && ctx->det_net);
-    return enqueue_preprocess(ctx, ctx->det, ctx->det_net, ctx->frame_cur);
+    const uint8_t* f = ctx->frame_cur;
+    return enqueue_preprocess(ctx, ctx->det, ctx->det_net, det_source(ctx, ctx->det, &f, 1), 1);
 }
 
-static int detect_async_on(fm_ctx* ctx, const uint8_t* frame);
+static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n);
 
 extern "C" int fm_detect_async(fm_ctx* ctx) {
     FM_CHECK_ARG(ctx);
-    return detect_async_on(ctx, ctx->frame_cur);
+    const uint8_t* f = ctx->frame_cur;
+    const hipEvent_t none = nullptr;
+    return detect_pass(ctx, &f, &none, 1);
 }
 
 // detector on the prefetched next frame (fm_frame_upload_next / fm_frame_ring_select_next)
 extern "C" int fm_detect_async_next(fm_ctx* ctx) {
     FM_CHECK_ARG(ctx && ctx->frame_next);
-    return detect_async_on(ctx, ctx->frame_next);
+    return fm_detect_async_ahead(ctx, 1);
 }
 
-static int detect_async_on(fm_ctx* ctx, const uint8_t* frame) {
+extern "C" int fm_detect_async_ahead(fm_ctx* ctx, int n) {
+    FM_CHECK_ARG(ctx && ctx->det_net && n >= 1 && n <= FM_MAX_DET_BATCH);
+    if (n > ctx->det_net->max_batch) {
+        fm_set_error("detector look-ahead of %d frames > the detector network's max_batch %d", n, ctx->det_net->max_batch);
+        return FM_ERR_ARG;
+    }
+    const uint8_t* frames[FM_MAX_DET_BATCH];
+    hipEvent_t uploads[FM_MAX_DET_BATCH];
+    for (int k = 1; k <= n; ++k) {
+        frames[k - 1] = ahead_frame(ctx, k);
+        if (!frames[k - 1]) {
+            fm_set_error("look-ahead slot %d holds no frame (fm_frame_upload_ahead / fm_frame_ring_select_ahead)", k);
+            return FM_ERR_ARG;
+        }
+        // a frame in its upload slot: the pass waits for that copy
+        uploads[k - 1] = frames[k - 1] == ahead_buf(ctx, k) ? ahead_event(ctx, k) : nullptr;
+    }
+    return detect_pass(ctx, frames, uploads, n);
+}
+
+// One network pass at batch n over frames[0..n-1] (n = 1: the single-frame pass), decode of every image into slots
+// d->wr .. d->wr + n - 1, their post-processing left pending (flush_post).
+static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n) {
     FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured && ctx->det_net);
     DetState* d = ctx->det;
     NetState* net = ctx->det_net;
     const fm_yolo_cfg& c = d->cfg;
+    FM_CHECK_ARG(n >= 1 && n <= FM_MAX_DET_BATCH && n <= net->max_batch);
     hipStream_t s = ctx->s_det;
     fm_trace_mark(ctx, s, 10);
-    if (frame == ctx->frame_own2 && ctx->ev_next_upload) FM_HIP(hipStreamWaitEvent(s, ctx->ev_next_upload, 0));
-    int rc = acquire_slot(d, s);
+    for (int i = 0; i < n; ++i)
+        if (uploads[i]) FM_HIP(hipStreamWaitEvent(s, uploads[i], 0));
+    int rc = acquire_slots(ctx, d, s, n);
     if (rc) return rc;
     fm_trace_mark(ctx, s, 14);
+    const StemSrc src = det_source(ctx, d, frames, n);
     // Round 6: when the network begins with a stem convolution over its input tensor, that convolution computes the
     // resized / normalised pixels itself while it stages its patch (stemconv.hip, pixel_source.h): the preprocess launch
     // (15 us inside the pipeline, between two passes of the stream whose period is the step) and the input tensor's
@@ -1323,32 +1427,34 @@ static int detect_async_on(fm_ctx* ctx, const uint8_t* frame) {
     const bool fused = ctx->opt_fused_input && fm_net_stem_fusable(net, c.input_tensor);
     // the event pair around the network is measurement, not product: two more packets on the stream whose period is the
     // step cost 1.2 % of the frame rate (profiles/r06_net_timing_events_ab.txt) -- recorded on every N-th pass only when
-    // a caller asked for it (option "net_timing" = N; bench.py samples every 4th pass)
+    // a caller asked for it (option "net_timing" = N; bench.py samples every 4th pass).  A batched pass carries them in
+    // its first image's slot.
     const bool timing = ctx->opt_net_timing > 0 && d->n_passes++ % ctx->opt_net_timing == 0;
-    d->timed[d->wr] = timing;
+    for (int i = 0; i < n; ++i) d->timed[(d->wr + i) % DetState::NSLOT] = timing && i == 0;
     if (fused) {
         if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
         fm_trace_mark(ctx, s, 11);
-        StemSrc src{};
-        src.kind = 1; src.frame = frame; src.fw = ctx->frame_w; src.fh = ctx->frame_h;
-        src.roi_x = c.roi_x; src.roi_y = c.roi_y; src.roi_w = c.roi_w; src.roi_h = c.roi_h;
-        src.zero4 = filter_args(d, d->wr).counters;
-        if ((rc = fm_net_run_stem_from(ctx, net, src, 1))) return rc;
+        if ((rc = fm_net_run_stem_from(ctx, net, src, n))) return rc;
         fm_trace_mark(ctx, s, 15);
         net->first = 1;
-        rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, 1);
+        rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n);
         net->first = 0;
         if (rc) return rc;
     } else {
-        if ((rc = enqueue_preprocess(ctx, d, net, frame))) return rc;
+        if ((rc = enqueue_preprocess(ctx, d, net, src, n))) return rc;
         if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
         fm_trace_mark(ctx, s, 11);
-        if ((rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, 1))) return rc;
+        if ((rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n))) return rc;
     }
     if (timing) FM_HIP(hipEventRecord(d->ev1[d->wr], s));
     fm_trace_mark(ctx, s, 12);
-    FilterArgs fa = filter_args(d, d->wr);      // (counters were zeroed by this frame's preprocess kernel)
+    FilterArgs fa = filter_args(d, d->wr);      // (counters were zeroed by this pass's preprocess / stem kernel)
     HeadSet hs{};
+    for (int i = 0; i < n; ++i) {
+        const int slot = (d->wr + i) % DetState::NSLOT;
+        hs.cand[i] = d->cand[slot];
+        hs.counters[i] = d->counters[slot];
+    }
     int base = 0, blocks = 0;
     for (int i = 0; i < FM_MAX_HEADS + 1; ++i) hs.first_block[i] = 0x7fffffff;
     for (int i = 0; i < c.n_heads; ++i) {
@@ -1361,15 +1467,15 @@ static int detect_async_on(fm_ctx* ctx, const uint8_t* frame) {
         h.base_index = base;
         memcpy(h.anchors, c.anchors[i], sizeof(float) * 2 * FM_MAX_ANCHORS);
         h.scale_xy = c.scale_xy[i];
-        const int n = h.gw * h.gh * h.na;
+        const int cnt = h.gw * h.gh * h.na;
         hs.first_block[i] = blocks;
-        blocks += (n + 255) / 256;
-        base += n;
+        blocks += (cnt + 255) / 256;
+        base += cnt;
     }
-    if (blocks) hipLaunchKernelGGL(decode_kernel, dim3(blocks), dim3(256), 0, s, hs, fa, c.in_w, c.in_h, c.new_coords);
+    if (blocks) hipLaunchKernelGGL(decode_kernel, dim3(blocks, n), dim3(256), 0, s, hs, fa, c.in_w, c.in_h, c.new_coords);
     FM_HIP(hipGetLastError());
     fm_trace_mark(ctx, s, 13);
-    return enqueue_post(ctx, d, s);
+    return enqueue_post(ctx, d, s, n);
 }
 
 extern "C" int fm_detect_sync(fm_ctx* ctx, fm_det48* out, int cap, int* n) {
@@ -1385,6 +1491,7 @@ extern "C" int fm_filter_dets(fm_ctx* ctx, const float* rows, int n, fm_det48* o
     FM_HIP(hipStreamSynchronize(s));
     FM_HIP(hipStreamSynchronize(ctx->s_up));
     d->post_pending = -1;
+    d->post_pending_n = 0;
     d->rd = d->wr;            // (test hook: passes nobody collected are dropped; the streams are idle here)
     d->pending = 0;
     if (n > d->rows_cap) {

@@ -107,7 +107,7 @@ static int front_end(fm_ctx* ctx, ExtState* e, NetState* ni, hipStream_t si, int
     ni->first = 0;
     if (ctx->opt_fused_input && fm_net_stem_fusable(ni, e->input_tensor)) {
         StemSrc src{};
-        src.kind = 2; src.frame = ctx->frame_cur; src.fw = ctx->frame_w; src.fh = ctx->frame_h;
+        src.kind = 2; src.frame[0] = ctx->frame_cur; src.fw = ctx->frame_w; src.fh = ctx->frame_h;
         src.boxes = e->boxes_host + (size_t)off * 4;
         int rc = fm_net_run_stem_from(ctx, ni, src, b);
         if (rc) return rc;

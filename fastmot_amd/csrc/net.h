@@ -25,6 +25,9 @@ struct ConvParams {
     int act, res_mode;
     int grid_p, grid_c, grid_z, weight_major;   // tile grid + XCD-aware order (filled by launch_conv)
     int up;                                 // 2: every output pixel is stored to its 2x2 block of a (2Ho, 2Wo) view
+    int batch_inv;                          // 1 (detector net): every choice that fixes an output's summation order is taken
+                                            // from the batch-1 geometry (P = Ho * Wo), so that a sample of a batch-N launch
+                                            // equals a batch-1 launch on it bit for bit; tile shape / grid follow the real P
 };
 
 int launch_conv(const ConvParams& p, float* ws, size_t ws_floats, hipStream_t s);

@@ -3,6 +3,7 @@
 // enqueues every layer on the network's own HIP stream; nothing synchronises until the caller
 // asks for results (detect_async/postprocess protocol of fastmot/detector.py:26-42).
 #include "pixel_source.h"
+#include <algorithm>
 #include <memory>
 
 int launch_dwconv3(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, const f16* w,
@@ -21,7 +22,7 @@ int launch_gated_sum(int nstreams, const f16* const* in, const int* in_cs, const
 constexpr int GATE_SLOT_TILES = 32;
 int launch_pair11(const f16* xa, int xa_cs, int xa_coff, const f16* xc, int xc_cs, int xc_coff, f16* out, int out_cs,
                   int out_coff, const f16* w1, const float* b1, const f16* w2, const float* b2, long P, int cout, int act1,
-                  int act2, hipStream_t s);
+                  int act2, hipStream_t s, long p_choice);
 bool pair11_supported(int cin, int mid, int extra, int cout);
 int launch_ostail(const f16* in, int in_cs, int in_coff, const f16* ph, const float* pf, int N, float* out, float* raw_out,
                   float* mirror, hipStream_t s);
@@ -140,7 +141,9 @@ extern "C" int fm_net_create(fm_ctx* ctx, int which, int max_batch, int n_tensor
     net->weight_bytes = weight_bytes;
     net->n_gates = n_gates;
     net->gate_c = gate_channels;
-    net->ws_floats = (size_t)16 << 20;   // 64 MB of fp32 split-K partials
+    // 64 MB of fp32 split-K partials; the detector net keeps its batch-1 split counts at batch N (ConvParams::batch_inv),
+    // so its partials scale with the batch
+    net->ws_floats = ((size_t)16 << 20) * (which == FM_NET_DETECTOR ? (size_t)std::min(max_batch, FM_MAX_DET_BATCH) : 1);
     FM_HIP(hipMalloc(&net->ws, net->ws_floats * sizeof(float)));
     if (n_gates > 0) {
         FM_CHECK_ARG(gate_channels > 0);
@@ -184,6 +187,7 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             p.K = L.k * L.k * L.cin; p.Kpad = (p.K + 63) & ~63; p.P = B * p.Ho * p.Wo;
             p.cout_store = (L.cout + 7) & ~7;
             p.act = L.act; p.res_mode = L.res_mode;
+            p.batch_inv = net->which == FM_NET_DETECTOR ? 1 : 0;
             FM_CHECK_ARG((ti.h + 2 * L.pad - L.k) / L.stride + 1 == p.Ho);
             FM_CHECK_ARG(L.out_coff + p.cout_store <= to.c && L.in_coff[0] + L.cin <= ti.c);
             if (L.op == FM_OP_CONVS) return launch_conv_streamed(p, s);
@@ -273,7 +277,8 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             return launch_pair11(in0, ti.c, L.in_coff[0], (const f16*)net->bufs[L.in[1]], tc.c, L.in_coff[1], out, to.c, L.out_coff,
                                  (const f16*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off),
                                  (const f16*)(net->weights + L.w2_off), (const float*)(net->weights + L.b2_off),
-                                 (long)B * ti.h * ti.w, L.cout, L.gate[0], L.act, s);
+                                 (long)B * ti.h * ti.w, L.cout, L.gate[0], L.act, s,
+                                 net->which == FM_NET_DETECTOR ? (long)ti.h * ti.w : (long)B * ti.h * ti.w);   // (tile choice: batch-1 geometry)
         }
         case FM_OP_STEM2:
             return launch_stem2_layer(L, StemSrc{}, net, B, s);

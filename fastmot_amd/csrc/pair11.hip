@@ -148,11 +148,12 @@ bool pair11_supported(int cin, int mid, int extra, int cout) { return cin == 64 
 // w1 [64 x 64], w2 [cout x 128] in MFMA A-fragment order ([cout / 32][K / 16][lane][8], Graph._pack_frag); b1 f32[64], b2 f32[cout]
 int launch_pair11(const f16* xa, int xa_cs, int xa_coff, const f16* xc, int xc_cs, int xc_coff, f16* out, int out_cs,
                   int out_coff, const f16* w1, const float* b1, const f16* w2, const float* b2, long P, int cout, int act1,
-                  int act2, hipStream_t s) {
+                  int act2, hipStream_t s, long p_choice) {
     FM_CHECK_ARG((cout == 64 || cout == 128) && xa_cs % 8 == 0 && xa_coff % 8 == 0 && xc_cs % 8 == 0 && xc_coff % 8 == 0 &&
                  out_cs % 4 == 0 && out_coff % 4 == 0 && P > 0);
-    // 128-pixel tiles where they fill the chip (>= 256 workgroups), 64-pixel tiles below
-    const bool small = P < 256 * 128;
+    // 128-pixel tiles where they fill the chip (>= 256 workgroups), 64-pixel tiles below; decided on p_choice pixels (the
+    // detector net passes one sample's: the same instance at every batch size)
+    const bool small = p_choice < 256 * 128;
 #define PAIR11_ARGS xa, xa_cs, xa_coff, xc, xc_cs, xc_coff, out, out_cs, out_coff, w1, b1, w2, b2, P, act1, act2, s
     if (cout == 64) return small ? launch_pt<64, 2>(PAIR11_ARGS) : launch_pt<64, 4>(PAIR11_ARGS);
     return small ? launch_pt<128, 2>(PAIR11_ARGS) : launch_pt<128, 4>(PAIR11_ARGS);

@@ -121,12 +121,22 @@ __device__ __forceinline__ void crop_input_pixel(const uint8_t* __restrict__ fra
 // the frame; 2: the extractor's crops of the frame.
 struct StemSrc {
     int kind;
-    const uint8_t* frame;
+    const uint8_t* frame[FM_MAX_DET_BATCH];   // kind 1: the frame of sample n (a batched detector pass); kind 2: frame[0]
     int fw, fh;
     int roi_x, roi_y, roi_w, roi_h;   // kind 1
     const double* boxes;              // kind 2: [N][4] tlbr on the device
-    int32_t* zero4;                   // optional: four int32 the launch sets to zero (the decode's candidate counters)
+    int32_t* zero4[FM_MAX_DET_BATCH]; // optional, kind 1: four int32 per sample the launch sets to zero (that image's candidate counters)
 };
+
+// a[i] for a wave-uniform i < FM_MAX_DET_BATCH (else a[0]) as a chain of selects: a dynamic index into a kernel's
+// by-value argument would copy the array to scratch memory
+template <typename T>
+__device__ __forceinline__ T pick_sample(const T (&a)[FM_MAX_DET_BATCH], int i) {
+    T r = a[0];
+#pragma unroll
+    for (int k = 1; k < FM_MAX_DET_BATCH; ++k) r = i == k ? a[k] : r;
+    return r;
+}
 
 int launch_stemconv_src(const StemSrc& src, const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff,
                         const f16* w, const float* bias, int N, int H, int W, int Ho, int Wo, int k, int stride, int pad,

@@ -39,8 +39,12 @@ __global__ __launch_bounds__(256) void stem2_kernel(const StemSrc src, const f16
     const int frow = lane & 31, fh = lane >> 5;
     const int ox0 = blockIdx.x * TO, oy0 = blockIdx.y * TO;
     const long n = blockIdx.z;
+    const uint8_t* frame1 = SRC == 1 ? pick_sample(src.frame, (int)n) : nullptr;     // (kind 1: this sample's frame)
     const int sy0 = 2 * oy0 - 1, sx0 = 2 * ox0 - 1;        // stem position of mid[0][0] (second conv: pad 1, stride 2)
-    if (SRC != 0 && src.zero4 && tid < 4 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) src.zero4[tid] = 0;
+    if (SRC == 1 && tid < 4 && blockIdx.x == 0 && blockIdx.y == 0) {     // (this sample's candidate counters)
+        int32_t* z = pick_sample(src.zero4, (int)n);
+        if (z) z[tid] = 0;
+    }
 
     // ---- phase-2 weights of this wave's accumulator tiles: taps 0..2 are requested first and consumed last, taps 3..8 are
     // requested when phase 2 begins (all 18 fragments up front held 72 VGPRs through phase 1: 144 in all, three workgroups
@@ -73,7 +77,7 @@ __global__ __launch_bounds__(256) void stem2_kernel(const StemSrc src, const f16
             v = *reinterpret_cast<const uint2*>(img + ((long)cy * W + cx) * in_cs);
         } else {
             float rgb[3];
-            det_input_pixel(src.frame, src.fw, src.fh, cx, cy, src.roi_x, src.roi_y, src.roi_w, src.roi_h, rgb);
+            det_input_pixel(frame1, src.fw, src.fh, cx, cy, src.roi_x, src.roi_y, src.roi_w, src.roi_h, rgb);
             union { f16 h[4]; uint2 u; } pk;
             pk.h[0] = (f16)rgb[0]; pk.h[1] = (f16)rgb[1]; pk.h[2] = (f16)rgb[2]; pk.h[3] = (f16)0.f;
             v = pk.u;
@@ -239,7 +243,8 @@ int launch_stem2(const StemSrc& src, const f16* in, int in_cs, f16* out, int out
                  int act2, hipStream_t s, int cout3, const f16* w3, const float* b3, int act3) {
     FM_CHECK_ARG(stem2_supported(32, cout) && in_cs % 4 == 0 && out_cs % 4 == 0 && out_coff % 4 == 0);
     FM_CHECK_ARG(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1);
-    FM_CHECK_ARG(src.kind == 0 || (src.kind == 1 && src.frame && src.fw > 0 && src.fh > 0));
+    FM_CHECK_ARG(src.kind == 0 || (src.kind == 1 && src.fw > 0 && src.fh > 0 && N <= FM_MAX_DET_BATCH));
+    for (int i = 0; src.kind == 1 && i < N; ++i) FM_CHECK_ARG(src.frame[i] != nullptr);
     FM_CHECK_ARG(cout3 == 0 || (stem3_supported(cout, cout3) && w3 && b3));
 #define STEM2_ARGS src, in, in_cs, out, out_cs, out_coff, w1, b1, w2, b2, w3, b3, N, H, W, Ho, Wo, act1, act2, act3, s
     if (cout3 == 64) return launch_cout<64, 64>(STEM2_ARGS);

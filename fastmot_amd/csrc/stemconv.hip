@@ -34,8 +34,12 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemSrc src, const
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ox0 = blockIdx.x * 16, oy0 = blockIdx.y * 16;
     const long n = blockIdx.z;
+    const uint8_t* frame1 = SRC == 1 ? pick_sample(src.frame, (int)n) : nullptr;     // (kind 1: this sample's frame)
     const f16* img = in + n * (long)H * W * in_cs + in_coff;
-    if (SRC != 0 && src.zero4 && tid < 4 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) src.zero4[tid] = 0;
+    if (SRC == 1 && tid < 4 && blockIdx.x == 0 && blockIdx.y == 0) {     // (this sample's candidate counters)
+        int32_t* z = pick_sample(src.zero4, (int)n);
+        if (z) z[tid] = 0;
+    }
     // crops: the normalisation (v / 255 - mean) / std costs two float64 divisions per channel; it is a function of the uint8
     // value alone, so the workgroup tabulates its 3 x 256 results once (crop_normalise: the values of the front-end kernel)
     __shared__ f16 norm_lut[SRC == 2 ? 3 * 256 : 2];
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemSrc src, const
             v = *reinterpret_cast<const uint2*>(img + ((long)cy * W + cx) * in_cs);
         } else if constexpr (SRC == 1) {
             float rgb[3];
-            det_input_pixel(src.frame, src.fw, src.fh, cx, cy, src.roi_x, src.roi_y, src.roi_w, src.roi_h, rgb);
+            det_input_pixel(frame1, src.fw, src.fh, cx, cy, src.roi_x, src.roi_y, src.roi_w, src.roi_h, rgb);
             union { f16 h[4]; uint2 u; } pk;
             pk.h[0] = (f16)rgb[0]; pk.h[1] = (f16)rgb[1]; pk.h[2] = (f16)rgb[2]; pk.h[3] = (f16)0.f;
             v = pk.u;
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemSrc src, const
             int bgr[3];
             union { f16 h[4]; uint2 u; } pk;
             pk.u = make_uint2(0u, 0u);
-            if (crop_u8_pixel(src.frame, src.fw, src.fh, src.boxes + n * 4, cx, cy, W, H, bgr)) {
+            if (crop_u8_pixel(src.frame[0], src.fw, src.fh, src.boxes + n * 4, cx, cy, W, H, bgr)) {
                 pk.h[0] = norm_lut[0 * 256 + bgr[2]]; pk.h[1] = norm_lut[1 * 256 + bgr[1]]; pk.h[2] = norm_lut[2 * 256 + bgr[0]];
             }
             v = pk.u;
@@ -150,7 +154,9 @@ int launch_stemconv_src(const StemSrc& src, const f16* in, int in_cs, int in_cof
                         const f16* w, const float* bias, int N, int H, int W, int Ho, int Wo, int k, int stride, int pad,
                         int cout, int act, hipStream_t s) {
     FM_CHECK_ARG(cout >= 1 && cout <= 32 && in_cs % 4 == 0 && in_coff % 4 == 0 && out_cs % 4 == 0 && out_coff % 4 == 0);
-    FM_CHECK_ARG(src.kind == 0 || (src.frame && src.fw > 0 && src.fh > 0 && (src.kind == 1 || (src.kind == 2 && src.boxes))));
+    FM_CHECK_ARG(src.kind == 0 || (src.frame[0] && src.fw > 0 && src.fh > 0 && (src.kind == 1 || (src.kind == 2 && src.boxes))));
+    FM_CHECK_ARG(src.kind != 1 || N <= FM_MAX_DET_BATCH);
+    for (int i = 0; src.kind == 1 && i < N; ++i) FM_CHECK_ARG(src.frame[i] != nullptr);
     if (src.kind == 1) return launch_stem_kind<1>(src, in, in_cs, in_coff, out, out_cs, out_coff, w, bias, N, H, W, Ho, Wo, k, stride, pad, cout, act, s);
     if (src.kind == 2) return launch_stem_kind<2>(src, in, in_cs, in_coff, out, out_cs, out_coff, w, bias, N, H, W, Ho, Wo, k, stride, pad, cout, act, s);
     return launch_stem_kind<0>(src, in, in_cs, in_coff, out, out_cs, out_coff, w, bias, N, H, W, Ho, Wo, k, stride, pad, cout, act, s);

@@ -39,12 +39,15 @@ def bind_frame(ctx, frame, size, begin_step=False):
     if not begin_step and getattr(ctx, 'in_step', False) and getattr(ctx, 'bound_frame', None) is frame:
         return
     if getattr(ctx, 'next_frame', None) is frame:
-        # the frame was prefetched (prefetch_frame): it is already on the device
+        # the frame was prefetched (prefetch_frame / prefetch_frames): it is already on the device; the frames announced
+        # further ahead move up one look-ahead slot with it
         ctx.frame_promote_next()
-        ctx.next_frame = None
+        ahead = getattr(ctx, 'ahead_frames', None) or []
+        ctx.next_frame, ctx.ahead_frames = (ahead[0], ahead[1:]) if ahead else (None, [])
         ctx.bound_frame = frame
         return
     ctx.next_frame = None
+    ctx.ahead_frames = []
     if isinstance(frame, DeviceFrame):
         ctx.frame_ring_select(frame.index)
     else:
@@ -62,6 +65,20 @@ def prefetch_frame(ctx, frame, size):
     else:
         ctx.frame_upload_next(frame)
     ctx.next_frame = frame
+    ctx.ahead_frames = []
+
+
+def prefetch_frames(ctx, frames, size):
+    """prefetch_frame for the frames of the next len(frames) steps: frame k - 1 goes to look-ahead slot k; each following
+    bind_frame promotes the next of them."""
+    if getattr(ctx, 'frame_size', None) != tuple(size):
+        ctx.frame_configure(size[0], size[1], getattr(ctx, 'ring_size', 0))
+    for k, frame in enumerate(frames, 1):
+        if isinstance(frame, DeviceFrame):
+            ctx.frame_ring_select_ahead(k, frame.index)
+        else:
+            ctx.frame_upload_ahead(k, frame)
+    ctx.next_frame, ctx.ahead_frames = frames[0], list(frames[1:])
 
 
 class Detector(abc.ABC):
@@ -81,6 +98,11 @@ class Detector(abc.ABC):
     def prefetch(self, frame):
         """Optional: start detecting on the NEXT frame while the current one is still being tracked
         (MOT.step(frame, next_frame)).  The following detect_async(frame) is then a no-op."""
+
+    def prefetch_batch(self, frames):
+        """Optional: start detecting on the frames of the next len(frames) steps (MOT detector look-ahead); each of the
+        following detect_async calls with these frames, in order, is then a no-op.  Default: prefetch the first."""
+        self.prefetch(frames[0])
 
     @abc.abstractmethod
     def postprocess(self):
@@ -258,10 +280,12 @@ class YOLODetector(Detector):
                  min_aspect_ratio=1.2,
                  weights=None,
                  max_candidates=8192,
-                 reuse_buffers=True):
+                 reuse_buffers=True,
+                 max_batch=1):
         """An object detector for YOLO models; parameters as fastmot/detector.py:221-253
         (`weights`: optional weight source for the layer table, default seeded random;
-        `max_candidates`: capacity of the on-device candidate list)."""
+        `max_candidates`: capacity of the on-device candidate list; `max_batch`: frames one network pass may take,
+        detect_batch / prefetch_batch, at most FM_MAX_DET_BATCH)."""
         super().__init__(size)
         self.model = models.YOLO.get_model(model)
         assert 0 <= conf_thresh <= 1
@@ -279,10 +303,13 @@ class YOLODetector(Detector):
         except IndexError as err:
             raise ValueError('Unsupported class IDs') from err
 
+        if not 1 <= max_batch <= _lib.FM_MAX_DET_BATCH:
+            raise ValueError(f'max_batch must be 1..{_lib.FM_MAX_DET_BATCH}')
+        self.max_batch = max_batch
         self.ctx = get_context()
-        self._prefetched = None
+        self._announced = []                    # frames whose passes prefetch / prefetch_batch enqueued, in order
         self.graph, self.heads = self.model.build_graph(weights)
-        self.backend = HipNet(self.ctx, NET_DETECTOR, self.graph, 1, reuse_buffers=reuse_buffers)
+        self.backend = HipNet(self.ctx, NET_DETECTOR, self.graph, max_batch, reuse_buffers=reuse_buffers)
         self.roi, self.upscaled_sz, self.bbox_offset = self._create_letterbox()
         self._configure(max_candidates)
 
@@ -333,22 +360,60 @@ class YOLODetector(Detector):
 
     def detect_async(self, frame):
         """Detects objects asynchronously (preprocess + network + decode + NMS enqueued)."""
-        if self._prefetched is frame and frame is not None:
-            self._prefetched = None              # already enqueued by prefetch()
+        if self._announced and self._announced[0] is frame and frame is not None:
+            self._announced.pop(0)              # already enqueued by prefetch() / prefetch_batch()
             bind_frame(self.ctx, frame, self.size)
             return
-        if self._prefetched is not None:
-            # the caller announced another frame than the one it passes now: collect and drop that pass, so that
-            # postprocess() returns THIS frame's detections (passes are collected in the order they were enqueued)
-            self._prefetched = None
-            self.ctx.detect_sync()
+        self._drop_announced()
         bind_frame(self.ctx, frame, self.size)
         self.ctx.detect_async()
+
+    def _drop_announced(self):
+        # the caller announced other frames than the one it passes now: collect and drop their results, so that
+        # postprocess() returns THIS frame's detections (frames are collected in the order they were enqueued)
+        announced, self._announced = self._announced, []
+        for _ in announced:
+            self.ctx.detect_sync()
 
     def prefetch(self, frame):
         prefetch_frame(self.ctx, frame, self.size)
         self.ctx.detect_async_next()
-        self._prefetched = frame
+        self._announced = [frame]
+
+    def prefetch_batch(self, frames):
+        """One network pass at batch len(frames) <= max_batch over the frames of the next steps (fm_detect_async_ahead)."""
+        frames = list(frames)
+        if len(frames) == 1:
+            return self.prefetch(frames[0])
+        if not 1 <= len(frames) <= self.max_batch:
+            raise ValueError(f'{len(frames)} frames for a detector of max_batch {self.max_batch}')
+        prefetch_frames(self.ctx, frames, self.size)
+        self.ctx.detect_async_ahead(len(frames))
+        self._announced = frames
+
+    def detect_batch(self, frames):
+        """Detects objects on every frame (ndarrays or DeviceFrames) synchronously, max_batch frames per network pass;
+        returns one record array per frame, each equal to what detect_async + postprocess return for that frame."""
+        self._drop_announced()
+        frames = list(frames)
+        out = []
+        try:
+            for i in range(0, len(frames), self.max_batch):
+                part = frames[i:i + self.max_batch]
+                prefetch_frames(self.ctx, part, self.size)
+                self.ctx.detect_async_ahead(len(part))
+                err = None
+                for _ in part:          # (every frame of the pass is collected, an error is raised after the last)
+                    try:
+                        out.append(self.ctx.detect_sync())
+                    except _lib.FastMOTHipError as e:
+                        err = err or e
+                if err is not None:
+                    raise err
+        finally:
+            # (the frames stay in their look-ahead slots, but no step announced them)
+            self.ctx.next_frame, self.ctx.ahead_frames = None, []
+        return out
 
     def postprocess(self):
         """Synchronizes and returns a record array of detections (DET_DTYPE), sorted in ascending

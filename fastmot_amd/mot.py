@@ -11,6 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from . import _lib
 from .detector import SSDDetector, YOLODetector, PublicDetector, bind_frame
 from .feature_extractor import FeatureExtractor
 from .tracker import MultiTracker
@@ -36,6 +37,32 @@ class _NativeFlowJob:
                 self._tracker.predict_finish(job)
 
 
+class DetectorLookahead:
+    """Schedule of the detector look-ahead (MOT(detector_lookahead=k)): which upcoming frames a step hands to the
+    detector as one batched pass.  A pass over frames t+1..t+k starts whenever none of the frames announced before is
+    still to come; near the end of a sequence the batch is what is left.  A step whose frame is not the next announced
+    one makes the announced frames stale (the detector drops their results)."""
+
+    def __init__(self, k):
+        self.k = k
+        self.announced = []
+
+    def consume(self, frame):
+        """Called with the frame of each step; True when its detector pass was announced (already enqueued)."""
+        if self.announced and self.announced[0] is frame:
+            self.announced.pop(0)
+            return True
+        self.announced = []
+        return False
+
+    def to_enqueue(self, upcoming):
+        """The frames (of `upcoming`, the next frames in order) to start one pass on in this step, or []."""
+        if self.announced or not upcoming:
+            return []
+        self.announced = list(upcoming[:self.k])
+        return list(self.announced)
+
+
 class DetectorType(Enum):
     SSD = 0
     YOLO = 1
@@ -53,13 +80,25 @@ class MOT:
                  feature_extractor_cfgs=None,
                  tracker_cfg=None,
                  visualizer_cfg=None,
-                 draw=False):
+                 draw=False,
+                 detector_lookahead=1):
         """Top level module that integrates detection, feature extraction and tracking
         (parameters: fastmot/mot.py:37-67).  `draw=True` renders the overlays of `visualizer_cfg` onto every
-        frame handed to `step` as a host ndarray, in place, after tracking (mot.py:166-167,191-196)."""
+        frame handed to `step` as a host ndarray, in place, after tracking (mot.py:166-167,191-196).
+        `detector_lookahead=k` (not in the reference; YOLO with detector_frame_skip 1 only): the detector runs one
+        network pass over the next k frames handed to `step` as `next_frames` (DetectorLookahead); results unchanged."""
         self.size = size
         self.detector_type = DetectorType[detector_type.upper()]
         assert detector_frame_skip >= 1
+        if detector_lookahead != 1:
+            if not 1 <= detector_lookahead <= _lib.FM_MAX_DET_BATCH:
+                raise ValueError(f'detector_lookahead must be 1..{_lib.FM_MAX_DET_BATCH}')
+            if self.detector_type != DetectorType.YOLO:
+                raise ValueError('detector_lookahead > 1 needs the YOLO detector')
+            if detector_frame_skip != 1:
+                raise ValueError('detector_lookahead > 1 needs detector_frame_skip == 1')
+        self.detector_lookahead = detector_lookahead
+        self._lookahead = DetectorLookahead(detector_lookahead)
         self.detector_frame_skip = detector_frame_skip
         self.class_ids = tuple(np.unique(class_ids))
         self.draw = draw
@@ -84,7 +123,8 @@ class MOT:
         if self.detector_type == DetectorType.SSD:
             self.detector = SSDDetector(self.size, self.class_ids, **vars(ssd_detector_cfg))
         elif self.detector_type == DetectorType.YOLO:
-            self.detector = YOLODetector(self.size, self.class_ids, **vars(yolo_detector_cfg))
+            extra = {'max_batch': detector_lookahead} if detector_lookahead > 1 else {}
+            self.detector = YOLODetector(self.size, self.class_ids, **vars(yolo_detector_cfg), **extra)
         elif self.detector_type == DetectorType.PUBLIC:
             self.detector = PublicDetector(self.size, self.class_ids, self.detector_frame_skip,
                                            **vars(public_detector_cfg))
@@ -95,6 +135,7 @@ class MOT:
         self.tracker = MultiTracker(self.size, self.extractors[0].metric, **vars(tracker_cfg))
         self.frame_count = 0
         self._next_frame = None
+        self._next_frames = []
         # KLT + Kalman run on a second host thread while this one drives detector -> ReID network (the
         # C-ABI calls release the GIL; the stages use separate HIP streams and share no state)
         self._flow_thread = ThreadPoolExecutor(max_workers=1, thread_name_prefix='fastmot-flow',
@@ -110,28 +151,46 @@ class MOT:
         self.frame_count = 0
         self.tracker.reset(cap_dt)
 
-    def step(self, frame, next_frame=None):
+    def step(self, frame, next_frame=None, next_frames=None):
         """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, or a
         detector.DeviceFrame that is already resident on the GPU).
 
         next_frame (optional, not in the reference): the frame the following `step` will receive, when
         the caller already has it (file sources, a capture queue).  The detector network is then started
         on it right behind this frame's own pass, so that it overlaps this frame's KLT, ReID and association
-        stages; results are unchanged (the detector is stateless), per-frame latency too."""
+        stages; results are unchanged (the detector is stateless), per-frame latency too.
+        next_frames (optional): the frames of the following steps in order (next_frame = next_frames[0]); with
+        detector_lookahead = k the detector takes up to k of them in one network pass."""
         ctx = self.tracker.ctx
         bind_frame(ctx, frame, self.size, begin_step=True)
         ctx.in_step = True
+        if next_frames is not None:
+            next_frames = list(next_frames)
+            if next_frame is None and next_frames:
+                next_frame = next_frames[0]
         self._next_frame = next_frame
+        self._next_frames = next_frames if next_frames is not None else ([] if next_frame is None else [next_frame])
+        if self.detector_lookahead > 1:
+            self._lookahead.consume(frame)
         try:
             self._step(frame)
         finally:
             ctx.in_step = False
             self._next_frame = None
+            self._next_frames = []
         if self.draw:
             self._draw(frame, self._last_detections)
         self.frame_count += 1
 
     def _prefetch_next(self):
+        if self.detector_lookahead > 1:
+            batch = self._lookahead.to_enqueue(self._next_frames)
+            self._next_frame, self._next_frames = None, []
+            if len(batch) > 1:
+                self.detector.prefetch_batch(batch)
+            elif batch:
+                self.detector.prefetch(batch[0])
+            return
         nxt = self._next_frame
         if nxt is not None and (self.frame_count + 1) % self.detector_frame_skip == 0:
             self._next_frame = None

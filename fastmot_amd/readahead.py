@@ -5,23 +5,32 @@ tests/test_dropin_app.py) and its loop calls `mot.step(frame)`.  A caller that a
 file source, the capture queue of VideoIO) can hand it over as `next_frame`: the detector pass of frame t+1 then
 overlaps the ReID / association stages of frame t, with identical results.  This function is
 that loop; everything around it (arguments, configuration file, logging) is the reference's."""
+from collections import deque
+
 from .utils.motchallenge import write_rows
 
 
-def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False):
+def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False, lookahead=1):
     """stream: a started VideoIO; mot: a reset MOT (None: frames are only passed through); txt: an open text file for
     MOT Challenge result rows (app.py:91-97), needs `resize_to`; write_frames: stream.write(frame) after each step
-    (the frame carries the overlays when the MOT draws).  Returns the number of frames."""
+    (the frame carries the overlays when the MOT draws); lookahead: upcoming frames read ahead and handed to each step
+    as `next_frames` (a MOT with detector_lookahead = k batches up to k of them).  Returns the number of frames."""
     n = 0
     frame = stream.read()
+    upcoming = deque()
     while frame is not None:
-        upcoming = stream.read()
+        while len(upcoming) < max(lookahead, 1) and (not upcoming or upcoming[-1] is not None):
+            upcoming.append(stream.read())
+        ahead = [f for f in upcoming if f is not None]
         if mot is not None:
-            mot.step(frame, next_frame=upcoming)
+            if lookahead > 1:
+                mot.step(frame, next_frames=ahead)
+            else:
+                mot.step(frame, next_frame=upcoming[0])
             if txt is not None:
                 write_rows(txt, mot.frame_count, mot.visible_tracks(), resize_to, stream.resolution)
         if write_frames:
             stream.write(frame)
-        frame = upcoming
+        frame = upcoming.popleft()
         n += 1
     return n

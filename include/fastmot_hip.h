@@ -377,8 +377,25 @@ int fm_host_free(void* p);
  * frame; fm_frame_promote_next makes it the current frame of the next step without another upload. */
 int fm_frame_upload_next(fm_ctx* ctx, const uint8_t* bgr);
 int fm_frame_ring_select_next(fm_ctx* ctx, int index);
+/* Promotes the frame of look-ahead slot 1 to the current frame and moves slot k to k - 1 (k = 2..FM_MAX_DET_BATCH). */
 int fm_frame_promote_next(fm_ctx* ctx);
 int fm_detect_async_next(fm_ctx* ctx);
+/* Detector look-ahead over several frames (no counterpart in the reference).  Slot k (1 <= k <= FM_MAX_DET_BATCH) holds
+ * the frame that the step k steps ahead will receive; k = 1 is the slot of fm_frame_upload_next /
+ * fm_frame_ring_select_next, and the two calls below with k = 1 are exactly those.
+ * fm_frame_upload_ahead copies a host frame into upload slot k (asynchronously, on the ReID stream; one completion
+ * event per slot).  Slots k >= 2 and their page-locked staging buffers are allocated on first use.
+ * fm_frame_ring_select_ahead points slot k at a resident ring frame. */
+#define FM_MAX_DET_BATCH 4
+int fm_frame_upload_ahead(fm_ctx* ctx, int k, const uint8_t* bgr);
+int fm_frame_ring_select_ahead(fm_ctx* ctx, int k, int index);
+/* One detector network pass at batch n over the frames of look-ahead slots 1..n, then decode, sort, NMS and box
+ * filters for each image on its own.  Queues n results: each following fm_detect_sync returns one frame's detections,
+ * in frame order.  Every image's head tensors equal those of a batch-1 pass over that frame bit for bit (the detector
+ * network takes every reduction-order choice from the batch-1 geometry).  n = 1 is fm_detect_async_next.
+ * FM_ERR_ARG when n exceeds the detector network's max_batch or a slot 1..n holds no frame.  A candidate-list
+ * overflow is reported by the fm_detect_sync of the frame that overflowed. */
+int fm_detect_async_ahead(fm_ctx* ctx, int n);
 int fm_frame_ring_store(fm_ctx* ctx, int index, const uint8_t* bgr);
 int fm_frame_ring_select(fm_ctx* ctx, int index);
 int fm_frame_read(fm_ctx* ctx, uint8_t* bgr);   /* current device frame -> host (tests) */
@@ -426,7 +443,8 @@ int fm_detect_preprocess_only(fm_ctx* ctx);
 int fm_filter_dets(fm_ctx* ctx, const float* rows, int n, fm_det48* out, int cap, int* n_out);
 int fm_detect_raw_candidates(fm_ctx* ctx, float* rows, int cap, int* n);
 /* HIP-event duration (ms) of the network launches of the pass fm_detect_sync collected last, recorded on the detector
- * stream (the bench's live roofline measurement); -1 when that pass carried no events (option "net_timing") */
+ * stream (the bench's live roofline measurement); -1 when that pass carried no events (option "net_timing").  A batch
+ * pass (fm_detect_async_ahead) reports its duration on the collect of its first frame and -1 on the others. */
 int fm_detect_net_ms(fm_ctx* ctx, float* ms);
 
 /* ---------------------------------------------------------------- feature extractor --- */
