@@ -137,6 +137,10 @@ def yolov4_graph(model, weights):
         return g.conv(name(), x, cout, k, stride, act, **kw)
 
     merge_siblings = os.environ.get('FASTMOT_CSP_MERGE', '1') != '0'
+    if not merge_siblings:
+        # unmerged, the first stage's stride-2 conv has TWO readers (both sibling 1x1 convs): it cannot disappear into the
+        # three-stage stem launch, which stores only the first sibling's output (Graph.check_fusions refused such a table)
+        g.use_stem3 = False
 
     def csp(x, c_out, n_res, h, m):
         d = conv(x, c_out, 3, 2)

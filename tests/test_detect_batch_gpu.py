@@ -26,15 +26,20 @@ def _same(a, b):
     np.testing.assert_array_equal(a.conf, b.conf)
 
 
-@pytest.mark.parametrize('model', ['TinyYOLO', 'TinyLetterbox', 'YOLOv4_608', 'YOLOv4CSP_640'])
+@pytest.mark.parametrize('model', ['TinyYOLO', 'TinyLetterbox', 'YOLOv4_608', 'YOLOv4CSP_640', 'YOLOv4P6_1280'])
 def test_batch_heads_equal_batch1(ctx, model):
+    """Heads of a batched pass == heads of batch-1 passes, bit for bit.  YOLOv4-P6 @ 1280 (config[4]): 4K frames,
+    max_batch 2, the default option combination only (its batch-1 pass is compared with the reference, tensor by tensor
+    and layer by layer, in test_fullsize_gpu.py)."""
     full = model.startswith('YOLOv4')
-    size = (1920, 1080) if full else (320, 180)
+    p6 = model == 'YOLOv4P6_1280'
+    size = (3840, 2160) if p6 else (1920, 1080) if full else (320, 180)
+    max_batch = 2 if p6 else 3
     det = YOLODetector(size, (0, 1, 2), model=model, conf_thresh=0.1, nms_thresh=0.5, weights=RandomWeights(seed=4),
-                       max_candidates=65536, reuse_buffers=False, max_batch=3)
-    frames = _frames(size, 3)
+                       max_candidates=65536, reuse_buffers=False, max_batch=max_batch)
+    frames = _frames(size, max_batch)
     # (full-size models: one of the two stem paths with graphs off, to bound the suite's time)
-    cases = [(1, 1), (0, 1), (1, 0)] if full else [(1, 1), (0, 1), (1, 0), (0, 0)]
+    cases = [(1, 1)] if p6 else [(1, 1), (0, 1), (1, 0)] if full else [(1, 1), (0, 1), (1, 0), (0, 0)]
     try:
         for fused, graphs in cases:
             ctx.set_option('fused_input', fused)
@@ -43,7 +48,7 @@ def test_batch_heads_equal_batch1(ctx, model):
             for f in frames:
                 det(f)
                 ref.append([det.backend.read(h, 1)[0] for h in det.heads])
-            for n in (2, 3):
+            for n in range(2, max_batch + 1):
                 det.detect_batch(frames[:n])
                 for h_i, h in enumerate(det.heads):
                     got = det.backend.read(h, n)
@@ -52,7 +57,7 @@ def test_batch_heads_equal_batch1(ctx, model):
     finally:
         ctx.set_option('fused_input', 1)
         ctx.set_option('use_graphs', 1)
-    if model == 'YOLOv4_608':
+    if model in ('YOLOv4_608', 'YOLOv4P6_1280'):
         assert det.graph.layers[0]['op'] in (12, 18)          # the fused stem really ran on the fused path
 
 

@@ -252,12 +252,13 @@ def test_reid_split_batches_identical(ctx):
         np.testing.assert_array_equal(embs[4, n], embs[1, n])
 
 
-@pytest.mark.parametrize('model', ['TinyYOLO', 'TinyLetterbox', 'YOLOv4_608'])
+@pytest.mark.parametrize('model', ['TinyYOLO', 'TinyLetterbox', 'YOLOv4_608', 'YOLOv4CSP_640', 'YOLOv4P6_1280'])
 def test_fused_input_stem_equals_preprocess_kernel(ctx, model):
     """Round 6: the detector's stem convolution computes the resized / normalised input pixels itself (fm_ctx option
     "fused_input", default 1; stemconv.hip + pixel_source.h) instead of reading the tensor preprocess_kernel wrote.
-    Same pixel function on both paths: every head tensor and the detections are equal bit for bit."""
-    size = (1920, 1080) if model == 'YOLOv4_608' else (320, 180)
+    Same pixel function on both paths: every head tensor and the detections are equal bit for bit.  The three benchmark
+    geometries: 1080p -> 608^2 (stretched), 1080p -> 640^2 (letterboxed), 4K -> 1280^2 (the three-stage stem)."""
+    size = {'YOLOv4_608': (1920, 1080), 'YOLOv4CSP_640': (1920, 1080), 'YOLOv4P6_1280': (3840, 2160)}.get(model, (320, 180))
     det = YOLODetector(size, (0, 1, 2), model=model, conf_thresh=0.1, nms_thresh=0.5, weights=RandomWeights(seed=4),
                        max_candidates=65536, reuse_buffers=False)
     frame = synthetic_frame(*size, seed=11)
@@ -272,6 +273,10 @@ def test_fused_input_stem_equals_preprocess_kernel(ctx, model):
     finally:
         ctx.set_option('fused_input', 1)
     assert det.graph.layers[0]['op'] in (12, 18)                # FM_OP_STEMCONV / FM_OP_STEM2: the fused path really is in use
+    if model == 'YOLOv4CSP_640':
+        assert YOLO.get_model(model).LETTERBOX
+    if model in ('YOLOv4CSP_640', 'YOLOv4P6_1280'):             # the benchmark tables start with the fused stem launch
+        assert det.graph.layers[0]['op'] == 18 and (model != 'YOLOv4P6_1280' or 'stem3_ref' in det.graph.layers[0])
     for dets, heads, stem in outs[1][1:] + outs[0]:
         ref = outs[1][0]
         np.testing.assert_array_equal(stem, ref[2])

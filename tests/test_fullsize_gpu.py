@@ -11,6 +11,8 @@ to fp16 at the same points as the engine stores them).  Tolerances (stated in DE
 KLT oracle: oracle/cv_oracle.py (OpenCV algorithms restated): keypoints (GFTT, FAST and the LK-tracked points),
 status / inlier flags, per-track result codes and rounded boxes IDENTICAL; homography rtol 1e-6 (double precision
 Jacobi / Levenberg-Marquardt on the host vs numpy)."""
+import copy
+
 import numpy as np
 import pytest
 import torch
@@ -21,7 +23,7 @@ import scenes
 import torch_ref
 from fastmot_amd.engine import HipNet, NET_DETECTOR, NET_EXTRACTOR
 from fastmot_amd.models import YOLO, ReID
-from fastmot_amd.models.graph import RandomWeights, View
+from fastmot_amd.models.graph import CONV_OPS, RandomWeights, View
 
 pytestmark = pytest.mark.gpu
 
@@ -44,30 +46,119 @@ def check_tensor(gpu, ref, what):
     return err.max() / max(np.abs(ref).max(), 1e-12), rms_err / max(rms_ref, 1e-12)
 
 
+def _device_tensors(net, g, batch, tids=None):
+    """tid -> torch view [N, cpad, h, w] of what the device holds (fp16 tensors stay fp16: lossless, half the host memory)."""
+    out = {}
+    for tid, (h, w, c, f32) in enumerate(g.tensors):
+        if tids is None or tid in tids:
+            a = net.read(_whole(g, tid), batch)
+            out[tid] = torch.from_numpy(a if f32 else a.astype(np.float16)).permute(0, 3, 1, 2)
+    return out
+
+
+class _Forced:
+    """The tensors layer `i` of a finished run saw: the final state, except for tensors a later layer overwrote in place
+    (torch_ref.clobbers: the merged CSP stages) -- those come from a run of the table cut before the overwriting layer."""
+
+    def __init__(self, final, snaps):
+        self.final, self.snaps, self.i = final, snaps, 0       # snaps: [(layer index L, tid, tensor before layer L ran)]
+
+    def __getitem__(self, tid):
+        later = [(L, t) for L, st, t in self.snaps if st == tid and L > self.i]
+        return min(later, key=lambda p: p[0])[1] if later else self.final[tid]
+
+
+def _every_tensor_and_every_layer(ctx, which, g, x, batch, label, heads=()):
+    """(1) the whole table against torch_ref.run_graph, every written tensor and every head view, with the whole-tensor
+    bar; (2) every layer against torch_ref.run_layer (float64, S in float64 too) fed with the tensors THE DEVICE produced
+    for that layer's inputs, with the derived per-element bound of DESIGN.md section 7.  -> device embeddings / None."""
+    torch.set_num_threads(max(torch.get_num_threads(), 8))
+    net = HipNet(ctx, which, g, batch, reuse_buffers=False)
+    net.write(g.input, x)
+    net.run(batch)
+    final = _device_tensors(net, g, batch)
+    emb = net.read_embeddings(batch) if which != NET_DETECTOR else None
+    head_views = [net.read(hd, batch) for hd in heads]
+    net.close()
+    snaps = []
+    for L, tid in torch_ref.clobbers(g):
+        cut = copy.copy(g)
+        cut.layers = g.layers[:L]
+        net = HipNet(ctx, which, cut, batch, reuse_buffers=False)
+        net.write(g.input, x)
+        net.run(batch)
+        snaps.append((L, tid, _device_tensors(net, g, batch, {tid})[tid]))
+        net.close()
+    # (1) whole network, whole-tensor bar
+    bufs, ref_emb = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
+    # the conv kernels write ceil8(cout) channels (net.h: cout_store), the padding ones from zero weights and zero bias:
+    # act(0), which is 0 for every activation but the logistic one (the 255- / 340-channel NEW_COORDS heads: 0.5)
+    for d in g.layers:
+        o = d['out']
+        if d['op'] in CONV_OPS and o.c % 8:
+            bufs[o.tid][:, o.coff + o.c:o.coff + o.cpad] = torch_ref.act_fn(torch.zeros(()), d['act'])
+    worst = (-1.0, -1)
+    written = sorted({d['out'].tid for d in g.layers if d.get('out') is not None})
+    for tid in written:
+        h, w, c, f32 = g.tensors[tid]
+        ref = bufs.pop(tid).numpy().transpose(0, 2, 3, 1)
+        rel, rms = check_tensor(final[tid].permute(0, 2, 3, 1).float().numpy(), ref, f'{label} tensor {tid} ({h}x{w}x{c})')
+        worst = max(worst, (rel, tid))
+        for i, hd in enumerate(heads):
+            if hd.tid == tid:
+                check_tensor(head_views[i], ref[..., hd.coff:hd.coff + hd.c], f'{label} head {i}')
+    del bufs
+    print(f'{label}: {len(written)} tensors, worst max-err/max {worst[0]:.2e} (tensor {worst[1]})')
+    # (2) layer by layer on the device's own inputs, per-element bound
+    forced, gates, ratios = _Forced(final, snaps), {}, {}
+    for i, d in enumerate(g.layers):
+        forced.i = i
+        kind, ref, bound = torch_ref.run_layer(g, i, forced, gates=gates)
+        if kind == 'gate':
+            continue
+        o = d['out']
+        got = emb if kind == 'emb' else forced[o.tid][:, o.coff:o.coff + o.c]
+        op = torch_ref.OP_NAMES[d['op']] + ('/3' if 'stem3_ref' in d else '')
+        r = torch_ref.check_layer(got, ref, bound, f'{label} layer {i} {op} {d.get("name", "")} k{d["k"]} s{d["stride"]} '
+                                                   f'cin {d["cin"]} cout {d["cout"]}')
+        ratios[op] = max(ratios.get(op, 0.0), r)
+    for op, r in sorted(ratios.items()):
+        print(f'LAYERBOUND {label:24s} {op:14s} worst err/bound {r:.3g}')
+    return emb, ref_emb
+
+
+def _detector_every_tensor(ctx, name):
+    model = YOLO.get_model(name)
+    g, heads = model.build_graph(RandomWeights(seed=31))
+    _, H, W = model.INPUT_SHAPE
+    x = np.random.default_rng(32).uniform(0, 1, (1, H, W, 3)).astype(np.float16)
+    _every_tensor_and_every_layer(ctx, NET_DETECTOR, g, x, 1, name, heads)
+    return g
+
+
 def test_yolov4_608_every_tensor(ctx):
     """BASELINE config[1] detector: all 3 heads AND every intermediate tensor of the 608x608 / 80-class graph
-    (fused residual units, streamed 19x19 / 38x38 convs, stem, SPP, upsample-in-epilogue, in-place concats)."""
-    torch.set_num_threads(max(torch.get_num_threads(), 8))
-    model = YOLO.get_model('YOLOv4_608')
-    g, heads = model.build_graph(RandomWeights(seed=31))
-    net = HipNet(ctx, NET_DETECTOR, g, 1, reuse_buffers=False)
-    rng = np.random.default_rng(32)
-    x = rng.uniform(0, 1, (1, 608, 608, 3)).astype(np.float16)
-    net.write(g.input, x)
-    net.run(1)
-    bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
-    worst = (0, None)
-    written = {d['out'].tid for d in g.layers}
-    for tid in sorted(written):
-        h, w, c, f32 = g.tensors[tid]
-        full = net.read(_whole(g, tid), 1)
-        ref = bufs[tid].numpy().transpose(0, 2, 3, 1)
-        rel, rms = check_tensor(full, ref, f'tensor {tid} ({h}x{w}x{c})')
-        worst = max(worst, (rel, tid))
-    for i, hd in enumerate(heads):
-        check_tensor(net.read(hd, 1), bufs[hd.tid][:, hd.coff:hd.coff + hd.c].numpy().transpose(0, 2, 3, 1), f'head {i}')
-    print(f'YOLOv4@608: {len(written)} tensors, worst max-err/max {worst[0]:.2e} (tensor {worst[1]})')
-    net.close()
+    (fused residual units, streamed 19x19 / 38x38 convs, stem, SPP, upsample-in-epilogue, in-place concats), and every
+    layer on its own from the device's inputs."""
+    _detector_every_tensor(ctx, 'YOLOv4_608')
+
+
+@pytest.mark.parametrize('name', ['YOLOv4CSP_640', 'YOLOv4P6_1280'])
+def test_scaled_yolov4_every_tensor(ctx, name):
+    """The detectors of BASELINE config[2] (91 layers) and config[4] (194 layers; DMA-fed convs on 640^2 .. 80^2 maps,
+    the three-stage stem at 1280^2, four 340-channel heads) at their own input size: the per-layer kernel, tile and
+    K-split SELECTION of Graph / net.hip at full size and the full-size edge geometry, not only the kernel instances."""
+    g = _detector_every_tensor(ctx, name)
+    assert len(g.layers) == {'YOLOv4CSP_640': 91, 'YOLOv4P6_1280': 194}[name]
+
+
+def test_yolov4_608_unmerged_csp_every_tensor(ctx, monkeypatch):
+    """FASTMOT_CSP_MERGE=0: the CSP stages' two sibling 1x1 convs as separate layers -- another table, same checks."""
+    merged = len(YOLO.get_model('YOLOv4_608').build_graph(RandomWeights(seed=31))[0].layers)
+    monkeypatch.setenv('FASTMOT_CSP_MERGE', '0')
+    g = _detector_every_tensor(ctx, 'YOLOv4_608')
+    # one more layer per CSP stage, and the first stage's pointwise conv no longer is the stem launch's third stage
+    assert len(g.layers) == merged + 6, (len(g.layers), merged)
 
 
 def _whole(g, tid):
@@ -76,29 +167,21 @@ def _whole(g, tid):
     return View(tid, 0, c, h, w)
 
 
-@pytest.mark.parametrize('model,batch', [('OSNet025', 50), ('OSNet10', 16)])
+@pytest.mark.parametrize('model,batch', [('OSNet025', 50), ('OSNet10', 16), ('OSNet10', 50)])
 def test_osnet_256x128_embeddings_and_tensors(ctx, model, batch):
     """OSNet at its real input size: x0.25 at the 50-crop batch of config[1], x1.0 (config[2], 12x the FLOPs,
-    per-depth grouped LightConv launches where the chain kernel's LDS budget is exceeded) at batch 16."""
-    torch.set_num_threads(max(torch.get_num_threads(), 8))
+    per-depth grouped LightConv launches where the chain kernel's LDS budget is exceeded) at batch 16 and at the 50 crops
+    config[2] runs it on.  Every tensor (whole-tensor bar), every layer (per-element bound), the embeddings."""
     cls = ReID.get_model(model)
     g, _ = cls.build_graph(RandomWeights(seed=41))
     ctx.feat_configure(512)
-    net = HipNet(ctx, NET_EXTRACTOR, g, batch, reuse_buffers=False)
     rng = np.random.default_rng(42)
     x = rng.normal(0, 1, (batch, 256, 128, 3)).astype(np.float16)
-    net.write(g.input, x)
-    net.run(batch)
-    emb = net.read_embeddings(batch)
-    bufs, ref = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
+    emb, ref = _every_tensor_and_every_layer(ctx, NET_EXTRACTOR, g, x, batch, f'{model} x{batch}')
     ref = ref.numpy()
     np.testing.assert_allclose(np.linalg.norm(emb, axis=1), 1.0, atol=1e-5)
-    for tid in sorted({d['out'].tid for d in g.layers if d.get('out') is not None}):
-        h, w, c, _ = g.tensors[tid]
-        check_tensor(net.read(_whole(g, tid), batch), bufs[tid].numpy().transpose(0, 2, 3, 1), f'{model} tensor {tid} ({h}x{w}x{c})')
     assert np.abs(emb - ref).max() <= 4e-3, np.abs(emb - ref).max()
     assert (np.sum(emb * ref, axis=1) >= 0.99999).all(), np.sum(emb * ref, axis=1).min()
-    net.close()
 
 
 def test_feature_extractor_batch_64_two_instances(ctx):

@@ -49,3 +49,27 @@ def test_descriptor_table_equals_the_cfg_interpreter(name, n_heads):
         assert got.shape == r.shape
         err = (got - r).abs().max().item()
         assert err <= 1e-2 * r.abs().max().item() + 1e-3, f'{name} stride {stride}: {err}'    # fp16-rounded weights only
+
+
+def test_unmerged_csp_table_builds_and_equals_the_merged_one(monkeypatch):
+    """FASTMOT_CSP_MERGE=0 (sibling 1x1 convs of a CSP stage as separate layers): the table passes Graph.tables() -- it did
+    not while the first sibling was taken for the third stage of the stem launch, whose input the second one still reads --
+    and computes what the merged table computes."""
+    base = YOLO.get_model('YOLOv4_608')
+
+    class Quarter(base):
+        INPUT_SHAPE = (3, 160, 160)
+        MODEL_PATH = None
+
+    from fastmot_amd.models.graph import RandomWeights
+    x = torch.from_numpy(np.random.default_rng(4).uniform(0, 1, (1, 3, 160, 160)).astype(np.float32))
+    outs = []
+    for merge in ('1', '0'):
+        monkeypatch.setenv('FASTMOT_CSP_MERGE', merge)
+        g, heads = Quarter.build_graph(RandomWeights(seed=9))
+        g.tables()
+        bufs, _ = torch_ref.run_graph(g, x, emulate_fp16_storage=False)
+        outs.append((len(g.layers), [bufs[h.tid][:, h.coff:h.coff + h.c] for h in heads]))
+    assert outs[1][0] == outs[0][0] + 6
+    for a, b in zip(outs[0][1], outs[1][1]):
+        assert (a - b).abs().max().item() <= 1e-4 * a.abs().max().item()
