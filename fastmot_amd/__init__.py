@@ -11,8 +11,9 @@ from .tracker import MultiTracker
 from .kalman_filter import KalmanFilter, MeasType
 from .flow import Flow
 from .track import Track
+from .utils.nv12 import NV12Frame
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'models']
 
 
 def __getattr__(name):

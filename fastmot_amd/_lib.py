@@ -12,6 +12,8 @@ from pathlib import Path
 import numpy as np
 from types import SimpleNamespace
 
+from .utils.nv12 import NV12Frame
+
 LIB_PATH = Path(os.environ.get('FASTMOT_LIB_PATH', Path(__file__).parent / 'libfastmot_hip.so'))
 
 c_int_p = C.POINTER(C.c_int)
@@ -451,7 +453,15 @@ def _bind_device_io(cls):
         self.frame_size = (width, height)
         self.ring_size = ring_size
 
+    def _nv12_args(self, frame):
+        if frame.size != tuple(self.frame_size):
+            raise ValueError(f'NV12 frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames {self.frame_size[0]}x{self.frame_size[1]}')
+        return _ptr(frame.y), _ptr(frame.uv), C.c_int(frame.pitch), C.c_int(frame.matrix_id)
+
     def frame_upload(self, frame):
+        if isinstance(frame, NV12Frame):
+            check(self.lib.fm_frame_upload_nv12(self._ctx, *self._nv12_args(frame)))
+            return
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
             raise ValueError(f'frame must be uint8 {h}x{w}x3')
@@ -464,7 +474,17 @@ def _bind_device_io(cls):
         w, h = self.frame_size
         return pinned_empty(self.lib, (n, h, w, 3), np.uint8)
 
+    def pinned_nv12_frames(self, n, matrix='bt601'):
+        """n NV12Frames whose planes (pitch = width, UV behind Y) lie in page-locked host memory (fm_host_alloc): fill
+        `f.y[...]` / `f.uv[...]`; they are uploaded without a staging copy.  The buffer lives as long as any of them."""
+        w, h = self.frame_size
+        buf = pinned_empty(self.lib, (n, h + h // 2, w), np.uint8)
+        return [NV12Frame(buf[i, :h], buf[i, h:], matrix) for i in range(n)]
+
     def frame_ring_store(self, index, frame):
+        if isinstance(frame, NV12Frame):
+            check(self.lib.fm_frame_ring_store_nv12(self._ctx, C.c_int(index), *self._nv12_args(frame)))
+            return
         f = np.ascontiguousarray(frame, np.uint8)
         check(self.lib.fm_frame_ring_store(self._ctx, C.c_int(index), _ptr(f)))
 
@@ -472,6 +492,8 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
 
     def frame_upload_next(self, frame):
+        if isinstance(frame, NV12Frame):
+            return self.frame_upload_ahead(1, frame)
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
             raise ValueError(f'frame must be uint8 {h}x{w}x3')
@@ -489,6 +511,9 @@ def _bind_device_io(cls):
 
     def frame_upload_ahead(self, k, frame):
         """Host frame for the step k steps ahead (look-ahead slot k, 1 <= k <= FM_MAX_DET_BATCH; k = 1: frame_upload_next)."""
+        if isinstance(frame, NV12Frame):
+            check(self.lib.fm_frame_upload_ahead_nv12(self._ctx, C.c_int(k), *self._nv12_args(frame)))
+            return
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
             raise ValueError(f'frame must be uint8 {h}x{w}x3')
@@ -569,7 +594,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, frame_upload, pinned_frames, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
+    for fn in (frame_configure, _nv12_args, frame_upload, pinned_frames, pinned_nv12_frames, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,

@@ -185,6 +185,11 @@ struct fm_ctx {
     std::atomic<int> trace_busy{0};      // fm_trace_mark calls in flight (the prediction worker marks too): fm_trace_read
                                          // takes the vectors away only when none is left
     hipEvent_t trace_base = nullptr;
+
+    // ---- device staging of NV12 frames (1.5 bytes per pixel; csrc/nv12.hip converts out of it), allocated on first NV12 use:
+    // [0] fm_frame_upload_nv12, [k] look-ahead slot k, [FM_MAX_DET_BATCH + 1] fm_frame_ring_store_nv12.  Unlike the
+    // slots' BGR buffers these stay where they are at a promote: copy and kernel of a slot share one stream.
+    uint8_t* frame_nv12[FM_MAX_DET_BATCH + 2] = {};
 };
 
 // one timed event on stream `s` (no-op unless a trace is running; both host threads of a context may call it)
@@ -202,6 +207,7 @@ inline void fm_trace_mark(fm_ctx* ctx, hipStream_t s, int tag) {
 }
 
 int fm_ensure_slots(fm_ctx* ctx, int max_slot_plus_1);
+int fm_nv12_to_bgr(const uint8_t* nv12, uint8_t* bgr, int w, int h, int matrix, hipStream_t s);   // nv12.hip
 void fm_ext_invalidate_export(fm_ctx* ctx);
 void fm_predict_worker_free(fm_ctx* ctx);
 void fm_gallery_free(fm_ctx* ctx);

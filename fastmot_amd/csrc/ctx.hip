@@ -174,6 +174,8 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
         if (ctx->frame_up_pinned[k]) (void)hipHostFree(ctx->frame_up_pinned[k]);
         if (ctx->ev_up[k]) (void)hipEventDestroy(ctx->ev_up[k]);
     }
+    for (uint8_t* p : ctx->frame_nv12)
+        if (p) (void)hipFree(p);
     if (ctx->det_net) fm_net_free(ctx->det_net);
     if (ctx->ext_net) fm_net_free(ctx->ext_net);
     for (NetState* x : ctx->ext_net_x)

@@ -1110,6 +1110,10 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         if (ctx->frame_up_pinned[k]) (void)hipHostFree(ctx->frame_up_pinned[k]);
         ctx->frame_up[k] = ctx->frame_up_pinned[k] = ctx->frame_ahead[k] = nullptr;
     }
+    for (uint8_t*& p : ctx->frame_nv12) {              // NV12 staging: allocated again on first NV12 use
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
     const size_t bytes = (size_t)width * height * 3;
     FM_HIP(hipMalloc(&ctx->frame_own, bytes + FM_FRAME_SLACK));        // (pixel_source.h load_px2 reads 8 bytes at a pixel)
     FM_HIP(hipMalloc(&ctx->frame_own2, bytes + FM_FRAME_SLACK));
@@ -1307,6 +1311,96 @@ extern "C" int fm_frame_read(fm_ctx* ctx, uint8_t* bgr) {
     FM_HIP(hipMemcpy(bgr, ctx->frame_cur, (size_t)ctx->frame_w * ctx->frame_h * 3, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// ---- NV12 ingest: the three host-frame entry points again, for a Y plane + an interleaved UV plane with a row pitch.
+// Same slots, streams, syncs and events as their BGR counterparts above; between the H2D copy (1.5 bytes per pixel, into
+// ctx->frame_nv12[entry]) and whatever followed it there, the conversion kernel of nv12.hip writes the BGR frame.
+#define FM_CHECK_NV12(ctx, y, uv, pitch, matrix)                                                                  \
+    FM_CHECK_ARG((y) && (uv) && (pitch) >= (ctx)->frame_w && ((matrix) == FM_NV12_BT601 || (matrix) == FM_NV12_BT709) && \
+                 !((ctx)->frame_w & 1) && !((ctx)->frame_h & 1))
+
+// H2D copy of an NV12 frame into the entry's device staging and its conversion into `dst`, both on `s`.  Planes that
+// cannot be copied from where they are (pageable memory, or a pitch) are packed into `pinned` first, after `reuse` --
+// the event behind the previous copy out of that staging buffer -- when one is given.
+static int enqueue_nv12(fm_ctx* ctx, int entry, uint8_t* dst, const uint8_t* y, const uint8_t* uv, int pitch, int matrix,
+                        uint8_t* pinned, hipEvent_t reuse, hipStream_t s) {
+    const int w = ctx->frame_w, h = ctx->frame_h;
+    const size_t npx = (size_t)w * h;
+    uint8_t*& stage = ctx->frame_nv12[entry];
+    if (!stage) FM_HIP(hipMalloc(&stage, npx + npx / 2));
+    if (pitch == w && is_pinned_range(y, npx) && is_pinned_range(uv, npx / 2)) {
+        if (uv == y + npx) {
+            FM_HIP(hipMemcpyAsync(stage, y, npx + npx / 2, hipMemcpyHostToDevice, s));
+        } else {
+            FM_HIP(hipMemcpyAsync(stage, y, npx, hipMemcpyHostToDevice, s));
+            FM_HIP(hipMemcpyAsync(stage + npx, uv, npx / 2, hipMemcpyHostToDevice, s));
+        }
+    } else {
+        if (reuse) FM_HIP(hipEventSynchronize(reuse));
+        for (int r = 0; r < h; ++r) memcpy(pinned + (size_t)r * w, y + (size_t)r * pitch, w);
+        for (int r = 0; r < h / 2; ++r) memcpy(pinned + npx + (size_t)r * w, uv + (size_t)r * pitch, w);
+        FM_HIP(hipMemcpyAsync(stage, pinned, npx + npx / 2, hipMemcpyHostToDevice, s));
+    }
+    fm_trace_mark(ctx, s, 36);                 // (the conversion's share of the caller's 30 .. 31 interval)
+    return fm_nv12_to_bgr(stage, dst, w, h, matrix, s);
+}
+
+extern "C" int fm_frame_upload_nv12(fm_ctx* ctx, const uint8_t* y, const uint8_t* uv, int pitch, int matrix) {
+    FM_CHECK_ARG(ctx && ctx->frame_own);
+    FM_CHECK_NV12(ctx, y, uv, pitch, matrix);
+    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    int rc = enqueue_nv12(ctx, 0, ctx->frame_own, y, uv, pitch, matrix, ctx->frame_pinned, nullptr, ctx->s_det);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
+    ctx->frame_cur = ctx->frame_own;
+    return 0;
+}
+
+extern "C" int fm_frame_upload_ahead_nv12(fm_ctx* ctx, int k, const uint8_t* y, const uint8_t* uv, int pitch, int matrix) {
+    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH);
+    FM_CHECK_NV12(ctx, y, uv, pitch, matrix);
+    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (the BGR-sized staging holds an NV12 frame twice over)
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
+    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the KERNEL: a reader
+    // that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.
+    hipStream_t cs = ctx->s_ext;
+    fm_trace_mark(ctx, cs, 30);
+    int rc = enqueue_nv12(ctx, k, buf, y, uv, pitch, matrix, ahead_pinned(ctx, k), ev, cs);
+    if (rc) return rc;
+    fm_trace_mark(ctx, cs, 31);
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
+    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
+    ahead_frame(ctx, k) = buf;
+    return 0;
+}
+
+extern "C" int fm_frame_ring_store_nv12(fm_ctx* ctx, int index, const uint8_t* y, const uint8_t* uv, int pitch, int matrix) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size);
+    FM_CHECK_NV12(ctx, y, uv, pitch, matrix);
+    const int w = ctx->frame_w, h = ctx->frame_h;
+    const size_t npx = (size_t)w * h;
+    uint8_t*& stage = ctx->frame_nv12[FM_MAX_DET_BATCH + 1];
+    if (!stage) FM_HIP(hipMalloc(&stage, npx + npx / 2));
+    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies that pack the rows, then
+    // the kernel on the null stream
+    FM_HIP(hipMemcpy2D(stage, w, y, pitch, w, h, hipMemcpyHostToDevice));
+    FM_HIP(hipMemcpy2D(stage + npx, w, uv, pitch, w, h / 2, hipMemcpyHostToDevice));
+    int rc = fm_nv12_to_bgr(stage, ctx->frame_ring + npx * 3 * index, w, h, matrix, nullptr);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+#undef FM_CHECK_NV12
 
 // ---------------------------------------------------------------------------------------- detector
 extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {

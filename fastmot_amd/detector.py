@@ -30,6 +30,10 @@ class DeviceFrame:
         self.index = index
 
 
+# Host frames come as BGR ndarrays or as utils.nv12.NV12Frame (Y + interleaved UV planes, converted on the device while
+# they are uploaded): the ctx frame calls below take either, and everything behind them reads the same BGR device frame.
+
+
 def bind_frame(ctx, frame, size, begin_step=False):
     """Makes `frame` the current device frame.  MOT.step binds once per step (`begin_step=True`);
     the stages it calls with the same frame object then reuse the resident copy.  Stand-alone
@@ -392,7 +396,7 @@ class YOLODetector(Detector):
         self._announced = frames
 
     def detect_batch(self, frames):
-        """Detects objects on every frame (ndarrays or DeviceFrames) synchronously, max_batch frames per network pass;
+        """Detects objects on every frame (ndarrays, NV12Frames or DeviceFrames) synchronously, max_batch frames per network pass;
         returns one record array per frame, each equal to what detect_async + postprocess return for that frame."""
         self._drop_announced()
         frames = list(frames)

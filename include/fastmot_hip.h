@@ -399,6 +399,27 @@ int fm_detect_async_ahead(fm_ctx* ctx, int n);
 int fm_frame_ring_store(fm_ctx* ctx, int index, const uint8_t* bgr);
 int fm_frame_ring_select(fm_ctx* ctx, int index);
 int fm_frame_read(fm_ctx* ctx, uint8_t* bgr);   /* current device frame -> host (tests) */
+/* NV12 frames (what hardware decoders, capture cards and cameras deliver): a Y plane of `height` rows at `y` and a plane
+ * of height / 2 rows of interleaved U, V bytes at `uv`, rows `pitch` >= width bytes apart in both planes (`uv` is a
+ * pointer of its own because decoders align the Y plane's height).  The three calls mirror fm_frame_upload,
+ * fm_frame_upload_ahead and fm_frame_ring_store one for one: same slots, same streams, same events.  The rows are
+ * packed to `width` on the way into the page-locked staging buffer (planes with pitch == width inside a buffer from
+ * fm_host_alloc are copied from where they are), 1.5 * width * height bytes cross to the device -- into an NV12 staging
+ * buffer per entry point / look-ahead slot, allocated on its first NV12 use and freed by fm_frame_configure and
+ * fm_ctx_destroy -- and a kernel on the copy's stream (csrc/nv12.hip) writes the BGR frame where the BGR call would
+ * have put it; a look-ahead slot's completion event follows that kernel.  From there on the frame is an ordinary BGR
+ * frame.  The conversion is integer and exact, limited range, chroma sample of a 2 x 2 block used for its four pixels:
+ *   y = max(Y - 16, 0) * CY, u = U - 128, v = V - 128, h = 1 << 19
+ *   R = sat8((y + h + CVR v) >> 20), G = sat8((y + h + CVG v + CUG u) >> 20), B = sat8((y + h + CUB u) >> 20)
+ *   FM_NV12_BT601 (OpenCV's COLOR_YUV2BGR_NV12): CY 1220542, CVR 1673527, CUB 2116026, CUG -409993, CVG -852492
+ *   FM_NV12_BT709 (round(coef * 2^20)):          CY 1220945, CVR 1879825, CUB 2215014, CUG -223607, CVG -558796
+ * FM_ERR_ARG for pitch < width, an unknown matrix, a bad k / index, or a frame size that is not even in both
+ * directions; nothing is copied or launched then. */
+#define FM_NV12_BT601 0
+#define FM_NV12_BT709 1
+int fm_frame_upload_nv12(fm_ctx* ctx, const uint8_t* y, const uint8_t* uv, int pitch, int matrix);
+int fm_frame_upload_ahead_nv12(fm_ctx* ctx, int k, const uint8_t* y, const uint8_t* uv, int pitch, int matrix);
+int fm_frame_ring_store_nv12(fm_ctx* ctx, int index, const uint8_t* y, const uint8_t* uv, int pitch, int matrix);
 
 /* ---------------------------------------------------------------- detector ------------ */
 #define FM_MAX_HEADS 4
