@@ -12,8 +12,9 @@ from .kalman_filter import KalmanFilter, MeasType
 from .flow import Flow
 from .track import Track
 from .utils.nv12 import NV12Frame
+from .utils.jpeg import JPEGFrame
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'models']
 
 
 def __getattr__(name):

@@ -13,6 +13,7 @@ import numpy as np
 from types import SimpleNamespace
 
 from .utils.nv12 import NV12Frame
+from .utils.jpeg import JPEGFrame, QT_ENTRIES, max_coefficients
 
 LIB_PATH = Path(os.environ.get('FASTMOT_LIB_PATH', Path(__file__).parent / 'libfastmot_hip.so'))
 
@@ -458,9 +459,17 @@ def _bind_device_io(cls):
             raise ValueError(f'NV12 frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames {self.frame_size[0]}x{self.frame_size[1]}')
         return _ptr(frame.y), _ptr(frame.uv), C.c_int(frame.pitch), C.c_int(frame.matrix_id)
 
+    def _jpeg_args(self, frame):
+        if frame.size != tuple(self.frame_size):
+            raise ValueError(f'JPEG frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames {self.frame_size[0]}x{self.frame_size[1]}')
+        return C.byref(frame.info), _ptr(frame.coef), _ptr(frame.qt)
+
     def frame_upload(self, frame):
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_nv12(self._ctx, *self._nv12_args(frame)))
+            return
+        if isinstance(frame, JPEGFrame):
+            check(self.lib.fm_frame_upload_jpeg(self._ctx, *self._jpeg_args(frame)))
             return
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -481,9 +490,20 @@ def _bind_device_io(cls):
         buf = pinned_empty(self.lib, (n, h + h // 2, w), np.uint8)
         return [NV12Frame(buf[i, :h], buf[i, h:], matrix) for i in range(n)]
 
+    def pinned_jpeg_buffers(self, n):
+        """n int16 buffers in page-locked host memory (fm_host_alloc), each large enough for the coefficients and tables of
+        any supported JPEG of the context's frame size: `JPEGFrame(data, buffer=b)` decodes into one, and the frame is
+        uploaded without a staging copy.  The memory lives as long as any of them."""
+        w, h = self.frame_size
+        buf = pinned_empty(self.lib, (n, max_coefficients(w, h) + QT_ENTRIES), np.int16)
+        return [buf[i] for i in range(n)]
+
     def frame_ring_store(self, index, frame):
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_ring_store_nv12(self._ctx, C.c_int(index), *self._nv12_args(frame)))
+            return
+        if isinstance(frame, JPEGFrame):
+            check(self.lib.fm_frame_ring_store_jpeg(self._ctx, C.c_int(index), *self._jpeg_args(frame)))
             return
         f = np.ascontiguousarray(frame, np.uint8)
         check(self.lib.fm_frame_ring_store(self._ctx, C.c_int(index), _ptr(f)))
@@ -492,7 +512,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
 
     def frame_upload_next(self, frame):
-        if isinstance(frame, NV12Frame):
+        if isinstance(frame, (NV12Frame, JPEGFrame)):
             return self.frame_upload_ahead(1, frame)
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -513,6 +533,9 @@ def _bind_device_io(cls):
         """Host frame for the step k steps ahead (look-ahead slot k, 1 <= k <= FM_MAX_DET_BATCH; k = 1: frame_upload_next)."""
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_ahead_nv12(self._ctx, C.c_int(k), *self._nv12_args(frame)))
+            return
+        if isinstance(frame, JPEGFrame):
+            check(self.lib.fm_frame_upload_ahead_jpeg(self._ctx, C.c_int(k), *self._jpeg_args(frame)))
             return
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -594,7 +617,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, _nv12_args, frame_upload, pinned_frames, pinned_nv12_frames, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
+    for fn in (frame_configure, _nv12_args, _jpeg_args, frame_upload, pinned_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,

@@ -190,6 +190,13 @@ struct fm_ctx {
     // [0] fm_frame_upload_nv12, [k] look-ahead slot k, [FM_MAX_DET_BATCH + 1] fm_frame_ring_store_nv12.  Unlike the
     // slots' BGR buffers these stay where they are at a promote: copy and kernel of a slot share one stream.
     uint8_t* frame_nv12[FM_MAX_DET_BATCH + 2] = {};
+
+    // ---- device staging of entropy-decoded JPEG frames (coefficients, quantisation tables and the sample planes
+    // csrc/jpeg.hip makes of them), entries as frame_nv12's, allocated on first JPEG use for the largest layout of the
+    // frame size; frame_jpeg_pinned: page-locked host staging for coefficient buffers that are not in fm_host_alloc memory
+    uint8_t* frame_jpeg[FM_MAX_DET_BATCH + 2] = {};
+    uint8_t* frame_jpeg_pinned[FM_MAX_DET_BATCH + 2] = {};
+    hipEvent_t ev_jpeg[FM_MAX_DET_BATCH + 2] = {};      // [k]: behind the last H2D copy out of frame_jpeg_pinned[k]
 };
 
 // one timed event on stream `s` (no-op unless a trace is running; both host threads of a context may call it)
@@ -208,6 +215,10 @@ inline void fm_trace_mark(fm_ctx* ctx, hipStream_t s, int tag) {
 
 int fm_ensure_slots(fm_ctx* ctx, int max_slot_plus_1);
 int fm_nv12_to_bgr(const uint8_t* nv12, uint8_t* bgr, int w, int h, int matrix, hipStream_t s);   // nv12.hip
+int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s);   // jpeg.hip
+// fm_jpeg_info's description of a width x height frame with ncomp 1 or 3 and luma sampling hsamp0 x vsamp0 (jpeg_host.hip)
+int fm_jpeg_layout(int width, int height, int ncomp, int hsamp0, int vsamp0, struct fm_jpeg_info* out);
+size_t fm_jpeg_sample_offset(long long coef_count);                                               // jpeg.hip
 void fm_ext_invalidate_export(fm_ctx* ctx);
 void fm_predict_worker_free(fm_ctx* ctx);
 void fm_gallery_free(fm_ctx* ctx);

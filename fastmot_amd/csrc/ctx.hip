@@ -176,6 +176,12 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
     }
     for (uint8_t* p : ctx->frame_nv12)
         if (p) (void)hipFree(p);
+    for (uint8_t* p : ctx->frame_jpeg)
+        if (p) (void)hipFree(p);
+    for (uint8_t* p : ctx->frame_jpeg_pinned)
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : ctx->ev_jpeg)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->det_net) fm_net_free(ctx->det_net);
     if (ctx->ext_net) fm_net_free(ctx->ext_net);
     for (NetState* x : ctx->ext_net_x)

@@ -1114,6 +1114,14 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         if (p) (void)hipFree(p);
         p = nullptr;
     }
+    for (uint8_t*& p : ctx->frame_jpeg) {              // JPEG staging: allocated again on first JPEG use
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    for (uint8_t*& p : ctx->frame_jpeg_pinned) {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+    }
     const size_t bytes = (size_t)width * height * 3;
     FM_HIP(hipMalloc(&ctx->frame_own, bytes + FM_FRAME_SLACK));        // (pixel_source.h load_px2 reads 8 bytes at a pixel)
     FM_HIP(hipMalloc(&ctx->frame_own2, bytes + FM_FRAME_SLACK));
@@ -1401,6 +1409,122 @@ extern "C" int fm_frame_ring_store_nv12(fm_ctx* ctx, int index, const uint8_t* y
     return 0;
 }
 #undef FM_CHECK_NV12
+
+// ---- JPEG ingest: the three host-frame entry points once more, for a frame that arrives as the output of
+// fm_jpeg_entropy_decode (jpeg_host.hip).  Same slots, streams, syncs and events as their BGR counterparts; between the
+// H2D copy (coefficients + quantisation tables, into ctx->frame_jpeg[entry]) and whatever followed it there, the two
+// kernels of jpeg.hip write the BGR frame.
+
+// int16 coefficients of the largest supported layout of a w x h frame: 4:4:4 on a grid padded to 16 pixels (which bounds
+// the 8-pixel grid 4:4:4 really has, and 4:2:2 / 4:2:0 / one component at half that or less)
+static size_t jpeg_max_coefs(int w, int h) { return (size_t)3 * ((w + 15) & ~15) * ((h + 15) & ~15); }
+static size_t jpeg_stage_bytes(int w, int h) { return fm_jpeg_sample_offset((long long)jpeg_max_coefs(w, h)) + jpeg_max_coefs(w, h); }
+
+// `info` describes a supported layout of the configured frame size, every derived field as fm_jpeg_info computes it
+static bool jpeg_layout_ok(const fm_ctx* ctx, const struct fm_jpeg_info* info) {
+    if (!info || info->width != ctx->frame_w || info->height != ctx->frame_h) return false;
+    struct fm_jpeg_info want;
+    if (fm_jpeg_layout(info->width, info->height, info->ncomp, info->hsamp[0], info->vsamp[0], &want)) return false;
+    for (int c = 0; c < 3; ++c)
+        if (info->blocks_w[c] != want.blocks_w[c] || info->blocks_h[c] != want.blocks_h[c] || info->coef_offset[c] != want.coef_offset[c])
+            return false;
+    // (the launch grids of jpeg.hip: one lane per block row, one thread per 8 pixels of a row)
+    if (want.coef_count / 64 >= (1ll << 28) || (long long)((info->width + 7) >> 3) * info->height >= (1ll << 31)) return false;
+    return info->coef_count == want.coef_count && (size_t)want.coef_count <= jpeg_max_coefs(ctx->frame_w, ctx->frame_h);
+}
+#define FM_CHECK_JPEG(ctx, info, coef, qt) FM_CHECK_ARG((coef) && (qt) && jpeg_layout_ok(ctx, info))
+
+// H2D copy of a frame's coefficients and tables into the entry's device staging and its decode into `dst`, both on `s`.
+// Buffers that cannot be copied from where they are (pageable memory) are packed into the entry's page-locked staging
+// first; `reuse`, when given, is the entry's event behind the previous copy out of that staging buffer: waited for
+// before the buffer is written, recorded again behind the new copy.
+static int enqueue_jpeg(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt,
+                        hipEvent_t* reuse, hipStream_t s) {
+    const size_t cbytes = (size_t)info->coef_count * 2, qbytes = 3 * 64 * 2;
+    uint8_t*& stage = ctx->frame_jpeg[entry];
+    if (!stage) FM_HIP(hipMalloc(&stage, jpeg_stage_bytes(ctx->frame_w, ctx->frame_h)));
+    const uint8_t* const c8 = reinterpret_cast<const uint8_t*>(coef);
+    const uint8_t* const q8 = reinterpret_cast<const uint8_t*>(qt);
+    if (is_pinned_range(c8, cbytes) && is_pinned_range(q8, qbytes)) {
+        if (q8 == c8 + cbytes) {
+            FM_HIP(hipMemcpyAsync(stage, c8, cbytes + qbytes, hipMemcpyHostToDevice, s));
+        } else {
+            FM_HIP(hipMemcpyAsync(stage, c8, cbytes, hipMemcpyHostToDevice, s));
+            FM_HIP(hipMemcpyAsync(stage + cbytes, q8, qbytes, hipMemcpyHostToDevice, s));
+        }
+    } else {
+        uint8_t*& pinned = ctx->frame_jpeg_pinned[entry];
+        if (!pinned) FM_HIP(hipHostMalloc(&pinned, jpeg_max_coefs(ctx->frame_w, ctx->frame_h) * 2 + qbytes, hipHostMallocDefault));
+        if (reuse && *reuse) FM_HIP(hipEventSynchronize(*reuse));
+        memcpy(pinned, c8, cbytes);
+        memcpy(pinned + cbytes, q8, qbytes);
+        FM_HIP(hipMemcpyAsync(stage, pinned, cbytes + qbytes, hipMemcpyHostToDevice, s));
+        if (reuse) {
+            if (!*reuse) FM_HIP(hipEventCreateWithFlags(reuse, hipEventDisableTiming));
+            FM_HIP(hipEventRecord(*reuse, s));
+        }
+    }
+    fm_trace_mark(ctx, s, 37);                 // (the decode's share of the caller's 30 .. 31 interval)
+    return fm_jpeg_to_bgr(stage, dst, info, s);
+}
+
+extern "C" int fm_frame_upload_jpeg(fm_ctx* ctx, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt) {
+    FM_CHECK_ARG(ctx && ctx->frame_own);
+    FM_CHECK_JPEG(ctx, info, coef, qt);
+    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    int rc = enqueue_jpeg(ctx, 0, ctx->frame_own, info, coef, qt, nullptr, ctx->s_det);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
+    ctx->frame_cur = ctx->frame_own;
+    return 0;
+}
+
+extern "C" int fm_frame_upload_ahead_jpeg(fm_ctx* ctx, int k, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt) {
+    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH);
+    FM_CHECK_JPEG(ctx, info, coef, qt);
+    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
+    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the KERNELS: a reader
+    // that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.  The JPEG staging
+    // buffers stay with the slot NUMBER at a promote while that event moves with the frame: the device staging needs no
+    // event (copy and kernels of a slot share one stream), the page-locked one has ev_jpeg[k], which stays as well.
+    hipStream_t cs = ctx->s_ext;
+    fm_trace_mark(ctx, cs, 30);
+    int rc = enqueue_jpeg(ctx, k, buf, info, coef, qt, &ctx->ev_jpeg[k], cs);
+    if (rc) return rc;
+    fm_trace_mark(ctx, cs, 31);
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
+    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
+    ahead_frame(ctx, k) = buf;
+    return 0;
+}
+
+extern "C" int fm_frame_ring_store_jpeg(fm_ctx* ctx, int index, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size);
+    FM_CHECK_JPEG(ctx, info, coef, qt);
+    uint8_t*& stage = ctx->frame_jpeg[FM_MAX_DET_BATCH + 1];
+    if (!stage) FM_HIP(hipMalloc(&stage, jpeg_stage_bytes(ctx->frame_w, ctx->frame_h)));
+    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies, then the kernels on the
+    // null stream
+    const size_t cbytes = (size_t)info->coef_count * 2;
+    FM_HIP(hipMemcpy(stage, coef, cbytes, hipMemcpyHostToDevice));
+    FM_HIP(hipMemcpy(stage + cbytes, qt, 3 * 64 * 2, hipMemcpyHostToDevice));
+    int rc = fm_jpeg_to_bgr(stage, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, info, nullptr);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+#undef FM_CHECK_JPEG
 
 // ---------------------------------------------------------------------------------------- detector
 extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {

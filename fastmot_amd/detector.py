@@ -30,8 +30,10 @@ class DeviceFrame:
         self.index = index
 
 
-# Host frames come as BGR ndarrays or as utils.nv12.NV12Frame (Y + interleaved UV planes, converted on the device while
-# they are uploaded): the ctx frame calls below take either, and everything behind them reads the same BGR device frame.
+# Host frames come as BGR ndarrays, as utils.nv12.NV12Frame (Y + interleaved UV planes, converted on the device while
+# they are uploaded) or as utils.jpeg.JPEGFrame (an entropy-decoded baseline JPEG; inverse DCT, upsampling and colour
+# conversion run on the device while it is uploaded): the ctx frame calls below take any of them, and everything behind
+# them reads the same BGR device frame.
 
 
 def bind_frame(ctx, frame, size, begin_step=False):
@@ -396,7 +398,7 @@ class YOLODetector(Detector):
         self._announced = frames
 
     def detect_batch(self, frames):
-        """Detects objects on every frame (ndarrays, NV12Frames or DeviceFrames) synchronously, max_batch frames per network pass;
+        """Detects objects on every frame (ndarrays, NV12Frames, JPEGFrames or DeviceFrames) synchronously, max_batch frames per network pass;
         returns one record array per frame, each equal to what detect_async + postprocess return for that frame."""
         self._drop_announced()
         frames = list(frames)

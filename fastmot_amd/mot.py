@@ -152,7 +152,7 @@ class MOT:
         self.tracker.reset(cap_dt)
 
     def step(self, frame, next_frame=None, next_frames=None):
-        """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame -- converted to BGR
+        """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame or a JPEGFrame -- converted to BGR
         on the GPU while it is uploaded --, or a detector.DeviceFrame that is already resident on the GPU).
 
         next_frame (optional, not in the reference): the frame the following `step` will receive, when

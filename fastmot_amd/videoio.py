@@ -64,9 +64,13 @@ def resize_bgr(img, size):
 
 
 class _ImageSequence:
-    def __init__(self, pattern):
+    def __init__(self, pattern, gpu_size=None):
+        """gpu_size: (w, h) -- files that are supported baseline JPEGs of exactly this size come back as JPEGFrames
+        (entropy-decoded here, on the capture thread; the rest of the decode runs on the GPU when the frame is uploaded),
+        every other file as the BGR ndarray Pillow decodes.  None: ndarrays only."""
         from PIL import Image
         self._open = Image.open
+        self.gpu_size = None if gpu_size is None else tuple(gpu_size)
         self.pattern = pattern
         self.index = 0 if Path(pattern % 0).exists() else 1
         if not Path(pattern % self.index).exists():
@@ -77,9 +81,25 @@ class _ImageSequence:
         if not path.exists():
             return None
         self.index += 1
+        if self.gpu_size is not None:
+            frame = self._read_jpeg(path)
+            if frame is not None:
+                return frame
         with self._open(path) as im:
             rgb = np.asarray(im.convert('RGB'))
         return np.ascontiguousarray(rgb[:, :, ::-1])
+
+    def _read_jpeg(self, path):
+        """JPEGFrame of the file, or None when it is not a supported JPEG of the wanted size (the caller decodes it with
+        Pillow then: PNGs, progressive or CMYK JPEGs, a file of another size, a damaged file)."""
+        from .utils.jpeg import JPEGFrame
+        data = path.read_bytes()
+        if data[:2] != b'\xff\xd8':
+            return None
+        try:                        # (the size is compared after the header is parsed, before anything is allocated or decoded)
+            return JPEGFrame(data, size=self.gpu_size)
+        except ValueError:
+            return None
 
 
 class _FrameStack:
@@ -102,8 +122,15 @@ class VideoIO:
                  resolution=(1920, 1080),
                  frame_rate=30,
                  buffer_size=10,
-                 proc_fps=30):
-        """Parameters as fastmot/videoio.py:25-58."""
+                 proc_fps=30,
+                 gpu_decode=False):
+        """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` in the configuration
+        file's stream_cfg reaches it through an unmodified app.py):
+        gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
+            -- Huffman-decoded on the capture thread, everything else of the decode done on the GPU by the stage that
+            uploads the frame (MOT.step takes them like ndarrays).  Any other file (a PNG, a progressive JPEG, a frame
+            that needs resizing) comes back as the BGR ndarray it does today, file by file; so does every file when
+            an `output_uri` is set, because frames that are written or drawn on must be host pixels."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -117,8 +144,9 @@ class VideoIO:
 
         self.protocol = self._parse_uri(self.input_uri)
         self.is_live = self.protocol != Protocol.IMAGE and self.protocol != Protocol.VIDEO
+        self.gpu_decode = bool(gpu_decode)
         if self.protocol == Protocol.IMAGE:
-            self.source = _ImageSequence(self.input_uri)
+            self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and output_uri is None else None)
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy'):
             self.source = _FrameStack(self.input_uri)
         else:
@@ -179,7 +207,7 @@ class VideoIO:
                 return None
             frame = self.frame_queue.popleft()
             self.cond.notify()
-        if self.do_resize:
+        if self.do_resize and isinstance(frame, np.ndarray):      # (a JPEGFrame has the wanted size by construction)
             frame = resize_bgr(frame, self.size)
         return frame
 

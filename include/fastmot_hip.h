@@ -421,6 +421,71 @@ int fm_frame_upload_nv12(fm_ctx* ctx, const uint8_t* y, const uint8_t* uv, int p
 int fm_frame_upload_ahead_nv12(fm_ctx* ctx, int k, const uint8_t* y, const uint8_t* uv, int pitch, int matrix);
 int fm_frame_ring_store_nv12(fm_ctx* ctx, int index, const uint8_t* y, const uint8_t* uv, int pitch, int matrix);
 
+/* Baseline JPEG frames (an image sequence 'seq/img1/%06d.jpg', the MOTChallenge layout): replaces the decode of
+ * fastmot_amd/videoio.py's image-sequence source (Pillow: libjpeg-turbo on the capture thread, then two array copies)
+ * and, in the reference, what cv2.VideoCapture / cv2.imread do for such a sequence (fastmot/videoio.py:60-75).  The host
+ * keeps the serial part of the format -- marker parsing and Huffman decoding, the two functions below --, the device
+ * does the rest while the frame is uploaded (csrc/jpeg.hip): dequantisation, the 8 x 8 inverse DCT, chroma upsampling,
+ * YCbCr -> BGR and the store into the frame slot that every stage reads.  The arithmetic is libjpeg-turbo's default
+ * decode path (integer "ISLOW" inverse DCT, "fancy" triangle-filter chroma upsampling, 16-bit fixed-point colour
+ * conversion; fastmot_amd/utils/jpeg.py states it in numpy), so the BGR frame equals Pillow's / OpenCV's decode of the
+ * same file bit for bit.
+ *
+ * Supported: baseline sequential DCT (SOF0 / 8-bit SOF1), Huffman coding with any tables, one interleaved scan, any
+ * restart interval; one component (greyscale: B = G = R = Y) or three YCbCr components (JFIF, or Adobe transform 1) with
+ * luma sampling 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1.  Anything else -- progressive, arithmetic,
+ * lossless, 12-bit, CMYK / YCCK, RGB-coded, other sampling factors, several scans -- returns FM_ERR_UNSUPPORTED with
+ * fm_jpeg_info::unsupported saying which (the caller decodes such a file some other way); nothing else happens.
+ * Malformed data (truncated, corrupt, Huffman codes that do not exist, runs past coefficient 63) returns FM_ERR_ARG;
+ * no input bytes make either function read outside [data, data + n) or write outside the buffers described below.
+ * Both functions need no fm_ctx and no GPU and may be called from any number of threads at once. */
+#define FM_ERR_UNSUPPORTED (-4)
+#define FM_JPEG_UNSUPPORTED_PROGRESSIVE 1
+#define FM_JPEG_UNSUPPORTED_ARITHMETIC 2
+#define FM_JPEG_UNSUPPORTED_PROCESS 3      /* lossless / hierarchical */
+#define FM_JPEG_UNSUPPORTED_PRECISION 4    /* samples that are not 8-bit */
+#define FM_JPEG_UNSUPPORTED_COMPONENTS 5   /* not 1 or 3 components (CMYK / YCCK) */
+#define FM_JPEG_UNSUPPORTED_COLORSPACE 6   /* three components that are not YCbCr */
+#define FM_JPEG_UNSUPPORTED_SAMPLING 7
+#define FM_JPEG_UNSUPPORTED_SCANS 8        /* more than one scan */
+struct fm_jpeg_info {
+    int32_t width, height;          /* of the image, and of the BGR frame it becomes */
+    int32_t ncomp;                  /* 1 or 3 */
+    int32_t hsamp[3], vsamp[3];     /* sampling factors per component */
+    int32_t mcu_w, mcu_h;           /* MCU size in pixels: 8 * the luma's sampling factors (8 x 8 for one component) */
+    int32_t mcus_x, mcus_y;         /* MCU grid: ceil(width / mcu_w), ceil(height / mcu_h) */
+    int32_t restart_interval;       /* MCUs between RSTn markers, 0: none */
+    int32_t blocks_w[3], blocks_h[3]; /* 8 x 8 blocks per component over the MCU-padded grid */
+    int32_t unsupported;            /* FM_JPEG_UNSUPPORTED_* when fm_jpeg_info returned FM_ERR_UNSUPPORTED, else 0 */
+    int64_t coef_offset[3];         /* first coefficient of each component in the coefficient buffer (int16 elements) */
+    int64_t coef_count;             /* size of the coefficient buffer in int16 elements: 64 * the sum of all blocks */
+};
+/* (The struct shares its name with the function that fills it in: write `struct fm_jpeg_info` in C and C++ alike.)
+ * Parses SOI, APPn, DQT, SOF, DHT, DRI, SOS of the file at [data, data + n) and describes its frame. */
+int fm_jpeg_info(const uint8_t* data, size_t n, struct fm_jpeg_info* out);
+/* Huffman-decodes the file's scan (table-driven: a 9-bit look-ahead table per Huffman table, canonical decoding for
+ * longer codes; 0xFF00 stuffing, RSTn markers, DC prediction per component, EOB / ZRL).  `info`: what fm_jpeg_info
+ * returned for the same bytes.  coef[info->coef_count]: the quantised coefficients, per component (at coef_offset[c])
+ * as [block_row][block_col][64] over the MCU-padded grid, a block in row-major (de-zigzagged) order; blocks of the
+ * padding hold what the file codes for them.  qt[3 * 64]: the quantisation table of each component, row-major; zero
+ * for components the file does not have. */
+int fm_jpeg_entropy_decode(const uint8_t* data, size_t n, const struct fm_jpeg_info* info, int16_t* coef, uint16_t* qt);
+/* The three host-frame entry points for an entropy-decoded JPEG frame; they mirror fm_frame_upload,
+ * fm_frame_upload_ahead and fm_frame_ring_store (and their _nv12 forms) one for one: same slots, same streams, same
+ * events.  2 * coef_count + 384 bytes cross to the device -- into a staging buffer per entry point / look-ahead slot,
+ * allocated on its first JPEG use for the largest layout of the configured frame size and freed by fm_frame_configure
+ * and fm_ctx_destroy --; `coef` and `qt` inside a buffer from fm_host_alloc are copied from where they are (one copy
+ * when qt == coef + coef_count), otherwise through a page-locked staging buffer allocated likewise.  Two kernels on
+ * the copy's stream (csrc/jpeg.hip) then write the BGR frame where the BGR call would have put it; a look-ahead slot's
+ * completion event follows them.  From there on the frame is an ordinary BGR frame.
+ * FM_ERR_ARG when info's width x height is not the configured frame size, when info is not a supported layout that
+ * fm_jpeg_info could have returned, or for a bad k / index; nothing is copied or launched then.  The kernels read no
+ * address that depends on a coefficient's value: no coefficient values make them fault (the pixels of streams that no
+ * 8-bit encoder produces are unspecified). */
+int fm_frame_upload_jpeg(fm_ctx* ctx, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt);
+int fm_frame_upload_ahead_jpeg(fm_ctx* ctx, int k, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt);
+int fm_frame_ring_store_jpeg(fm_ctx* ctx, int index, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt);
+
 /* ---------------------------------------------------------------- detector ------------ */
 #define FM_MAX_HEADS 4
 #define FM_MAX_ANCHORS 6   /* yolo_layer.h:11 */

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 import bench  # noqa: E402
 
 NAMES = {15: 'det: first layer (input pixels computed in it) done', 10: 'det: stream reaches the pass', 11: 'det: inputs ready, preprocessed', 12: 'det: network done',
-         13: 'det: decode done', 20: 'post: begins', 21: 'post: ends', 30: 'copy(next): begins', 31: 'copy(next): ends', 36: 'copy(next): NV12 -> BGR begins',
+         13: 'det: decode done', 20: 'post: begins', 21: 'post: ends', 30: 'copy(next): begins', 31: 'copy(next): ends', 36: 'copy(next): NV12 -> BGR begins', 37: 'copy(next): JPEG -> BGR begins',
          32: 'reid: begins', 33: 'reid: ends', 40: 'lk: begins', 41: 'lk: ends',
          14: 'det: preprocess begins', 22: 'post: sort done', 23: 'post: bit matrix done', 34: 'reid: crops done',
          35: 'reid: network done', 42: 'klt: pyramid begins', 43: 'klt: pyramid done', 44: 'klt: keypoint kernels begin',
