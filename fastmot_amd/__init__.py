@@ -13,8 +13,9 @@ from .flow import Flow
 from .track import Track
 from .utils.nv12 import NV12Frame
 from .utils.jpeg import JPEGFrame
+from .utils.source import SourceFrame
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'models']
 
 
 def __getattr__(name):

@@ -14,6 +14,7 @@ from types import SimpleNamespace
 
 from .utils.nv12 import NV12Frame
 from .utils.jpeg import JPEGFrame, QT_ENTRIES, max_coefficients
+from .utils.source import SourceFrame
 
 LIB_PATH = Path(os.environ.get('FASTMOT_LIB_PATH', Path(__file__).parent / 'libfastmot_hip.so'))
 
@@ -471,6 +472,9 @@ def _bind_device_io(cls):
         if isinstance(frame, JPEGFrame):
             check(self.lib.fm_frame_upload_jpeg(self._ctx, *self._jpeg_args(frame)))
             return
+        if isinstance(frame, SourceFrame):      # any size: resized to the frame size on the device (csrc/resize.hip)
+            check(self.lib.fm_frame_upload_src(self._ctx, C.byref(frame.describe())))
+            return
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
             raise ValueError(f'frame must be uint8 {h}x{w}x3')
@@ -481,6 +485,14 @@ def _bind_device_io(cls):
         """n frames (n, H, W, 3) uint8 in page-locked host memory (fm_host_alloc): frames stored here are
         uploaded without a staging copy.  The buffer lives as long as the returned array's base object."""
         w, h = self.frame_size
+        return pinned_empty(self.lib, (n, h, w, 3), np.uint8)
+
+    def pinned_source_frames(self, n, size):
+        """n BGR frames (n, H, W, 3) uint8 of the SOURCE size `size` = (W, H) in page-locked host memory (fm_host_alloc):
+        `SourceFrame(buf[i])` is uploaded without a staging copy.  The buffer lives as long as the returned array's base object."""
+        w, h = size
+        if not (1 <= w <= 16384 and 1 <= h <= 16384):
+            raise ValueError(f'source size {w}x{h} outside 1..16384')
         return pinned_empty(self.lib, (n, h, w, 3), np.uint8)
 
     def pinned_nv12_frames(self, n, matrix='bt601'):
@@ -505,6 +517,9 @@ def _bind_device_io(cls):
         if isinstance(frame, JPEGFrame):
             check(self.lib.fm_frame_ring_store_jpeg(self._ctx, C.c_int(index), *self._jpeg_args(frame)))
             return
+        if isinstance(frame, SourceFrame):
+            check(self.lib.fm_frame_ring_store_src(self._ctx, C.c_int(index), C.byref(frame.describe())))
+            return
         f = np.ascontiguousarray(frame, np.uint8)
         check(self.lib.fm_frame_ring_store(self._ctx, C.c_int(index), _ptr(f)))
 
@@ -512,7 +527,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
 
     def frame_upload_next(self, frame):
-        if isinstance(frame, (NV12Frame, JPEGFrame)):
+        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame)):
             return self.frame_upload_ahead(1, frame)
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -536,6 +551,9 @@ def _bind_device_io(cls):
             return
         if isinstance(frame, JPEGFrame):
             check(self.lib.fm_frame_upload_ahead_jpeg(self._ctx, C.c_int(k), *self._jpeg_args(frame)))
+            return
+        if isinstance(frame, SourceFrame):
+            check(self.lib.fm_frame_upload_ahead_src(self._ctx, C.c_int(k), C.byref(frame.describe())))
             return
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -617,7 +635,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, _nv12_args, _jpeg_args, frame_upload, pinned_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
+    for fn in (frame_configure, _nv12_args, _jpeg_args, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,

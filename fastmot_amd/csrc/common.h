@@ -197,6 +197,18 @@ struct fm_ctx {
     uint8_t* frame_jpeg[FM_MAX_DET_BATCH + 2] = {};
     uint8_t* frame_jpeg_pinned[FM_MAX_DET_BATCH + 2] = {};
     hipEvent_t ev_jpeg[FM_MAX_DET_BATCH + 2] = {};      // [k]: behind the last H2D copy out of frame_jpeg_pinned[k]
+
+    // ---- frames that arrive at another size than frame_w x frame_h (fm_frame_*_src; csrc/resize.hip resizes out of
+    // `bgr`), entries as frame_nv12's.  Everything is sized by the SOURCE, allocated on first use, regrown for a larger
+    // source and separate from the staging above; like that staging it stays where it is at a promote.
+    struct SrcStage {
+        uint8_t* bgr = nullptr;      // the source-resolution BGR frame on the device (+ FM_FRAME_SLACK)
+        uint8_t* dev = nullptr;      // NV12 planes / JPEG coefficients, tables and sample planes on the device
+        uint8_t* pinned = nullptr;   // page-locked host staging for sources that are not in fm_host_alloc memory
+        size_t bgr_cap = 0, dev_cap = 0, pinned_cap = 0;
+        hipEvent_t ev = nullptr;     // behind the last H2D copy out of `pinned`
+    };
+    SrcStage frame_src[FM_MAX_DET_BATCH + 2];
 };
 
 // one timed event on stream `s` (no-op unless a trace is running; both host threads of a context may call it)
@@ -215,6 +227,8 @@ inline void fm_trace_mark(fm_ctx* ctx, hipStream_t s, int tag) {
 
 int fm_ensure_slots(fm_ctx* ctx, int max_slot_plus_1);
 int fm_nv12_to_bgr(const uint8_t* nv12, uint8_t* bgr, int w, int h, int matrix, hipStream_t s);   // nv12.hip
+int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
+void fm_frame_src_free(fm_ctx* ctx);                                                              // detect.hip
 int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s);   // jpeg.hip
 // fm_jpeg_info's description of a width x height frame with ncomp 1 or 3 and luma sampling hsamp0 x vsamp0 (jpeg_host.hip)
 int fm_jpeg_layout(int width, int height, int ncomp, int hsamp0, int vsamp0, struct fm_jpeg_info* out);

@@ -1122,6 +1122,7 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         if (p) (void)hipHostFree(p);
         p = nullptr;
     }
+    fm_frame_src_free(ctx);                            // off-size sources: allocated again on first use
     const size_t bytes = (size_t)width * height * 3;
     FM_HIP(hipMalloc(&ctx->frame_own, bytes + FM_FRAME_SLACK));        // (pixel_source.h load_px2 reads 8 bytes at a pixel)
     FM_HIP(hipMalloc(&ctx->frame_own2, bytes + FM_FRAME_SLACK));
@@ -1420,9 +1421,9 @@ extern "C" int fm_frame_ring_store_nv12(fm_ctx* ctx, int index, const uint8_t* y
 static size_t jpeg_max_coefs(int w, int h) { return (size_t)3 * ((w + 15) & ~15) * ((h + 15) & ~15); }
 static size_t jpeg_stage_bytes(int w, int h) { return fm_jpeg_sample_offset((long long)jpeg_max_coefs(w, h)) + jpeg_max_coefs(w, h); }
 
-// `info` describes a supported layout of the configured frame size, every derived field as fm_jpeg_info computes it
-static bool jpeg_layout_ok(const fm_ctx* ctx, const struct fm_jpeg_info* info) {
-    if (!info || info->width != ctx->frame_w || info->height != ctx->frame_h) return false;
+// `info` describes a supported layout of a w x h frame, every derived field as fm_jpeg_info computes it
+static bool jpeg_layout_ok_size(const struct fm_jpeg_info* info, int w, int h) {
+    if (!info || info->width != w || info->height != h) return false;
     struct fm_jpeg_info want;
     if (fm_jpeg_layout(info->width, info->height, info->ncomp, info->hsamp[0], info->vsamp[0], &want)) return false;
     for (int c = 0; c < 3; ++c)
@@ -1430,8 +1431,10 @@ static bool jpeg_layout_ok(const fm_ctx* ctx, const struct fm_jpeg_info* info) {
             return false;
     // (the launch grids of jpeg.hip: one lane per block row, one thread per 8 pixels of a row)
     if (want.coef_count / 64 >= (1ll << 28) || (long long)((info->width + 7) >> 3) * info->height >= (1ll << 31)) return false;
-    return info->coef_count == want.coef_count && (size_t)want.coef_count <= jpeg_max_coefs(ctx->frame_w, ctx->frame_h);
+    return info->coef_count == want.coef_count && (size_t)want.coef_count <= jpeg_max_coefs(w, h);
 }
+// ... of the configured frame size
+static bool jpeg_layout_ok(const fm_ctx* ctx, const struct fm_jpeg_info* info) { return jpeg_layout_ok_size(info, ctx->frame_w, ctx->frame_h); }
 #define FM_CHECK_JPEG(ctx, info, coef, qt) FM_CHECK_ARG((coef) && (qt) && jpeg_layout_ok(ctx, info))
 
 // H2D copy of a frame's coefficients and tables into the entry's device staging and its decode into `dst`, both on `s`.
@@ -1525,6 +1528,188 @@ extern "C" int fm_frame_ring_store_jpeg(fm_ctx* ctx, int index, const struct fm_
     return 0;
 }
 #undef FM_CHECK_JPEG
+
+// ---- frames at another size than the configured one: the three host-frame entry points for a described source
+// (struct fm_frame_src).  A source of the configured size goes to the counterpart above.  Any other is copied -- and, for
+// NV12 / JPEG, converted by the kernels above -- at ITS size into ctx->frame_src[entry].bgr, and the kernel of
+// resize.hip writes the frame the counterpart would have written.  Same slots, streams, syncs and events as the
+// counterparts; the staging is this path's own and sized by the source.
+void fm_frame_src_free(fm_ctx* ctx) {
+    for (fm_ctx::SrcStage& e : ctx->frame_src) {
+        if (e.bgr) (void)hipFree(e.bgr);
+        if (e.dev) (void)hipFree(e.dev);
+        if (e.pinned) (void)hipHostFree(e.pinned);
+        if (e.ev) (void)hipEventDestroy(e.ev);
+        e = fm_ctx::SrcStage{};
+    }
+}
+
+static bool src_ok(const struct fm_frame_src* f) {
+    if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
+    switch (f->kind) {
+    case FM_SRC_BGR: return f->bgr != nullptr;
+    case FM_SRC_NV12:
+        return f->y && f->uv && f->pitch >= f->width && (f->matrix == FM_NV12_BT601 || f->matrix == FM_NV12_BT709) &&
+               !(f->width & 1) && !(f->height & 1);
+    case FM_SRC_JPEG: return f->coef && f->qt && jpeg_layout_ok_size(f->info, f->width, f->height);
+    }
+    return false;
+}
+static bool src_on_size(const fm_ctx* ctx, const struct fm_frame_src* f) { return f->width == ctx->frame_w && f->height == ctx->frame_h; }
+
+// at least `bytes` at p; a buffer that has to grow is given up once `s`, the stream whose copies and kernels use it, is idle
+static int src_reserve(uint8_t*& p, size_t& cap, size_t bytes, bool host, hipStream_t s) {
+    if (bytes <= cap) return 0;
+    if (p) {
+        FM_HIP(hipStreamSynchronize(s));
+        if (host) (void)hipHostFree(p); else (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    if (host) FM_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    else FM_HIP(hipMalloc(&p, bytes));
+    cap = bytes;
+    return 0;
+}
+
+// page-locked staging of `bytes` for the entry, free to be written: the previous H2D copy out of it is done
+static int src_pinned(fm_ctx::SrcStage& st, size_t bytes, hipStream_t s) {
+    int rc = src_reserve(st.pinned, st.pinned_cap, bytes, true, s);
+    if (rc) return rc;
+    if (st.ev) FM_HIP(hipEventSynchronize(st.ev));
+    return 0;
+}
+static int src_pinned_copied(fm_ctx::SrcStage& st, hipStream_t s) {
+    if (!st.ev) FM_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(st.ev, s));
+    return 0;
+}
+
+// The off-size source `f` (checked by the caller) into the entry's source-resolution buffers and, resized, into `dst`:
+// copies and kernels on `s`; `blocking`: blocking copies from where the source lies (fm_frame_ring_store_src).
+static int enqueue_src(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_src* f, hipStream_t s, bool blocking) {
+    fm_ctx::SrcStage& st = ctx->frame_src[entry];
+    const int w = f->width, h = f->height;
+    const size_t npx = (size_t)w * h;
+    int rc = src_reserve(st.bgr, st.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s);     // (resize.hip reads 8 bytes at a pixel)
+    if (rc) return rc;
+    if (f->kind == FM_SRC_BGR) {
+        if (blocking) {
+            FM_HIP(hipMemcpy(st.bgr, f->bgr, npx * 3, hipMemcpyHostToDevice));
+        } else if (is_pinned_range(f->bgr, npx * 3)) {
+            FM_HIP(hipMemcpyAsync(st.bgr, f->bgr, npx * 3, hipMemcpyHostToDevice, s));
+        } else {
+            if ((rc = src_pinned(st, npx * 3, s))) return rc;
+            memcpy(st.pinned, f->bgr, npx * 3);
+            FM_HIP(hipMemcpyAsync(st.bgr, st.pinned, npx * 3, hipMemcpyHostToDevice, s));
+            if ((rc = src_pinned_copied(st, s))) return rc;
+        }
+    } else if (f->kind == FM_SRC_NV12) {
+        const size_t nbytes = npx + npx / 2;
+        if ((rc = src_reserve(st.dev, st.dev_cap, nbytes, false, s))) return rc;
+        if (blocking) {
+            FM_HIP(hipMemcpy2D(st.dev, w, f->y, f->pitch, w, h, hipMemcpyHostToDevice));
+            FM_HIP(hipMemcpy2D(st.dev + npx, w, f->uv, f->pitch, w, h / 2, hipMemcpyHostToDevice));
+        } else if (f->pitch == w && is_pinned_range(f->y, npx) && is_pinned_range(f->uv, npx / 2)) {
+            FM_HIP(hipMemcpyAsync(st.dev, f->y, npx, hipMemcpyHostToDevice, s));
+            FM_HIP(hipMemcpyAsync(st.dev + npx, f->uv, npx / 2, hipMemcpyHostToDevice, s));
+        } else {
+            if ((rc = src_pinned(st, nbytes, s))) return rc;
+            for (int r = 0; r < h; ++r) memcpy(st.pinned + (size_t)r * w, f->y + (size_t)r * f->pitch, w);
+            for (int r = 0; r < h / 2; ++r) memcpy(st.pinned + npx + (size_t)r * w, f->uv + (size_t)r * f->pitch, w);
+            FM_HIP(hipMemcpyAsync(st.dev, st.pinned, nbytes, hipMemcpyHostToDevice, s));
+            if ((rc = src_pinned_copied(st, s))) return rc;
+        }
+        fm_trace_mark(ctx, s, 36);
+        if ((rc = fm_nv12_to_bgr(st.dev, st.bgr, w, h, f->matrix, s))) return rc;
+    } else {
+        const size_t cbytes = (size_t)f->info->coef_count * 2, qbytes = 3 * 64 * 2;
+        if ((rc = src_reserve(st.dev, st.dev_cap, jpeg_stage_bytes(w, h), false, s))) return rc;
+        const uint8_t* const c8 = reinterpret_cast<const uint8_t*>(f->coef);
+        const uint8_t* const q8 = reinterpret_cast<const uint8_t*>(f->qt);
+        if (blocking) {
+            FM_HIP(hipMemcpy(st.dev, c8, cbytes, hipMemcpyHostToDevice));
+            FM_HIP(hipMemcpy(st.dev + cbytes, q8, qbytes, hipMemcpyHostToDevice));
+        } else if (is_pinned_range(c8, cbytes) && is_pinned_range(q8, qbytes)) {
+            FM_HIP(hipMemcpyAsync(st.dev, c8, cbytes, hipMemcpyHostToDevice, s));
+            FM_HIP(hipMemcpyAsync(st.dev + cbytes, q8, qbytes, hipMemcpyHostToDevice, s));
+        } else {
+            if ((rc = src_pinned(st, jpeg_max_coefs(w, h) * 2 + qbytes, s))) return rc;
+            memcpy(st.pinned, c8, cbytes);
+            memcpy(st.pinned + cbytes, q8, qbytes);
+            FM_HIP(hipMemcpyAsync(st.dev, st.pinned, cbytes + qbytes, hipMemcpyHostToDevice, s));
+            if ((rc = src_pinned_copied(st, s))) return rc;
+        }
+        fm_trace_mark(ctx, s, 37);
+        if ((rc = fm_jpeg_to_bgr(st.dev, st.bgr, f->info, s))) return rc;
+    }
+    fm_trace_mark(ctx, s, 38);                 // (the resize's share of the caller's 30 .. 31 interval)
+    return fm_resize_bgr(st.bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+}
+
+extern "C" int fm_frame_upload_src(fm_ctx* ctx, const struct fm_frame_src* src) {
+    FM_CHECK_ARG(ctx && ctx->frame_own && src_ok(src));
+    if (src_on_size(ctx, src)) {
+        if (src->kind == FM_SRC_BGR) return fm_frame_upload(ctx, src->bgr);
+        if (src->kind == FM_SRC_NV12) return fm_frame_upload_nv12(ctx, src->y, src->uv, src->pitch, src->matrix);
+        return fm_frame_upload_jpeg(ctx, src->info, src->coef, src->qt);
+    }
+    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    int rc = enqueue_src(ctx, 0, ctx->frame_own, src, ctx->s_det, false);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
+    ctx->frame_cur = ctx->frame_own;
+    return 0;
+}
+
+extern "C" int fm_frame_upload_ahead_src(fm_ctx* ctx, int k, const struct fm_frame_src* src) {
+    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && src_ok(src));
+    if (src_on_size(ctx, src)) {
+        if (src->kind == FM_SRC_BGR) return fm_frame_upload_ahead(ctx, k, src->bgr);
+        if (src->kind == FM_SRC_NV12) return fm_frame_upload_ahead_nv12(ctx, k, src->y, src->uv, src->pitch, src->matrix);
+        return fm_frame_upload_ahead_jpeg(ctx, k, src->info, src->coef, src->qt);
+    }
+    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
+    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the LAST kernel, the
+    // resize: a reader that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.  The
+    // source staging stays with the slot NUMBER at a promote while that event moves with the frame: the device buffers
+    // need no event (copies and kernels of a slot share one stream), the page-locked one has its own.
+    hipStream_t cs = ctx->s_ext;
+    fm_trace_mark(ctx, cs, 30);
+    int rc = enqueue_src(ctx, k, buf, src, cs, false);
+    if (rc) return rc;
+    fm_trace_mark(ctx, cs, 31);
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
+    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
+    ahead_frame(ctx, k) = buf;
+    return 0;
+}
+
+extern "C" int fm_frame_ring_store_src(fm_ctx* ctx, int index, const struct fm_frame_src* src) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && src_ok(src));
+    if (src_on_size(ctx, src)) {
+        if (src->kind == FM_SRC_BGR) return fm_frame_ring_store(ctx, index, src->bgr);
+        if (src->kind == FM_SRC_NV12) return fm_frame_ring_store_nv12(ctx, index, src->y, src->uv, src->pitch, src->matrix);
+        return fm_frame_ring_store_jpeg(ctx, index, src->info, src->coef, src->qt);
+    }
+    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies, then the kernels on the
+    // null stream
+    int rc = enqueue_src(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, src, nullptr, true);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------- detector
 extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {

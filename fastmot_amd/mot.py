@@ -17,6 +17,7 @@ from .feature_extractor import FeatureExtractor
 from .tracker import MultiTracker
 from .flow import Flow
 from .utils import Profiler
+from .utils.source import SourceFrame
 from .utils.visualization import Visualizer
 
 LOGGER = logging.getLogger(__name__)
@@ -153,7 +154,8 @@ class MOT:
 
     def step(self, frame, next_frame=None, next_frames=None):
         """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame or a JPEGFrame -- converted to BGR
-        on the GPU while it is uploaded --, or a detector.DeviceFrame that is already resident on the GPU).
+        on the GPU while it is uploaded --, a SourceFrame -- any of the three at capture resolution, resized to `size` on
+        the GPU --, or a detector.DeviceFrame that is already resident on the GPU).
 
         next_frame (optional, not in the reference): the frame the following `step` will receive, when
         the caller already has it (file sources, a capture queue).  The detector network is then started
@@ -162,6 +164,8 @@ class MOT:
         next_frames (optional): the frames of the following steps in order (next_frame = next_frames[0]); with
         detector_lookahead = k the detector takes up to k of them in one network pass."""
         ctx = self.tracker.ctx
+        if self.draw and isinstance(frame, SourceFrame):
+            raise ValueError('draw=True needs host pixels at the tracker\'s size: a SourceFrame is resized on the GPU')
         bind_frame(ctx, frame, self.size, begin_step=True)
         ctx.in_step = True
         if next_frames is not None:

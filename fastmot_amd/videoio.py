@@ -64,13 +64,15 @@ def resize_bgr(img, size):
 
 
 class _ImageSequence:
-    def __init__(self, pattern, gpu_size=None):
+    def __init__(self, pattern, gpu_size=None, any_size=False):
         """gpu_size: (w, h) -- files that are supported baseline JPEGs of exactly this size come back as JPEGFrames
         (entropy-decoded here, on the capture thread; the rest of the decode runs on the GPU when the frame is uploaded),
-        every other file as the BGR ndarray Pillow decodes.  None: ndarrays only."""
+        every other file as the BGR ndarray Pillow decodes.  None: ndarrays only.  any_size: supported JPEGs of every
+        size the GPU resize takes come back as JPEGFrames (the caller wraps those of another size in SourceFrames)."""
         from PIL import Image
         self._open = Image.open
         self.gpu_size = None if gpu_size is None else tuple(gpu_size)
+        self.any_size = bool(any_size)
         self.pattern = pattern
         self.index = 0 if Path(pattern % 0).exists() else 1
         if not Path(pattern % self.index).exists():
@@ -93,13 +95,15 @@ class _ImageSequence:
         """JPEGFrame of the file, or None when it is not a supported JPEG of the wanted size (the caller decodes it with
         Pillow then: PNGs, progressive or CMYK JPEGs, a file of another size, a damaged file)."""
         from .utils.jpeg import JPEGFrame
+        from .utils.source import MAX_DIM
         data = path.read_bytes()
         if data[:2] != b'\xff\xd8':
             return None
         try:                        # (the size is compared after the header is parsed, before anything is allocated or decoded)
-            return JPEGFrame(data, size=self.gpu_size)
+            frame = JPEGFrame(data, size=None if self.any_size else self.gpu_size)
         except ValueError:
             return None
+        return frame if max(frame.size) <= MAX_DIM else None
 
 
 class _FrameStack:
@@ -123,14 +127,21 @@ class VideoIO:
                  frame_rate=30,
                  buffer_size=10,
                  proc_fps=30,
-                 gpu_decode=False):
-        """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` in the configuration
-        file's stream_cfg reaches it through an unmodified app.py):
+                 gpu_decode=False,
+                 gpu_resize=False):
+        """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` / `"gpu_resize": true`
+        in the configuration file's stream_cfg reach it through an unmodified app.py):
         gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
             -- Huffman-decoded on the capture thread, everything else of the decode done on the GPU by the stage that
             uploads the frame (MOT.step takes them like ndarrays).  Any other file (a PNG, a progressive JPEG, a frame
             that needs resizing) comes back as the BGR ndarray it does today, file by file; so does every file when
-            an `output_uri` is set, because frames that are written or drawn on must be host pixels."""
+            an `output_uri` is set, because frames that are written or drawn on must be host pixels.
+        gpu_resize: a frame whose size is not `size` is returned by `read` as a SourceFrame -- the frame as it was
+            captured; the stage that uploads it resizes it on the GPU, with `resize_bgr`'s arithmetic bit for bit
+            (MOT.step takes them like ndarrays) -- in place of being resized here, on the thread that calls `read`.
+            A frame already at `size` comes back as it does today.  Together with gpu_decode, supported baseline JPEG
+            files of ANY size come back as JPEGFrames, those of another size than `size` wrapped in a SourceFrame.
+            With an `output_uri` everything stays host pixels, as above."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -145,8 +156,11 @@ class VideoIO:
         self.protocol = self._parse_uri(self.input_uri)
         self.is_live = self.protocol != Protocol.IMAGE and self.protocol != Protocol.VIDEO
         self.gpu_decode = bool(gpu_decode)
+        self.gpu_resize = bool(gpu_resize)
+        self._wrap_sources = self.gpu_resize and output_uri is None
         if self.protocol == Protocol.IMAGE:
-            self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and output_uri is None else None)
+            self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and output_uri is None else None,
+                                         any_size=self._wrap_sources)
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy'):
             self.source = _FrameStack(self.input_uri)
         else:
@@ -207,7 +221,13 @@ class VideoIO:
                 return None
             frame = self.frame_queue.popleft()
             self.cond.notify()
-        if self.do_resize and isinstance(frame, np.ndarray):      # (a JPEGFrame has the wanted size by construction)
+        if self._wrap_sources:
+            from .utils.source import MAX_DIM, SourceFrame
+            if not isinstance(frame, np.ndarray):                 # a JPEGFrame, of any size
+                return frame if frame.size == self.size else SourceFrame(frame)
+            if self.do_resize and frame.shape[:2] != self.size[::-1] and max(frame.shape[:2]) <= MAX_DIM:
+                return SourceFrame(frame)
+        if self.do_resize and isinstance(frame, np.ndarray):      # (without gpu_resize a JPEGFrame has the wanted size by construction)
             frame = resize_bgr(frame, self.size)
         return frame
 

@@ -486,6 +486,46 @@ int fm_frame_upload_jpeg(fm_ctx* ctx, const struct fm_jpeg_info* info, const int
 int fm_frame_upload_ahead_jpeg(fm_ctx* ctx, int k, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt);
 int fm_frame_ring_store_jpeg(fm_ctx* ctx, int index, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt);
 
+/* Frames at capture resolution (the reference's VideoIO resizes every captured frame to `size` with cv2.resize before
+ * the tracker sees it, fastmot/videoio.py; its default configuration is 1280 x 720 from 1920 x 1080 sources).  One
+ * described-source family: `src` says what the host frame is -- packed BGR, NV12 planes or an entropy-decoded JPEG, the
+ * arguments of the calls above -- and how large it is.  The three calls mirror fm_frame_upload, fm_frame_upload_ahead and
+ * fm_frame_ring_store one for one: same slots, same streams, same syncs, same events.
+ * width x height equal to the configured frame size: the call IS its counterpart above (it forwards to it).
+ * Otherwise the frame crosses to the device at its own resolution -- into buffers per entry point / look-ahead slot
+ * (the source's BGR frame of width * height * 3 bytes, NV12 / JPEG staging and page-locked staging sized by the SOURCE
+ * size, separate from the staging of the calls above), allocated on first use, regrown when a larger source arrives and
+ * freed by fm_frame_configure and fm_ctx_destroy --, the NV12 / JPEG kernels write the BGR frame at that resolution, and
+ * a kernel on the same stream (csrc/resize.hip) writes the configured-size BGR frame where the BGR call would have
+ * put it; a look-ahead slot's completion event follows that last kernel.  From there on the frame is an ordinary BGR
+ * frame: every stage reads the resized frame, as the reference's stages do.
+ * The resize is cv2.resize's 8-bit INTER_LINEAR, integer and exact (fastmot_amd/videoio.py resize_bgr states it in
+ * numpy).  Per axis, for output index d:
+ *   f = float((d + 0.5) * (ssize / dsize) - 0.5), s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= ssize - 1: s = ssize - 1, f = 0
+ *   a0 = rint((1 - f) * 2048), a1 = rint(f * 2048), s' = min(s + 1, ssize - 1)
+ * and per channel  S0 = p[y][x] ax0 + p[y][x'] ax1,  S1 = p[y'][x] ax0 + p[y'][x'] ax1,
+ *   v = clamp((((ay0 * (S0 >> 4)) >> 16) + ((ay1 * (S1 >> 4)) >> 16) + 2) >> 2, 0, 255);
+ * a source of exactly twice the frame size in both axes gives the rounded 2 x 2 mean (a + b + c + d + 2) >> 2 instead.
+ * FM_ERR_ARG for a null ctx / src / plane pointer, an unknown kind, a width or height outside 1..16384, NV12 with an odd
+ * source size, pitch < width or an unknown matrix, a JPEG info that is not a supported layout of width x height, or a
+ * bad k / index; nothing is copied, allocated or launched then. */
+#define FM_SRC_BGR 0
+#define FM_SRC_NV12 1
+#define FM_SRC_JPEG 2
+#define FM_SRC_MAX_DIM 16384
+struct fm_frame_src {
+    int32_t kind, width, height;          /* FM_SRC_*; the SOURCE's size */
+    const uint8_t* bgr;                   /* FM_SRC_BGR: packed, width * height * 3 bytes */
+    const uint8_t *y, *uv;                /* FM_SRC_NV12: as fm_frame_upload_nv12's */
+    int32_t pitch, matrix;
+    const struct fm_jpeg_info* info;      /* FM_SRC_JPEG: as fm_frame_upload_jpeg's; info->width / height == width / height */
+    const int16_t* coef;
+    const uint16_t* qt;
+};
+int fm_frame_upload_src(fm_ctx* ctx, const struct fm_frame_src* src);
+int fm_frame_upload_ahead_src(fm_ctx* ctx, int k, const struct fm_frame_src* src);
+int fm_frame_ring_store_src(fm_ctx* ctx, int index, const struct fm_frame_src* src);
+
 /* ---------------------------------------------------------------- detector ------------ */
 #define FM_MAX_HEADS 4
 #define FM_MAX_ANCHORS 6   /* yolo_layer.h:11 */
