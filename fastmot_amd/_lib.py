@@ -48,6 +48,7 @@ def load():
     except OSError as err:
         raise RuntimeError(f'Unable to load {LIB_PATH}') from err
     lib.fm_last_error.restype = C.c_char_p
+    lib.fm_jpeg_encode_bound.restype = C.c_size_t
     _lib = lib
     return lib
 
@@ -574,6 +575,45 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_read(self._ctx, _ptr(out)))
         return out
 
+    def _jpeg_out(self, width, height):
+        """The buffer encoded files are written to before they become `bytes`: the worst case for the size, kept across calls
+        (untouched pages of it cost nothing)."""
+        bound = self.lib.fm_jpeg_encode_bound(C.c_int(width), C.c_int(height))
+        if not bound:
+            raise ValueError(f'frame size {width}x{height} outside 1..16384')
+        out = getattr(self, '_jpeg_out_buf', None)
+        if out is None or out.size < bound:
+            out = self._jpeg_out_buf = np.empty(bound, np.uint8)
+        return out
+
+    def frame_encode_jpeg(self, quality=75):
+        """The frame the context holds on the device (the one bound last) as a baseline JPEG file -> bytes."""
+        if getattr(self, 'frame_size', None) is None:
+            raise FastMOTHipError('no frame on the device yet')
+        out = self._jpeg_out(*self.frame_size)
+        n = C.c_size_t(0)
+        check(self.lib.fm_frame_encode_jpeg(self._ctx, C.c_int(int(quality)), _ptr(out), C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def jpeg_encode_bgr(self, frame, quality=75):
+        """Host pixels [H, W, 3] uint8 BGR (rows may be strided) as a baseline JPEG file -> bytes."""
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError('frame must be a uint8 HxWx3 array')
+        if frame.strides[1:] != (3, 1) or frame.strides[0] < 3 * frame.shape[1]:
+            frame = np.ascontiguousarray(frame)
+        h, w = frame.shape[:2]
+        out = self._jpeg_out(w, h)
+        n = C.c_size_t(0)
+        check(self.lib.fm_jpeg_encode_bgr(self._ctx, _ptr(frame), C.c_int(w), C.c_int(h), C.c_size_t(frame.strides[0]), C.c_int(int(quality)),
+                                          _ptr(out), C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def jpeg_encode_stream_ms(self):
+        """HIP-event time of the kernels of the last encode, or None before the first."""
+        ms = C.c_float(0)
+        check(self.lib.fm_jpeg_encode_stream_ms(self._ctx, C.byref(ms)))
+        return ms.value if ms.value >= 0 else None
+
     def detect_configure(self, cfg):
         check(self.lib.fm_detect_configure(self._ctx, C.byref(cfg)))
 
@@ -636,6 +676,7 @@ def _bind_device_io(cls):
         return out
 
     for fn in (frame_configure, _nv12_args, _jpeg_args, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
+               _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,

@@ -84,6 +84,7 @@ struct NetState;     // conv engine (net.hip)
 struct DetState;     // detector pre/post (detect.hip)
 struct ExtState;     // extractor pre (extract.hip)
 struct FlowState;    // KLT (flow.hip)
+struct EncState;     // JPEG output path (jpegenc.hip)
 struct GalleryState; // cross-stream ReID-gallery all-gather over RCCL (gallery.hip)
 constexpr int FM_GALLERY_CHANNELS = 2;
 
@@ -175,6 +176,7 @@ struct fm_ctx {
     NetState* ext_net = nullptr;
     NetState* ext_net_x[FM_MAX_EXTRA_EXTRACTORS] = {};   // FM_NET_EXTRACTOR_B + i: further parts of a split batch
     FlowState* flow = nullptr;
+    EncState* enc = nullptr;             // created by the first fm_frame_encode_jpeg / fm_jpeg_encode_bgr
     GalleryState* gallery[2] = {nullptr, nullptr};   // [FM_GALLERY_CHANNELS]
 
     // ---- event trace of the pipeline (fm_trace_start / fm_trace_read, scripts/trace_pipeline.py); empty = off
@@ -236,3 +238,4 @@ size_t fm_jpeg_sample_offset(long long coef_count);                             
 void fm_ext_invalidate_export(fm_ctx* ctx);
 void fm_predict_worker_free(fm_ctx* ctx);
 void fm_gallery_free(fm_ctx* ctx);
+void fm_jpegenc_free(fm_ctx* ctx);                                                                // jpegenc.hip

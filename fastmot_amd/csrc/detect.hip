@@ -1149,6 +1149,8 @@ bool is_pinned_range(const uint8_t* p, size_t bytes) {
 }
 }  // namespace
 
+bool fm_host_is_pinned(const void* p, size_t bytes) { return is_pinned_range((const uint8_t*)p, bytes); }   // (jpegenc.hip)
+
 extern "C" int fm_host_alloc(size_t bytes, void** out) {
     FM_CHECK_ARG(out && bytes > 0);
     void* p = nullptr;

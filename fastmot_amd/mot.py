@@ -186,6 +186,18 @@ class MOT:
             self._draw(frame, self._last_detections)
         self.frame_count += 1
 
+    def encode_frame(self, quality=75):
+        """The frame of the last `step` as the bytes of a baseline JPEG file (YCbCr 4:2:0; utils.jpeg.encode_bgr's format
+        and arithmetic), encoded from the copy the tracker used on the GPU -- whatever the frame was handed over as:
+        ndarray, NV12Frame, JPEGFrame, SourceFrame (the resized frame), DeviceFrame.  Nothing is uploaded, the step's
+        results and the frames prefetched for the next steps are untouched.  Overlays are not part of it: `draw` renders
+        on the host copy (write that one, VideoIO(gpu_encode=True) encodes it on the GPU as well)."""
+        if not 1 <= int(quality) <= 100:
+            raise ValueError(f'quality {quality} outside 1..100')
+        if self.frame_count == 0:
+            raise RuntimeError('encode_frame needs a step before it')
+        return self.tracker.ctx.frame_encode_jpeg(quality)
+
     def _prefetch_next(self):
         if self.detector_lookahead > 1:
             batch = self._lookahead.to_enqueue(self._next_frames)

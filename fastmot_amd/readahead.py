@@ -13,7 +13,8 @@ from .utils.motchallenge import write_rows
 def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False, lookahead=1):
     """stream: a started VideoIO; mot: a reset MOT (None: frames are only passed through); txt: an open text file for
     MOT Challenge result rows (app.py:91-97), needs `resize_to`; write_frames: stream.write(frame) after each step
-    (the frame carries the overlays when the MOT draws); lookahead: upcoming frames read ahead and handed to each step
+    (the frame carries the overlays when the MOT draws; a frame that lives on the GPU only -- VideoIO(gpu_encode=True) with
+    gpu_decode / gpu_resize -- is written as mot.encode_frame()); lookahead: upcoming frames read ahead and handed to each step
     as `next_frames` (a MOT with detector_lookahead = k batches up to k of them).  Returns the number of frames."""
     n = 0
     frame = stream.read()
@@ -30,7 +31,10 @@ def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False,
             if txt is not None:
                 write_rows(txt, mot.frame_count, mot.visible_tracks(), resize_to, stream.resolution)
         if write_frames:
-            stream.write(frame)
+            if mot is not None and getattr(stream, 'gpu_encode', False) and not hasattr(frame, '__array_interface__'):
+                stream.write(mot.encode_frame(stream.jpeg_quality))
+            else:
+                stream.write(frame)
         frame = upcoming.popleft()
         n += 1
     return n

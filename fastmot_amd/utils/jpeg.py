@@ -505,3 +505,58 @@ class JPEGFrame:
             setattr(hd, name, getattr(self.info, name))
         hd.hsamp, hd.vsamp = list(self.info.hsamp), list(self.info.vsamp)
         return coefficients_to_bgr(self.coef, self.qt, geometry(hd))
+
+
+# ---------------------------------------------------------------------------------------------- the native encoder
+def encode_bgr(frame, quality=75, ctx=None):
+    """BGR frame [H, W, 3] uint8 -> the bytes of a baseline JPEG file (YCbCr 4:2:0, Annex-K tables, a restart interval of
+    one MCU row), encoded on the GPU (csrc/jpegenc.hip) with libjpeg's arithmetic: the file equals Pillow's
+    `save(..., quality=quality, subsampling=2, restart_marker_rows=1)` byte for byte.
+    ctx: the HipContext to encode on (default: the process-wide one).  ValueError for a quality outside 1..100 or a
+    width / height outside 1..16384."""
+    if not 1 <= int(quality) <= 100:
+        raise ValueError(f'quality {quality} outside 1..100')
+    if ctx is None:
+        from ..runtime import get_context
+        ctx = get_context()
+    return ctx.jpeg_encode_bgr(frame, quality)
+
+
+def encode_bound(width, height):
+    """Largest file a width x height frame can become (0: a size the encoder does not take)."""
+    from .. import _lib
+    return _lib.load().fm_jpeg_encode_bound(C.c_int(width), C.c_int(height))
+
+
+def encode_tables(quality):
+    """(luminance, chrominance) quantisation tables of a quality, 64 values each, row-major (csrc/jpegenc_host.hip)."""
+    from .. import _lib
+    qt = np.zeros(128, np.uint16)
+    _lib.check(_lib.load().fm_jpeg_encode_tables(C.c_int(quality), _lib._ptr(qt)))
+    return qt[:64].copy(), qt[64:].copy()
+
+
+def encode_header(width, height, quality, capacity=None):
+    """The marker segments SOI .. SOS of the file the encoder writes for such a frame -> bytes."""
+    from .. import _lib
+    out = np.zeros(1024 if capacity is None else capacity, np.uint8)
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().fm_jpeg_encode_header(C.c_int(width), C.c_int(height), C.c_int(quality), _lib._ptr(out), C.c_size_t(out.size), C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def encode_assemble(width, height, quality, segments, capacity=None):
+    """The file from its entropy-coded, byte-stuffed MCU-row segments (a list of bytes) -> bytes (csrc/jpegenc_host.hip)."""
+    from .. import _lib
+    lens = np.array([len(s) for s in segments], np.uint32)
+    segs = np.zeros(max(sum((len(s) + 15) & ~15 for s in segments), 16), np.uint8)
+    at = 0
+    for s in segments:
+        segs[at:at + len(s)] = np.frombuffer(s, np.uint8)
+        at += (len(s) + 15) & ~15
+    cap = encode_bound(width, height) if capacity is None else capacity
+    out = np.zeros(max(cap, 1), np.uint8)
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().fm_jpeg_encode_assemble(C.c_int(width), C.c_int(height), C.c_int(quality), _lib._ptr(lens), _lib._ptr(segs),
+                                                   C.c_size_t(segs.size), _lib._ptr(out), C.c_size_t(cap), C.byref(n)))
+    return out[:n.value].tobytes()

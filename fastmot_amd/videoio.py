@@ -6,7 +6,8 @@ Sources this implementation can decode:
   * image sequences  'dir/%06d.jpg' (any format Pillow reads; the MOTChallenge layout)  -> Protocol.IMAGE
   * raw frame stacks '*.npy' ([N, H, W, 3] uint8 BGR, memory-mapped)                     -> Protocol.VIDEO
 Video containers, cameras and network streams need a decoder this image does not have; they raise
-NotImplementedError with the URI.  Outputs: image sequence ('out/%06d.png') or '*.npy'.
+NotImplementedError with the URI.  Outputs: image sequence ('out/%06d.png') or '*.npy'; with gpu_encode also
+'*.mjpeg' (concatenated JPEG files), and '%06d.jpg' sequences are encoded on the GPU.
 
 Frames are BGR uint8 like cv2's; a source whose size differs from `size` is resized with cv2.resize's
 INTER_LINEAR arithmetic (imgproc/resize.cpp: 11-bit fixed-point coefficients, exact 2x decimation =
@@ -128,7 +129,9 @@ class VideoIO:
                  buffer_size=10,
                  proc_fps=30,
                  gpu_decode=False,
-                 gpu_resize=False):
+                 gpu_resize=False,
+                 gpu_encode=False,
+                 jpeg_quality=75):
         """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` / `"gpu_resize": true`
         in the configuration file's stream_cfg reach it through an unmodified app.py):
         gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
@@ -141,7 +144,14 @@ class VideoIO:
             (MOT.step takes them like ndarrays) -- in place of being resized here, on the thread that calls `read`.
             A frame already at `size` comes back as it does today.  Together with gpu_decode, supported baseline JPEG
             files of ANY size come back as JPEGFrames, those of another size than `size` wrapped in a SourceFrame.
-            With an `output_uri` everything stays host pixels, as above."""
+            With an `output_uri` everything stays host pixels, as above.
+        gpu_encode (`"gpu_encode": true`; jpeg_quality 1..100 goes with it): `write(frame)` to a 'dir/%06d.jpg' / '.jpeg'
+            output encodes the frame on the GPU (utils.jpeg.encode_bgr: baseline 4:2:0 with libjpeg's arithmetic) in place
+            of the Pillow save, and an `output_uri` ending in '.mjpeg' -- the same files, one behind the other in one file
+            -- is accepted.  `write` then also takes `bytes` that already are a JPEG file (MOT.encode_frame: the frame
+            the tracker saw, encoded where it lies on the GPU) and writes them as they are; with such an output the
+            frames need not be host pixels, so gpu_decode / gpu_resize stay in effect.  '.png' and '.npy' outputs are
+            untouched by the flag; without it everything is as it was."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -157,9 +167,17 @@ class VideoIO:
         self.is_live = self.protocol != Protocol.IMAGE and self.protocol != Protocol.VIDEO
         self.gpu_decode = bool(gpu_decode)
         self.gpu_resize = bool(gpu_resize)
-        self._wrap_sources = self.gpu_resize and output_uri is None
+        self.gpu_encode = bool(gpu_encode)
+        self.jpeg_quality = int(jpeg_quality)
+        if self.gpu_encode and not 1 <= self.jpeg_quality <= 100:
+            raise ValueError(f'jpeg_quality {jpeg_quality} outside 1..100')
+        out = str(output_uri).lower() if output_uri is not None else ''
+        self._mjpeg_out = self.gpu_encode and out.endswith('.mjpeg')
+        self._jpeg_out = self._mjpeg_out or (self.gpu_encode and '%' in out and out.endswith(('.jpg', '.jpeg')))
+        host_pixels = output_uri is not None and not self._jpeg_out      # frames that Pillow / numpy write
+        self._wrap_sources = self.gpu_resize and not host_pixels
         if self.protocol == Protocol.IMAGE:
-            self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and output_uri is None else None,
+            self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and not host_pixels else None,
                                          any_size=self._wrap_sources)
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy'):
             self.source = _FrameStack(self.input_uri)
@@ -185,10 +203,13 @@ class VideoIO:
 
         self._written = 0
         self._stack = None
+        self._mjpeg = None
         if self.output_uri is not None:
             Path(self.output_uri).parent.mkdir(parents=True, exist_ok=True)
             if str(self.output_uri).endswith('.npy'):
                 self._stack = []
+            elif self._mjpeg_out:
+                self._mjpeg = open(self.output_uri, 'wb')
             elif '%' not in str(self.output_uri):
                 raise NotImplementedError(f'{self.output_uri}: video encoding needs an encoder '
                                           "(supported here: image sequences 'dir/%06d.png' and .npy)")
@@ -234,7 +255,22 @@ class VideoIO:
     def write(self, frame):
         """Writes the next video frame."""
         assert self.output_uri is not None
-        if self._stack is not None:
+        if self._jpeg_out:
+            if isinstance(frame, (bytes, bytearray, memoryview)):
+                data = bytes(frame)
+                if data[:2] != b'\xff\xd8':
+                    raise ValueError('bytes handed to write must be a JPEG file')
+            elif isinstance(frame, np.ndarray):
+                from .utils.jpeg import encode_bgr
+                data = encode_bgr(frame, self.jpeg_quality)
+            else:
+                raise TypeError(f'write takes host pixels or JPEG bytes; a {type(frame).__name__} lives on the GPU: '
+                                'write MOT.encode_frame() for it')
+            if self._mjpeg is not None:
+                self._mjpeg.write(data)
+            else:
+                Path(str(self.output_uri) % self._written).write_bytes(data)
+        elif self._stack is not None:
             self._stack.append(np.array(frame))
         else:
             from PIL import Image
@@ -244,6 +280,9 @@ class VideoIO:
     def release(self):
         """Cleans up input and output sources."""
         self.stop_capture()
+        if self._mjpeg is not None:
+            self._mjpeg.close()
+            self._mjpeg = None
         if self._stack is not None and self._stack:
             np.save(self.output_uri, np.stack(self._stack))
 

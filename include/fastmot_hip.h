@@ -526,6 +526,58 @@ int fm_frame_upload_src(fm_ctx* ctx, const struct fm_frame_src* src);
 int fm_frame_upload_ahead_src(fm_ctx* ctx, int k, const struct fm_frame_src* src);
 int fm_frame_ring_store_src(fm_ctx* ctx, int index, const struct fm_frame_src* src);
 
+/* Frames OUT as baseline JPEG (an output 'out/%06d.jpg' or 'out.mjpeg'): replaces the Pillow save of
+ * fastmot_amd/videoio.py's writer and, in the reference, cv2.VideoWriter (fastmot/videoio.py).  The device does
+ * everything that is per pixel or per coefficient (csrc/jpegenc.hip): BGR -> YCbCr, edge replication to the 16 x 16 MCU
+ * grid, 2 x 2 chroma averaging, forward DCT, quantisation, Huffman coding and 0xFF byte stuffing; the host writes the
+ * marker segments and concatenates the entropy-coded segments (csrc/jpegenc_host.hip).  Only compressed bytes cross to
+ * the host.
+ * The file: JFIF, 8-bit, three components YCbCr 4:2:0, the Annex-K quantisation tables scaled by `quality` with
+ * libjpeg's rule (s = quality < 50 ? 5000 / quality : 200 - 2 quality; (base s + 50) / 100 clamped to 1..255), the
+ * Annex-K Huffman tables, one interleaved scan, a restart interval of ONE MCU ROW (DRI = ceil(width / 16)): each MCU row
+ * is an independent, byte-aligned segment, which is what lets the device code all of them at once.  Marker order: SOI,
+ * APP0, DQT x 2, SOF0, DHT x 4, DRI, SOS -- Pillow's.  The arithmetic is libjpeg's, integer and exact (tests/jpegenc_ref.py
+ * states it in numpy): the file equals the one Pillow (libjpeg-turbo) writes with subsampling 4:2:0, the same quality and
+ * restart_marker_rows = 1 byte for byte, at sizes that are no multiple of 16 as well (the padded blocks).
+ *   Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,  Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   chroma sample = (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2 ... along the output columns; pixels right of the image
+ *     repeat the last column, chroma rows below it repeat the last averaged row (luma rows the last pixel row)
+ *   forward DCT: jfdctint's "islow" on samples - 128, rows first; quantised value = sign(c) ((|c| + 4 q) / (8 q))
+ *   a luma block wholly right of / below the last block column / row that holds image pixels: AC 0, DC of the block before it
+ *
+ * fm_jpeg_encode_bound: the largest file a width x height frame can become (every byte of the scan stuffed), 0 for a
+ * size outside 1..FM_SRC_MAX_DIM.  fm_jpeg_encode_tables: qt[128], the luminance then the chrominance table of a quality,
+ * row-major.  fm_jpeg_encode_header: the marker segments SOI .. SOS.  fm_jpeg_encode_assemble: the whole file from the
+ * ceil(height / 16) entropy-coded segments -- seg_len[r] bytes each, stuffed, segment r at the sum of the lengths before
+ * it each rounded up to 16 inside segs[0, segs_bytes) -- with RST0..7 between them and EOI behind.  These four need no
+ * fm_ctx and no GPU and may be called from any number of threads at once.
+ * fm_frame_encode_jpeg: the frame the context currently holds on the device (whatever it was uploaded as: BGR, NV12,
+ * JPEG, a resized source, a ring frame); nothing is uploaded.  fm_jpeg_encode_bgr: host pixels (width x height, `pitch`
+ * bytes between rows; e.g. a frame with overlays drawn on it), through a device staging buffer; pixels inside a buffer
+ * from fm_host_alloc with pitch = 3 width are copied from where they are, others through page-locked staging.
+ * Both run on a stream of the encoder's own and wait for no pipeline stream, nor does any pipeline stream wait for the
+ * encoder: the current frame is complete on the device when the call that made it current returned (the upload calls
+ * and fm_frame_promote_next synchronise the stream that carried its copy / conversion / resize).
+ * Both return when the file is complete in out[0, *length).  Working buffers (worst case: 208 bytes per 8 x 8 block
+ * before stuffing, twice that after, the latter once more in page-locked memory) are allocated on first use, regrown for a
+ * larger frame and freed by fm_ctx_destroy.  The caller must not upload the next current frame while fm_frame_encode_jpeg
+ * runs (MOT.step and MOT.encode_frame are called from one thread).
+ * FM_ERR_ARG for a quality outside 1..100, a width or height outside 1..FM_SRC_MAX_DIM, pitch < 3 width, no current
+ * frame, a null pointer, or a capacity smaller than the file -- *length then says what it needs and nothing is written
+ * past out + capacity.
+ * fm_jpeg_encode_stream_ms: HIP-event time of the kernels (and, for fm_jpeg_encode_bgr, not the copy) of the last
+ * encode of this context, -1 before the first. */
+size_t fm_jpeg_encode_bound(int width, int height);
+int fm_jpeg_encode_tables(int quality, uint16_t* qt);
+int fm_jpeg_encode_header(int width, int height, int quality, uint8_t* out, size_t capacity, size_t* length);
+int fm_jpeg_encode_assemble(int width, int height, int quality, const uint32_t* seg_len, const uint8_t* segs, size_t segs_bytes,
+                            uint8_t* out, size_t capacity, size_t* length);
+int fm_frame_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size_t capacity, size_t* length);
+int fm_jpeg_encode_bgr(fm_ctx* ctx, const uint8_t* pixels, int width, int height, size_t pitch, int quality, uint8_t* out,
+                       size_t capacity, size_t* length);
+int fm_jpeg_encode_stream_ms(fm_ctx* ctx, float* ms);
+
 /* ---------------------------------------------------------------- detector ------------ */
 #define FM_MAX_HEADS 4
 #define FM_MAX_ANCHORS 6   /* yolo_layer.h:11 */
