@@ -73,6 +73,40 @@ def check(rc):
         raise FastMOTHipError(f'libfastmot_hip error {rc}: {load().fm_last_error().decode()}')
 
 
+# fm_overlay_cmd (32 bytes): one primitive of an overlay command list (utils/overlay.py builds them)
+OVERLAY_CMD_DTYPE = np.dtype([('kind', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'),
+                              ('color', 'u1', (3,)), ('thickness', 'u1'), ('mask_off', '<u4'), ('reserved', '<i4')])
+assert OVERLAY_CMD_DTYPE.itemsize == 32
+OVL_RECT_FILL, OVL_RECT_OUTLINE, OVL_LINE, OVL_DOT, OVL_MASK = range(5)
+FM_OVERLAY_MAX_CMDS = 65536
+FM_OVERLAY_MAX_MASK_BYTES = 4 << 20
+FM_OVERLAY_MAX_COORD = 1 << 20
+
+
+def _overlay_args(cmds, masks):
+    cmds = np.ascontiguousarray(cmds, dtype=OVERLAY_CMD_DTYPE).reshape(-1)
+    masks = np.frombuffer(bytes(masks), np.uint8) if not isinstance(masks, np.ndarray) else np.ascontiguousarray(masks, np.uint8).reshape(-1)
+    return cmds, masks, (_ptr(cmds) if len(cmds) else None, C.c_int(len(cmds)), _ptr(masks) if len(masks) else None,
+                         C.c_size_t(len(masks)))
+
+
+def overlay_check(cmds, masks, width, height):
+    """fm_overlay_check's return code (0: well formed) for a command list on a width x height frame."""
+    cmds, masks, args = _overlay_args(cmds, masks)
+    return load().fm_overlay_check(*args, C.c_int(width), C.c_int(height))
+
+
+def overlay_render_host(frame, cmds, masks=b''):
+    """Applies an overlay command list to host pixels [H, W, 3] uint8 BGR IN PLACE on the CPU, with the functions the kernel
+    is compiled from (csrc/overlay_pixel.h).  No GPU."""
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or \
+            frame.strides[1:] != (3, 1) or frame.strides[0] < 3 * frame.shape[1] or not frame.flags.writeable:
+        raise ValueError('frame must be a writeable uint8 HxWx3 array with packed pixels')
+    cmds, masks, args = _overlay_args(cmds, masks)
+    check(load().fm_overlay_render_host(_ptr(frame), C.c_int(frame.shape[1]), C.c_int(frame.shape[0]), C.c_size_t(frame.strides[0]), *args))
+    return frame
+
+
 def device_count():
     n = load().fm_device_count()
     if n < 0:
@@ -614,6 +648,36 @@ def _bind_device_io(cls):
         check(self.lib.fm_jpeg_encode_stream_ms(self._ctx, C.byref(ms)))
         return ms.value if ms.value >= 0 else None
 
+    def frame_render_overlay(self, cmds, masks=b''):
+        """The frame the context holds on the device + an overlay command list (utils/overlay.py) -> the context's overlay
+        buffer; the frame itself is not written."""
+        cmds, masks, args = _overlay_args(cmds, masks)
+        check(self.lib.fm_frame_render_overlay(self._ctx, *args))
+
+    def overlay_read(self):
+        """The overlay buffer of the last frame_render_overlay -> ndarray [H, W, 3] uint8 BGR."""
+        if getattr(self, 'frame_size', None) is None:
+            raise FastMOTHipError('no frame on the device yet')
+        w, h = self.frame_size
+        out = np.empty((h, w, 3), np.uint8)
+        check(self.lib.fm_overlay_read(self._ctx, _ptr(out)))
+        return out
+
+    def overlay_encode_jpeg(self, quality=75):
+        """The overlay buffer as a baseline JPEG file -> bytes (frame_encode_jpeg's format)."""
+        if getattr(self, 'frame_size', None) is None:
+            raise FastMOTHipError('no frame on the device yet')
+        out = self._jpeg_out(*self.frame_size)
+        n = C.c_size_t(0)
+        check(self.lib.fm_overlay_encode_jpeg(self._ctx, C.c_int(int(quality)), _ptr(out), C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def overlay_stream_ms(self):
+        """HIP-event time of the last render's kernel, or None before the first."""
+        ms = C.c_float(0)
+        check(self.lib.fm_overlay_stream_ms(self._ctx, C.byref(ms)))
+        return ms.value if ms.value >= 0 else None
+
     def detect_configure(self, cfg):
         check(self.lib.fm_detect_configure(self._ctx, C.byref(cfg)))
 
@@ -677,6 +741,7 @@ def _bind_device_io(cls):
 
     for fn in (frame_configure, _nv12_args, _jpeg_args, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
+               frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,

@@ -85,6 +85,7 @@ struct DetState;     // detector pre/post (detect.hip)
 struct ExtState;     // extractor pre (extract.hip)
 struct FlowState;    // KLT (flow.hip)
 struct EncState;     // JPEG output path (jpegenc.hip)
+struct OvlState;     // overlays on the device frame (overlay.hip)
 struct GalleryState; // cross-stream ReID-gallery all-gather over RCCL (gallery.hip)
 constexpr int FM_GALLERY_CHANNELS = 2;
 
@@ -177,6 +178,7 @@ struct fm_ctx {
     NetState* ext_net_x[FM_MAX_EXTRA_EXTRACTORS] = {};   // FM_NET_EXTRACTOR_B + i: further parts of a split batch
     FlowState* flow = nullptr;
     EncState* enc = nullptr;             // created by the first fm_frame_encode_jpeg / fm_jpeg_encode_bgr
+    OvlState* ovl = nullptr;             // created by the first fm_frame_render_overlay
     GalleryState* gallery[2] = {nullptr, nullptr};   // [FM_GALLERY_CHANNELS]
 
     // ---- event trace of the pipeline (fm_trace_start / fm_trace_read, scripts/trace_pipeline.py); empty = off
@@ -239,3 +241,8 @@ void fm_ext_invalidate_export(fm_ctx* ctx);
 void fm_predict_worker_free(fm_ctx* ctx);
 void fm_gallery_free(fm_ctx* ctx);
 void fm_jpegenc_free(fm_ctx* ctx);                                                                // jpegenc.hip
+int fm_jpegenc_ensure(fm_ctx* ctx, int mcus_x, int mcus_y);   // the encoder's stream, and its buffers for that many MCUs
+hipStream_t fm_jpegenc_stream(fm_ctx* ctx);                   // null before the first fm_jpegenc_ensure
+int fm_jpegenc_encode_device(fm_ctx* ctx, const uint8_t* src, int width, int height, int quality, uint8_t* out, size_t capacity,
+                             size_t* length);                 // packed BGR in device memory, ordered by the encoder's stream
+void fm_overlay_free(fm_ctx* ctx);                                                                // overlay.hip

@@ -183,6 +183,7 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_jpeg)
         if (e) (void)hipEventDestroy(e);
     fm_frame_src_free(ctx);
+    fm_overlay_free(ctx);        // (before the encoder: it works on the encoder's stream)
     fm_jpegenc_free(ctx);
     if (ctx->det_net) fm_net_free(ctx->det_net);
     if (ctx->ext_net) fm_net_free(ctx->ext_net);

@@ -480,6 +480,15 @@ void fm_jpegenc_free(fm_ctx* ctx) {
     ctx->enc = nullptr;
 }
 
+// For overlay.hip, which renders on the encoder's stream and encodes its own buffer
+int fm_jpegenc_ensure(fm_ctx* ctx, int mcus_x, int mcus_y) { return ensure(ctx, mcus_x, mcus_y); }
+hipStream_t fm_jpegenc_stream(fm_ctx* ctx) { return ctx->enc ? ctx->enc->s : nullptr; }
+int fm_jpegenc_encode_device(fm_ctx* ctx, const uint8_t* src, int width, int height, int quality, uint8_t* out, size_t capacity, size_t* length) {
+    FM_CHECK_ARG(args_ok(width, height, quality));
+    if (int rc = ensure(ctx, (width + 15) / 16, (height + 15) / 16)) return rc;
+    return encode(ctx, src, width, height, (long long)width * 3, quality, out, capacity, length);
+}
+
 extern "C" int fm_frame_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size_t capacity, size_t* length) {
     FM_CHECK_ARG(ctx && out && length && ctx->frame_cur && args_ok(ctx->frame_w, ctx->frame_h, quality));
     if (int rc = ensure(ctx, (ctx->frame_w + 15) / 16, (ctx->frame_h + 15) / 16)) return rc;

@@ -19,6 +19,7 @@ from .flow import Flow
 from .utils import Profiler
 from .utils.source import SourceFrame
 from .utils.visualization import Visualizer
+from .utils.overlay import build_commands
 
 LOGGER = logging.getLogger(__name__)
 _NATIVE_FLOW = True      # tests flip this to compare the native prediction worker with the Python-thread path
@@ -82,12 +83,20 @@ class MOT:
                  tracker_cfg=None,
                  visualizer_cfg=None,
                  draw=False,
-                 detector_lookahead=1):
+                 detector_lookahead=1,
+                 gpu_draw=False):
         """Top level module that integrates detection, feature extraction and tracking
         (parameters: fastmot/mot.py:37-67).  `draw=True` renders the overlays of `visualizer_cfg` onto every
         frame handed to `step` as a host ndarray, in place, after tracking (mot.py:166-167,191-196).
         `detector_lookahead=k` (not in the reference; YOLO with detector_frame_skip 1 only): the detector runs one
-        network pass over the next k frames handed to `step` as `next_frames` (DetectorLookahead); results unchanged."""
+        network pass over the next k frames handed to `step` as `next_frames` (DetectorLookahead); results unchanged.
+        `gpu_draw=True` (not in the reference; excludes `draw`): the same overlays, rendered on the GPU onto a COPY of the
+        frame the tracker holds there -- whatever the frame was handed over as -- when `render_frame` or `encode_frame`
+        asks for them; `step` itself draws nothing and the frame handed to it is not touched."""
+        if draw and gpu_draw:
+            raise ValueError('draw=True renders on the host frame, gpu_draw=True on the GPU copy: choose one')
+        self.gpu_draw = gpu_draw
+        self._overlay_rendered = False
         self.size = size
         self.detector_type = DetectorType[detector_type.upper()]
         assert detector_frame_skip >= 1
@@ -167,6 +176,7 @@ class MOT:
         if self.draw and isinstance(frame, SourceFrame):
             raise ValueError('draw=True needs host pixels at the tracker\'s size: a SourceFrame is resized on the GPU')
         bind_frame(ctx, frame, self.size, begin_step=True)
+        self._overlay_rendered = False
         ctx.in_step = True
         if next_frames is not None:
             next_frames = list(next_frames)
@@ -186,17 +196,42 @@ class MOT:
             self._draw(frame, self._last_detections)
         self.frame_count += 1
 
-    def encode_frame(self, quality=75):
+    def encode_frame(self, quality=75, overlays=None):
         """The frame of the last `step` as the bytes of a baseline JPEG file (YCbCr 4:2:0; utils.jpeg.encode_bgr's format
         and arithmetic), encoded from the copy the tracker used on the GPU -- whatever the frame was handed over as:
         ndarray, NV12Frame, JPEGFrame, SourceFrame (the resized frame), DeviceFrame.  Nothing is uploaded, the step's
-        results and the frames prefetched for the next steps are untouched.  Overlays are not part of it: `draw` renders
-        on the host copy (write that one, VideoIO(gpu_encode=True) encodes it on the GPU as well)."""
+        results and the frames prefetched for the next steps are untouched.  `overlays` (default: `gpu_draw`): encode the
+        frame with the overlays of `render_frame` on it instead of the bare frame.  (`draw=True` renders on the host copy:
+        write that one, VideoIO(gpu_encode=True) encodes it on the GPU as well.)"""
         if not 1 <= int(quality) <= 100:
             raise ValueError(f'quality {quality} outside 1..100')
         if self.frame_count == 0:
             raise RuntimeError('encode_frame needs a step before it')
+        if self.gpu_draw if overlays is None else overlays:
+            self._render_overlay()
+            return self.tracker.ctx.overlay_encode_jpeg(quality)
         return self.tracker.ctx.frame_encode_jpeg(quality)
+
+    def render_frame(self):
+        """The frame of the last `step` with the overlays of `visualizer_cfg` on it, as an HxWx3 uint8 BGR ndarray: what
+        `draw=True` leaves in a host frame, rendered on the GPU (csrc/overlay.hip) from the state the step left, onto a
+        copy of the frame the tracker holds there.  Works for every frame kind; the tracker's frame and the caller's
+        array are not written.  Valid until the next `step`, like `encode_frame`; the list is built and rendered once
+        per step, by whichever of the two comes first."""
+        if self.frame_count == 0:
+            raise RuntimeError('render_frame needs a step before it')
+        self._render_overlay()
+        return self.tracker.ctx.overlay_read()
+
+    def _render_overlay(self):
+        if self._overlay_rendered:
+            return
+        visible = list(self.visible_tracks())
+        cmds, masks = build_commands(self.visualizer, visible, self._last_detections, self.tracker.klt_bboxes.values(),
+                                     self.tracker.flow.prev_bg_keypoints, self.tracker.flow.bg_keypoints,
+                                     f'visible: {len(visible)}', self.size)
+        self.tracker.ctx.frame_render_overlay(cmds, masks)
+        self._overlay_rendered = True
 
     def _prefetch_next(self):
         if self.detector_lookahead > 1:

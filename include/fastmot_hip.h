@@ -578,6 +578,73 @@ int fm_jpeg_encode_bgr(fm_ctx* ctx, const uint8_t* pixels, int width, int height
                        size_t capacity, size_t* length);
 int fm_jpeg_encode_stream_ms(fm_ctx* ctx, float* ms);
 
+/* Overlays ON the device frame (boxes, labels, trajectories, flow matches, covariance ellipses, the caption): replaces
+ * Visualizer.render (fastmot_amd/utils/visualization.py; in the reference fastmot/utils/visualization.py on cv2) for a
+ * frame whose pixels never were on the host.  The caller states the picture as a COMMAND LIST in painter's order -- a
+ * later command paints over an earlier one --, a kernel (csrc/overlay.hip) applies the list to a COPY of the current
+ * device frame, and that copy, the context's overlay buffer, is what fm_overlay_read downloads and
+ * fm_overlay_encode_jpeg encodes.  The tracker's frame is never written: the next step's KLT and the ReID crops read it.
+ * The rasterisation is Pillow's (ImageDraw of 12.2.0, which visualization.py draws with), restated in integers in
+ * csrc/overlay_pixel.h -- one text for the kernel and for fm_overlay_render_host -- and in numpy in tests/overlay_ref.py:
+ *   FM_OVL_RECT_FILL     every pixel of [x0, x1] x [y0, y1], corners inclusive; nothing when x1 < x0 or y1 < y0.
+ *   FM_OVL_RECT_OUTLINE  `thickness` t rings growing INWARD: rows y0 + i and y1 - i over [x0, x1], and columns x0 + i and
+ *                        x1 - i (i < t) over the rows y0 + t .. y1 - t, or, when that range is empty (a box lower than
+ *                        2 t), over y1 - t + 2 .. y0 + t: Pillow draws those columns as lines without their last point
+ *                        from y0 + t towards y1 - t + 1, which is what makes a degenerate box spill past its corners.
+ *   FM_OVL_LINE          Bresenham from (x0, y0) to (x1, y1), both ends drawn: x-major when |dx| > |dy|, else y-major;
+ *                        i steps along the major axis from the START the minor offset is (2 minor i + major) / (2 major)
+ *                        in integer division (the closed form of the error term e = 2 minor - major, step when e >= 0).
+ *   FM_OVL_DOT           the five pixels (x0, y0), (x0 +- 1, y0), (x0, y0 +- 1): Pillow's ellipse of radius 1.
+ *   FM_OVL_MASK          an 8-bit alpha mask of x1 columns by y1 rows (row-major at masks + mask_off) with its top left
+ *                        pixel at (x0, y0), blended per channel: t = m ink + (255 - m) bg + 128, (t + (t >> 8)) >> 8.
+ *                        Text arrives this way (the glyph mask of the caller's font): the library knows no font.
+ * Colours are B, G, R.  Coordinates may lie anywhere in +-FM_OVERLAY_MAX_COORD, inside the frame or not; pixels
+ * outside it are clipped, intermediate products are 64-bit.
+ *
+ * fm_overlay_check: 0 when the list is well formed for a width x height frame; FM_ERR_ARG for a null list with n > 0, a
+ * null blob with mask_bytes > 0, n > FM_OVERLAY_MAX_CMDS, mask_bytes > FM_OVERLAY_MAX_MASK_BYTES, a width or height
+ * outside 1..FM_SRC_MAX_DIM, an unknown kind, a thickness outside 1..8 (FM_OVL_RECT_OUTLINE), a coordinate outside
+ * +-FM_OVERLAY_MAX_COORD, a mask whose columns or rows are negative or above FM_OVERLAY_MAX_COORD or whose x1 * y1 bytes
+ * do not lie inside [mask_off, mask_bytes).  It reads the list only, needs no context and no GPU and may be called from
+ * any number of threads; every entry point below calls it first and does nothing else when it fails.
+ * fm_overlay_render_host: applies the list IN PLACE to host pixels (width x height BGR, `pitch` >= 3 width bytes between
+ * rows) with the functions of overlay_pixel.h: the CPU statement of the kernel's arithmetic.  No context, no GPU.
+ * fm_frame_render_overlay: current device frame + list -> the context's overlay buffer (n == 0: a copy).  One kernel:
+ * a workgroup owns a 64 x 16 tile, bins the list against it 256 commands at a time in list order and applies the hits
+ * to its pixels in registers; every pixel is read once and written once.  The list and the masks travel through
+ * page-locked staging of the context; staging, device copies and the overlay buffer (3 width height bytes) are allocated
+ * on first use, regrown on demand and freed by fm_ctx_destroy.  Everything runs on the JPEG encoder's stream (created on
+ * first use, as by fm_frame_encode_jpeg), so a following fm_overlay_encode_jpeg is ordered behind it; no pipeline
+ * stream waits or is waited for -- fm_frame_encode_jpeg's argument for why the current frame is complete holds
+ * unchanged.  Returns when the buffer is complete.  FM_ERR_ARG without a current frame.
+ * fm_overlay_read: the overlay buffer -> out[3 width height]; FM_ERR_ARG before the first render at the current frame
+ * size.  fm_overlay_encode_jpeg: fm_frame_encode_jpeg's contract with the overlay buffer as the source.
+ * fm_overlay_stream_ms: HIP-event time of the last render's kernel (not the copies of list and masks), -1 before the
+ * first.  The caller must not upload the next current frame while fm_frame_render_overlay runs. */
+#define FM_OVL_RECT_FILL 0
+#define FM_OVL_RECT_OUTLINE 1
+#define FM_OVL_LINE 2
+#define FM_OVL_DOT 3
+#define FM_OVL_MASK 4
+#define FM_OVERLAY_MAX_CMDS 65536
+#define FM_OVERLAY_MAX_MASK_BYTES (4u << 20)
+#define FM_OVERLAY_MAX_COORD (1 << 20)
+typedef struct fm_overlay_cmd {   /* 32 bytes */
+    int32_t kind;                 /* FM_OVL_* */
+    int32_t x0, y0, x1, y1;       /* see above; FM_OVL_MASK: x1 columns, y1 rows */
+    uint8_t b, g, r;              /* colour; FM_OVL_MASK: the ink */
+    uint8_t thickness;            /* FM_OVL_RECT_OUTLINE: 1..8; others: ignored */
+    uint32_t mask_off;            /* FM_OVL_MASK: offset of the mask's first byte in the blob */
+    int32_t reserved;             /* 0 */
+} fm_overlay_cmd;
+int fm_overlay_check(const fm_overlay_cmd* cmds, int n, const uint8_t* masks, size_t mask_bytes, int width, int height);
+int fm_overlay_render_host(uint8_t* pixels, int width, int height, size_t pitch, const fm_overlay_cmd* cmds, int n,
+                           const uint8_t* masks, size_t mask_bytes);
+int fm_frame_render_overlay(fm_ctx* ctx, const fm_overlay_cmd* cmds, int n, const uint8_t* masks, size_t mask_bytes);
+int fm_overlay_read(fm_ctx* ctx, uint8_t* out);
+int fm_overlay_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size_t capacity, size_t* length);
+int fm_overlay_stream_ms(fm_ctx* ctx, float* ms);
+
 /* ---------------------------------------------------------------- detector ------------ */
 #define FM_MAX_HEADS 4
 #define FM_MAX_ANCHORS 6   /* yolo_layer.h:11 */
