@@ -14,8 +14,9 @@ from .track import Track
 from .utils.nv12 import NV12Frame
 from .utils.jpeg import JPEGFrame
 from .utils.source import SourceFrame
+from .utils.yuv import PlanarFrame, I420Image
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'models']
 
 
 def __getattr__(name):

@@ -15,6 +15,7 @@ from types import SimpleNamespace
 from .utils.nv12 import NV12Frame
 from .utils.jpeg import JPEGFrame, QT_ENTRIES, max_coefficients
 from .utils.source import SourceFrame
+from .utils.yuv import PlanarFrame, frame_bytes
 
 LIB_PATH = Path(os.environ.get('FASTMOT_LIB_PATH', Path(__file__).parent / 'libfastmot_hip.so'))
 
@@ -49,6 +50,7 @@ def load():
         raise RuntimeError(f'Unable to load {LIB_PATH}') from err
     lib.fm_last_error.restype = C.c_char_p
     lib.fm_jpeg_encode_bound.restype = C.c_size_t
+    lib.fm_i420_bound.restype = C.c_size_t
     _lib = lib
     return lib
 
@@ -434,6 +436,7 @@ SOLVER_GREEDY = 1
 
 # ---------------------------------------------------------------------- detector / extractor
 FM_MAX_HEADS, FM_MAX_ANCHORS = 4, 6
+FM_EXPORT_FRAME, FM_EXPORT_OVERLAY = 0, 1     # fm_frame_export_i420's `which` (fastmot_hip.h)
 FM_MAX_DET_BATCH = 4         # frames of one batched detector pass (fastmot_hip.h)
 
 
@@ -500,7 +503,23 @@ def _bind_device_io(cls):
             raise ValueError(f'JPEG frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames {self.frame_size[0]}x{self.frame_size[1]}')
         return C.byref(frame.info), _ptr(frame.coef), _ptr(frame.qt)
 
+    def _planar_of(self, frame):
+        """The PlanarFrame a planar call takes for `frame` -- a PlanarFrame of the context's size, or a SourceFrame around
+        one of any size (fm_frame_*_planar resizes it on the device) --, or None for every other frame kind."""
+        if isinstance(frame, SourceFrame) and isinstance(frame.frame, PlanarFrame):
+            return frame.frame
+        if isinstance(frame, PlanarFrame):
+            if frame.size != tuple(self.frame_size):
+                raise ValueError(f'planar frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
+                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
+            return frame
+        return None
+
     def frame_upload(self, frame):
+        planar = self._planar_of(frame)
+        if planar is not None:
+            check(self.lib.fm_frame_upload_planar(self._ctx, C.byref(planar.describe())))
+            return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_nv12(self._ctx, *self._nv12_args(frame)))
             return
@@ -545,7 +564,19 @@ def _bind_device_io(cls):
         buf = pinned_empty(self.lib, (n, max_coefficients(w, h) + QT_ENTRIES), np.int16)
         return [buf[i] for i in range(n)]
 
+    def pinned_planar_frames(self, n, chroma='420', matrix='bt601'):
+        """n PlanarFrames of the context's frame size, each one contiguous Y, U, V surface in page-locked host memory
+        (fm_host_alloc): fill `f.y[...]` / `f.u[...]` / `f.v[...]`; they are uploaded in one copy, without a staging copy.
+        The buffer lives as long as any of them."""
+        size = tuple(self.frame_size)
+        buf = pinned_empty(self.lib, (n, frame_bytes(size, chroma)), np.uint8)
+        return [PlanarFrame.from_buffer(buf[i], size, chroma, matrix) for i in range(n)]
+
     def frame_ring_store(self, index, frame):
+        planar = self._planar_of(frame)
+        if planar is not None:
+            check(self.lib.fm_frame_ring_store_planar(self._ctx, C.c_int(index), C.byref(planar.describe())))
+            return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_ring_store_nv12(self._ctx, C.c_int(index), *self._nv12_args(frame)))
             return
@@ -562,7 +593,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
 
     def frame_upload_next(self, frame):
-        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame)):
+        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame, PlanarFrame)):
             return self.frame_upload_ahead(1, frame)
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -581,6 +612,10 @@ def _bind_device_io(cls):
 
     def frame_upload_ahead(self, k, frame):
         """Host frame for the step k steps ahead (look-ahead slot k, 1 <= k <= FM_MAX_DET_BATCH; k = 1: frame_upload_next)."""
+        planar = self._planar_of(frame)
+        if planar is not None:
+            check(self.lib.fm_frame_upload_ahead_planar(self._ctx, C.c_int(k), C.byref(planar.describe())))
+            return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_ahead_nv12(self._ctx, C.c_int(k), *self._nv12_args(frame)))
             return
@@ -641,6 +676,42 @@ def _bind_device_io(cls):
         check(self.lib.fm_jpeg_encode_bgr(self._ctx, _ptr(frame), C.c_int(w), C.c_int(h), C.c_size_t(frame.strides[0]), C.c_int(int(quality)),
                                           _ptr(out), C.c_size_t(out.size), C.byref(n)))
         return out[:n.value].tobytes()
+
+    def _i420_out(self, width, height):
+        bound = self.lib.fm_i420_bound(C.c_int(width), C.c_int(height))
+        if not bound:
+            raise ValueError(f'frame size {width}x{height} outside 1..16384')
+        return np.empty(bound, np.uint8)
+
+    def _export_i420(self, which):
+        if getattr(self, 'frame_size', None) is None:
+            raise FastMOTHipError('no frame on the device yet')
+        out = self._i420_out(*self.frame_size)
+        n = C.c_size_t(0)
+        check(self.lib.fm_frame_export_i420(self._ctx, C.c_int(which), _ptr(out), C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value]
+
+    def frame_export_i420(self):
+        """The frame the context holds on the device (the one bound last) as planar 4:2:0 -> 1-D uint8 array: Y, then U,
+        then V (utils.yuv.bgr_to_planar420 of frame_read(), converted on the GPU; 1.5 bytes per pixel come back)."""
+        return self._export_i420(FM_EXPORT_FRAME)
+
+    def overlay_export_i420(self):
+        """The overlay buffer of the last frame_render_overlay as planar 4:2:0 (frame_export_i420's format)."""
+        return self._export_i420(FM_EXPORT_OVERLAY)
+
+    def i420_from_bgr(self, frame):
+        """Host pixels [H, W, 3] uint8 BGR (rows may be strided) as planar 4:2:0, converted on the GPU -> 1-D uint8 array."""
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError('frame must be a uint8 HxWx3 array')
+        if frame.strides[1:] != (3, 1) or frame.strides[0] < 3 * frame.shape[1]:
+            frame = np.ascontiguousarray(frame)
+        h, w = frame.shape[:2]
+        out = self._i420_out(w, h)
+        n = C.c_size_t(0)
+        check(self.lib.fm_i420_from_bgr(self._ctx, _ptr(frame), C.c_int(w), C.c_int(h), C.c_size_t(frame.strides[0]), _ptr(out),
+                                        C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value]
 
     def jpeg_encode_stream_ms(self):
         """HIP-event time of the kernels of the last encode, or None before the first."""
@@ -739,7 +810,8 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, _nv12_args, _jpeg_args, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
+    for fn in (frame_configure, _nv12_args, _jpeg_args, _planar_of, pinned_planar_frames, _i420_out, _export_i420, frame_export_i420,
+               overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,

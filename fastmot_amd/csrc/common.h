@@ -86,6 +86,7 @@ struct ExtState;     // extractor pre (extract.hip)
 struct FlowState;    // KLT (flow.hip)
 struct EncState;     // JPEG output path (jpegenc.hip)
 struct OvlState;     // overlays on the device frame (overlay.hip)
+struct YuvState;     // I420 export (yuv.hip)
 struct GalleryState; // cross-stream ReID-gallery all-gather over RCCL (gallery.hip)
 constexpr int FM_GALLERY_CHANNELS = 2;
 
@@ -179,6 +180,7 @@ struct fm_ctx {
     FlowState* flow = nullptr;
     EncState* enc = nullptr;             // created by the first fm_frame_encode_jpeg / fm_jpeg_encode_bgr
     OvlState* ovl = nullptr;             // created by the first fm_frame_render_overlay
+    YuvState* yuv = nullptr;             // created by the first fm_frame_export_i420 / fm_i420_from_bgr
     GalleryState* gallery[2] = {nullptr, nullptr};   // [FM_GALLERY_CHANNELS]
 
     // ---- event trace of the pipeline (fm_trace_start / fm_trace_read, scripts/trace_pipeline.py); empty = off
@@ -194,6 +196,9 @@ struct fm_ctx {
     // [0] fm_frame_upload_nv12, [k] look-ahead slot k, [FM_MAX_DET_BATCH + 1] fm_frame_ring_store_nv12.  Unlike the
     // slots' BGR buffers these stay where they are at a promote: copy and kernel of a slot share one stream.
     uint8_t* frame_nv12[FM_MAX_DET_BATCH + 2] = {};
+    // ... and of planar frames of the configured size (fm_frame_*_planar; csrc/yuv.hip converts out of it), entries and
+    // rules as frame_nv12's; sized for the largest layout, 4:4:4.  (Planar frames of another size use frame_src below.)
+    uint8_t* frame_planar[FM_MAX_DET_BATCH + 2] = {};
 
     // ---- device staging of entropy-decoded JPEG frames (coefficients, quantisation tables and the sample planes
     // csrc/jpeg.hip makes of them), entries as frame_nv12's, allocated on first JPEG use for the largest layout of the
@@ -231,6 +236,18 @@ inline void fm_trace_mark(fm_ctx* ctx, hipStream_t s, int tag) {
 
 int fm_ensure_slots(fm_ctx* ctx, int max_slot_plus_1);
 int fm_nv12_to_bgr(const uint8_t* nv12, uint8_t* bgr, int w, int h, int matrix, hipStream_t s);   // nv12.hip
+// width x height of the U and V planes of a w x h frame (0 x 0 for FM_YUV_MONO); false for an unknown `chroma`
+inline bool fm_yuv_chroma_dims(int w, int h, int chroma, int* cw, int* ch) {
+    switch (chroma) {
+    case FM_YUV_420: *cw = (w + 1) / 2, *ch = (h + 1) / 2; return true;
+    case FM_YUV_422: *cw = (w + 1) / 2, *ch = h; return true;
+    case FM_YUV_444: *cw = w, *ch = h; return true;
+    case FM_YUV_MONO: *cw = *ch = 0; return true;
+    }
+    return false;
+}
+int fm_planar_to_bgr(const uint8_t* planes, uint8_t* bgr, int w, int h, int chroma, int matrix, hipStream_t s);   // yuv.hip
+void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
 void fm_frame_src_free(fm_ctx* ctx);                                                              // detect.hip
 int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s);   // jpeg.hip

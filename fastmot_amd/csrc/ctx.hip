@@ -176,6 +176,8 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
     }
     for (uint8_t* p : ctx->frame_nv12)
         if (p) (void)hipFree(p);
+    for (uint8_t* p : ctx->frame_planar)
+        if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_jpeg)
         if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_jpeg_pinned)
@@ -184,6 +186,7 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     fm_frame_src_free(ctx);
     fm_overlay_free(ctx);        // (before the encoder: it works on the encoder's stream)
+    fm_yuv_free(ctx);            // (likewise)
     fm_jpegenc_free(ctx);
     if (ctx->det_net) fm_net_free(ctx->det_net);
     if (ctx->ext_net) fm_net_free(ctx->ext_net);

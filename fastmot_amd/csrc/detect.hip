@@ -1114,6 +1114,10 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         if (p) (void)hipFree(p);
         p = nullptr;
     }
+    for (uint8_t*& p : ctx->frame_planar) {            // planar staging: allocated again on first planar use
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
     for (uint8_t*& p : ctx->frame_jpeg) {              // JPEG staging: allocated again on first JPEG use
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -1708,6 +1712,123 @@ extern "C" int fm_frame_ring_store_src(fm_ctx* ctx, int index, const struct fm_f
     // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies, then the kernels on the
     // null stream
     int rc = enqueue_src(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, src, nullptr, true);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+// ---- planar YCbCr ingest (struct fm_frame_planar: what software decoders hand out, and a YUV4MPEG2 frame): the three
+// host-frame entry points once more.  Same slots, streams, syncs and events as their BGR counterparts.  A frame of the
+// configured size goes through ctx->frame_planar[entry] and the kernel of yuv.hip writes the BGR frame; a frame of any
+// other size takes the route of fm_frame_*_src with that path's buffers (ctx->frame_src[entry]): yuv.hip writes the
+// source-size BGR frame, resize.hip the frame.
+static bool planar_ok(const struct fm_frame_planar* f) {
+    if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
+    int cw = 0, ch = 0;
+    if (!fm_yuv_chroma_dims(f->width, f->height, f->chroma, &cw, &ch)) return false;
+    if (f->matrix != FM_NV12_BT601 && f->matrix != FM_NV12_BT709) return false;
+    if (!f->y || f->pitch_y < f->width) return false;
+    return f->chroma == FM_YUV_MONO || (f->u && f->v && f->pitch_c >= cw);
+}
+
+// H2D copy of the planes, rows packed to their width, into device staging, the conversion and -- off size -- the resize
+// into `dst`, all on `s`.  On size: planes that cannot be copied from where they are go through `pinned` (the slot's
+// BGR-sized staging) after `reuse`, the event behind the previous copy out of it, when one is given.  `blocking`:
+// blocking copies from where the planes lie (fm_frame_ring_store_planar).
+static int enqueue_planar(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_planar* f, uint8_t* pinned, hipEvent_t reuse,
+                          hipStream_t s, bool blocking) {
+    const int w = f->width, h = f->height;
+    int cw = 0, ch = 0;
+    fm_yuv_chroma_dims(w, h, f->chroma, &cw, &ch);
+    const size_t npx = (size_t)w * h, nc = (size_t)cw * ch, total = npx + 2 * nc;
+    const bool on_size = w == ctx->frame_w && h == ctx->frame_h;
+    fm_ctx::SrcStage& st = ctx->frame_src[entry];
+    uint8_t* stage = nullptr;
+    int rc;
+    if (on_size) {
+        uint8_t*& p = ctx->frame_planar[entry];
+        if (!p) FM_HIP(hipMalloc(&p, npx * 3));
+        stage = p;
+    } else {
+        if ((rc = src_reserve(st.bgr, st.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s))) return rc;     // (resize.hip reads 8 bytes at a pixel)
+        if ((rc = src_reserve(st.dev, st.dev_cap, total, false, s))) return rc;
+        stage = st.dev;
+    }
+    const bool one_surface = f->pitch_y == w && (!nc || (f->pitch_c == cw && f->u == f->y + npx && f->v == f->u + nc));
+    if (blocking) {
+        FM_HIP(hipMemcpy2D(stage, w, f->y, f->pitch_y, w, h, hipMemcpyHostToDevice));
+        if (nc) {
+            FM_HIP(hipMemcpy2D(stage + npx, cw, f->u, f->pitch_c, cw, ch, hipMemcpyHostToDevice));
+            FM_HIP(hipMemcpy2D(stage + npx + nc, cw, f->v, f->pitch_c, cw, ch, hipMemcpyHostToDevice));
+        }
+    } else if (one_surface && is_pinned_range(f->y, total)) {
+        FM_HIP(hipMemcpyAsync(stage, f->y, total, hipMemcpyHostToDevice, s));
+    } else {
+        uint8_t* pin = pinned;
+        if (on_size) {
+            if (reuse) FM_HIP(hipEventSynchronize(reuse));
+        } else {
+            if ((rc = src_pinned(st, total, s))) return rc;
+            pin = st.pinned;
+        }
+        for (int r = 0; r < h; ++r) memcpy(pin + (size_t)r * w, f->y + (size_t)r * f->pitch_y, w);
+        for (int r = 0; r < ch; ++r) {
+            memcpy(pin + npx + (size_t)r * cw, f->u + (size_t)r * f->pitch_c, cw);
+            memcpy(pin + npx + nc + (size_t)r * cw, f->v + (size_t)r * f->pitch_c, cw);
+        }
+        FM_HIP(hipMemcpyAsync(stage, pin, total, hipMemcpyHostToDevice, s));
+        if (!on_size && (rc = src_pinned_copied(st, s))) return rc;
+    }
+    fm_trace_mark(ctx, s, 39);                 // (the conversion's share of the caller's 30 .. 31 interval)
+    if (on_size) return fm_planar_to_bgr(stage, dst, w, h, f->chroma, f->matrix, s);
+    if ((rc = fm_planar_to_bgr(stage, st.bgr, w, h, f->chroma, f->matrix, s))) return rc;
+    fm_trace_mark(ctx, s, 38);                 // (the resize's share)
+    return fm_resize_bgr(st.bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+}
+
+extern "C" int fm_frame_upload_planar(fm_ctx* ctx, const struct fm_frame_planar* f) {
+    FM_CHECK_ARG(ctx && ctx->frame_own && planar_ok(f));
+    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    int rc = enqueue_planar(ctx, 0, ctx->frame_own, f, ctx->frame_pinned, nullptr, ctx->s_det, false);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
+    ctx->frame_cur = ctx->frame_own;
+    return 0;
+}
+
+extern "C" int fm_frame_upload_ahead_planar(fm_ctx* ctx, int k, const struct fm_frame_planar* f) {
+    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && planar_ok(f));
+    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (the BGR-sized staging holds every planar layout)
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
+    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the LAST kernel: a reader
+    // that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.
+    hipStream_t cs = ctx->s_ext;
+    fm_trace_mark(ctx, cs, 30);
+    int rc = enqueue_planar(ctx, k, buf, f, ahead_pinned(ctx, k), ev, cs, false);
+    if (rc) return rc;
+    fm_trace_mark(ctx, cs, 31);
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
+    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
+    ahead_frame(ctx, k) = buf;
+    return 0;
+}
+
+extern "C" int fm_frame_ring_store_planar(fm_ctx* ctx, int index, const struct fm_frame_planar* f) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && planar_ok(f));
+    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies that pack the rows, then
+    // the kernels on the null stream
+    int rc = enqueue_planar(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr,
+                            nullptr, nullptr, true);
     if (rc) return rc;
     FM_HIP(hipStreamSynchronize(nullptr));
     return 0;

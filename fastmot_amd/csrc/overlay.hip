@@ -190,6 +190,12 @@ extern "C" int fm_overlay_read(fm_ctx* ctx, uint8_t* out) {
     return 0;
 }
 
+// For yuv.hip (fm_frame_export_i420): the picture fm_overlay_read would download, or null when there is none
+const uint8_t* fm_overlay_buffer(fm_ctx* ctx) {
+    const OvlState* o = ctx->ovl;
+    return o && o->w > 0 && o->w == ctx->frame_w && o->h == ctx->frame_h ? o->buf : nullptr;
+}
+
 extern "C" int fm_overlay_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size_t capacity, size_t* length) {
     FM_CHECK_ARG(ctx && out && length && ctx->ovl && ctx->ovl->w == ctx->frame_w && ctx->ovl->h == ctx->frame_h && ctx->ovl->w > 0);
     return fm_jpegenc_encode_device(ctx, ctx->ovl->buf, ctx->ovl->w, ctx->ovl->h, quality, out, capacity, length);

@@ -162,8 +162,8 @@ class MOT:
         self.tracker.reset(cap_dt)
 
     def step(self, frame, next_frame=None, next_frames=None):
-        """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame or a JPEGFrame -- converted to BGR
-        on the GPU while it is uploaded --, a SourceFrame -- any of the three at capture resolution, resized to `size` on
+        """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame, a PlanarFrame or a JPEGFrame -- converted to BGR
+        on the GPU while it is uploaded --, a SourceFrame -- any of them at capture resolution, resized to `size` on
         the GPU --, or a detector.DeviceFrame that is already resident on the GPU).
 
         next_frame (optional, not in the reference): the frame the following `step` will receive, when
@@ -211,6 +211,21 @@ class MOT:
             self._render_overlay()
             return self.tracker.ctx.overlay_encode_jpeg(quality)
         return self.tracker.ctx.frame_encode_jpeg(quality)
+
+    def export_frame_i420(self, overlays=None):
+        """The frame of the last `step` as an utils.yuv.I420Image -- planar 4:2:0 bytes, the payload of a Y4M frame
+        (VideoIO.write takes it for a '.y4m' output) --, converted from the copy the tracker used on the GPU
+        (csrc/yuv.hip; utils.yuv.bgr_to_planar420's arithmetic): 1.5 bytes per pixel come back, nothing is uploaded.
+        `overlays` (default: `gpu_draw`): the picture with the overlays of `render_frame` on it, as `encode_frame`
+        chooses.  Valid until the next `step`."""
+        from .utils.yuv import I420Image
+        if self.frame_count == 0:
+            raise RuntimeError('export_frame_i420 needs a step before it')
+        ctx = self.tracker.ctx
+        if self.gpu_draw if overlays is None else overlays:
+            self._render_overlay()
+            return I420Image(ctx.overlay_export_i420(), self.size)
+        return I420Image(ctx.frame_export_i420(), self.size)
 
     def render_frame(self):
         """The frame of the last `step` with the overlays of `visualizer_cfg` on it, as an HxWx3 uint8 BGR ndarray: what

@@ -14,7 +14,7 @@ def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False,
     """stream: a started VideoIO; mot: a reset MOT (None: frames are only passed through); txt: an open text file for
     MOT Challenge result rows (app.py:91-97), needs `resize_to`; write_frames: stream.write(frame) after each step
     (the frame carries the overlays when the MOT draws; a frame that lives on the GPU only -- VideoIO(gpu_encode=True) with
-    gpu_decode / gpu_resize -- is written as mot.encode_frame()); lookahead: upcoming frames read ahead and handed to each step
+    gpu_decode / gpu_resize -- is written as mot.encode_frame(), or as mot.export_frame_i420() to a '.y4m' output); lookahead: upcoming frames read ahead and handed to each step
     as `next_frames` (a MOT with detector_lookahead = k batches up to k of them).  Returns the number of frames."""
     n = 0
     frame = stream.read()
@@ -32,7 +32,8 @@ def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False,
                 write_rows(txt, mot.frame_count, mot.visible_tracks(), resize_to, stream.resolution)
         if write_frames:
             if mot is not None and getattr(stream, 'gpu_encode', False) and not hasattr(frame, '__array_interface__'):
-                stream.write(mot.encode_frame(stream.jpeg_quality))
+                i420 = getattr(stream, 'i420_output', False)
+                stream.write(mot.export_frame_i420() if i420 else mot.encode_frame(stream.jpeg_quality))
             else:
                 stream.write(frame)
         frame = upcoming.popleft()

@@ -5,9 +5,11 @@ queue with the reference's semantics (file sources block when the buffer is full
 Sources this implementation can decode:
   * image sequences  'dir/%06d.jpg' (any format Pillow reads; the MOTChallenge layout)  -> Protocol.IMAGE
   * raw frame stacks '*.npy' ([N, H, W, 3] uint8 BGR, memory-mapped)                     -> Protocol.VIDEO
-Video containers, cameras and network streams need a decoder this image does not have; they raise
-NotImplementedError with the URI.  Outputs: image sequence ('out/%06d.png') or '*.npy'; with gpu_encode also
-'*.mjpeg' (concatenated JPEG files), and '%06d.jpg' sequences are encoded on the GPU.
+  * YUV4MPEG2 '*.y4m' (a text header + uncompressed planar YCbCr frames, 4:2:0 / 4:2:2 / 4:4:4 / mono, 8-bit limited
+    range, progressive; a file or a named pipe fed by any decoder: `ffmpeg -i x.mp4 -f yuv4mpegpipe x.y4m`) -> Protocol.VIDEO
+Other video containers, cameras and network streams need a decoder this image does not have; they raise
+NotImplementedError with the URI.  Outputs: image sequence ('out/%06d.png'), '*.npy' or '*.y4m' (4:2:0); with gpu_encode
+also '*.mjpeg' (concatenated JPEG files), and '%06d.jpg' sequences and '.y4m' frames are converted on the GPU.
 
 Frames are BGR uint8 like cv2's; a source whose size differs from `size` is resized with cv2.resize's
 INTER_LINEAR arithmetic (imgproc/resize.cpp: 11-bit fixed-point coefficients, exact 2x decimation =
@@ -121,6 +123,53 @@ class _FrameStack:
         return np.array(self.frames[self.index - 1])
 
 
+class _Y4MStream:
+    """A YUV4MPEG2 stream, read strictly forward (no seek, no stat: a named pipe works).  `fps`: the header's F ratio as
+    a float, None when the stream does not know it (F0:0).  read() returns the next frame -- a PlanarFrame over the
+    frame's own buffer when `planar` is set, the BGR ndarray `planar_to_bgr` makes of it otherwise --, or None at the
+    end of the stream; a last frame that is cut short ends the stream like that, without an error."""
+
+    def __init__(self, path, planar=None, matrix='bt601'):
+        """planar: a predicate on the stream's (W, H) -- frames come back as PlanarFrames where it holds."""
+        from .utils import yuv
+        from .utils.nv12 import matrix_id
+        matrix_id(matrix)
+        self._yuv = yuv
+        self.matrix = matrix
+        self.file = open(path, 'rb')
+        try:
+            line = self.file.readline(4096)
+            if not line.endswith(b'\n'):
+                raise RuntimeError('Unable to read video stream: no YUV4MPEG2 header')
+            info = yuv.parse_y4m_header(line)
+        except Exception:
+            self.file.close()
+            raise
+        self.size, self.chroma = info['size'], info['chroma']
+        self.fps = float(info['fps']) if info['fps'] else None
+        self.planar = bool(planar(self.size)) if planar is not None else False
+        self.frame_bytes = yuv.frame_bytes(self.size, self.chroma)
+
+    def read(self):
+        line = self.file.readline(4096)          # 'FRAME' + optional parameters up to the newline
+        if not line.endswith(b'\n'):
+            return None
+        if not line.startswith(self._yuv.FRAME_MAGIC):
+            raise RuntimeError(f'Unable to read video stream: {line[:16]!r} where a FRAME header belongs')
+        buf = np.empty(self.frame_bytes, np.uint8)
+        view, got = memoryview(buf), 0
+        while got < self.frame_bytes:             # (a pipe hands over what it has)
+            n = self.file.readinto(view[got:])
+            if not n:
+                return None                       # the stream ends inside this frame
+            got += n
+        frame = self._yuv.PlanarFrame.from_buffer(buf, self.size, self.chroma, self.matrix)
+        return frame if self.planar else frame.to_bgr()
+
+    def close(self):
+        self.file.close()
+
+
 class VideoIO:
     def __init__(self, size, input_uri,
                  output_uri=None,
@@ -131,7 +180,8 @@ class VideoIO:
                  gpu_decode=False,
                  gpu_resize=False,
                  gpu_encode=False,
-                 jpeg_quality=75):
+                 jpeg_quality=75,
+                 yuv_matrix='bt601'):
         """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` / `"gpu_resize": true`
         in the configuration file's stream_cfg reach it through an unmodified app.py):
         gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
@@ -151,7 +201,17 @@ class VideoIO:
             -- is accepted.  `write` then also takes `bytes` that already are a JPEG file (MOT.encode_frame: the frame
             the tracker saw, encoded where it lies on the GPU) and writes them as they are; with such an output the
             frames need not be host pixels, so gpu_decode / gpu_resize stay in effect.  '.png' and '.npy' outputs are
-            untouched by the flag; without it everything is as it was."""
+            untouched by the flag; without it everything is as it was.
+        '.y4m' input (YUV4MPEG2; `cap_fps` is the header's frame rate, `frame_rate` when the header has none): frames are
+            converted to BGR here with utils.yuv.planar_to_bgr and `yuv_matrix` ('bt601' / 'bt709'; the format does not
+            say which); with gpu_decode `read` returns them as PlanarFrames instead -- 1.5 bytes per pixel are uploaded
+            and csrc/yuv.hip converts them, bit for bit the same pixels --, those of another size than `size` wrapped in
+            a SourceFrame under gpu_resize and converted and resized here without it.
+        '.y4m' output (4:2:0, BT.601 limited range; the header is written with the first frame, from its size and
+            `frame_rate`): `write` takes host pixels -- converted with utils.yuv.bgr_to_planar420, on the GPU with
+            gpu_encode -- or an utils.yuv.I420Image (MOT.export_frame_i420: the frame the tracker saw, converted where
+            it lies on the GPU), written as it is.  With gpu_encode and such an output the frames need not be host
+            pixels, so gpu_decode / gpu_resize stay in effect, as for '.mjpeg'."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -174,16 +234,24 @@ class VideoIO:
         out = str(output_uri).lower() if output_uri is not None else ''
         self._mjpeg_out = self.gpu_encode and out.endswith('.mjpeg')
         self._jpeg_out = self._mjpeg_out or (self.gpu_encode and '%' in out and out.endswith(('.jpg', '.jpeg')))
-        host_pixels = output_uri is not None and not self._jpeg_out      # frames that Pillow / numpy write
+        self._y4m_out = out.endswith('.y4m')
+        self.i420_output = self._y4m_out and self.gpu_encode       # `write` takes MOT.export_frame_i420() for GPU-only frames
+        # frames that Pillow / numpy write
+        host_pixels = output_uri is not None and not self._jpeg_out and not (self._y4m_out and self.gpu_encode)
         self._wrap_sources = self.gpu_resize and not host_pixels
         if self.protocol == Protocol.IMAGE:
             self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and not host_pixels else None,
                                          any_size=self._wrap_sources)
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy'):
             self.source = _FrameStack(self.input_uri)
+        elif self.protocol == Protocol.VIDEO and str(self.input_uri).lower().endswith('.y4m'):
+            from .utils.source import MAX_DIM
+            on_gpu = self.gpu_decode and not host_pixels
+            self.source = _Y4MStream(self.input_uri, matrix=yuv_matrix, planar=lambda size: on_gpu and max(size) <= MAX_DIM and (
+                tuple(size) == self.size or self._wrap_sources))
         else:
             raise NotImplementedError(f'{self.input_uri}: {self.protocol.name} sources need a video decoder '
-                                      '(supported here: image sequences and .npy frame stacks)')
+                                      '(supported here: image sequences, .npy frame stacks and .y4m streams)')
 
         self.frame_queue = deque([], maxlen=self.buffer_size)
         self.cond = threading.Condition()
@@ -197,22 +265,26 @@ class VideoIO:
 
         height, width = frame.shape[:2]
         self.resolution = (width, height)
-        self.cap_fps = self.frame_rate          # neither source kind carries a frame rate
+        self.cap_fps = getattr(self.source, 'fps', None) or self.frame_rate     # (only a .y4m stream carries a frame rate)
         self.do_resize = (width, height) != self.size
         LOGGER.info('%dx%d stream @ %d FPS', width, height, self.cap_fps)
 
         self._written = 0
         self._stack = None
         self._mjpeg = None
+        self._y4m = None
+        self._y4m_size = None
         if self.output_uri is not None:
             Path(self.output_uri).parent.mkdir(parents=True, exist_ok=True)
             if str(self.output_uri).endswith('.npy'):
                 self._stack = []
             elif self._mjpeg_out:
                 self._mjpeg = open(self.output_uri, 'wb')
+            elif self._y4m_out:
+                self._y4m = open(self.output_uri, 'wb')
             elif '%' not in str(self.output_uri):
                 raise NotImplementedError(f'{self.output_uri}: video encoding needs an encoder '
-                                          "(supported here: image sequences 'dir/%06d.png' and .npy)")
+                                          "(supported here: image sequences 'dir/%06d.png', .npy and .y4m)")
 
     @property
     def cap_dt(self):
@@ -255,7 +327,9 @@ class VideoIO:
     def write(self, frame):
         """Writes the next video frame."""
         assert self.output_uri is not None
-        if self._jpeg_out:
+        if self._y4m is not None:
+            self._write_y4m(frame)
+        elif self._jpeg_out:
             if isinstance(frame, (bytes, bytearray, memoryview)):
                 data = bytes(frame)
                 if data[:2] != b'\xff\xd8':
@@ -277,9 +351,38 @@ class VideoIO:
             Image.fromarray(np.ascontiguousarray(frame[:, :, ::-1])).save(str(self.output_uri) % self._written)
         self._written += 1
 
+    def _write_y4m(self, frame):
+        from .utils import yuv
+        if isinstance(frame, yuv.I420Image):
+            size, data = frame.size, frame.data
+        elif isinstance(frame, np.ndarray):
+            if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
+                raise ValueError('frame must be uint8 HxWx3')
+            size = frame.shape[1::-1]
+            if self.gpu_encode:
+                from .runtime import get_context
+                data = get_context().i420_from_bgr(frame)
+            else:
+                data = np.concatenate([p.reshape(-1) for p in yuv.bgr_to_planar420(frame)])
+        else:
+            raise TypeError(f'write takes host pixels or an I420Image; a {type(frame).__name__} lives on the GPU: '
+                            'write MOT.export_frame_i420() for it')
+        if self._y4m_size is None:
+            self._y4m.write(yuv.y4m_header(size[0], size[1], yuv.fps_ratio(self.frame_rate)))
+            self._y4m_size = tuple(size)
+        elif tuple(size) != self._y4m_size:
+            raise ValueError(f'frame is {size[0]}x{size[1]}, the stream {self._y4m_size[0]}x{self._y4m_size[1]}')
+        self._y4m.write(yuv.FRAME_MAGIC + b'\n')
+        self._y4m.write(memoryview(np.ascontiguousarray(data)))
+
     def release(self):
         """Cleans up input and output sources."""
         self.stop_capture()
+        if self._y4m is not None:
+            self._y4m.close()
+            self._y4m = None
+        if hasattr(self.source, 'close'):
+            self.source.close()
         if self._mjpeg is not None:
             self._mjpeg.close()
             self._mjpeg = None

@@ -526,6 +526,38 @@ int fm_frame_upload_src(fm_ctx* ctx, const struct fm_frame_src* src);
 int fm_frame_upload_ahead_src(fm_ctx* ctx, int k, const struct fm_frame_src* src);
 int fm_frame_ring_store_src(fm_ctx* ctx, int index, const struct fm_frame_src* src);
 
+/* Planar YCbCr frames (what software decoders -- libavcodec, libvpx, dav1d -- hand out, and the payload of a YUV4MPEG2
+ * '.y4m' frame): replaces, for a video file or pipe, the reference's cv2.VideoCapture with its `videoconvert` stage
+ * (fastmot/videoio.py:73-75,156-170), whose decoder output is converted to BGR on the host.  A Y plane of `height` rows
+ * of `width` samples at `y`, rows `pitch_y` >= width bytes apart, and U and V planes at `u`, `v`, rows `pitch_c` apart,
+ * of     FM_YUV_420: ceil(width / 2) x ceil(height / 2)      FM_YUV_422: ceil(width / 2) x height
+ *        FM_YUV_444: width x height                          FM_YUV_MONO: none (u, v may be null; U = V = 128)
+ * samples; odd sizes are legal.  Pixel (r, c) uses the chroma sample (r >> sv, c >> sh): nearest replication, no siting
+ * filter, as fm_frame_upload_nv12; the per-pixel arithmetic, the two limited-range matrices and their ids
+ * (FM_NV12_BT601 / FM_NV12_BT709) are that call's.
+ * The three calls mirror fm_frame_upload_nv12, fm_frame_upload_ahead_nv12 and fm_frame_ring_store_nv12 one for one:
+ * same slots, same streams, same syncs, same events.  The rows are packed to their width on the way into page-locked
+ * staging (one surface -- pitch_y == width, pitch_c == the chroma width, U right behind Y and V right behind U -- inside
+ * a buffer from fm_host_alloc is copied from where it lies, in one copy); the device staging per entry point /
+ * look-ahead slot is allocated on its first planar use and freed by fm_frame_configure and fm_ctx_destroy; a kernel on
+ * the copy's stream (csrc/yuv.hip) writes the BGR frame where the BGR call would have put it.  width x height other than
+ * the configured frame size: the frame takes the route of fm_frame_upload_src -- that family's buffers, grown and freed
+ * by its rules; the kernel writes the source-size BGR frame and csrc/resize.hip the frame.
+ * FM_ERR_ARG for a null ctx / f / plane pointer, an unknown chroma or matrix, a pitch below the plane's width, a width or
+ * height outside 1..FM_SRC_MAX_DIM, or a bad k / index; nothing is copied, allocated or launched then. */
+#define FM_YUV_420 0
+#define FM_YUV_422 1
+#define FM_YUV_444 2
+#define FM_YUV_MONO 3
+struct fm_frame_planar {
+    int32_t width, height, chroma, matrix;    /* FM_YUV_*, FM_NV12_BT601 / FM_NV12_BT709 */
+    const uint8_t *y, *u, *v;
+    int32_t pitch_y, pitch_c;
+};
+int fm_frame_upload_planar(fm_ctx* ctx, const struct fm_frame_planar* f);
+int fm_frame_upload_ahead_planar(fm_ctx* ctx, int k, const struct fm_frame_planar* f);
+int fm_frame_ring_store_planar(fm_ctx* ctx, int index, const struct fm_frame_planar* f);
+
 /* Frames OUT as baseline JPEG (an output 'out/%06d.jpg' or 'out.mjpeg'): replaces the Pillow save of
  * fastmot_amd/videoio.py's writer and, in the reference, cv2.VideoWriter (fastmot/videoio.py).  The device does
  * everything that is per pixel or per coefficient (csrc/jpegenc.hip): BGR -> YCbCr, edge replication to the 16 x 16 MCU
@@ -644,6 +676,31 @@ int fm_frame_render_overlay(fm_ctx* ctx, const fm_overlay_cmd* cmds, int n, cons
 int fm_overlay_read(fm_ctx* ctx, uint8_t* out);
 int fm_overlay_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size_t capacity, size_t* length);
 int fm_overlay_stream_ms(fm_ctx* ctx, float* ms);
+
+/* Frames OUT as planar I420 (a '.y4m' output, or the input of a software encoder): replaces, for such an output, the
+ * reference's cv2.VideoWriter with its `autovideoconvert` stage (fastmot/videoio.py:99-103,222-232), which takes host
+ * BGR pixels.  Output: width * height Y bytes, then ceil(width / 2) * ceil(height / 2) U bytes, then as many V bytes --
+ * fm_i420_bound(width, height) in all (0 for a size outside 1..FM_SRC_MAX_DIM).  BT.601 limited range, integer and exact
+ * (fastmot_amd/utils/yuv.py bgr_to_planar420 states it in numpy):
+ *   Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16
+ *   U = ((-38 R - 74 G + 112 B + 128) >> 8) + 128,  V = ((112 R - 94 G - 18 B + 128) >> 8) + 128   (arithmetic shifts)
+ *   chroma sample = (the 2 x 2 block's four U (V) values + 2) >> 2; the column / row an odd size lacks is the last repeated.
+ * fm_frame_export_i420: `which` = FM_EXPORT_FRAME, the frame the context currently holds on the device (whatever it was
+ * uploaded as), or FM_EXPORT_OVERLAY, the context's overlay buffer after fm_frame_render_overlay; nothing is uploaded.
+ * fm_i420_from_bgr: host pixels (`pitch` >= 3 width bytes between rows) through a device staging buffer, as
+ * fm_jpeg_encode_bgr.  Both run on the JPEG encoder's stream (created on first use) under fm_frame_encode_jpeg's rules:
+ * no pipeline stream waits or is waited for, the call returns when out[0, *length) is complete; the planes pass through
+ * a device buffer and a page-locked buffer (skipped when `out` lies in fm_host_alloc memory), allocated on first use,
+ * regrown for a larger frame, freed by fm_ctx_destroy.  The kernel (csrc/yuv.hip): one thread per 8 columns x 2 rows.
+ * FM_ERR_ARG for a null pointer, an unknown `which`, no current frame / no overlay rendered at the current frame size,
+ * a size outside 1..FM_SRC_MAX_DIM, pitch < 3 width, or capacity < the output -- *length then says what it needs and
+ * nothing is written to out. */
+#define FM_EXPORT_FRAME 0
+#define FM_EXPORT_OVERLAY 1
+size_t fm_i420_bound(int width, int height);
+int fm_frame_export_i420(fm_ctx* ctx, int which, uint8_t* out, size_t capacity, size_t* length);
+int fm_i420_from_bgr(fm_ctx* ctx, const uint8_t* pixels, int width, int height, size_t pitch, uint8_t* out, size_t capacity,
+                     size_t* length);
 
 /* ---------------------------------------------------------------- detector ------------ */
 #define FM_MAX_HEADS 4
