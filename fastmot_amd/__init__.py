@@ -15,8 +15,9 @@ from .utils.nv12 import NV12Frame
 from .utils.jpeg import JPEGFrame
 from .utils.source import SourceFrame
 from .utils.yuv import PlanarFrame, I420Image
+from .utils.packed import PackedFrame
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'PackedFrame', 'models']
 
 
 def __getattr__(name):

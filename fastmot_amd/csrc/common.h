@@ -199,6 +199,10 @@ struct fm_ctx {
     // ... and of planar frames of the configured size (fm_frame_*_planar; csrc/yuv.hip converts out of it), entries and
     // rules as frame_nv12's; sized for the largest layout, 4:4:4.  (Planar frames of another size use frame_src below.)
     uint8_t* frame_planar[FM_MAX_DET_BATCH + 2] = {};
+    // ... and of packed 4:2:2 / RGB frames of the configured size (fm_frame_*_packed; csrc/packed.hip converts out of
+    // it), entries and rules as frame_nv12's; sized for the widest layout, 4 bytes per pixel.  Their page-locked staging
+    // is frame_src[entry].pinned with its event: the slots' BGR-sized buffers are too small for 4 bytes per pixel.
+    uint8_t* frame_packed[FM_MAX_DET_BATCH + 2] = {};
 
     // ---- device staging of entropy-decoded JPEG frames (coefficients, quantisation tables and the sample planes
     // csrc/jpeg.hip makes of them), entries as frame_nv12's, allocated on first JPEG use for the largest layout of the
@@ -247,6 +251,16 @@ inline bool fm_yuv_chroma_dims(int w, int h, int chroma, int* cw, int* ch) {
     return false;
 }
 int fm_planar_to_bgr(const uint8_t* planes, uint8_t* bgr, int w, int h, int chroma, int matrix, hipStream_t s);   // yuv.hip
+// bytes of a row of w pixels in the packed layout `format` (FM_PACKED_*); 0 for an unknown format
+inline size_t fm_packed_row_bytes(int w, int format) {
+    if (format < FM_PACKED_RGB || format > FM_PACKED_YVYU) return 0;
+    if (format >= FM_PACKED_YUY2) return 4 * (size_t)((w + 1) / 2);
+    return (size_t)w * (format <= FM_PACKED_BGR ? 3 : 4);
+}
+inline bool fm_packed_matrix_ok(int matrix) {
+    return matrix == FM_PACKED_BT601 || matrix == FM_PACKED_BT709 || matrix == FM_PACKED_BT601_FULL || matrix == FM_PACKED_BT709_FULL;
+}
+int fm_packed_to_bgr(const uint8_t* src, uint8_t* bgr, int w, int h, int format, int matrix, hipStream_t s);   // packed.hip
 void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
 void fm_frame_src_free(fm_ctx* ctx);                                                              // detect.hip

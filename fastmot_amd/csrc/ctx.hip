@@ -178,6 +178,8 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
         if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_planar)
         if (p) (void)hipFree(p);
+    for (uint8_t* p : ctx->frame_packed)
+        if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_jpeg)
         if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_jpeg_pinned)

@@ -4,7 +4,8 @@ queue with the reference's semantics (file sources block when the buffer is full
 
 Sources this implementation can decode:
   * image sequences  'dir/%06d.jpg' (any format Pillow reads; the MOTChallenge layout)  -> Protocol.IMAGE
-  * raw frame stacks '*.npy' ([N, H, W, 3] uint8 BGR, memory-mapped)                     -> Protocol.VIDEO
+  * raw frame stacks '*.npy' ([N, H, W, 3] uint8 BGR, memory-mapped; with `pixel_format` a stack of packed RGB / BGRx /
+    YUY2 / UYVY ... frames as a camera or an image library hands them out, see VideoIO)  -> Protocol.VIDEO
   * YUV4MPEG2 '*.y4m' (a text header + uncompressed planar YCbCr frames, 4:2:0 / 4:2:2 / 4:4:4 / mono, 8-bit limited
     range, progressive; a file or a named pipe fed by any decoder: `ffmpeg -i x.mp4 -f yuv4mpegpipe x.y4m`) -> Protocol.VIDEO
 Other video containers, cameras and network streams need a decoder this image does not have; they raise
@@ -123,6 +124,46 @@ class _FrameStack:
         return np.array(self.frames[self.index - 1])
 
 
+class _PackedStack:
+    """A '.npy' stack of packed frames in the layout `fmt` (utils.packed.FORMATS), memory-mapped.  Accepted shapes, uint8:
+    (N, H, W, bpp) for the RGB family (bpp 3 or 4, as the layout says), and (N, H, row bytes) for every layout -- row bytes
+    a multiple of the layout's bytes per pixel for RGB, of 4 for the 4:2:2 family, which carries two pixels in 4 bytes, so
+    W = row bytes / 2 (an odd width cannot be told from the shape: such a stack reads as W + 1 wide).  read() returns the
+    next frame -- a PackedFrame over a copy of the frame's bytes when `packed` holds for the stack's (W, H), the BGR
+    ndarray `packed_to_bgr` makes of it otherwise --, or None at the end."""
+
+    def __init__(self, path, fmt, matrix='bt601', packed=None):
+        from .utils import packed as pk
+        pk.format_id(fmt)
+        pk.matrix_id(matrix)
+        self._pk, self.format, self.matrix = pk, fmt, matrix
+        self.frames = np.load(path, mmap_mode='r')
+        _, family, bpp, _ = pk.FORMATS[fmt]
+        shape = self.frames.shape
+        unit = 4 if family == '422' else bpp
+        ok = self.frames.dtype == np.uint8 and len(shape) in (3, 4) and all(shape[1:])
+        if ok and len(shape) == 4:
+            ok = family == 'rgb' and shape[3] == bpp
+            w = shape[2]
+        elif ok:
+            ok = shape[2] % unit == 0
+            w = shape[2] // (2 if family == '422' else bpp)
+        if not ok:
+            raise ValueError(f'{path}: a {fmt!r} frame stack is a uint8 array (N, H, row bytes) with row bytes a multiple of {unit}'
+                             + (f' or (N, H, W, {bpp})' if family == 'rgb' else '') + f', not {self.frames.dtype} {shape}')
+        self.size = (w, shape[1])
+        self.packed = bool(packed(self.size)) if packed is not None else False
+        self.index = 0
+
+    def read(self):
+        if self.index >= len(self.frames):
+            return None
+        self.index += 1
+        data = np.array(self.frames[self.index - 1]).reshape(self.size[1], -1)
+        frame = self._pk.PackedFrame(data, self.format, self.size, self.matrix)
+        return frame if self.packed else frame.to_bgr()
+
+
 class _Y4MStream:
     """A YUV4MPEG2 stream, read strictly forward (no seek, no stat: a named pipe works).  `fps`: the header's F ratio as
     a float, None when the stream does not know it (F0:0).  read() returns the next frame -- a PlanarFrame over the
@@ -181,7 +222,8 @@ class VideoIO:
                  gpu_resize=False,
                  gpu_encode=False,
                  jpeg_quality=75,
-                 yuv_matrix='bt601'):
+                 yuv_matrix='bt601',
+                 pixel_format=None):
         """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` / `"gpu_resize": true`
         in the configuration file's stream_cfg reach it through an unmodified app.py):
         gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
@@ -211,7 +253,17 @@ class VideoIO:
             `frame_rate`): `write` takes host pixels -- converted with utils.yuv.bgr_to_planar420, on the GPU with
             gpu_encode -- or an utils.yuv.I420Image (MOT.export_frame_i420: the frame the tracker saw, converted where
             it lies on the GPU), written as it is.  With gpu_encode and such an output the frames need not be host
-            pixels, so gpu_decode / gpu_resize stay in effect, as for '.mjpeg'."""
+            pixels, so gpu_decode / gpu_resize stay in effect, as for '.mjpeg'.
+        pixel_format (`"pixel_format": "yuy2"` in stream_cfg; None: everything as it was): the layout of a '.npy' frame
+            stack that holds frames as a camera, a capture card or an image library hands them out -- a key of
+            utils.packed.FORMATS: 'rgb', 'bgr', 'rgbx' / 'rgba', 'bgrx' / 'bgra', 'xrgb' / 'argb', 'xbgr' / 'abgr',
+            'yuy2' / 'yuyv', 'uyvy', 'yvyu'.  The stack is uint8 (N, H, W, 3 | 4) for the RGB family or (N, H, row bytes)
+            for any layout (row bytes = bytes per pixel * W; 4 * ceil(W / 2) for 4:2:2, read as W = row bytes / 2); any
+            other shape, and any other kind of input, is a ValueError when the stream is opened.  Frames are converted
+            to BGR here with utils.packed.packed_to_bgr and, for 4:2:2, `yuv_matrix` -- which for this option alone also
+            takes 'bt601-full' / 'bt709-full', a camera's full-range YCbCr; with gpu_decode `read` returns them as
+            PackedFrames instead and csrc/packed.hip converts them, bit for bit the same pixels, those of another size
+            than `size` wrapped in a SourceFrame under gpu_resize -- the '.y4m' input's rules for both flags."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -239,9 +291,16 @@ class VideoIO:
         # frames that Pillow / numpy write
         host_pixels = output_uri is not None and not self._jpeg_out and not (self._y4m_out and self.gpu_encode)
         self._wrap_sources = self.gpu_resize and not host_pixels
+        if pixel_format is not None and not (self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy')):
+            raise ValueError(f"pixel_format={pixel_format!r} describes a '.npy' frame stack, not {self.input_uri}")
         if self.protocol == Protocol.IMAGE:
             self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and not host_pixels else None,
                                          any_size=self._wrap_sources)
+        elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy') and pixel_format is not None:
+            from .utils.source import MAX_DIM
+            on_gpu = self.gpu_decode and not host_pixels
+            self.source = _PackedStack(self.input_uri, pixel_format, matrix=yuv_matrix, packed=lambda size: on_gpu and max(size) <= MAX_DIM and (
+                tuple(size) == self.size or self._wrap_sources))
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy'):
             self.source = _FrameStack(self.input_uri)
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).lower().endswith('.y4m'):
@@ -316,7 +375,7 @@ class VideoIO:
             self.cond.notify()
         if self._wrap_sources:
             from .utils.source import MAX_DIM, SourceFrame
-            if not isinstance(frame, np.ndarray):                 # a JPEGFrame, of any size
+            if not isinstance(frame, np.ndarray):                 # a JPEGFrame / PlanarFrame / PackedFrame, of any size
                 return frame if frame.size == self.size else SourceFrame(frame)
             if self.do_resize and frame.shape[:2] != self.size[::-1] and max(frame.shape[:2]) <= MAX_DIM:
                 return SourceFrame(frame)

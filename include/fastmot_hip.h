@@ -558,6 +558,56 @@ int fm_frame_upload_planar(fm_ctx* ctx, const struct fm_frame_planar* f);
 int fm_frame_upload_ahead_planar(fm_ctx* ctx, int k, const struct fm_frame_planar* f);
 int fm_frame_ring_store_planar(fm_ctx* ctx, int index, const struct fm_frame_planar* f);
 
+/* Packed frames: packed 4:2:2 (the raw format of every UVC / V4L2 camera and of most capture cards) and packed RGB in
+ * any channel order with or without a fourth byte (what image libraries hand out; BGRx is what `nvvidconv` / `appsink`
+ * do): replaces the host `videoconvert` of the reference's V4L2 and CSI pipelines (fastmot/videoio.py) and the channel
+ * shuffle an application does on its capture thread.  `height` rows at `data`, `pitch` bytes apart, each of
+ *   FM_PACKED_RGB / _BGR: 3 width bytes, R (B) first      FM_PACKED_RGBX / _BGRX: 4 width bytes, the fourth byte ignored
+ *   FM_PACKED_XRGB / _XBGR: 4 width bytes, the first byte ignored
+ *   FM_PACKED_YUY2 / _UYVY / _YVYU: 4 ceil(width / 2) bytes, macropixels Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U
+ * The RGB family is a byte permutation into B, G, R (`matrix` is checked but not used).  A macropixel carries two
+ * horizontally adjacent pixels; an odd width is legal, the last macropixel's second luma byte is then no pixel.  Pixel
+ * (r, c) uses luma sample c of its row and the U, V of macropixel c >> 1 (nearest replication, as FM_YUV_422), with
+ *   FM_PACKED_BT601 / FM_PACKED_BT709: fm_frame_upload_nv12's limited-range arithmetic and constants
+ *   FM_PACKED_BT601_FULL / _BT709_FULL: y = Y << 20, u = U - 128, v = V - 128, h = 1 << 19,
+ *     R = sat8((y + h + CVR v) >> 20)   G = sat8((y + h + CVG v + CUG u) >> 20)   B = sat8((y + h + CUB u) >> 20)
+ *     BT.601: CVR 1470104, CUB 1858077, CUG -360853, CVG -748826      (round(c * 2^20) of 1.402, 1.772, -0.344136, -0.714136)
+ *     BT.709: CVR 1651297, CUB 1945738, CUG -196423, CVG -490864      (of 1.5748, 1.8556, -0.187324, -0.468124)
+ * integer and exact (fastmot_amd/utils/packed.py packed_to_bgr states it in numpy).  The matrix ids are this family's
+ * own; the NV12 / planar / src calls accept theirs as before.
+ * The three calls mirror fm_frame_upload_planar, fm_frame_upload_ahead_planar and fm_frame_ring_store_planar one for
+ * one: same slots, same streams, same syncs, same events.  The rows are packed to their byte width on the way into
+ * page-locked staging (a surface with pitch == that width inside a buffer from fm_host_alloc is copied from where it
+ * lies); the device staging per entry point / look-ahead slot is allocated on its first packed use and freed by
+ * fm_frame_configure and fm_ctx_destroy (the page-locked staging is fm_frame_upload_src's, with its rules); a kernel
+ * on the copy's stream (csrc/packed.hip) writes the BGR frame where the BGR call would have put it, and a look-ahead
+ * slot's completion event follows it.  width x height other than the configured frame size: the frame takes the route
+ * of fm_frame_upload_src -- that family's buffers, grown and freed by its rules; the kernel writes the source-size BGR
+ * frame and csrc/resize.hip the frame.
+ * FM_ERR_ARG for a null ctx / f / data pointer, an unknown format or matrix (2..15 are none), a pitch below the row's
+ * byte width, a width or height outside 1..FM_SRC_MAX_DIM, or a bad k / index; nothing is copied, allocated or
+ * launched then. */
+#define FM_PACKED_RGB 0
+#define FM_PACKED_BGR 1
+#define FM_PACKED_RGBX 2
+#define FM_PACKED_BGRX 3
+#define FM_PACKED_XRGB 4
+#define FM_PACKED_XBGR 5
+#define FM_PACKED_YUY2 6
+#define FM_PACKED_UYVY 7
+#define FM_PACKED_YVYU 8
+#define FM_PACKED_BT601 0
+#define FM_PACKED_BT709 1
+#define FM_PACKED_BT601_FULL 16
+#define FM_PACKED_BT709_FULL 17
+struct fm_frame_packed {
+    int32_t format, width, height, pitch, matrix;    /* FM_PACKED_* layout, FM_PACKED_BT* */
+    const uint8_t* data;
+};
+int fm_frame_upload_packed(fm_ctx* ctx, const struct fm_frame_packed* f);
+int fm_frame_upload_ahead_packed(fm_ctx* ctx, int k, const struct fm_frame_packed* f);
+int fm_frame_ring_store_packed(fm_ctx* ctx, int index, const struct fm_frame_packed* f);
+
 /* Frames OUT as baseline JPEG (an output 'out/%06d.jpg' or 'out.mjpeg'): replaces the Pillow save of
  * fastmot_amd/videoio.py's writer and, in the reference, cv2.VideoWriter (fastmot/videoio.py).  The device does
  * everything that is per pixel or per coefficient (csrc/jpegenc.hip): BGR -> YCbCr, edge replication to the 16 x 16 MCU
