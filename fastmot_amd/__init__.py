@@ -16,8 +16,9 @@ from .utils.jpeg import JPEGFrame
 from .utils.source import SourceFrame
 from .utils.yuv import PlanarFrame, I420Image
 from .utils.packed import PackedFrame
+from .utils.bayer import BayerFrame
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'PackedFrame', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'PackedFrame', 'BayerFrame', 'models']
 
 
 def __getattr__(name):

@@ -17,6 +17,7 @@ from .utils.jpeg import JPEGFrame, QT_ENTRIES, max_coefficients
 from .utils.source import SourceFrame
 from .utils.yuv import PlanarFrame, frame_bytes
 from .utils.packed import PackedFrame, row_bytes
+from .utils.bayer import BayerFrame
 
 LIB_PATH = Path(os.environ.get('FASTMOT_LIB_PATH', Path(__file__).parent / 'libfastmot_hip.so'))
 
@@ -527,6 +528,17 @@ def _bind_device_io(cls):
             return frame
         return None
 
+    def _bayer_of(self, frame):
+        """The BayerFrame a Bayer call takes for `frame`, by `_planar_of`'s rules, or None for every other frame kind."""
+        if isinstance(frame, SourceFrame) and isinstance(frame.frame, BayerFrame):
+            return frame.frame
+        if isinstance(frame, BayerFrame):
+            if frame.size != tuple(self.frame_size):
+                raise ValueError(f'Bayer frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
+                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
+            return frame
+        return None
+
     def frame_upload(self, frame):
         planar = self._planar_of(frame)
         if planar is not None:
@@ -535,6 +547,10 @@ def _bind_device_io(cls):
         packed = self._packed_of(frame)
         if packed is not None:
             check(self.lib.fm_frame_upload_packed(self._ctx, C.byref(packed.describe())))
+            return
+        bayer = self._bayer_of(frame)
+        if bayer is not None:
+            check(self.lib.fm_frame_upload_bayer(self._ctx, C.byref(bayer.describe())))
             return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_nv12(self._ctx, *self._nv12_args(frame)))
@@ -596,6 +612,16 @@ def _bind_device_io(cls):
         buf = pinned_empty(self.lib, (n, h, row_bytes(w, fmt)), np.uint8)
         return [PackedFrame(buf[i], fmt, (w, h), matrix) for i in range(n)]
 
+    def pinned_bayer_frames(self, n, pattern, depth=8, size=None, method='mhc', wb=(1., 1., 1.), black=0):
+        """n BayerFrames of the context's frame size (or the SOURCE size `size` = (W, H), for `SourceFrame(f)`), each one
+        surface with pitch = its row bytes in page-locked host memory (fm_host_alloc): fill `f.rows[...]` (uint8 for
+        depth 8, uint16 above); they are uploaded without a staging copy.  The buffer lives as long as any of them."""
+        w, h = tuple(self.frame_size) if size is None else size
+        if w < 2 or h < 2:
+            raise ValueError(f'a mosaic is at least 2x2, not {w}x{h}')
+        buf = pinned_empty(self.lib, (n, h, w), np.uint8 if depth == 8 else np.dtype('<u2'))
+        return [BayerFrame(buf[i], pattern, (w, h), depth, method, wb, black) for i in range(n)]
+
     def frame_ring_store(self, index, frame):
         planar = self._planar_of(frame)
         if planar is not None:
@@ -604,6 +630,10 @@ def _bind_device_io(cls):
         packed = self._packed_of(frame)
         if packed is not None:
             check(self.lib.fm_frame_ring_store_packed(self._ctx, C.c_int(index), C.byref(packed.describe())))
+            return
+        bayer = self._bayer_of(frame)
+        if bayer is not None:
+            check(self.lib.fm_frame_ring_store_bayer(self._ctx, C.c_int(index), C.byref(bayer.describe())))
             return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_ring_store_nv12(self._ctx, C.c_int(index), *self._nv12_args(frame)))
@@ -621,7 +651,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
 
     def frame_upload_next(self, frame):
-        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame, PlanarFrame, PackedFrame)):
+        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame, PlanarFrame, PackedFrame, BayerFrame)):
             return self.frame_upload_ahead(1, frame)
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -647,6 +677,10 @@ def _bind_device_io(cls):
         packed = self._packed_of(frame)
         if packed is not None:
             check(self.lib.fm_frame_upload_ahead_packed(self._ctx, C.c_int(k), C.byref(packed.describe())))
+            return
+        bayer = self._bayer_of(frame)
+        if bayer is not None:
+            check(self.lib.fm_frame_upload_ahead_bayer(self._ctx, C.c_int(k), C.byref(bayer.describe())))
             return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_ahead_nv12(self._ctx, C.c_int(k), *self._nv12_args(frame)))
@@ -842,7 +876,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, _nv12_args, _jpeg_args, _planar_of, _packed_of, pinned_planar_frames, pinned_packed_frames, _i420_out, _export_i420, frame_export_i420,
+    for fn in (frame_configure, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
                overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,

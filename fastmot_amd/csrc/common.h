@@ -203,6 +203,9 @@ struct fm_ctx {
     // it), entries and rules as frame_nv12's; sized for the widest layout, 4 bytes per pixel.  Their page-locked staging
     // is frame_src[entry].pinned with its event: the slots' BGR-sized buffers are too small for 4 bytes per pixel.
     uint8_t* frame_packed[FM_MAX_DET_BATCH + 2] = {};
+    // ... and of Bayer mosaics of the configured size (fm_frame_*_bayer; csrc/bayer.hip demosaics out of it), entries
+    // and rules as frame_packed's, page-locked staging included; sized for 16-bit samples, 2 bytes per pixel.
+    uint8_t* frame_bayer[FM_MAX_DET_BATCH + 2] = {};
 
     // ---- device staging of entropy-decoded JPEG frames (coefficients, quantisation tables and the sample planes
     // csrc/jpeg.hip makes of them), entries as frame_nv12's, allocated on first JPEG use for the largest layout of the
@@ -261,6 +264,13 @@ inline bool fm_packed_matrix_ok(int matrix) {
     return matrix == FM_PACKED_BT601 || matrix == FM_PACKED_BT709 || matrix == FM_PACKED_BT601_FULL || matrix == FM_PACKED_BT709_FULL;
 }
 int fm_packed_to_bgr(const uint8_t* src, uint8_t* bgr, int w, int h, int format, int matrix, hipStream_t s);   // packed.hip
+// bytes of one Bayer sample of `depth` bits (FM_BAYER frames); 0 for an unknown depth
+inline int fm_bayer_sample_bytes(int depth) {
+    return depth == 8 ? 1 : depth == 10 || depth == 12 || depth == 14 || depth == 16 ? 2 : 0;
+}
+inline bool fm_bayer_gain_ok(int gain) { return gain >= 1 && gain <= 4096; }
+int fm_bayer_to_bgr(const uint8_t* src, uint8_t* bgr, int w, int h, int pattern, int depth, int method, int black, int gain_r, int gain_g,
+                    int gain_b, hipStream_t s);                                                   // bayer.hip
 void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
 void fm_frame_src_free(fm_ctx* ctx);                                                              // detect.hip

@@ -180,6 +180,8 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
         if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_packed)
         if (p) (void)hipFree(p);
+    for (uint8_t* p : ctx->frame_bayer)
+        if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_jpeg)
         if (p) (void)hipFree(p);
     for (uint8_t* p : ctx->frame_jpeg_pinned)

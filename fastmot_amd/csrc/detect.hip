@@ -1122,6 +1122,10 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         if (p) (void)hipFree(p);
         p = nullptr;
     }
+    for (uint8_t*& p : ctx->frame_bayer) {             // Bayer staging: allocated again on first Bayer use
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
     for (uint8_t*& p : ctx->frame_jpeg) {              // JPEG staging: allocated again on first JPEG use
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -1930,6 +1934,104 @@ extern "C" int fm_frame_ring_store_packed(fm_ctx* ctx, int index, const struct f
     // synchronous like fm_frame_ring_store (filling the ring is set-up work): a blocking copy that packs the rows, then
     // the kernels on the null stream
     int rc = enqueue_packed(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+// ---- Bayer ingest (struct fm_frame_bayer: the raw mosaic of an industrial or embedded camera): the three host-frame
+// entry points once more, mirroring the packed ones above.  Same slots, streams, syncs and events as their BGR
+// counterparts.  A frame of the configured size goes through ctx->frame_bayer[entry] and the kernel of bayer.hip writes
+// the BGR frame; a frame of any other size takes the route of fm_frame_*_src with that path's buffers
+// (ctx->frame_src[entry]): bayer.hip writes the source-size BGR frame, resize.hip the frame.  Rows that cannot be copied
+// from where they lie are packed into ctx->frame_src[entry].pinned for both sizes, as packed frames' are.
+static bool bayer_ok(const struct fm_frame_bayer* f) {
+    if (!f || f->width < 2 || f->height < 2 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
+    const int bps = fm_bayer_sample_bytes(f->depth);
+    if (!bps || f->pattern < FM_BAYER_RGGB || f->pattern > FM_BAYER_BGGR) return false;
+    if (f->method != FM_BAYER_BILINEAR && f->method != FM_BAYER_MHC) return false;
+    if (f->black < 0 || f->black >= (1 << f->depth)) return false;
+    if (!fm_bayer_gain_ok(f->gain_r) || !fm_bayer_gain_ok(f->gain_g) || !fm_bayer_gain_ok(f->gain_b)) return false;
+    return f->data && f->pitch > 0 && (size_t)f->pitch >= (size_t)f->width * bps;
+}
+
+// H2D copy of the rows, packed to their byte width, into device staging, the demosaicing and -- off size -- the resize
+// into `dst`, all on `s`.  `blocking`: blocking copies from where the rows lie (fm_frame_ring_store_bayer).
+static int enqueue_bayer(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_bayer* f, hipStream_t s, bool blocking) {
+    const int w = f->width, h = f->height;
+    const size_t rb = (size_t)w * fm_bayer_sample_bytes(f->depth), total = rb * h, npx = (size_t)w * h;
+    const bool on_size = w == ctx->frame_w && h == ctx->frame_h;
+    fm_ctx::SrcStage& st = ctx->frame_src[entry];
+    uint8_t* stage = nullptr;
+    int rc;
+    if (on_size) {
+        uint8_t*& p = ctx->frame_bayer[entry];
+        if (!p) FM_HIP(hipMalloc(&p, npx * 2));            // (16-bit samples: every depth fits)
+        stage = p;
+    } else {
+        if ((rc = src_reserve(st.bgr, st.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s))) return rc;     // (resize.hip reads 8 bytes at a pixel)
+        if ((rc = src_reserve(st.dev, st.dev_cap, total, false, s))) return rc;
+        stage = st.dev;
+    }
+    if (blocking) {
+        FM_HIP(hipMemcpy2D(stage, rb, f->data, f->pitch, rb, h, hipMemcpyHostToDevice));
+    } else if ((size_t)f->pitch == rb && is_pinned_range(f->data, total)) {
+        FM_HIP(hipMemcpyAsync(stage, f->data, total, hipMemcpyHostToDevice, s));
+    } else {
+        if ((rc = src_pinned(st, total, s))) return rc;
+        for (int r = 0; r < h; ++r) memcpy(st.pinned + (size_t)r * rb, f->data + (size_t)r * f->pitch, rb);
+        FM_HIP(hipMemcpyAsync(stage, st.pinned, total, hipMemcpyHostToDevice, s));
+        if ((rc = src_pinned_copied(st, s))) return rc;
+    }
+    fm_trace_mark(ctx, s, 49);                 // (the demosaicing's share of the caller's 30 .. 31 interval)
+    uint8_t* const out = on_size ? dst : st.bgr;
+    if ((rc = fm_bayer_to_bgr(stage, out, w, h, f->pattern, f->depth, f->method, f->black, f->gain_r, f->gain_g, f->gain_b, s))) return rc;
+    if (on_size) return 0;
+    fm_trace_mark(ctx, s, 38);                 // (the resize's share)
+    return fm_resize_bgr(st.bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+}
+
+extern "C" int fm_frame_upload_bayer(fm_ctx* ctx, const struct fm_frame_bayer* f) {
+    FM_CHECK_ARG(ctx && ctx->frame_own && bayer_ok(f));
+    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    int rc = enqueue_bayer(ctx, 0, ctx->frame_own, f, ctx->s_det, false);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
+    ctx->frame_cur = ctx->frame_own;
+    return 0;
+}
+
+extern "C" int fm_frame_upload_ahead_bayer(fm_ctx* ctx, int k, const struct fm_frame_bayer* f) {
+    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && bayer_ok(f));
+    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
+    // stream, order of calls, event and staging: see fm_frame_upload_ahead_packed
+    hipStream_t cs = ctx->s_ext;
+    fm_trace_mark(ctx, cs, 30);
+    int rc = enqueue_bayer(ctx, k, buf, f, cs, false);
+    if (rc) return rc;
+    fm_trace_mark(ctx, cs, 31);
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
+    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
+    ahead_frame(ctx, k) = buf;
+    return 0;
+}
+
+extern "C" int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm_frame_bayer* f) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && bayer_ok(f));
+    // synchronous like fm_frame_ring_store (filling the ring is set-up work): a blocking copy that packs the rows, then
+    // the kernels on the null stream
+    int rc = enqueue_bayer(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
     if (rc) return rc;
     FM_HIP(hipStreamSynchronize(nullptr));
     return 0;

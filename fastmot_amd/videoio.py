@@ -164,6 +164,44 @@ class _PackedStack:
         return frame if self.packed else frame.to_bgr()
 
 
+def _bayer_format(pixel_format):
+    """(pattern, depth) of a Bayer `pixel_format` -- 'rggb', 'grbg', 'gbrg' or 'bggr', with '10', '12', '14' or '16' behind it
+    for samples deeper than 8 bits --, or None for every other value."""
+    from .utils.bayer import PATTERNS
+    if not isinstance(pixel_format, str) or pixel_format[:4] not in PATTERNS or pixel_format[4:] not in ('', '10', '12', '14', '16'):
+        return None
+    return pixel_format[:4], int(pixel_format[4:] or 8)
+
+
+class _BayerStack:
+    """A '.npy' stack (N, H, W) of Bayer mosaics, memory-mapped: uint8 for depth 8, uint16 for the deeper ones, H and W at
+    least 2.  read() returns the next frame -- a BayerFrame over a copy of the frame's samples when `bayer` holds for the
+    stack's (W, H), the BGR ndarray `bayer_to_bgr` makes of it otherwise --, or None at the end."""
+
+    def __init__(self, path, pattern, depth, method='mhc', wb=None, black=0, bayer=None):
+        from .utils import bayer as by
+        by.method_id(method)
+        self._by, self.pattern, self.depth, self.method = by, pattern, depth, method
+        self.wb = (1., 1., 1.) if wb is None else tuple(wb)
+        by.gains(self.wb)
+        self.black = by._black(black, depth)
+        self.frames = np.load(path, mmap_mode='r')
+        shape, want = self.frames.shape, np.dtype(np.uint8 if depth == 8 else '<u2')
+        if self.frames.dtype != want or len(shape) != 3 or shape[1] < 2 or shape[2] < 2:
+            raise ValueError(f'{path}: a {pattern!r} frame stack of depth {depth} is a {want.name} array (N, H, W) with H, W >= 2, '
+                             f'not {self.frames.dtype} {shape}')
+        self.size = (shape[2], shape[1])
+        self.bayer = bool(bayer(self.size)) if bayer is not None else False
+        self.index = 0
+
+    def read(self):
+        if self.index >= len(self.frames):
+            return None
+        self.index += 1
+        frame = self._by.BayerFrame(np.array(self.frames[self.index - 1]), self.pattern, None, self.depth, self.method, self.wb, self.black)
+        return frame if self.bayer else frame.to_bgr()
+
+
 class _Y4MStream:
     """A YUV4MPEG2 stream, read strictly forward (no seek, no stat: a named pipe works).  `fps`: the header's F ratio as
     a float, None when the stream does not know it (F0:0).  read() returns the next frame -- a PlanarFrame over the
@@ -223,7 +261,10 @@ class VideoIO:
                  gpu_encode=False,
                  jpeg_quality=75,
                  yuv_matrix='bt601',
-                 pixel_format=None):
+                 pixel_format=None,
+                 demosaic='mhc',
+                 white_balance=None,
+                 black_level=0):
         """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` / `"gpu_resize": true`
         in the configuration file's stream_cfg reach it through an unmodified app.py):
         gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
@@ -263,7 +304,11 @@ class VideoIO:
             to BGR here with utils.packed.packed_to_bgr and, for 4:2:2, `yuv_matrix` -- which for this option alone also
             takes 'bt601-full' / 'bt709-full', a camera's full-range YCbCr; with gpu_decode `read` returns them as
             PackedFrames instead and csrc/packed.hip converts them, bit for bit the same pixels, those of another size
-            than `size` wrapped in a SourceFrame under gpu_resize -- the '.y4m' input's rules for both flags."""
+            than `size` wrapped in a SourceFrame under gpu_resize -- the '.y4m' input's rules for both flags.
+            Bayer keys -- 'rggb', 'grbg', 'gbrg', 'bggr' for a uint8 stack (N, H, W) of raw mosaics, the same with '10',
+            '12', '14' or '16' behind them ('rggb12') for a uint16 stack of that depth -- follow the same rules with
+            utils.bayer.bayer_to_bgr, BayerFrames and csrc/bayer.hip; `demosaic` ('mhc' / 'bilinear'), `white_balance`
+            (gains (R, G, B); None: 1.0 each) and `black_level` (in sample units) go with them and with nothing else."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -296,6 +341,12 @@ class VideoIO:
         if self.protocol == Protocol.IMAGE:
             self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and not host_pixels else None,
                                          any_size=self._wrap_sources)
+        elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy') and _bayer_format(pixel_format) is not None:
+            from .utils.source import MAX_DIM
+            on_gpu = self.gpu_decode and not host_pixels
+            pattern, depth = _bayer_format(pixel_format)
+            self.source = _BayerStack(self.input_uri, pattern, depth, demosaic, white_balance, black_level,
+                                      bayer=lambda size: on_gpu and max(size) <= MAX_DIM and (tuple(size) == self.size or self._wrap_sources))
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy') and pixel_format is not None:
             from .utils.source import MAX_DIM
             on_gpu = self.gpu_decode and not host_pixels
@@ -375,7 +426,7 @@ class VideoIO:
             self.cond.notify()
         if self._wrap_sources:
             from .utils.source import MAX_DIM, SourceFrame
-            if not isinstance(frame, np.ndarray):                 # a JPEGFrame / PlanarFrame / PackedFrame, of any size
+            if not isinstance(frame, np.ndarray):                 # a JPEGFrame / PlanarFrame / PackedFrame / BayerFrame, of any size
                 return frame if frame.size == self.size else SourceFrame(frame)
             if self.do_resize and frame.shape[:2] != self.size[::-1] and max(frame.shape[:2]) <= MAX_DIM:
                 return SourceFrame(frame)

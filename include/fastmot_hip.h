@@ -608,6 +608,54 @@ int fm_frame_upload_packed(fm_ctx* ctx, const struct fm_frame_packed* f);
 int fm_frame_upload_ahead_packed(fm_ctx* ctx, int k, const struct fm_frame_packed* f);
 int fm_frame_ring_store_packed(fm_ctx* ctx, int index, const struct fm_frame_packed* f);
 
+/* Bayer frames: the raw colour-filter mosaic of an industrial or embedded camera (GigE Vision / USB3 Vision BayerRG8 /
+ * BayerRG12, V4L2 SRGGB8 / SRGGB10, CSI sensors), one sample per pixel: replaces the demosaicing an application does on
+ * its capture thread (the reference's pipelines get BGR from `videoconvert` / `nvvidconv`) and the 3 bytes per pixel
+ * it uploads afterwards.  `height` rows of `width` samples at `data`, `pitch` BYTES apart; a sample is one byte for
+ * `depth` 8 and a little-endian 16-bit word with the value in its low bits for `depth` 10, 12, 14 and 16 (the unpacked
+ * form of SRGGB10 / BayerRG12; `data` and `pitch` need no alignment).
+ *   pattern: where R sits in the 2 x 2 tile -- bit 0 its column parity, bit 1 its row parity; B sits at the opposite
+ *     parity in both directions, G at the other two positions: FM_BAYER_RGGB 0, _GRBG 1, _GBRG 2, _BGGR 3
+ *   sample preparation, before any interpolation: v = max(s - black, 0), p = min(255, (v * gain + (1 << (depth - 1))) >> depth)
+ *     with the gain (1/256 units: 256 is 1.0) of the colour the sample's position carries; p == s for black 0, gains 256
+ *     and depth 8
+ *   borders: reflect-101 on the index in both directions (m = 2 (n - 1), i <- i mod m, i <- m - i where i >= n): m is
+ *     even, so a reflected index keeps its colour -- which takes two samples each way, hence width, height >= 2; odd
+ *     sizes are legal
+ *   a position's own colour is p; with c the centre, card = N + S + E + W, hor = E + W, ver = N + S, diag the four
+ *   diagonals, h2 / v2 the two samples at distance 2 horizontally / vertically:
+ *   FM_BAYER_BILINEAR: G at R / B (card + 2) >> 2; R / B at G (a + b + 1) >> 1 of that colour's two neighbours; R at B and
+ *     B at R (diag + 2) >> 2
+ *   FM_BAYER_MHC (Malvar-He-Cutler, gradient-corrected, in sixteenths): sat8((sum + 8) >> 4) of
+ *     G at R / B: 8 c + 4 card - 2 (h2 + v2)              R at B, B at R: 12 c + 4 diag - 3 (h2 + v2)
+ *     R / B at G, that colour left and right: 10 c + 8 hor - 2 diag - 2 h2 + v2;  above and below: 10 c + 8 ver - 2 diag - 2 v2 + h2
+ * integer and exact (fastmot_amd/utils/bayer.py bayer_to_bgr states it in numpy).
+ * The three calls mirror fm_frame_upload_packed, fm_frame_upload_ahead_packed and fm_frame_ring_store_packed one for
+ * one: same slots, same streams, same syncs, same events.  The rows cross as they lie, width or 2 width bytes each,
+ * packed to that width on the way -- through page-locked staging (fm_frame_upload_src's, with its rules) only when the
+ * source is pageable or pitched: a surface with pitch == its row bytes inside a buffer from fm_host_alloc is copied from
+ * where it lies; the device staging per entry point / look-ahead slot is allocated on its first Bayer use and freed by
+ * fm_frame_configure and fm_ctx_destroy; a kernel on the copy's stream (csrc/bayer.hip) writes the BGR frame where the BGR
+ * call would have put it, and a look-ahead slot's completion event follows it.  width x height other than the
+ * configured frame size: the frame takes the route of fm_frame_upload_src -- that family's buffers; the kernel writes
+ * the source-size BGR frame and csrc/resize.hip the frame.
+ * FM_ERR_ARG for a null ctx / f / data pointer, a pattern, method or depth outside their sets, a width or height outside
+ * 2..FM_SRC_MAX_DIM, a pitch below the row's bytes, a gain outside 1..4096, a black level outside 0..2^depth - 1, or a
+ * bad k / index; nothing is copied, allocated or launched then. */
+#define FM_BAYER_RGGB 0
+#define FM_BAYER_GRBG 1
+#define FM_BAYER_GBRG 2
+#define FM_BAYER_BGGR 3
+#define FM_BAYER_BILINEAR 0
+#define FM_BAYER_MHC 1
+struct fm_frame_bayer {
+    int32_t pattern, width, height, pitch, depth, method, black, gain_r, gain_g, gain_b;   /* FM_BAYER_*; pitch in bytes */
+    const uint8_t* data;
+};
+int fm_frame_upload_bayer(fm_ctx* ctx, const struct fm_frame_bayer* f);
+int fm_frame_upload_ahead_bayer(fm_ctx* ctx, int k, const struct fm_frame_bayer* f);
+int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm_frame_bayer* f);
+
 /* Frames OUT as baseline JPEG (an output 'out/%06d.jpg' or 'out.mjpeg'): replaces the Pillow save of
  * fastmot_amd/videoio.py's writer and, in the reference, cv2.VideoWriter (fastmot/videoio.py).  The device does
  * everything that is per pixel or per coefficient (csrc/jpegenc.hip): BGR -> YCbCr, edge replication to the 16 x 16 MCU
