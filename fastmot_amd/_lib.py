@@ -494,6 +494,30 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_configure(self._ctx, C.c_int(width), C.c_int(height), C.c_int(ring_size)))
         self.frame_size = (width, height)
         self.ring_size = ring_size
+        self._lens = None                  # (fm_frame_configure drops the map)
+
+    def frame_set_lens(self, lens):
+        """Sets the correction map of the described-source calls (a LensMap whose dst_size is the context's frame size),
+        or none.  A per-stream setting: it synchronises the detector and ReID streams and uploads the map, so it may
+        change but should not alternate per frame.  The SourceFrame branches of frame_upload / frame_upload_next /
+        frame_upload_ahead / frame_ring_store call it when a frame carries another LensMap object than the one set."""
+        if lens is None:
+            check(self.lib.fm_frame_remap_clear(self._ctx))
+            self._lens = None
+            return
+        if lens.dst_size != tuple(self.frame_size):
+            raise ValueError(f'the lens map gives {lens.dst_size[0]}x{lens.dst_size[1]} frames, the context\'s are '
+                             f'{self.frame_size[0]}x{self.frame_size[1]}')
+        check(self.lib.fm_frame_remap_set(self._ctx, C.c_int(lens.src_size[0]), C.c_int(lens.src_size[1]), _ptr(lens.xy),
+                                          (C.c_uint8 * 3)(*lens.border)))
+        self._lens = lens
+
+    def _described(self, frame):
+        """Before a described-source call (fm_frame_*_src / _planar / _packed / _bayer) on `frame`: the context's map is
+        the one the frame carries -- none for a frame that is not a SourceFrame."""
+        lens = getattr(frame, 'lens', None)
+        if lens is not getattr(self, '_lens', None):
+            self.frame_set_lens(lens)
 
     def _nv12_args(self, frame):
         if frame.size != tuple(self.frame_size):
@@ -542,14 +566,17 @@ def _bind_device_io(cls):
     def frame_upload(self, frame):
         planar = self._planar_of(frame)
         if planar is not None:
+            self._described(frame)
             check(self.lib.fm_frame_upload_planar(self._ctx, C.byref(planar.describe())))
             return
         packed = self._packed_of(frame)
         if packed is not None:
+            self._described(frame)
             check(self.lib.fm_frame_upload_packed(self._ctx, C.byref(packed.describe())))
             return
         bayer = self._bayer_of(frame)
         if bayer is not None:
+            self._described(frame)
             check(self.lib.fm_frame_upload_bayer(self._ctx, C.byref(bayer.describe())))
             return
         if isinstance(frame, NV12Frame):
@@ -559,6 +586,7 @@ def _bind_device_io(cls):
             check(self.lib.fm_frame_upload_jpeg(self._ctx, *self._jpeg_args(frame)))
             return
         if isinstance(frame, SourceFrame):      # any size: resized to the frame size on the device (csrc/resize.hip)
+            self._described(frame)
             check(self.lib.fm_frame_upload_src(self._ctx, C.byref(frame.describe())))
             return
         w, h = self.frame_size
@@ -625,14 +653,17 @@ def _bind_device_io(cls):
     def frame_ring_store(self, index, frame):
         planar = self._planar_of(frame)
         if planar is not None:
+            self._described(frame)
             check(self.lib.fm_frame_ring_store_planar(self._ctx, C.c_int(index), C.byref(planar.describe())))
             return
         packed = self._packed_of(frame)
         if packed is not None:
+            self._described(frame)
             check(self.lib.fm_frame_ring_store_packed(self._ctx, C.c_int(index), C.byref(packed.describe())))
             return
         bayer = self._bayer_of(frame)
         if bayer is not None:
+            self._described(frame)
             check(self.lib.fm_frame_ring_store_bayer(self._ctx, C.c_int(index), C.byref(bayer.describe())))
             return
         if isinstance(frame, NV12Frame):
@@ -642,6 +673,7 @@ def _bind_device_io(cls):
             check(self.lib.fm_frame_ring_store_jpeg(self._ctx, C.c_int(index), *self._jpeg_args(frame)))
             return
         if isinstance(frame, SourceFrame):
+            self._described(frame)
             check(self.lib.fm_frame_ring_store_src(self._ctx, C.c_int(index), C.byref(frame.describe())))
             return
         f = np.ascontiguousarray(frame, np.uint8)
@@ -672,14 +704,17 @@ def _bind_device_io(cls):
         """Host frame for the step k steps ahead (look-ahead slot k, 1 <= k <= FM_MAX_DET_BATCH; k = 1: frame_upload_next)."""
         planar = self._planar_of(frame)
         if planar is not None:
+            self._described(frame)
             check(self.lib.fm_frame_upload_ahead_planar(self._ctx, C.c_int(k), C.byref(planar.describe())))
             return
         packed = self._packed_of(frame)
         if packed is not None:
+            self._described(frame)
             check(self.lib.fm_frame_upload_ahead_packed(self._ctx, C.c_int(k), C.byref(packed.describe())))
             return
         bayer = self._bayer_of(frame)
         if bayer is not None:
+            self._described(frame)
             check(self.lib.fm_frame_upload_ahead_bayer(self._ctx, C.c_int(k), C.byref(bayer.describe())))
             return
         if isinstance(frame, NV12Frame):
@@ -689,6 +724,7 @@ def _bind_device_io(cls):
             check(self.lib.fm_frame_upload_ahead_jpeg(self._ctx, C.c_int(k), *self._jpeg_args(frame)))
             return
         if isinstance(frame, SourceFrame):
+            self._described(frame)
             check(self.lib.fm_frame_upload_ahead_src(self._ctx, C.c_int(k), C.byref(frame.describe())))
             return
         w, h = self.frame_size
@@ -876,7 +912,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
+    for fn in (frame_configure, frame_set_lens, _described, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
                overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,

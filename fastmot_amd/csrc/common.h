@@ -225,6 +225,13 @@ struct fm_ctx {
         hipEvent_t ev = nullptr;     // behind the last H2D copy out of `pinned`
     };
     SrcStage frame_src[FM_MAX_DET_BATCH + 2];
+
+    // ---- the correction map of the described-source calls (fm_frame_remap_set; csrc/remap.hip gathers through it in
+    // place of the resize): [frame_h][frame_w][2] int32 on the device, null = none.  Dropped by fm_frame_remap_clear,
+    // fm_frame_configure and fm_ctx_destroy.
+    int32_t* remap_xy = nullptr;
+    int remap_sw = 0, remap_sh = 0;        // the one source size the map is for
+    uint32_t remap_border = 0;             // b | g << 8 | r << 16
 };
 
 // one timed event on stream `s` (no-op unless a trace is running; both host threads of a context may call it)
@@ -273,7 +280,10 @@ int fm_bayer_to_bgr(const uint8_t* src, uint8_t* bgr, int w, int h, int pattern,
                     int gain_b, hipStream_t s);                                                   // bayer.hip
 void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
+// remap.hip: `src` through the device map `xy` ([dh][dw][2] int32, remap_pixel.h); border = b | g << 8 | r << 16
+int fm_remap_bgr(const uint8_t* src, int sw, int sh, const int32_t* xy, uint8_t* dst, int dw, int dh, uint32_t border, hipStream_t s);
 void fm_frame_src_free(fm_ctx* ctx);                                                              // detect.hip
+void fm_frame_remap_free(fm_ctx* ctx);                                                            // detect.hip (no sync: the caller's)
 int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s);   // jpeg.hip
 // fm_jpeg_info's description of a width x height frame with ncomp 1 or 3 and luma sampling hsamp0 x vsamp0 (jpeg_host.hip)
 int fm_jpeg_layout(int width, int height, int ncomp, int hsamp0, int vsamp0, struct fm_jpeg_info* out);

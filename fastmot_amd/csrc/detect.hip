@@ -19,6 +19,7 @@
 // Roofline: HBM bound -- reads (5+C)*A*sum(HW)*4 B of head tensors (7.7 MB @608/80 classes),
 // frame 6.2 MB in, 608*608*8*2 B out.
 #include "pixel_source.h"
+#include "remap_pixel.h"
 #include <cmath>
 #include <mutex>
 #include <utility>
@@ -1135,6 +1136,7 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         p = nullptr;
     }
     fm_frame_src_free(ctx);                            // off-size sources: allocated again on first use
+    fm_frame_remap_free(ctx);                          // a correction map is for one frame size: set again by the caller
     const size_t bytes = (size_t)width * height * 3;
     FM_HIP(hipMalloc(&ctx->frame_own, bytes + FM_FRAME_SLACK));        // (pixel_source.h load_px2 reads 8 bytes at a pixel)
     FM_HIP(hipMalloc(&ctx->frame_own2, bytes + FM_FRAME_SLACK));
@@ -1569,7 +1571,68 @@ static bool src_ok(const struct fm_frame_src* f) {
     }
     return false;
 }
-static bool src_on_size(const fm_ctx* ctx, const struct fm_frame_src* f) { return f->width == ctx->frame_w && f->height == ctx->frame_h; }
+
+// ---- the correction map (remap.hip): while one is set, every described-source call -- fm_frame_*_src and the planar,
+// packed and Bayer families below -- takes sources of the map's size only, stages them at that size even when it is the
+// configured one, and ends in fm_remap_bgr where it ends in fm_resize_bgr without.
+void fm_frame_remap_free(fm_ctx* ctx) {
+    if (ctx->remap_xy) (void)hipFree(ctx->remap_xy);
+    ctx->remap_xy = nullptr;
+    ctx->remap_sw = ctx->remap_sh = 0;
+    ctx->remap_border = 0;
+}
+
+// the streams whose queued kernels may still read the map: the three the described-source calls launch on
+static int remap_idle(fm_ctx* ctx) {
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+extern "C" int fm_frame_remap_set(fm_ctx* ctx, int src_w, int src_h, const int32_t* xy, const uint8_t border_bgr[3]) {
+    FM_CHECK_ARG(ctx && ctx->frame_own && xy && border_bgr);
+    FM_CHECK_ARG(src_w >= 1 && src_h >= 1 && src_w <= FM_SRC_MAX_DIM && src_h <= FM_SRC_MAX_DIM);
+    const size_t n = (size_t)ctx->frame_w * ctx->frame_h;
+    for (size_t i = 0; i < n; ++i) FM_CHECK_ARG(fm_remap_entry_ok(xy[2 * i], xy[2 * i + 1], src_w, src_h));
+    int rc = remap_idle(ctx);
+    if (rc) return rc;
+    int32_t* dev = nullptr;
+    FM_HIP(hipMalloc(&dev, n * 2 * sizeof(int32_t)));
+    if (hipError_t e = hipMemcpy(dev, xy, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice); e != hipSuccess) {
+        (void)hipFree(dev);
+        FM_HIP(e);
+    }
+    fm_frame_remap_free(ctx);
+    ctx->remap_xy = dev;
+    ctx->remap_sw = src_w, ctx->remap_sh = src_h;
+    ctx->remap_border = (uint32_t)border_bgr[0] | (uint32_t)border_bgr[1] << 8 | (uint32_t)border_bgr[2] << 16;
+    return 0;
+}
+
+extern "C" int fm_frame_remap_clear(fm_ctx* ctx) {
+    FM_CHECK_ARG(ctx);
+    if (!ctx->remap_xy) return 0;
+    int rc = remap_idle(ctx);
+    if (rc) return rc;
+    fm_frame_remap_free(ctx);
+    return 0;
+}
+
+// a w x h source is one the described-source calls take now: any without a map, the map's size with one
+static bool remap_takes(const fm_ctx* ctx, int w, int h) { return !ctx->remap_xy || (w == ctx->remap_sw && h == ctx->remap_sh); }
+
+// a w x h source needs no kernel of the tail below: it has the configured size and no map is set
+static bool src_on_size(const fm_ctx* ctx, int w, int h) { return !ctx->remap_xy && w == ctx->frame_w && h == ctx->frame_h; }
+static bool src_on_size(const fm_ctx* ctx, const struct fm_frame_src* f) { return src_on_size(ctx, f->width, f->height); }
+
+// The last kernel of every described-source route: the source-size BGR frame `bgr` (w x h, + FM_FRAME_SLACK) into the
+// configured-size frame `dst` on `s` -- through the correction map when one is set, resized otherwise.
+static int enqueue_src_tail(fm_ctx* ctx, const uint8_t* bgr, int w, int h, uint8_t* dst, hipStream_t s) {
+    fm_trace_mark(ctx, s, 38);                 // (the resize's / remap's share of the caller's 30 .. 31 interval)
+    if (ctx->remap_xy) return fm_remap_bgr(bgr, w, h, ctx->remap_xy, dst, ctx->frame_w, ctx->frame_h, ctx->remap_border, s);
+    return fm_resize_bgr(bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+}
 
 // at least `bytes` at p; a buffer that has to grow is given up once `s`, the stream whose copies and kernels use it, is idle
 static int src_reserve(uint8_t*& p, size_t& cap, size_t bytes, bool host, hipStream_t s) {
@@ -1657,12 +1720,12 @@ static int enqueue_src(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_fra
         fm_trace_mark(ctx, s, 37);
         if ((rc = fm_jpeg_to_bgr(st.dev, st.bgr, f->info, s))) return rc;
     }
-    fm_trace_mark(ctx, s, 38);                 // (the resize's share of the caller's 30 .. 31 interval)
-    return fm_resize_bgr(st.bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
 }
 
 extern "C" int fm_frame_upload_src(fm_ctx* ctx, const struct fm_frame_src* src) {
     FM_CHECK_ARG(ctx && ctx->frame_own && src_ok(src));
+    FM_CHECK_ARG(remap_takes(ctx, src->width, src->height));      // (a correction map is for one source size)
     if (src_on_size(ctx, src)) {
         if (src->kind == FM_SRC_BGR) return fm_frame_upload(ctx, src->bgr);
         if (src->kind == FM_SRC_NV12) return fm_frame_upload_nv12(ctx, src->y, src->uv, src->pitch, src->matrix);
@@ -1682,6 +1745,7 @@ extern "C" int fm_frame_upload_src(fm_ctx* ctx, const struct fm_frame_src* src) 
 
 extern "C" int fm_frame_upload_ahead_src(fm_ctx* ctx, int k, const struct fm_frame_src* src) {
     FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && src_ok(src));
+    FM_CHECK_ARG(remap_takes(ctx, src->width, src->height));      // (a correction map is for one source size)
     if (src_on_size(ctx, src)) {
         if (src->kind == FM_SRC_BGR) return fm_frame_upload_ahead(ctx, k, src->bgr);
         if (src->kind == FM_SRC_NV12) return fm_frame_upload_ahead_nv12(ctx, k, src->y, src->uv, src->pitch, src->matrix);
@@ -1712,6 +1776,7 @@ extern "C" int fm_frame_upload_ahead_src(fm_ctx* ctx, int k, const struct fm_fra
 
 extern "C" int fm_frame_ring_store_src(fm_ctx* ctx, int index, const struct fm_frame_src* src) {
     FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && src_ok(src));
+    FM_CHECK_ARG(remap_takes(ctx, src->width, src->height));      // (a correction map is for one source size)
     if (src_on_size(ctx, src)) {
         if (src->kind == FM_SRC_BGR) return fm_frame_ring_store(ctx, index, src->bgr);
         if (src->kind == FM_SRC_NV12) return fm_frame_ring_store_nv12(ctx, index, src->y, src->uv, src->pitch, src->matrix);
@@ -1749,7 +1814,7 @@ static int enqueue_planar(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_
     int cw = 0, ch = 0;
     fm_yuv_chroma_dims(w, h, f->chroma, &cw, &ch);
     const size_t npx = (size_t)w * h, nc = (size_t)cw * ch, total = npx + 2 * nc;
-    const bool on_size = w == ctx->frame_w && h == ctx->frame_h;
+    const bool on_size = src_on_size(ctx, w, h);
     fm_ctx::SrcStage& st = ctx->frame_src[entry];
     uint8_t* stage = nullptr;
     int rc;
@@ -1790,12 +1855,12 @@ static int enqueue_planar(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_
     fm_trace_mark(ctx, s, 39);                 // (the conversion's share of the caller's 30 .. 31 interval)
     if (on_size) return fm_planar_to_bgr(stage, dst, w, h, f->chroma, f->matrix, s);
     if ((rc = fm_planar_to_bgr(stage, st.bgr, w, h, f->chroma, f->matrix, s))) return rc;
-    fm_trace_mark(ctx, s, 38);                 // (the resize's share)
-    return fm_resize_bgr(st.bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
 }
 
 extern "C" int fm_frame_upload_planar(fm_ctx* ctx, const struct fm_frame_planar* f) {
     FM_CHECK_ARG(ctx && ctx->frame_own && planar_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_ext));
@@ -1810,6 +1875,7 @@ extern "C" int fm_frame_upload_planar(fm_ctx* ctx, const struct fm_frame_planar*
 
 extern "C" int fm_frame_upload_ahead_planar(fm_ctx* ctx, int k, const struct fm_frame_planar* f) {
     FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && planar_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
     if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (the BGR-sized staging holds every planar layout)
         FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
@@ -1833,6 +1899,7 @@ extern "C" int fm_frame_upload_ahead_planar(fm_ctx* ctx, int k, const struct fm_
 
 extern "C" int fm_frame_ring_store_planar(fm_ctx* ctx, int index, const struct fm_frame_planar* f) {
     FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && planar_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies that pack the rows, then
     // the kernels on the null stream
     int rc = enqueue_planar(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr,
@@ -1860,7 +1927,7 @@ static bool packed_ok(const struct fm_frame_packed* f) {
 static int enqueue_packed(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_packed* f, hipStream_t s, bool blocking) {
     const int w = f->width, h = f->height;
     const size_t rb = fm_packed_row_bytes(w, f->format), total = rb * h, npx = (size_t)w * h;
-    const bool on_size = w == ctx->frame_w && h == ctx->frame_h;
+    const bool on_size = src_on_size(ctx, w, h);
     fm_ctx::SrcStage& st = ctx->frame_src[entry];
     uint8_t* stage = nullptr;
     int rc;
@@ -1886,12 +1953,12 @@ static int enqueue_packed(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_
     fm_trace_mark(ctx, s, 48);                 // (the conversion's share of the caller's 30 .. 31 interval)
     if (on_size) return fm_packed_to_bgr(stage, dst, w, h, f->format, f->matrix, s);
     if ((rc = fm_packed_to_bgr(stage, st.bgr, w, h, f->format, f->matrix, s))) return rc;
-    fm_trace_mark(ctx, s, 38);                 // (the resize's share)
-    return fm_resize_bgr(st.bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
 }
 
 extern "C" int fm_frame_upload_packed(fm_ctx* ctx, const struct fm_frame_packed* f) {
     FM_CHECK_ARG(ctx && ctx->frame_own && packed_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_ext));
@@ -1906,6 +1973,7 @@ extern "C" int fm_frame_upload_packed(fm_ctx* ctx, const struct fm_frame_packed*
 
 extern "C" int fm_frame_upload_ahead_packed(fm_ctx* ctx, int k, const struct fm_frame_packed* f) {
     FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && packed_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
     if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
         FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
@@ -1931,6 +1999,7 @@ extern "C" int fm_frame_upload_ahead_packed(fm_ctx* ctx, int k, const struct fm_
 
 extern "C" int fm_frame_ring_store_packed(fm_ctx* ctx, int index, const struct fm_frame_packed* f) {
     FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && packed_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     // synchronous like fm_frame_ring_store (filling the ring is set-up work): a blocking copy that packs the rows, then
     // the kernels on the null stream
     int rc = enqueue_packed(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
@@ -1960,7 +2029,7 @@ static bool bayer_ok(const struct fm_frame_bayer* f) {
 static int enqueue_bayer(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_bayer* f, hipStream_t s, bool blocking) {
     const int w = f->width, h = f->height;
     const size_t rb = (size_t)w * fm_bayer_sample_bytes(f->depth), total = rb * h, npx = (size_t)w * h;
-    const bool on_size = w == ctx->frame_w && h == ctx->frame_h;
+    const bool on_size = src_on_size(ctx, w, h);
     fm_ctx::SrcStage& st = ctx->frame_src[entry];
     uint8_t* stage = nullptr;
     int rc;
@@ -1987,12 +2056,12 @@ static int enqueue_bayer(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_f
     uint8_t* const out = on_size ? dst : st.bgr;
     if ((rc = fm_bayer_to_bgr(stage, out, w, h, f->pattern, f->depth, f->method, f->black, f->gain_r, f->gain_g, f->gain_b, s))) return rc;
     if (on_size) return 0;
-    fm_trace_mark(ctx, s, 38);                 // (the resize's share)
-    return fm_resize_bgr(st.bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
+    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
 }
 
 extern "C" int fm_frame_upload_bayer(fm_ctx* ctx, const struct fm_frame_bayer* f) {
     FM_CHECK_ARG(ctx && ctx->frame_own && bayer_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_ext));
@@ -2007,6 +2076,7 @@ extern "C" int fm_frame_upload_bayer(fm_ctx* ctx, const struct fm_frame_bayer* f
 
 extern "C" int fm_frame_upload_ahead_bayer(fm_ctx* ctx, int k, const struct fm_frame_bayer* f) {
     FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && bayer_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
     if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
         FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
@@ -2029,6 +2099,7 @@ extern "C" int fm_frame_upload_ahead_bayer(fm_ctx* ctx, int k, const struct fm_f
 
 extern "C" int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm_frame_bayer* f) {
     FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && bayer_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
     // synchronous like fm_frame_ring_store (filling the ring is set-up work): a blocking copy that packs the rows, then
     // the kernels on the null stream
     int rc = enqueue_bayer(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);

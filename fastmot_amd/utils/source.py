@@ -12,6 +12,7 @@ import numpy as np
 
 from .bayer import BayerFrame
 from .jpeg import JPEGFrame, JpegInfo
+from .lens import LensMap
 from .nv12 import NV12Frame
 from .packed import PackedFrame
 from .yuv import PlanarFrame
@@ -39,9 +40,14 @@ class SourceFrame:
     frame: a BGR ndarray (H, W, 3) uint8, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame or a BayerFrame, at most 16384 pixels in either direction.  It
     is not copied (an ndarray that is not C-contiguous is, once): it must stay unmodified until the step that uses the
     frame has returned.  `size` is the SOURCE's (W, H) and `shape` its (H, W, 3); the frame every stage reads has the
-    size of the context it is uploaded to."""
+    size of the context it is uploaded to.
 
-    def __init__(self, frame):
+    lens: a LensMap for frames of this size (utils/lens.py), or None.  With one, the kernel of csrc/remap.hip takes the
+    resize's place and the device frame equals `utils.lens.remap_bgr(frame, lens)` bit for bit -- also for a frame that
+    already has the tracker's size.  Hand every frame of a stream the SAME LensMap object: the context switches maps,
+    and synchronises, when a frame carries another object than the one it has set."""
+
+    def __init__(self, frame, lens=None):
         if isinstance(frame, SourceFrame):
             raise TypeError('frame is a SourceFrame already')
         if isinstance(frame, (NV12Frame, JPEGFrame, PlanarFrame, PackedFrame, BayerFrame)):
@@ -55,6 +61,12 @@ class SourceFrame:
             raise TypeError(f'frame must be a BGR ndarray, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame or a BayerFrame, not {type(frame).__name__}')
         if not (1 <= w <= MAX_DIM and 1 <= h <= MAX_DIM):
             raise ValueError(f'source size {w}x{h} outside 1..{MAX_DIM}')
+        if lens is not None:
+            if not isinstance(lens, LensMap):
+                raise TypeError(f'lens must be a LensMap, not {type(lens).__name__}')
+            if lens.src_size != (w, h):
+                raise ValueError(f'the lens map is for {lens.src_size[0]}x{lens.src_size[1]} frames, this one is {w}x{h}')
+        self.lens = lens
         self.frame = frame
         self.size = (w, h)
         self.shape = (h, w, 3)

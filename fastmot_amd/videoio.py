@@ -264,7 +264,8 @@ class VideoIO:
                  pixel_format=None,
                  demosaic='mhc',
                  white_balance=None,
-                 black_level=0):
+                 black_level=0,
+                 lens=None):
         """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` / `"gpu_resize": true`
         in the configuration file's stream_cfg reach it through an unmodified app.py):
         gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
@@ -308,7 +309,15 @@ class VideoIO:
             Bayer keys -- 'rggb', 'grbg', 'gbrg', 'bggr' for a uint8 stack (N, H, W) of raw mosaics, the same with '10',
             '12', '14' or '16' behind them ('rggb12') for a uint16 stack of that depth -- follow the same rules with
             utils.bayer.bayer_to_bgr, BayerFrames and csrc/bayer.hip; `demosaic` ('mhc' / 'bilinear'), `white_balance`
-            (gains (R, G, B); None: 1.0 each) and `black_level` (in sample units) go with them and with nothing else."""
+            (gains (R, G, B); None: 1.0 each) and `black_level` (in sample units) go with them and with nothing else.
+        lens (`"lens": {"model": "pinhole" | "fisheye", "camera_matrix": ..., "dist_coeffs": ..., "zoom": 1.0,
+            "border": [b, g, r]}` in stream_cfg, or a utils.lens.LensMap; None: everything as it was): every frame is
+            undistorted -- and brought to `size` by the same map -- in place of being resized.  The LensMap is built once,
+            from the first frame's resolution (`self.lens`).  Where `read` would return a SourceFrame under gpu_resize it
+            returns `SourceFrame(frame, lens=self.lens)`, also for frames already at `size`, and csrc/remap.hip corrects
+            them on the GPU; in every other case `read` applies utils.lens.remap_bgr here, on the thread that calls it,
+            and returns host pixels (GPU frame kinds of gpu_decode are then converted here too).  The flags decide where
+            the work happens, never what the pixels are."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -336,27 +345,29 @@ class VideoIO:
         # frames that Pillow / numpy write
         host_pixels = output_uri is not None and not self._jpeg_out and not (self._y4m_out and self.gpu_encode)
         self._wrap_sources = self.gpu_resize and not host_pixels
+        # a lens without gpu_resize is applied to host pixels: nothing may stay a GPU frame kind then
+        gpu_kinds = not host_pixels and (lens is None or self._wrap_sources)
         if pixel_format is not None and not (self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy')):
             raise ValueError(f"pixel_format={pixel_format!r} describes a '.npy' frame stack, not {self.input_uri}")
         if self.protocol == Protocol.IMAGE:
-            self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and not host_pixels else None,
+            self.source = _ImageSequence(self.input_uri, self.size if self.gpu_decode and gpu_kinds else None,
                                          any_size=self._wrap_sources)
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy') and _bayer_format(pixel_format) is not None:
             from .utils.source import MAX_DIM
-            on_gpu = self.gpu_decode and not host_pixels
+            on_gpu = self.gpu_decode and gpu_kinds
             pattern, depth = _bayer_format(pixel_format)
             self.source = _BayerStack(self.input_uri, pattern, depth, demosaic, white_balance, black_level,
                                       bayer=lambda size: on_gpu and max(size) <= MAX_DIM and (tuple(size) == self.size or self._wrap_sources))
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy') and pixel_format is not None:
             from .utils.source import MAX_DIM
-            on_gpu = self.gpu_decode and not host_pixels
+            on_gpu = self.gpu_decode and gpu_kinds
             self.source = _PackedStack(self.input_uri, pixel_format, matrix=yuv_matrix, packed=lambda size: on_gpu and max(size) <= MAX_DIM and (
                 tuple(size) == self.size or self._wrap_sources))
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).endswith('.npy'):
             self.source = _FrameStack(self.input_uri)
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).lower().endswith('.y4m'):
             from .utils.source import MAX_DIM
-            on_gpu = self.gpu_decode and not host_pixels
+            on_gpu = self.gpu_decode and gpu_kinds
             self.source = _Y4MStream(self.input_uri, matrix=yuv_matrix, planar=lambda size: on_gpu and max(size) <= MAX_DIM and (
                 tuple(size) == self.size or self._wrap_sources))
         else:
@@ -377,6 +388,12 @@ class VideoIO:
         self.resolution = (width, height)
         self.cap_fps = getattr(self.source, 'fps', None) or self.frame_rate     # (only a .y4m stream carries a frame rate)
         self.do_resize = (width, height) != self.size
+        self.lens = None
+        if lens is not None:
+            from .utils.lens import LensMap
+            self.lens = lens if isinstance(lens, LensMap) else LensMap.from_config(lens, (width, height), self.size)
+            if self.lens.src_size != (width, height) or self.lens.dst_size != self.size:
+                raise ValueError(f'the lens map is {self.lens.src_size} -> {self.lens.dst_size}, the stream {(width, height)} -> {self.size}')
         LOGGER.info('%dx%d stream @ %d FPS', width, height, self.cap_fps)
 
         self._written = 0
@@ -424,6 +441,12 @@ class VideoIO:
                 return None
             frame = self.frame_queue.popleft()
             self.cond.notify()
+        if self.lens is not None:
+            if self._wrap_sources:
+                from .utils.source import SourceFrame
+                return SourceFrame(frame, lens=self.lens)
+            from .utils.lens import remap_bgr
+            return remap_bgr(frame, self.lens)
         if self._wrap_sources:
             from .utils.source import MAX_DIM, SourceFrame
             if not isinstance(frame, np.ndarray):                 # a JPEGFrame / PlanarFrame / PackedFrame / BayerFrame, of any size

@@ -656,6 +656,35 @@ int fm_frame_upload_bayer(fm_ctx* ctx, const struct fm_frame_bayer* f);
 int fm_frame_upload_ahead_bayer(fm_ctx* ctx, int k, const struct fm_frame_bayer* f);
 int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm_frame_bayer* f);
 
+/* Geometry between sensor and tracker: lens undistortion, or any fixed correction that is one map (a rotation by 90
+ * degrees, a mirror, a perspective crop), applied by the gather that already ends every described-source call.  A map
+ * holds, for every pixel of the configured width x height frame, a source coordinate in fixed point with 5 fractional
+ * bits: `xy` is int32 [height][width][2], X = rint(32 x), Y = rint(32 y), X in [-64, 32 (src_w + 1)], Y in
+ * [-64, 32 (src_h + 1)] (-64: fully outside).  With ix = X >> 5 (arithmetic), fx = X & 31 and the same for y, the four
+ * taps are (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1); a tap outside [0, src_w) x [0, src_h) contributes the
+ * channel of `border_bgr`, chosen per tap, and per channel
+ *   v = ((32 - fy) ((32 - fx) p00 + fx p01) + fy ((32 - fx) p10 + fx p11) + 512) >> 10
+ * -- exact in 32 bits, the float64 bilinear value of the quantised coordinate rounded half up (csrc/remap_pixel.h: one
+ * text for the kernel of csrc/remap.hip and for fm_remap_bgr_host; fastmot_amd/utils/lens.py remap_bgr in numpy).  It
+ * is NOT the resize's arithmetic: an identity-geometry map gives pixels near fm_frame_upload_src's, not equal to them.
+ * fm_frame_remap_set is set-up work: it checks every entry's range on the host, waits for the detector stream, the
+ * ReID stream and the null stream (those whose queued kernels may still read the previous map) and uploads a copy of
+ * the map for the configured frame size.  FM_ERR_ARG, with the previous map untouched, for a null pointer, no configured
+ * frame, src_w / src_h outside 1..FM_SRC_MAX_DIM or an entry out of range.  fm_frame_remap_clear, fm_frame_configure
+ * and fm_ctx_destroy drop the map.
+ * While a map is set the described-source calls -- fm_frame_upload_src / _ahead_src / _ring_store_src and their
+ * _planar, _packed and _bayer forms -- take sources of src_w x src_h only (FM_ERR_ARG for any other, nothing copied or
+ * launched), stage them at that size even when it is the configured one, and end in the remap kernel where they end in
+ * the resize kernel without a map: same slots, streams, syncs, events and trace marks.  Every other call, and every
+ * call while no map is set, is untouched.  A per-stream setting: it may change, it should not alternate per frame.
+ * fm_remap_bgr_host: the same arithmetic on host pixels (src_w x src_h packed BGR -> width x height packed BGR, both
+ * within 1..FM_SRC_MAX_DIM), compiled from the kernel's text; no context, no GPU, any number of threads.  FM_ERR_ARG for
+ * a null pointer, a size out of range or a map entry out of range. */
+int fm_frame_remap_set(fm_ctx* ctx, int src_w, int src_h, const int32_t* xy, const uint8_t border_bgr[3]);
+int fm_frame_remap_clear(fm_ctx* ctx);
+int fm_remap_bgr_host(const uint8_t* src, int src_w, int src_h, const int32_t* xy, uint8_t* dst, int width, int height,
+                      const uint8_t border_bgr[3]);
+
 /* Frames OUT as baseline JPEG (an output 'out/%06d.jpg' or 'out.mjpeg'): replaces the Pillow save of
  * fastmot_amd/videoio.py's writer and, in the reference, cv2.VideoWriter (fastmot/videoio.py).  The device does
  * everything that is per pixel or per coefficient (csrc/jpegenc.hip): BGR -> YCbCr, edge replication to the 16 x 16 MCU
