@@ -17,9 +17,10 @@ from .utils.source import SourceFrame
 from .utils.yuv import PlanarFrame, I420Image
 from .utils.packed import PackedFrame
 from .utils.bayer import BayerFrame
+from .utils.deep import DeepFrame
 from .utils.lens import LensMap
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'PackedFrame', 'BayerFrame', 'LensMap', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'PackedFrame', 'BayerFrame', 'DeepFrame', 'LensMap', 'models']
 
 
 def __getattr__(name):

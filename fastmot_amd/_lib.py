@@ -18,6 +18,7 @@ from .utils.source import SourceFrame
 from .utils.yuv import PlanarFrame, frame_bytes
 from .utils.packed import PackedFrame, row_bytes
 from .utils.bayer import BayerFrame
+from .utils.deep import DeepFrame, deep_frame_bytes
 
 LIB_PATH = Path(os.environ.get('FASTMOT_LIB_PATH', Path(__file__).parent / 'libfastmot_hip.so'))
 
@@ -513,7 +514,7 @@ def _bind_device_io(cls):
         self._lens = lens
 
     def _described(self, frame):
-        """Before a described-source call (fm_frame_*_src / _planar / _packed / _bayer) on `frame`: the context's map is
+        """Before a described-source call (fm_frame_*_src / _planar / _packed / _bayer / _deep) on `frame`: the context's map is
         the one the frame carries -- none for a frame that is not a SourceFrame."""
         lens = getattr(frame, 'lens', None)
         if lens is not getattr(self, '_lens', None):
@@ -563,6 +564,17 @@ def _bind_device_io(cls):
             return frame
         return None
 
+    def _deep_of(self, frame):
+        """The DeepFrame a deep call takes for `frame`, by `_planar_of`'s rules, or None for every other frame kind."""
+        if isinstance(frame, SourceFrame) and isinstance(frame.frame, DeepFrame):
+            return frame.frame
+        if isinstance(frame, DeepFrame):
+            if frame.size != tuple(self.frame_size):
+                raise ValueError(f'deep frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
+                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
+            return frame
+        return None
+
     def frame_upload(self, frame):
         planar = self._planar_of(frame)
         if planar is not None:
@@ -578,6 +590,11 @@ def _bind_device_io(cls):
         if bayer is not None:
             self._described(frame)
             check(self.lib.fm_frame_upload_bayer(self._ctx, C.byref(bayer.describe())))
+            return
+        deep = self._deep_of(frame)
+        if deep is not None:
+            self._described(frame)
+            check(self.lib.fm_frame_upload_deep(self._ctx, C.byref(deep.describe())))
             return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_nv12(self._ctx, *self._nv12_args(frame)))
@@ -650,6 +667,19 @@ def _bind_device_io(cls):
         buf = pinned_empty(self.lib, (n, h, w), np.uint8 if depth == 8 else np.dtype('<u2'))
         return [BayerFrame(buf[i], pattern, (w, h), depth, method, wb, black) for i in range(n)]
 
+    def pinned_deep_frames(self, n, chroma='420', depth=10, matrix='bt709', semiplanar=False):
+        """n DeepFrames of the context's frame size, each one contiguous surface of 16-bit samples -- Y, U, V, or for
+        `semiplanar` (P010 / P012 / P016; chroma '420') Y and interleaved UV -- in page-locked host memory (fm_host_alloc):
+        fill `f.y[...]` and `f.u[...]` / `f.v[...]` (`f.uv[...]`); they are uploaded in one copy, without a staging copy.
+        The buffer lives as long as any of them."""
+        size = tuple(self.frame_size)
+        if semiplanar and chroma != '420':
+            raise ValueError(f"a semi-planar frame is '420', not {chroma!r}")
+        buf = pinned_empty(self.lib, (n, deep_frame_bytes(size, chroma)), np.uint8)
+        if semiplanar:
+            return [DeepFrame.semiplanar_from_buffer(buf[i], size, depth=depth, matrix=matrix) for i in range(n)]
+        return [DeepFrame.from_buffer(buf[i], size, chroma, depth, matrix) for i in range(n)]
+
     def frame_ring_store(self, index, frame):
         planar = self._planar_of(frame)
         if planar is not None:
@@ -665,6 +695,11 @@ def _bind_device_io(cls):
         if bayer is not None:
             self._described(frame)
             check(self.lib.fm_frame_ring_store_bayer(self._ctx, C.c_int(index), C.byref(bayer.describe())))
+            return
+        deep = self._deep_of(frame)
+        if deep is not None:
+            self._described(frame)
+            check(self.lib.fm_frame_ring_store_deep(self._ctx, C.c_int(index), C.byref(deep.describe())))
             return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_ring_store_nv12(self._ctx, C.c_int(index), *self._nv12_args(frame)))
@@ -683,7 +718,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
 
     def frame_upload_next(self, frame):
-        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame, PlanarFrame, PackedFrame, BayerFrame)):
+        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame, PlanarFrame, PackedFrame, BayerFrame, DeepFrame)):
             return self.frame_upload_ahead(1, frame)
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -716,6 +751,11 @@ def _bind_device_io(cls):
         if bayer is not None:
             self._described(frame)
             check(self.lib.fm_frame_upload_ahead_bayer(self._ctx, C.c_int(k), C.byref(bayer.describe())))
+            return
+        deep = self._deep_of(frame)
+        if deep is not None:
+            self._described(frame)
+            check(self.lib.fm_frame_upload_ahead_deep(self._ctx, C.c_int(k), C.byref(deep.describe())))
             return
         if isinstance(frame, NV12Frame):
             check(self.lib.fm_frame_upload_ahead_nv12(self._ctx, C.c_int(k), *self._nv12_args(frame)))
@@ -912,7 +952,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, frame_set_lens, _described, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
+    for fn in (frame_configure, frame_set_lens, _described, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, _deep_of, pinned_deep_frames, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
                overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,

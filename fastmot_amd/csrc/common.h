@@ -225,6 +225,11 @@ struct fm_ctx {
         hipEvent_t ev = nullptr;     // behind the last H2D copy out of `pinned`
     };
     SrcStage frame_src[FM_MAX_DET_BATCH + 2];
+    // ... and the staging of deep YCbCr frames of every size (fm_frame_*_deep; csrc/deep.hip converts out of `dev`),
+    // entries as frame_nv12's: `dev` and `pinned` grow to the frame's bytes -- up to 6 per pixel, which the slots'
+    // BGR-sized buffers do not hold -- by frame_src's rules; `bgr` stays unused (an off-size frame's BGR form is
+    // frame_src[entry].bgr).  Freed by fm_frame_configure and fm_ctx_destroy (fm_frame_deep_free).
+    SrcStage frame_deep[FM_MAX_DET_BATCH + 2];
 
     // ---- the correction map of the described-source calls (fm_frame_remap_set; csrc/remap.hip gathers through it in
     // place of the resize): [frame_h][frame_w][2] int32 on the device, null = none.  Dropped by fm_frame_remap_clear,
@@ -278,11 +283,21 @@ inline int fm_bayer_sample_bytes(int depth) {
 inline bool fm_bayer_gain_ok(int gain) { return gain >= 1 && gain <= 4096; }
 int fm_bayer_to_bgr(const uint8_t* src, uint8_t* bgr, int w, int h, int pattern, int depth, int method, int black, int gain_r, int gain_g,
                     int gain_b, hipStream_t s);                                                   // bayer.hip
+// a deep frame's description apart from its pointers and pitches (struct fm_frame_deep) is one csrc/deep.hip converts
+inline bool fm_deep_layout_ok(int w, int h, int chroma, int matrix, int depth, int layout) {
+    int cw = 0, ch = 0;
+    if (depth < 9 || depth > 16 || matrix < FM_DEEP_BT601 || matrix > FM_DEEP_BT2020 || !fm_yuv_chroma_dims(w, h, chroma, &cw, &ch)) return false;
+    if (layout == FM_DEEP_SEMIPLANAR) return chroma == FM_YUV_420 && w % 2 == 0 && h % 2 == 0;
+    return layout == FM_DEEP_PLANAR;
+}
+int fm_deep_to_bgr(const uint8_t* planes, uint8_t* bgr, int w, int h, int chroma, int matrix, int depth, int layout,
+                   hipStream_t s);                                                                // deep.hip
 void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
 // remap.hip: `src` through the device map `xy` ([dh][dw][2] int32, remap_pixel.h); border = b | g << 8 | r << 16
 int fm_remap_bgr(const uint8_t* src, int sw, int sh, const int32_t* xy, uint8_t* dst, int dw, int dh, uint32_t border, hipStream_t s);
 void fm_frame_src_free(fm_ctx* ctx);                                                              // detect.hip
+void fm_frame_deep_free(fm_ctx* ctx);                                                             // detect.hip
 void fm_frame_remap_free(fm_ctx* ctx);                                                            // detect.hip (no sync: the caller's)
 int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s);   // jpeg.hip
 // fm_jpeg_info's description of a width x height frame with ncomp 1 or 3 and luma sampling hsamp0 x vsamp0 (jpeg_host.hip)

@@ -1136,6 +1136,7 @@ extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_s
         p = nullptr;
     }
     fm_frame_src_free(ctx);                            // off-size sources: allocated again on first use
+    fm_frame_deep_free(ctx);                           // deep staging: allocated again on first deep use
     fm_frame_remap_free(ctx);                          // a correction map is for one frame size: set again by the caller
     const size_t bytes = (size_t)width * height * 3;
     FM_HIP(hipMalloc(&ctx->frame_own, bytes + FM_FRAME_SLACK));        // (pixel_source.h load_px2 reads 8 bytes at a pixel)
@@ -1550,8 +1551,9 @@ extern "C" int fm_frame_ring_store_jpeg(fm_ctx* ctx, int index, const struct fm_
 // NV12 / JPEG, converted by the kernels above -- at ITS size into ctx->frame_src[entry].bgr, and the kernel of
 // resize.hip writes the frame the counterpart would have written.  Same slots, streams, syncs and events as the
 // counterparts; the staging is this path's own and sized by the source.
-void fm_frame_src_free(fm_ctx* ctx) {
-    for (fm_ctx::SrcStage& e : ctx->frame_src) {
+static void src_stages_free(fm_ctx::SrcStage* stages, int n) {
+    for (int i = 0; i < n; ++i) {
+        fm_ctx::SrcStage& e = stages[i];
         if (e.bgr) (void)hipFree(e.bgr);
         if (e.dev) (void)hipFree(e.dev);
         if (e.pinned) (void)hipHostFree(e.pinned);
@@ -1559,6 +1561,8 @@ void fm_frame_src_free(fm_ctx* ctx) {
         e = fm_ctx::SrcStage{};
     }
 }
+void fm_frame_src_free(fm_ctx* ctx) { src_stages_free(ctx->frame_src, FM_MAX_DET_BATCH + 2); }
+void fm_frame_deep_free(fm_ctx* ctx) { src_stages_free(ctx->frame_deep, FM_MAX_DET_BATCH + 2); }     // (the fm_frame_*_deep calls' staging)
 
 static bool src_ok(const struct fm_frame_src* f) {
     if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
@@ -1573,7 +1577,7 @@ static bool src_ok(const struct fm_frame_src* f) {
 }
 
 // ---- the correction map (remap.hip): while one is set, every described-source call -- fm_frame_*_src and the planar,
-// packed and Bayer families below -- takes sources of the map's size only, stages them at that size even when it is the
+// packed, Bayer and deep families below -- takes sources of the map's size only, stages them at that size even when it is the
 // configured one, and ends in fm_remap_bgr where it ends in fm_resize_bgr without.
 void fm_frame_remap_free(fm_ctx* ctx) {
     if (ctx->remap_xy) (void)hipFree(ctx->remap_xy);
@@ -2103,6 +2107,118 @@ extern "C" int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm
     // synchronous like fm_frame_ring_store (filling the ring is set-up work): a blocking copy that packs the rows, then
     // the kernels on the null stream
     int rc = enqueue_bayer(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+// ---- deep YCbCr ingest (struct fm_frame_deep: 9- to 16-bit samples in 16-bit words, planar as a software decoder or a
+// Y4M C420p10 frame holds them, semi-planar as a hardware decoder's P010 / P016 surface): the three host-frame entry
+// points once more, mirroring the planar ones above.  Same slots, streams, syncs and events as their BGR counterparts.
+// The staging is this family's own for every size, ctx->frame_deep[entry].dev and .pinned, grown by src_reserve /
+// src_pinned with their reuse ordering: a frame is up to 6 bytes per pixel, and the slots' device and page-locked
+// buffers hold 3.  The kernel of deep.hip writes the BGR frame; for a frame of another size than the configured one it
+// writes ctx->frame_src[entry].bgr and resize.hip (remap.hip) the frame, the route of fm_frame_*_src.
+static bool deep_ok(const struct fm_frame_deep* f) {
+    if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
+    if (!fm_deep_layout_ok(f->width, f->height, f->chroma, f->matrix, f->depth, f->layout)) return false;
+    int cw = 0, ch = 0;
+    fm_yuv_chroma_dims(f->width, f->height, f->chroma, &cw, &ch);
+    if (!f->y || f->pitch_y % 2 || f->pitch_y < 2 * f->width) return false;
+    if (f->chroma == FM_YUV_MONO) return true;
+    if (f->layout == FM_DEEP_SEMIPLANAR) cw = f->width;        // (U, V pairs: width words a row)
+    return f->u && (f->v || f->layout == FM_DEEP_SEMIPLANAR) && f->pitch_c % 2 == 0 && f->pitch_c >= 2 * cw;
+}
+
+// H2D copy of the planes, rows packed to their width, into the entry's device staging, the conversion and -- off size --
+// the resize into `dst`, all on `s`.  `blocking`: blocking copies from where the planes lie (fm_frame_ring_store_deep).
+static int enqueue_deep(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_deep* f, hipStream_t s, bool blocking) {
+    const int w = f->width, h = f->height;
+    const bool semi = f->layout == FM_DEEP_SEMIPLANAR;
+    int cw = 0, ch = 0;
+    fm_yuv_chroma_dims(w, h, f->chroma, &cw, &ch);
+    // the chroma planes as byte rows: two (U, V) of 2 cw bytes for planar, one (UV) of 2 w bytes for semi-planar
+    const int nplanes = !ch ? 0 : semi ? 1 : 2;
+    const size_t yrow = (size_t)w * 2, crow = semi ? yrow : (size_t)cw * 2;
+    const size_t ybytes = yrow * h, cbytes = crow * ch, total = ybytes + nplanes * cbytes, npx = (size_t)w * h;
+    const uint8_t* const cplane[2] = {f->u, f->v};
+    const bool on_size = src_on_size(ctx, w, h);
+    fm_ctx::SrcStage& st = ctx->frame_deep[entry];
+    fm_ctx::SrcStage& off = ctx->frame_src[entry];
+    int rc;
+    if (!on_size && (rc = src_reserve(off.bgr, off.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s))) return rc;     // (resize.hip reads 8 bytes at a pixel)
+    if ((rc = src_reserve(st.dev, st.dev_cap, total, false, s))) return rc;
+    bool one_surface = (size_t)f->pitch_y == yrow && (!nplanes || ((size_t)f->pitch_c == crow && f->u == f->y + ybytes));
+    if (nplanes == 2) one_surface = one_surface && f->v == f->u + cbytes;
+    if (blocking) {
+        FM_HIP(hipMemcpy2D(st.dev, yrow, f->y, f->pitch_y, yrow, h, hipMemcpyHostToDevice));
+        for (int p = 0; p < nplanes; ++p)
+            FM_HIP(hipMemcpy2D(st.dev + ybytes + p * cbytes, crow, cplane[p], f->pitch_c, crow, ch, hipMemcpyHostToDevice));
+    } else if (one_surface && is_pinned_range(f->y, total)) {
+        FM_HIP(hipMemcpyAsync(st.dev, f->y, total, hipMemcpyHostToDevice, s));
+    } else {
+        if ((rc = src_pinned(st, total, s))) return rc;
+        for (int r = 0; r < h; ++r) memcpy(st.pinned + (size_t)r * yrow, f->y + (size_t)r * f->pitch_y, yrow);
+        for (int p = 0; p < nplanes; ++p)
+            for (int r = 0; r < ch; ++r)
+                memcpy(st.pinned + ybytes + p * cbytes + (size_t)r * crow, cplane[p] + (size_t)r * f->pitch_c, crow);
+        FM_HIP(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, s));
+        if ((rc = src_pinned_copied(st, s))) return rc;
+    }
+    fm_trace_mark(ctx, s, 58);                 // (the conversion's share of the caller's 30 .. 31 interval)
+    uint8_t* const out = on_size ? dst : off.bgr;
+    if ((rc = fm_deep_to_bgr(st.dev, out, w, h, f->chroma, f->matrix, f->depth, f->layout, s))) return rc;
+    if (on_size) return 0;
+    return enqueue_src_tail(ctx, off.bgr, w, h, dst, s);
+}
+
+// replaces the host narrowing + conversion of a Main10 decoder's / a 10-bit Y4M file's frames (see fm_frame_deep)
+extern "C" int fm_frame_upload_deep(fm_ctx* ctx, const struct fm_frame_deep* f) {
+    FM_CHECK_ARG(ctx && ctx->frame_own && deep_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
+    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    int rc = enqueue_deep(ctx, 0, ctx->frame_own, f, ctx->s_det, false);
+    if (rc) return rc;
+    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
+    ctx->frame_cur = ctx->frame_own;
+    return 0;
+}
+
+// the same for the frame of a step ahead (fm_frame_upload_ahead's role for deep frames)
+extern "C" int fm_frame_upload_ahead_deep(fm_ctx* ctx, int k, const struct fm_frame_deep* f) {
+    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && deep_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
+    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
+    // stream, order of calls, event and staging: see fm_frame_upload_ahead_packed
+    hipStream_t cs = ctx->s_ext;
+    fm_trace_mark(ctx, cs, 30);
+    int rc = enqueue_deep(ctx, k, buf, f, cs, false);
+    if (rc) return rc;
+    fm_trace_mark(ctx, cs, 31);
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
+    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
+    ahead_frame(ctx, k) = buf;
+    return 0;
+}
+
+// the same into ring entry `index` (fm_frame_ring_store's role for deep frames)
+extern "C" int fm_frame_ring_store_deep(fm_ctx* ctx, int index, const struct fm_frame_deep* f) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && deep_ok(f));
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
+    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies that pack the rows, then
+    // the kernels on the null stream
+    int rc = enqueue_deep(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
     if (rc) return rc;
     FM_HIP(hipStreamSynchronize(nullptr));
     return 0;

@@ -162,7 +162,7 @@ class MOT:
         self.tracker.reset(cap_dt)
 
     def step(self, frame, next_frame=None, next_frames=None):
-        """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame, a PlanarFrame, a PackedFrame, a BayerFrame or a JPEGFrame -- converted to BGR
+        """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame, a PlanarFrame, a PackedFrame, a BayerFrame, a DeepFrame or a JPEGFrame -- converted to BGR
         on the GPU while it is uploaded --, a SourceFrame -- any of them at capture resolution, resized to `size` on
         the GPU --, or a detector.DeviceFrame that is already resident on the GPU).
 

@@ -223,21 +223,29 @@ class I420Image:
 Y4M_MAGIC = b'YUV4MPEG2'
 FRAME_MAGIC = b'FRAME'
 _Y4M_CHROMA = {'420': '420', '420jpeg': '420', '420mpeg2': '420', '420paldv': '420', '422': '422', '444': '444', 'mono': 'mono'}
+# the C tokens of 9- to 16-bit streams (read only with parse_y4m_header(..., deep=True)): name -> (chroma, depth)
+_Y4M_DEEP_CHROMA = {f'{c}p{d}': (c, d) for c in ('420', '422', '444') for d in (9, 10, 12, 14, 16)}
+_Y4M_DEEP_CHROMA.update({f'mono{d}': ('mono', d) for d in (9, 10, 12, 16)})
 
 
-def parse_y4m_header(line):
+def parse_y4m_header(line, deep=False):
     """The stream header line of a YUV4MPEG2 file (bytes or str, with or without its newline) -> dict with `size` (W, H),
     `fps` (a Fraction, or None for F0:0 / no F), `chroma` ('420', '422', '444', 'mono'), `interlace` ('p' or '?') and
     `aspect` (the A token's text, or None).  C420 / C420jpeg / C420mpeg2 / C420paldv are all '420' (see planar_to_bgr);
     no C token means 420.  X... tokens are ignored, except XCOLORRANGE=FULL.  ValueError naming the token for everything
     this library does not read: interlaced material (It / Ib / Im), C411, C444alpha, 9- to 16-bit samples
-    (C420p10 ...), full range, malformed or missing W / H."""
+    (C420p10 ...), full range, malformed or missing W / H.
+    deep=True: C420p9 / p10 / p12 / p14 / p16, the C422p* and C444p* forms and Cmono9 / 10 / 12 / 16 parse too -- samples
+    are little-endian 16-bit words with the value in the low bits (utils.deep.DeepFrame), a frame's payload is twice
+    `frame_bytes` -- and the result gains `depth` (8 for the tokens above)."""
     if isinstance(line, (bytes, bytearray, memoryview)):
         line = bytes(line).decode('ascii', 'replace')
     tokens = line.rstrip('\n').split(' ')
     if tokens[0] != Y4M_MAGIC.decode():
         raise ValueError(f'not a YUV4MPEG2 stream: it begins with {tokens[0][:16]!r}')
     out = {'size': None, 'fps': None, 'chroma': '420', 'interlace': '?', 'aspect': None}
+    if deep:
+        out['depth'] = 8
     w = h = None
     for tok in tokens[1:]:
         if not tok:
@@ -260,7 +268,12 @@ def parse_y4m_header(line):
             elif tag == 'A':
                 out['aspect'] = val
             elif tag == 'C':
-                out['chroma'] = _Y4M_CHROMA[val]
+                if deep and val in _Y4M_DEEP_CHROMA:
+                    out['chroma'], out['depth'] = _Y4M_DEEP_CHROMA[val]
+                else:
+                    out['chroma'] = _Y4M_CHROMA[val]
+                    if deep:
+                        out['depth'] = 8
             elif tag == 'X':
                 if tok.upper() == 'XCOLORRANGE=FULL':
                     raise ValueError

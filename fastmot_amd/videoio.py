@@ -7,7 +7,7 @@ Sources this implementation can decode:
   * raw frame stacks '*.npy' ([N, H, W, 3] uint8 BGR, memory-mapped; with `pixel_format` a stack of packed RGB / BGRx /
     YUY2 / UYVY ... frames as a camera or an image library hands them out, see VideoIO)  -> Protocol.VIDEO
   * YUV4MPEG2 '*.y4m' (a text header + uncompressed planar YCbCr frames, 4:2:0 / 4:2:2 / 4:4:4 / mono, 8-bit limited
-    range, progressive; a file or a named pipe fed by any decoder: `ffmpeg -i x.mp4 -f yuv4mpegpipe x.y4m`) -> Protocol.VIDEO
+    range -- 9- to 16-bit with `deep_color` --, progressive; a file or a named pipe fed by any decoder: `ffmpeg -i x.mp4 -f yuv4mpegpipe x.y4m`) -> Protocol.VIDEO
 Other video containers, cameras and network streams need a decoder this image does not have; they raise
 NotImplementedError with the URI.  Outputs: image sequence ('out/%06d.png'), '*.npy' or '*.y4m' (4:2:0); with gpu_encode
 also '*.mjpeg' (concatenated JPEG files), and '%06d.jpg' sequences and '.y4m' frames are converted on the GPU.
@@ -206,13 +206,16 @@ class _Y4MStream:
     """A YUV4MPEG2 stream, read strictly forward (no seek, no stat: a named pipe works).  `fps`: the header's F ratio as
     a float, None when the stream does not know it (F0:0).  read() returns the next frame -- a PlanarFrame over the
     frame's own buffer when `planar` is set, the BGR ndarray `planar_to_bgr` makes of it otherwise --, or None at the
-    end of the stream; a last frame that is cut short ends the stream like that, without an error."""
+    end of the stream; a last frame that is cut short ends the stream like that, without an error.  With `deep` a 9- to
+    16-bit stream (C420p10 ...) opens too: `depth` is its sample depth, its frames are utils.deep.DeepFrames and
+    `deep_to_bgr`'s pixels, and `matrix` may be 'bt2020' for it."""
 
-    def __init__(self, path, planar=None, matrix='bt601'):
-        """planar: a predicate on the stream's (W, H) -- frames come back as PlanarFrames where it holds."""
+    def __init__(self, path, planar=None, matrix='bt601', deep=False):
+        """planar: a predicate on the stream's (W, H) -- frames come back as PlanarFrames (DeepFrames) where it holds."""
         from .utils import yuv
         from .utils.nv12 import matrix_id
-        matrix_id(matrix)
+        if not deep:
+            matrix_id(matrix)
         self._yuv = yuv
         self.matrix = matrix
         self.file = open(path, 'rb')
@@ -220,14 +223,21 @@ class _Y4MStream:
             line = self.file.readline(4096)
             if not line.endswith(b'\n'):
                 raise RuntimeError('Unable to read video stream: no YUV4MPEG2 header')
-            info = yuv.parse_y4m_header(line)
+            info = yuv.parse_y4m_header(line, deep=True) if deep else yuv.parse_y4m_header(line)
+            self.depth = info.get('depth', 8)
+            if self.depth > 8:
+                from .utils import deep as deep_mod
+                self._deep = deep_mod
+                deep_mod.matrix_id(matrix)
+            else:
+                matrix_id(matrix)
         except Exception:
             self.file.close()
             raise
         self.size, self.chroma = info['size'], info['chroma']
         self.fps = float(info['fps']) if info['fps'] else None
         self.planar = bool(planar(self.size)) if planar is not None else False
-        self.frame_bytes = yuv.frame_bytes(self.size, self.chroma)
+        self.frame_bytes = yuv.frame_bytes(self.size, self.chroma) * (2 if self.depth > 8 else 1)
 
     def read(self):
         line = self.file.readline(4096)          # 'FRAME' + optional parameters up to the newline
@@ -242,7 +252,10 @@ class _Y4MStream:
             if not n:
                 return None                       # the stream ends inside this frame
             got += n
-        frame = self._yuv.PlanarFrame.from_buffer(buf, self.size, self.chroma, self.matrix)
+        if self.depth > 8:
+            frame = self._deep.DeepFrame.from_buffer(buf, self.size, self.chroma, self.depth, self.matrix)
+        else:
+            frame = self._yuv.PlanarFrame.from_buffer(buf, self.size, self.chroma, self.matrix)
         return frame if self.planar else frame.to_bgr()
 
     def close(self):
@@ -265,7 +278,8 @@ class VideoIO:
                  demosaic='mhc',
                  white_balance=None,
                  black_level=0,
-                 lens=None):
+                 lens=None,
+                 deep_color=False):
         """Parameters as fastmot/videoio.py:25-58, and (not in the reference; `"gpu_decode": true` / `"gpu_resize": true`
         in the configuration file's stream_cfg reach it through an unmodified app.py):
         gpu_decode: an image sequence's baseline JPEG files whose size is `size` are returned by `read` as JPEGFrames
@@ -317,7 +331,16 @@ class VideoIO:
             returns `SourceFrame(frame, lens=self.lens)`, also for frames already at `size`, and csrc/remap.hip corrects
             them on the GPU; in every other case `read` applies utils.lens.remap_bgr here, on the thread that calls it,
             and returns host pixels (GPU frame kinds of gpu_decode are then converted here too).  The flags decide where
-            the work happens, never what the pixels are."""
+            the work happens, never what the pixels are.
+        deep_color (`"deep_color": true` in stream_cfg; False: everything as it was, error messages included): a '.y4m'
+            input of 9- to 16-bit samples -- C420p9 / p10 / p12 / p14 / p16, the C422p* and C444p* forms, Cmono9 / 10 /
+            12 / 16; little-endian 16-bit words, limited range -- opens.  Its frames are converted to BGR here with
+            utils.deep.deep_to_bgr, at full precision, and `yuv_matrix`, which for such a stream, and only there, also
+            takes 'bt2020'; with gpu_decode `read` returns them as DeepFrames instead -- 3 bytes per pixel are uploaded
+            for 4:2:0 and csrc/deep.hip converts them, bit for bit the same pixels --, those of another size than `size`
+            wrapped in a SourceFrame under gpu_resize, and with `lens` under the rules above: the 8-bit '.y4m'
+            input's rules for every flag.  An 8-bit '.y4m' file reads as it does without the flag.  XCOLORRANGE=FULL
+            and interlaced material stay refused."""
         self.size = tuple(size)
         self.input_uri = input_uri
         self.output_uri = output_uri
@@ -368,7 +391,7 @@ class VideoIO:
         elif self.protocol == Protocol.VIDEO and str(self.input_uri).lower().endswith('.y4m'):
             from .utils.source import MAX_DIM
             on_gpu = self.gpu_decode and gpu_kinds
-            self.source = _Y4MStream(self.input_uri, matrix=yuv_matrix, planar=lambda size: on_gpu and max(size) <= MAX_DIM and (
+            self.source = _Y4MStream(self.input_uri, matrix=yuv_matrix, deep=bool(deep_color), planar=lambda size: on_gpu and max(size) <= MAX_DIM and (
                 tuple(size) == self.size or self._wrap_sources))
         else:
             raise NotImplementedError(f'{self.input_uri}: {self.protocol.name} sources need a video decoder '
@@ -449,7 +472,7 @@ class VideoIO:
             return remap_bgr(frame, self.lens)
         if self._wrap_sources:
             from .utils.source import MAX_DIM, SourceFrame
-            if not isinstance(frame, np.ndarray):                 # a JPEGFrame / PlanarFrame / PackedFrame / BayerFrame, of any size
+            if not isinstance(frame, np.ndarray):                 # a JPEGFrame / PlanarFrame / PackedFrame / BayerFrame / DeepFrame, of any size
                 return frame if frame.size == self.size else SourceFrame(frame)
             if self.do_resize and frame.shape[:2] != self.size[::-1] and max(frame.shape[:2]) <= MAX_DIM:
                 return SourceFrame(frame)

@@ -656,6 +656,55 @@ int fm_frame_upload_bayer(fm_ctx* ctx, const struct fm_frame_bayer* f);
 int fm_frame_upload_ahead_bayer(fm_ctx* ctx, int k, const struct fm_frame_bayer* f);
 int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm_frame_bayer* f);
 
+/* Deep YCbCr frames, 9 to 16 bits per sample in 16-bit little-endian words: what a hardware HEVC / AV1 Main10 decoder
+ * delivers (P010 / P012 / P016), what libavcodec's yuv420p10le and a YUV4MPEG2 'C420p10' frame hold, the rule for 4K
+ * cameras and HDR material: replaces the narrowing to 8 bits and the conversion to BGR that an application does in
+ * host arithmetic on its capture thread (the reference's pipelines get 8-bit BGR from `videoconvert` / `nvvidconv`,
+ * fastmot/videoio.py) and the 3 bytes per pixel it uploads afterwards.
+ *   FM_DEEP_PLANAR: fm_frame_planar's planes and chroma layouts (FM_YUV_*) with 16-bit samples, the value in the LOW
+ *     `depth` bits; the bits above them are masked off.  Any size from 1 x 1.
+ *   FM_DEEP_SEMIPLANAR: a Y plane and, at `u`, a plane of height / 2 rows of width words, U and V interleaved (`v` is
+ *     null, `chroma` is FM_YUV_420, width and height are even); the value in the HIGH `depth` bits, sample =
+ *     word >> (16 - depth), the low bits are ignored.
+ * Rows are `pitch_y` / `pitch_c` BYTES apart: even, and at least 2 x the plane's width in samples (for the semi-planar
+ * UV plane: 2 width).  The planes need no alignment.  Pixel (r, c) uses the chroma sample (r >> sv, c >> sh) as
+ * fm_frame_upload_planar.  With d = depth, s = d - 8, limited range:
+ *   y = max(Y - (16 << s), 0) CY, u = U - (128 << s), v = V - (128 << s), h = 1 << (19 + s)
+ *   R = sat8((y + h + CVR v) >> (20 + s))   G = sat8((y + h + CVG v + CUG u) >> (20 + s))   B = sat8((y + h + CUB u) >> (20 + s))
+ * in 64-bit integers (the sums reach 2^37.2 at depth 16), arithmetic shifts, integer and exact
+ * (fastmot_amd/utils/deep.py deep_to_bgr states it in numpy).  For samples that are 8-bit samples shifted left by s it
+ * is fm_frame_upload_nv12's result bit for bit.  The matrix ids are this family's own:
+ *   FM_DEEP_BT601 / FM_DEEP_BT709: fm_frame_upload_nv12's constants
+ *   FM_DEEP_BT2020 (non-constant luminance, Kr 0.2627, Kb 0.0593): CY 1220945, CVR 1760217, CUB 2245811, CUG -196426, CVG -682019
+ * Full range, transfer functions (PQ / HLG), big-endian samples, P210 / P410 and packed 10-bit words are not read.
+ * The three calls mirror fm_frame_upload_planar, fm_frame_upload_ahead_planar and fm_frame_ring_store_planar one for
+ * one: same slots, same streams, same syncs, same events, same trace marks, the same rule while a correction map is
+ * set.  The rows are packed to their width on the way into page-locked staging (one surface -- every pitch twice the
+ * plane's width, U right behind Y and V right behind U -- inside a buffer from fm_host_alloc is copied from where it
+ * lies, in one copy).  A deep frame is up to 6 bytes per pixel (4:4:4), more than the BGR-sized staging of the slots
+ * holds, so this family has staging of its own per entry point / look-ahead slot, on the device and page-locked,
+ * allocated on first use, regrown when a larger frame arrives (after the stream that uses it is idle) and freed by
+ * fm_frame_configure and fm_ctx_destroy; a kernel on the copy's stream (csrc/deep.hip) writes the BGR frame where the
+ * BGR call would have put it, and a look-ahead slot's completion event follows it.  width x height other than the
+ * configured frame size: the kernel writes the source-size BGR frame into fm_frame_upload_src's buffer and
+ * csrc/resize.hip -- csrc/remap.hip while a correction map is set -- the frame.
+ * FM_ERR_ARG for a null ctx / f / plane pointer, a depth outside 9..16, an unknown layout, chroma or matrix, a pitch
+ * that is odd or below twice the plane's width, a width or height outside 1..FM_SRC_MAX_DIM, a semi-planar frame that
+ * is not FM_YUV_420 or has an odd width or height, or a bad k / index; nothing is copied, allocated or launched then. */
+#define FM_DEEP_PLANAR 0
+#define FM_DEEP_SEMIPLANAR 1
+#define FM_DEEP_BT601 0
+#define FM_DEEP_BT709 1
+#define FM_DEEP_BT2020 2
+struct fm_frame_deep {
+    int32_t width, height, chroma, matrix, depth, layout;    /* FM_YUV_*, FM_DEEP_BT*, 9..16, FM_DEEP_PLANAR / _SEMIPLANAR */
+    const uint8_t *y, *u, *v;                                 /* FM_DEEP_SEMIPLANAR: u is the UV plane, v null */
+    int32_t pitch_y, pitch_c;                                 /* bytes */
+};
+int fm_frame_upload_deep(fm_ctx* ctx, const struct fm_frame_deep* f);
+int fm_frame_upload_ahead_deep(fm_ctx* ctx, int k, const struct fm_frame_deep* f);
+int fm_frame_ring_store_deep(fm_ctx* ctx, int index, const struct fm_frame_deep* f);
+
 /* Geometry between sensor and tracker: lens undistortion, or any fixed correction that is one map (a rotation by 90
  * degrees, a mirror, a perspective crop), applied by the gather that already ends every described-source call.  A map
  * holds, for every pixel of the configured width x height frame, a source coordinate in fixed point with 5 fractional
@@ -673,7 +722,7 @@ int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm_frame_baye
  * frame, src_w / src_h outside 1..FM_SRC_MAX_DIM or an entry out of range.  fm_frame_remap_clear, fm_frame_configure
  * and fm_ctx_destroy drop the map.
  * While a map is set the described-source calls -- fm_frame_upload_src / _ahead_src / _ring_store_src and their
- * _planar, _packed and _bayer forms -- take sources of src_w x src_h only (FM_ERR_ARG for any other, nothing copied or
+ * _planar, _packed, _bayer and _deep forms -- take sources of src_w x src_h only (FM_ERR_ARG for any other, nothing copied or
  * launched), stage them at that size even when it is the configured one, and end in the remap kernel where they end in
  * the resize kernel without a map: same slots, streams, syncs, events and trace marks.  Every other call, and every
  * call while no map is set, is untouched.  A per-stream setting: it may change, it should not alternate per frame.
