@@ -464,6 +464,19 @@ DET_DTYPE = np.dtype([('tlbr', float, 4), ('label', int), ('conf', float)], alig
 assert DET_DTYPE.itemsize == 48
 
 
+def merge_tiles(dets, tile_ids, n_tiles, thresh):
+    """fm_detect_merge_tiles: the cross-tile merge of SSDDetector.merge_dets in the library (host code, no device call)."""
+    d = np.ascontiguousarray(np.asarray(dets, DET_DTYPE))
+    t = np.ascontiguousarray(np.asarray(tile_ids, np.int32))
+    assert len(d) == len(t)
+    out = np.zeros(max(len(d), 1), DET_DTYPE)
+    n = C.c_int(0)
+    check(load().fm_detect_merge_tiles(d.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), C.c_int(len(d)),
+                                       C.c_int(int(n_tiles)), C.c_double(thresh), out.ctypes.data_as(C.c_void_p),
+                                       C.byref(n)))
+    return out[:n.value].view(np.recarray)
+
+
 class _PinnedBlock:
     def __init__(self, lib, nbytes):
         self._lib = lib
@@ -928,6 +941,27 @@ def _bind_device_io(cls):
         check(self.lib.fm_detect_last_counts(self._ctx, C.byref(nc), C.byref(nd)))
         return nc.value, nd.value
 
+    def detect_configure_tiles(self, origins, region, offsets, merge_thresh):
+        """Makes the configured detector tiled (fm_detect_configure_tiles): `origins` [n][2] tile corners in the tiling
+        region `region` = (w, h); `offsets` [n][2]: the decode's box offset per tile (its scale is the configuration's
+        `size`).  No origins: untiled again."""
+        o = _as(origins, np.int32).reshape(-1, 2)
+        off = _as(offsets, np.float64).reshape(-1, 2)
+        assert len(off) == len(o)
+        check(self.lib.fm_detect_configure_tiles(self._ctx, C.c_int(len(o)), _ptr(o), C.c_int(int(region[0])),
+                                                 C.c_int(int(region[1])), _ptr(off), C.c_double(merge_thresh)))
+
+    def detect_last_tiles(self):
+        """The per-tile detections of the frame detect_sync collected last, before the cross-tile merge: a list of record
+        arrays (DET_DTYPE), one per tile."""
+        cap = max(self.detect_last_counts()[1], 1)          # (tiled: the detections summed over the tiles)
+        out = np.zeros(cap, DET_DTYPE)
+        counts = np.zeros(FM_MAX_DET_BATCH, np.int32)
+        n = C.c_int(0)
+        check(self.lib.fm_detect_last_tiles(self._ctx, _ptr(out), C.c_int(cap), _ptr(counts), C.byref(n)))
+        ends = np.cumsum(counts[:n.value])
+        return [out[e - c:e].copy().view(np.recarray) for c, e in zip(counts[:n.value], ends)]
+
     def detect_raw_candidates(self, cap=65536):
         rows = np.empty((cap, 8), np.float32)
         n = C.c_int(0)
@@ -959,7 +993,7 @@ def _bind_device_io(cls):
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,
-               detect_raw_candidates, detect_last_counts, extract_configure, extract_async, extract_sync, extract_read_input):
+               detect_raw_candidates, detect_last_counts, detect_configure_tiles, detect_last_tiles, extract_configure, extract_async, extract_sync, extract_read_input):
         setattr(cls, fn.__name__, fn)
 
 

@@ -16,6 +16,7 @@
 //
 // Roofline: T=D=50, M=512 -> 0.33 MB and 7.7 MFLOP fp64 per frame: launch-latency bound.
 #include "common.h"
+#include "numba_set.h"
 #include <algorithm>
 #include <cmath>
 
@@ -839,20 +840,7 @@ void unmatched_order(int n, const std::vector<uint8_t>& gone, std::vector<int>& 
     const int mask = size - 1;
     if (out.empty() || out.back() <= mask) return;
     std::vector<int> table(size, -1);
-    for (int k : out) {
-        unsigned index = k & mask, perturb = k;
-        int probes = 0;
-        for (; probes < 3; ++probes) {
-            if (table[index] < 0) break;
-            index = (index + 1) & mask;
-        }
-        if (probes == 3)
-            while (table[index] >= 0) {
-                perturb >>= 5;
-                index = (index * 5 + 1 + perturb) & mask;
-            }
-        table[index] = k;
-    }
+    for (int k : out) table[numba_set_slot(table, k)] = k;      // (numba_set.h: shared with tilemerge.hip)
     out.clear();
     for (int k : table)
         if (k >= 0) out.push_back(k);

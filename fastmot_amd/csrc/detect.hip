@@ -22,6 +22,8 @@
 #include "remap_pixel.h"
 #include <cmath>
 #include <mutex>
+#include <string>
+#include <vector>
 #include <utility>
 
 struct DetState {
@@ -32,8 +34,23 @@ struct DetState {
     // NEXT frame(s) can be queued behind this one (MOT.step with next_frame / detector look-ahead: the detector stream never
     // idles) while the host still has to collect this frame's detections.  Frames are collected in enqueue order.  A
     // batched pass (fm_detect_async_ahead) fills FM_MAX_DET_BATCH consecutive slots at most; the ring holds such a pass,
-    // the frame being collected and a stale prefetch.
-    static constexpr int NSLOT = FM_MAX_DET_BATCH + 2;
+    // the frame being collected and a stale prefetch: `nslot` = FM_MAX_DET_BATCH + 2 slots.  A tiled detector
+    // (fm_detect_configure_tiles) fills one slot per TILE and every frame is a pass of n_tiles slots: the ring then holds
+    // three such passes -- the one being collected, a prefetched one and a stale one to drop -- `nslot` = 3 n_tiles.
+    static constexpr int NSLOT_UNTILED = FM_MAX_DET_BATCH + 2;
+    static constexpr int NSLOT = 3 * FM_MAX_DET_BATCH;      // (capacity of the arrays below; slots [0, nslot) are in use)
+    int nslot = NSLOT_UNTILED;
+    // tiling (n_tiles >= 2; 0: untiled): sample t of every pass is tile t of the ONE frame of the pass
+    int n_tiles = 0;
+    int tile_x[FM_MAX_DET_BATCH] = {}, tile_y[FM_MAX_DET_BATCH] = {};   // tile origins in the tiling region
+    int region_w = 0, region_h = 0;
+    double tile_offset[FM_MAX_DET_BATCH][2] = {};           // the decode's box offset per tile (its scale: cfg.size)
+    double merge_thresh = 0.6;
+    std::vector<fm_det48> tile_stage;                       // one tile's detections while a frame is collected
+    std::vector<fm_det48> tile_dets;                        // the frame collected last: per-tile detections, tile-major ...
+    std::vector<int32_t> tile_ids;                          // ... their tiles ...
+    int tile_count[FM_MAX_DET_BATCH] = {};                  // ... rows per tile
+    int tile_sum[2] = {};                                   // ... and the candidates / detections summed over the tiles
     float* cand[NSLOT] = {};        // [cap][8] : x y w h box_conf class cls_prob orig_idx(as float bits)
     float* sorted[NSLOT] = {};      // [cap][8]
     int32_t* counters[NSLOT] = {};  // [0]=n_cand [1]=overflow [2]=n_det
@@ -98,8 +115,8 @@ __global__ void preprocess_kernel(const StemSrc src, f16* __restrict__ inp, int 
     if (counters && x < 4 && y == 0) counters[x] = 0;
     if (x >= in_w || y >= in_h) return;
     float rgb[3];
-    det_input_pixel(pick_sample(src.frame, n), src.fw, src.fh, x, y, src.roi_x, src.roi_y, src.roi_w, src.roi_h,
-                    rgb);      // (pixel_source.h: shared with the fused stem)
+    det_input_pixel(pick_sample(src.frame, n), src.fw, src.fh, x, y, pick_sample(src.roi_x, n), pick_sample(src.roi_y, n),
+                    src.roi_w, src.roi_h, rgb);      // (pixel_source.h: shared with the fused stem)
     f16x8 o;
     o[0] = (f16)rgb[0]; o[1] = (f16)rgb[1]; o[2] = (f16)rgb[2];
 #pragma unroll
@@ -157,6 +174,8 @@ struct HeadSet {
     int first_block[FM_MAX_HEADS + 1];   // head i owns blocks [first_block[i], first_block[i + 1])
     float* cand[FM_MAX_DET_BATCH];       // image z (blockIdx.y) of a batched pass: its slot's candidate list ...
     int32_t* counters[FM_MAX_DET_BATCH]; // ... and counters (FilterArgs.cand / counters are image 0's)
+    double off_x[FM_MAX_DET_BATCH], off_y[FM_MAX_DET_BATCH];   // ... and box offset (FilterArgs.offset): one value for the frames
+                                                               // of a batched pass, one per tile for a tiled pass
 };
 
 // one thread per (head, anchor, cell), all heads in one launch: plugins/yolo_layer.cu:127-173 (classic) /
@@ -173,6 +192,8 @@ __global__ void decode_kernel(HeadSet hs, FilterArgs fa, int in_w, int in_h, int
     const int img = blockIdx.y;
     fa.cand = pick_sample(hs.cand, img);
     fa.counters = pick_sample(hs.counters, img);
+    fa.offset[0] = pick_sample(hs.off_x, img);
+    fa.offset[1] = pick_sample(hs.off_y, img);
     const int a = idx / cells, cell = idx - a * cells;
     const int row = cell / h.gw, col = cell - row * h.gw;
     const int info = 5 + fa.num_classes;
@@ -849,40 +870,43 @@ int ensure_det(fm_ctx* ctx) {
     return 0;
 }
 
-int alloc_post(DetState* d, int cap) {
+int alloc_post(DetState* d, int cap, int nslot) {
     cap = (cap + 63) & ~63;
-    if (d->cand[0] && cap == d->cap) return 0;
-    for (int i = 0; i < DetState::NSLOT; ++i) {
+    if (d->cand[0] && cap == d->cap && nslot == d->nslot) return 0;
+    // (every slot at a new capacity; at the same one only the slots beyond a shorter ring: a tiled detector's nine or
+    // twelve slots do not outlive it -- at 65536 candidates the suppression mask alone is 0.5 GB a slot)
+    for (int i = (cap != d->cap || !d->cand[0]) ? 0 : nslot; i < DetState::NSLOT; ++i) {
         for (void* p : {(void*)d->cand[i], (void*)d->sorted[i], (void*)d->mask[i], (void*)d->dets[i]})
             if (p) (void)hipFree(p);
         if (d->dets_host[i]) (void)hipHostFree(d->dets_host[i]);
         d->dets_host[i] = nullptr;
         d->cand[i] = d->sorted[i] = nullptr; d->mask[i] = nullptr; d->dets[i] = nullptr;
-        d->used[i] = false;
     }
+    for (int i = 0; i < DetState::NSLOT; ++i) d->used[i] = false;
     d->cap = cap;
+    d->nslot = nslot;
     d->wr = d->rd = d->pending = 0;
     d->last = -1;
     d->post_pending = -1;
     d->post_pending_n = 0;
-    for (int i = 0; i < DetState::NSLOT; ++i) {
+    for (int i = 0; i < nslot; ++i) {
+        if (d->cand[i]) continue;                       // (a slot the shorter ring of the same capacity had already)
         FM_HIP(hipMalloc(&d->cand[i], sizeof(float) * 8 * cap));
         FM_HIP(hipMalloc(&d->sorted[i], sizeof(float) * 8 * cap));
         FM_HIP(hipMalloc(&d->mask[i], sizeof(uint64_t) * (size_t)cap * (cap / 64)));
         FM_HIP(hipMalloc(&d->dets[i], sizeof(fm_det48) * cap));
         FM_HIP(hipHostMalloc(&d->dets_host[i], sizeof(fm_det48) * cap, hipHostMallocDefault));
     }
-    if (!d->counters[0]) {
-        for (int i = 0; i < DetState::NSLOT; ++i) {
-            FM_HIP(hipMalloc(&d->counters[i], sizeof(int32_t) * 4));
-            FM_HIP(hipHostMalloc(&d->counters_host[i], sizeof(int32_t) * 4, hipHostMallocDefault));
-            FM_HIP(hipEventCreateWithFlags(&d->ev_done[i], hipEventDisableTiming));
-            FM_HIP(hipEventCreateWithFlags(&d->ev_dec[i], hipEventDisableTiming));
-            FM_HIP(hipEventCreate(&d->ev0[i]));
-            FM_HIP(hipEventCreate(&d->ev1[i]));
-        }
-        FM_HIP(hipMalloc(&d->label_mask, 128));
+    for (int i = 0; i < nslot; ++i) {
+        if (d->counters[i]) continue;
+        FM_HIP(hipMalloc(&d->counters[i], sizeof(int32_t) * 4));
+        FM_HIP(hipHostMalloc(&d->counters_host[i], sizeof(int32_t) * 4, hipHostMallocDefault));
+        FM_HIP(hipEventCreateWithFlags(&d->ev_done[i], hipEventDisableTiming));
+        FM_HIP(hipEventCreateWithFlags(&d->ev_dec[i], hipEventDisableTiming));
+        FM_HIP(hipEventCreate(&d->ev0[i]));
+        FM_HIP(hipEventCreate(&d->ev1[i]));
     }
+    if (!d->label_mask) FM_HIP(hipMalloc(&d->label_mask, 128));
     return 0;
 }
 
@@ -891,8 +915,9 @@ FilterArgs filter_args(DetState* d, int slot) {
     fa.label_mask = d->label_mask;
     fa.num_classes = d->cfg.num_classes;
     fa.conf_thresh = (float)d->cfg.conf_thresh;
+    const bool tiled = d->n_tiles > 1;      // (the offset is tile 0's: decode_kernel takes each image's from its HeadSet)
     fa.size[0] = d->cfg.size[0]; fa.size[1] = d->cfg.size[1];
-    fa.offset[0] = d->cfg.offset[0]; fa.offset[1] = d->cfg.offset[1];
+    fa.offset[0] = tiled ? d->tile_offset[0][0] : d->cfg.offset[0]; fa.offset[1] = tiled ? d->tile_offset[0][1] : d->cfg.offset[1];
     fa.cand = d->cand[slot];
     fa.counters = d->counters[slot];
     fa.cap = d->cap;
@@ -976,7 +1001,7 @@ static int flush_post(fm_ctx* ctx, DetState* d) {
     hipStream_t sp = ctx->s_up;
     FM_HIP(hipStreamWaitEvent(sp, d->ev_dec[first], 0));
     for (int i = 0; i < n; ++i) {
-        const int slot = (first + i) % DetState::NSLOT;
+        const int slot = (first + i) % d->nslot;
         fm_trace_mark(ctx, sp, 20);
         int rc_p = (d->general_post || ctx->opt_nms_general) ? enqueue_general_post(ctx, d, slot, sp) : enqueue_greedy_post(ctx, d, slot, sp);
         if (rc_p) return rc_p;
@@ -998,16 +1023,17 @@ static int flush_post(fm_ctx* ctx, DetState* d) {
 int enqueue_post(fm_ctx* ctx, DetState* d, hipStream_t s, int n = 1) {
     int rc = flush_post(ctx, d);              // (a pass whose post-processing nobody flushed yet: keep the order)
     if (rc) return rc;
-    while (d->pending + n > DetState::NSLOT) {      // never collected (a caller that only ever enqueues): drop the oldest
-        d->rd = (d->rd + 1) % DetState::NSLOT;
-        --d->pending;
+    while (d->pending + n > d->nslot) {      // never collected (a caller that only ever enqueues): drop the oldest
+        const int drop = d->n_tiles > 1 ? d->n_tiles : 1;       // (a tiled frame is its n_tiles slots: all or none)
+        d->rd = (d->rd + drop) % d->nslot;
+        d->pending -= drop;
     }
     const int slot = d->wr;
     FM_HIP(hipEventRecord(d->ev_dec[slot], s));
     d->post_pending = slot;
     d->post_pending_n = n;
-    for (int i = 0; i < n; ++i) d->used[(slot + i) % DetState::NSLOT] = true;
-    d->wr = (slot + n) % DetState::NSLOT;
+    for (int i = 0; i < n; ++i) d->used[(slot + i) % d->nslot] = true;
+    d->wr = (slot + n) % d->nslot;
     d->pending += n;
     return 0;
 }
@@ -1017,12 +1043,12 @@ int enqueue_post(fm_ctx* ctx, DetState* d, hipStream_t s, int n = 1) {
 static int acquire_slots(fm_ctx* ctx, DetState* d, hipStream_t s, int n = 1) {
     // (a pending pass among them -- only when a batched pass follows a batched pass nobody collected: enqueue its
     // post-processing first, so that its ev_done is the event waited for below)
-    if (d->post_pending >= 0 && d->post_pending_n + n > DetState::NSLOT) {
+    if (d->post_pending >= 0 && d->post_pending_n + n > d->nslot) {
         int rc = flush_post(ctx, d);
         if (rc) return rc;
     }
     for (int i = 0; i < n; ++i) {
-        const int slot = (d->wr + i) % DetState::NSLOT;
+        const int slot = (d->wr + i) % d->nslot;
         // (in steady state that post-processing ended a step ago: the host can see it, and a wait that is not enqueued is
         // one packet fewer on the stream whose period is the step -- every packet there costs microseconds,
         // r06_net_timing_events_ab.txt)
@@ -1073,7 +1099,7 @@ int collect(fm_ctx* ctx, DetState* d, hipStream_t s, fm_det48* out, int cap_out,
         else if (want < d->greedy_kmax && ++d->greedy_shrink >= 64) { d->greedy_kmax = want; d->greedy_shrink = 0; }
         else if (want == d->greedy_kmax) d->greedy_shrink = 0;
     }
-    d->rd = (slot + 1) % DetState::NSLOT;
+    d->rd = (slot + 1) % d->nslot;
     --d->pending;
     d->last = slot;
     if (d->counters_host[slot][1]) {
@@ -1092,6 +1118,66 @@ int collect(fm_ctx* ctx, DetState* d, hipStream_t s, fm_det48* out, int cap_out,
     memcpy(out, d->dets_host[slot], sizeof(fm_det48) * nd);
     *n = nd;
     return 0;
+}
+
+// A frame of a tiled detector: its n_tiles slots are collected in tile order, each exactly like a frame of a batched pass,
+// and their union goes through the cross-tile merge (fm_detect_merge_tiles, host: the walk over the groups is serial and
+// the rows are on the host in any case).  The frame's slots are consumed whatever happens in one of them, so that the
+// ring stays in step: a candidate-list overflow in any tile is this frame's error, reported once all tiles are collected.
+int collect_tiles(fm_ctx* ctx, DetState* d, hipStream_t s, fm_det48* out, int cap_out, int* n) {
+    const int nt = d->n_tiles;
+    if (d->pending < nt) {
+        fm_set_error("no detector pass in flight (fm_detect_async first)");
+        return FM_ERR_STATE;
+    }
+    const int first = d->rd, pending = d->pending;
+    d->tile_stage.resize((size_t)d->cap);
+    d->tile_dets.clear();
+    d->tile_ids.clear();
+    d->tile_sum[0] = d->tile_sum[1] = 0;
+    int rc_first = 0;
+    std::string err;
+    for (int t = 0; t < nt; ++t) {
+        const int slot = (first + t) % d->nslot;
+        int k = 0;
+        d->rd = slot;                                       // (collect() takes the slot at d->rd)
+        const int rc = collect(ctx, d, s, d->tile_stage.data(), d->cap, &k);
+        d->tile_count[t] = rc ? 0 : k;
+        if (rc) {
+            if (!rc_first) { rc_first = rc; err = fm_last_error(); }
+            if (rc == FM_ERR_HIP) break;                    // (the device is gone: nothing more to wait for)
+            continue;
+        }
+        d->tile_sum[0] += d->counters_host[slot][0];
+        d->tile_sum[1] += k;
+        d->tile_dets.insert(d->tile_dets.end(), d->tile_stage.begin(), d->tile_stage.begin() + k);
+        d->tile_ids.insert(d->tile_ids.end(), (size_t)k, (int32_t)t);
+    }
+    d->rd = (first + nt) % d->nslot;
+    d->pending = pending - nt;
+    d->last = first;                                        // (the pass's network time lies in its first slot)
+    if (rc_first) {
+        d->tile_dets.clear();
+        d->tile_ids.clear();
+        for (int t = 0; t < nt; ++t) d->tile_count[t] = 0;
+        fm_set_error("%s", err.c_str());
+        return rc_first;
+    }
+    const int total = (int)d->tile_dets.size();
+    if (total > cap_out) {                                  // (the merge never returns more rows than it is given)
+        d->tile_stage.resize((size_t)std::max(total, d->cap));
+        int nm = 0;
+        int rc = fm_detect_merge_tiles(d->tile_dets.data(), d->tile_ids.data(), total, nt, d->merge_thresh, d->tile_stage.data(), &nm);
+        if (rc) return rc;
+        if (nm > cap_out) {
+            fm_set_error("output capacity %d < %d detections", cap_out, nm);
+            return FM_ERR_ARG;
+        }
+        memcpy(out, d->tile_stage.data(), sizeof(fm_det48) * nm);
+        *n = nm;
+        return 0;
+    }
+    return fm_detect_merge_tiles(d->tile_dets.data(), d->tile_ids.data(), total, nt, d->merge_thresh, out, n);
 }
 
 }  // namespace
@@ -2248,21 +2334,66 @@ extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
     d->pending = 0;
     d->cfg = *cfg;
     d->general_post = ctx->opt_nms_general != 0;
-    if ((rc = alloc_post(d, cfg->max_candidates > 0 ? cfg->max_candidates : 8192))) return rc;
+    d->n_tiles = 0;           // (untiled until fm_detect_configure_tiles says otherwise)
+    d->tile_dets.clear();
+    d->tile_ids.clear();
+    if ((rc = alloc_post(d, cfg->max_candidates > 0 ? cfg->max_candidates : 8192, DetState::NSLOT_UNTILED))) return rc;
     FM_HIP(hipMemcpy(d->label_mask, cfg->label_mask, 128, hipMemcpyHostToDevice));
     d->configured = true;
     return 0;
 }
 
-// the detector's frame source for the n images of a pass: frame i, the candidate counters of slot d->wr + i
+extern "C" int fm_detect_configure_tiles(fm_ctx* ctx, int n_tiles, const int32_t* origins, int region_w, int region_h,
+                                         const double* offsets, double merge_thresh) {
+    FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured);
+    FM_CHECK_ARG(n_tiles == 0 || (n_tiles >= 2 && n_tiles <= FM_MAX_DET_BATCH));
+    DetState* d = ctx->det;
+    if (n_tiles) {
+        FM_CHECK_ARG(origins && offsets && region_w > 0 && region_h > 0 && merge_thresh >= 0. && merge_thresh <= 1.);
+        // every pixel of every tile lies inside the tiling region (det_input_pixel is called with an ROI of that size)
+        for (int t = 0; t < n_tiles; ++t)
+            FM_CHECK_ARG(origins[2 * t] >= 0 && origins[2 * t + 1] >= 0 && origins[2 * t] + d->cfg.in_w <= region_w &&
+                         origins[2 * t + 1] + d->cfg.in_h <= region_h);
+    }
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_up));
+    d->post_pending = -1;
+    d->post_pending_n = 0;
+    d->rd = d->wr;            // (passes of the previous geometry are not collected any more)
+    d->pending = 0;
+    d->tile_dets.clear();
+    d->tile_ids.clear();
+    d->n_tiles = n_tiles;
+    for (int t = 0; t < n_tiles; ++t) {
+        d->tile_x[t] = origins[2 * t]; d->tile_y[t] = origins[2 * t + 1];
+        d->tile_offset[t][0] = offsets[2 * t]; d->tile_offset[t][1] = offsets[2 * t + 1];
+        d->tile_count[t] = 0;
+    }
+    if (n_tiles) {
+        d->region_w = region_w; d->region_h = region_h;
+        d->merge_thresh = merge_thresh;
+    }
+    d->last = -1;             // (nothing of the previous geometry is reported any more: fm_detect_last_counts, _last_tiles)
+    d->tile_sum[0] = d->tile_sum[1] = 0;
+    for (int t = 0; t < FM_MAX_DET_BATCH; ++t) d->tile_count[t] = 0;
+    return alloc_post(d, d->cap, n_tiles ? 3 * n_tiles : DetState::NSLOT_UNTILED);
+}
+
+// the detector's frame source for the n images of a pass: frame i (tiled: tile i of frames[0]), the candidate counters of
+// slot d->wr + i
 static StemSrc det_source(fm_ctx* ctx, DetState* d, const uint8_t* const* frames, int n) {
     const fm_yolo_cfg& c = d->cfg;
     StemSrc src{};
     src.kind = 1; src.fw = ctx->frame_w; src.fh = ctx->frame_h;
-    src.roi_x = c.roi_x; src.roi_y = c.roi_y; src.roi_w = c.roi_w; src.roi_h = c.roi_h;
+    const bool tiled = d->n_tiles > 1;      // (n = n_tiles then, and frames[0] is the frame of all of them)
+    src.roi_w = tiled ? d->region_w : c.roi_w; src.roi_h = tiled ? d->region_h : c.roi_h;
+    for (int i = 0; i < FM_MAX_DET_BATCH; ++i) {
+        src.roi_x[i] = tiled && i < n ? -d->tile_x[i] : c.roi_x;
+        src.roi_y[i] = tiled && i < n ? -d->tile_y[i] : c.roi_y;
+    }
     for (int i = 0; i < n; ++i) {
-        src.frame[i] = frames[i];
-        src.zero4[i] = d->counters[(d->wr + i) % DetState::NSLOT];
+        src.frame[i] = tiled ? frames[0] : frames[i];
+        src.zero4[i] = d->counters[(d->wr + i) % d->nslot];
     }
     return src;
 }
@@ -2282,7 +2413,9 @@ static int enqueue_preprocess(fm_ctx* ctx, DetState* d, NetState* net, const Ste
 extern "C" int fm_detect_preprocess_only(fm_ctx* ctx) {
     FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured && ctx->det_net);
     const uint8_t* f = ctx->frame_cur;
-    return enqueue_preprocess(ctx, ctx->det, ctx->det_net, det_source(ctx, ctx->det, &f, 1), 1);
+    const int n = ctx->det->n_tiles > 1 ? ctx->det->n_tiles : 1;
+    FM_CHECK_ARG(n <= ctx->det_net->max_batch);
+    return enqueue_preprocess(ctx, ctx->det, ctx->det_net, det_source(ctx, ctx->det, &f, n), n);
 }
 
 static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n);
@@ -2295,12 +2428,23 @@ extern "C" int fm_detect_async(fm_ctx* ctx) {
 }
 
 // detector on the prefetched next frame (fm_frame_upload_next / fm_frame_ring_select_next)
+static int detect_ahead(fm_ctx* ctx, int n);
+
 extern "C" int fm_detect_async_next(fm_ctx* ctx) {
     FM_CHECK_ARG(ctx && ctx->frame_next);
-    return fm_detect_async_ahead(ctx, 1);
+    return detect_ahead(ctx, 1);
 }
 
 extern "C" int fm_detect_async_ahead(fm_ctx* ctx, int n) {
+    FM_CHECK_ARG(ctx);
+    if (ctx->det && ctx->det->n_tiles > 1) {
+        fm_set_error("fm_detect_async_ahead: the detector is tiled, its passes take the tiles of one frame");
+        return FM_ERR_STATE;
+    }
+    return detect_ahead(ctx, n);
+}
+
+static int detect_ahead(fm_ctx* ctx, int n) {
     FM_CHECK_ARG(ctx && ctx->det_net && n >= 1 && n <= FM_MAX_DET_BATCH);
     if (n > ctx->det_net->max_batch) {
         fm_set_error("detector look-ahead of %d frames > the detector network's max_batch %d", n, ctx->det_net->max_batch);
@@ -2321,16 +2465,27 @@ extern "C" int fm_detect_async_ahead(fm_ctx* ctx, int n) {
 }
 
 // One network pass at batch n over frames[0..n-1] (n = 1: the single-frame pass), decode of every image into slots
-// d->wr .. d->wr + n - 1, their post-processing left pending (flush_post).
+// d->wr .. d->wr + n - 1, their post-processing left pending (flush_post).  A tiled detector takes ONE frame and runs the
+// pass at batch n_tiles over its tiles: from here on the tiles are the images of a batched pass.
 static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n) {
     FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured && ctx->det_net);
     DetState* d = ctx->det;
     NetState* net = ctx->det_net;
     const fm_yolo_cfg& c = d->cfg;
+    const bool tiled = d->n_tiles > 1;
+    const int n_frames = n;
+    if (tiled) {
+        FM_CHECK_ARG(n_frames == 1);
+        n = d->n_tiles;
+        if (n > net->max_batch) {
+            fm_set_error("%d tiles > the detector network's max_batch %d", n, net->max_batch);
+            return FM_ERR_ARG;
+        }
+    }
     FM_CHECK_ARG(n >= 1 && n <= FM_MAX_DET_BATCH && n <= net->max_batch);
     hipStream_t s = ctx->s_det;
     fm_trace_mark(ctx, s, 10);
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n_frames; ++i)
         if (uploads[i]) FM_HIP(hipStreamWaitEvent(s, uploads[i], 0));
     int rc = acquire_slots(ctx, d, s, n);
     if (rc) return rc;
@@ -2346,7 +2501,7 @@ static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent
     // a caller asked for it (option "net_timing" = N; bench.py samples every 4th pass).  A batched pass carries them in
     // its first image's slot.
     const bool timing = ctx->opt_net_timing > 0 && d->n_passes++ % ctx->opt_net_timing == 0;
-    for (int i = 0; i < n; ++i) d->timed[(d->wr + i) % DetState::NSLOT] = timing && i == 0;
+    for (int i = 0; i < n; ++i) d->timed[(d->wr + i) % d->nslot] = timing && i == 0;
     if (fused) {
         if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
         fm_trace_mark(ctx, s, 11);
@@ -2367,9 +2522,13 @@ static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent
     FilterArgs fa = filter_args(d, d->wr);      // (counters were zeroed by this pass's preprocess / stem kernel)
     HeadSet hs{};
     for (int i = 0; i < n; ++i) {
-        const int slot = (d->wr + i) % DetState::NSLOT;
+        const int slot = (d->wr + i) % d->nslot;
         hs.cand[i] = d->cand[slot];
         hs.counters[i] = d->counters[slot];
+    }
+    for (int i = 0; i < FM_MAX_DET_BATCH; ++i) {
+        hs.off_x[i] = tiled && i < n ? d->tile_offset[i][0] : c.offset[0];
+        hs.off_y[i] = tiled && i < n ? d->tile_offset[i][1] : c.offset[1];
     }
     int base = 0, blocks = 0;
     for (int i = 0; i < FM_MAX_HEADS + 1; ++i) hs.first_block[i] = 0x7fffffff;
@@ -2396,6 +2555,7 @@ static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent
 
 extern "C" int fm_detect_sync(fm_ctx* ctx, fm_det48* out, int cap, int* n) {
     FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured && out && n);
+    if (ctx->det->n_tiles > 1) return collect_tiles(ctx, ctx->det, ctx->s_det, out, cap, n);
     return collect(ctx, ctx->det, ctx->s_det, out, cap, n);
 }
 
@@ -2433,8 +2593,24 @@ extern "C" int fm_detect_last_counts(fm_ctx* ctx, int* n_candidates, int* n_dete
         *n_candidates = *n_detections = 0;
         return 0;
     }
+    if (d->n_tiles > 1) {                   // (a tiled frame: the sums over its tiles, before the cross-tile merge)
+        *n_candidates = d->tile_sum[0];
+        *n_detections = d->tile_sum[1];
+        return 0;
+    }
     *n_candidates = d->counters_host[d->last][0];
     *n_detections = d->counters_host[d->last][2];
+    return 0;
+}
+
+// the per-tile detections of the frame fm_detect_sync collected last, before the merge: tile-major, counts[t] rows of tile t
+extern "C" int fm_detect_last_tiles(fm_ctx* ctx, fm_det48* out, int cap, int32_t* counts, int* n_tiles) {
+    FM_CHECK_ARG(ctx && ctx->det && out && counts && n_tiles);
+    const DetState* d = ctx->det;
+    FM_CHECK_ARG(d->n_tiles > 1 && (int)d->tile_dets.size() <= cap);
+    if (!d->tile_dets.empty()) memcpy(out, d->tile_dets.data(), sizeof(fm_det48) * d->tile_dets.size());
+    for (int t = 0; t < d->n_tiles; ++t) counts[t] = d->tile_count[t];
+    *n_tiles = d->n_tiles;
     return 0;
 }
 
@@ -2445,7 +2621,7 @@ extern "C" int fm_detect_raw_candidates(fm_ctx* ctx, float* rows, int cap, int* 
     if (rc_f) return rc_f;
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_up));
-    const int slot = (d->wr + DetState::NSLOT - 1) % DetState::NSLOT;       // the pass enqueued last
+    const int slot = (d->wr + d->nslot - 1) % d->nslot;       // the pass enqueued last
     int32_t cnt[4];
     FM_HIP(hipMemcpy(cnt, d->counters[slot], sizeof(cnt), hipMemcpyDeviceToHost));
     const int k = cnt[0] < d->cap ? cnt[0] : d->cap;

@@ -123,7 +123,12 @@ struct StemSrc {
     int kind;
     const uint8_t* frame[FM_MAX_DET_BATCH];   // kind 1: the frame of sample n (a batched detector pass); kind 2: frame[0]
     int fw, fh;
-    int roi_x, roi_y, roi_w, roi_h;   // kind 1
+    // kind 1: the ROI of the network input that receives the resized frame.  Its origin is per sample: an untiled pass
+    // gives every sample the letterbox origin; a tiled pass (fm_detect_configure_tiles) gives sample t the origin
+    // (-tile_x, -tile_y) of an ROI as large as the tiling region, so that input pixel (x, y) of tile t is pixel
+    // (x + tile_x, y + tile_y) of the frame resized to the region
+    int roi_x[FM_MAX_DET_BATCH], roi_y[FM_MAX_DET_BATCH];
+    int roi_w, roi_h;
     const double* boxes;              // kind 2: [N][4] tlbr on the device
     int32_t* zero4[FM_MAX_DET_BATCH]; // optional, kind 1: four int32 per sample the launch sets to zero (that image's candidate counters)
 };

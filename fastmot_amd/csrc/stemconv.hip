@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemSrc src, const
     const int ox0 = blockIdx.x * 16, oy0 = blockIdx.y * 16;
     const long n = blockIdx.z;
     const uint8_t* frame1 = SRC == 1 ? pick_sample(src.frame, (int)n) : nullptr;     // (kind 1: this sample's frame)
+    const int roi_x = SRC == 1 ? pick_sample(src.roi_x, (int)n) : 0, roi_y = SRC == 1 ? pick_sample(src.roi_y, (int)n) : 0;
     const f16* img = in + n * (long)H * W * in_cs + in_coff;
     if (SRC == 1 && tid < 4 && blockIdx.x == 0 && blockIdx.y == 0) {     // (this sample's candidate counters)
         int32_t* z = pick_sample(src.zero4, (int)n);
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemSrc src, const
             v = *reinterpret_cast<const uint2*>(img + ((long)cy * W + cx) * in_cs);
         } else if constexpr (SRC == 1) {
             float rgb[3];
-            det_input_pixel(frame1, src.fw, src.fh, cx, cy, src.roi_x, src.roi_y, src.roi_w, src.roi_h, rgb);
+            det_input_pixel(frame1, src.fw, src.fh, cx, cy, roi_x, roi_y, src.roi_w, src.roi_h, rgb);
             union { f16 h[4]; uint2 u; } pk;
             pk.h[0] = (f16)rgb[0]; pk.h[1] = (f16)rgb[1]; pk.h[2] = (f16)rgb[2]; pk.h[3] = (f16)0.f;
             v = pk.u;

@@ -88,6 +88,49 @@ def prefetch_frames(ctx, frames, size):
     ctx.next_frame, ctx.ahead_frames = frames[0], list(frames[1:])
 
 
+def generate_tiles(tile_wh, tiling_grid, tile_overlap):
+    """Tile rectangles (tlbr, inclusive) in the tiling region and the region's size (fastmot/detector.py:122-130):
+    `tiling_grid` = (columns, rows) tiles of `tile_wh` = (w, h), row-major, `(1 - tile_overlap) * tile_wh` apart, corners
+    rounded; the region is rint((grid - 1) * step + tile_wh).  Shared by SSDDetector and the tiled YOLODetector."""
+    tile_wh = np.array(tile_wh, float)
+    grid = np.array(tiling_grid)
+    step = (1 - tile_overlap) * tile_wh
+    region = np.rint((grid - 1) * step + tile_wh).astype(int)
+    tiles = []
+    for row in range(grid[1]):
+        for col in range(grid[0]):
+            x, y = float(col * step[0]), float(row * step[1])
+            tiles.append([round(x, 0), round(y, 0), round(x + tile_wh[0] - 1., 0), round(y + tile_wh[1] - 1., 0)])
+    return np.array(tiles), tuple(region)
+
+
+def tile_box_transforms(size, tile_wh, tiles, region):
+    """Box transform of each tile of a tiled YOLO pass, in the form the decode takes it (`det[:4] *= upscaled_sz;
+    det[:2] -= offset`): a box in fractions of the tile becomes frame pixels.  One `upscaled_sz` for all tiles
+    (tile_wh * size / region) and one offset per tile (-tile origin * size / region), float64."""
+    scale = np.array(size, float) / np.array(region, float)
+    upscaled_sz = np.array(tile_wh, float) * scale
+    offsets = [-(np.array(t[:2], float) * scale) for t in tiles]
+    return upscaled_sz, offsets
+
+
+def check_tiling(tiling_grid, max_batch=1, detector_lookahead=1):
+    """Raises ValueError for a tiled YOLO configuration that cannot run: more tiles than one network pass takes, or tiling
+    together with a batched pass over several frames.  Returns the number of tiles."""
+    cols, rows = (int(v) for v in tiling_grid)
+    if cols < 1 or rows < 1:
+        raise ValueError(f'tiling_grid {tuple(tiling_grid)}: at least one column and one row')
+    n = cols * rows
+    if n > _lib.FM_MAX_DET_BATCH:
+        raise ValueError(f'tiling_grid {cols} x {rows} = {n} tiles: one pass takes at most {_lib.FM_MAX_DET_BATCH} '
+                         f'(FM_MAX_DET_BATCH)')
+    if n > 1 and max_batch > 1:
+        raise ValueError('tiling uses the batch dimension for the tiles: max_batch must be 1')
+    if n > 1 and detector_lookahead > 1:
+        raise ValueError('tiling uses the batch dimension for the tiles: detector_lookahead must be 1')
+    return n
+
+
 class Detector(abc.ABC):
     @abc.abstractmethod
     def __init__(self, size):
@@ -179,16 +222,7 @@ class SSDDetector(Detector):
 
     def _generate_tiles(self):
         """Tile rectangles (tlbr, inclusive) in the tiling region and the region's size (detector.py:122-130)."""
-        tile_wh = np.array(self.model.INPUT_SHAPE[:0:-1], float)
-        grid = np.array(self.tiling_grid)
-        step = (1 - self.tile_overlap) * tile_wh
-        region = np.rint((grid - 1) * step + tile_wh).astype(int)
-        tiles = []
-        for row in range(grid[1]):
-            for col in range(grid[0]):
-                x, y = float(col * step[0]), float(row * step[1])
-                tiles.append([round(x, 0), round(y, 0), round(x + tile_wh[0] - 1., 0), round(y + tile_wh[1] - 1., 0)])
-        return np.array(tiles), tuple(region)
+        return generate_tiles(self.model.INPUT_SHAPE[:0:-1], self.tiling_grid, self.tile_overlap)
 
     @staticmethod
     def normalize(frame, tiles, out):
@@ -288,12 +322,27 @@ class YOLODetector(Detector):
                  weights=None,
                  max_candidates=8192,
                  reuse_buffers=True,
-                 max_batch=1):
+                 max_batch=1,
+                 tiling_grid=(1, 1),
+                 tile_overlap=0.25,
+                 merge_thresh=0.6):
         """An object detector for YOLO models; parameters as fastmot/detector.py:221-253
         (`weights`: optional weight source for the layer table, default seeded random;
         `max_candidates`: capacity of the on-device candidate list; `max_batch`: frames one network pass may take,
-        detect_batch / prefetch_batch, at most FM_MAX_DET_BATCH)."""
+        detect_batch / prefetch_batch, at most FM_MAX_DET_BATCH).
+        `tiling_grid` = (columns, rows) with more than one tile (SSDDetector's tiling, fastmot/detector.py:46-139, not
+        in the reference for YOLO): the frame is resized to the tiling region, cut into overlapping tiles of the
+        network's input size (`tile_overlap`, generate_tiles) and ONE network pass takes the tiles as its batch, at most
+        FM_MAX_DET_BATCH of them; decode, NMS and box filters run per tile in frame coordinates, detections of one
+        object in several tiles are merged (`merge_thresh`, SSDDetector.merge_dets; in the library:
+        fm_detect_merge_tiles).  The model's LETTERBOX does not apply: a tile fills the whole input.  Excludes
+        `max_batch` > 1.  Published: `tiles`, `tiling_region_sz`, the decode's box transform `upscaled_sz` /
+        `tile_bbox_offsets[t]`, and after each collect `last_tile_detections`."""
         super().__init__(size)
+        self.n_tiles = check_tiling(tiling_grid, max_batch)         # (before any device call)
+        assert 0 <= tile_overlap <= 1
+        assert 0 <= merge_thresh <= 1
+        self.tiling_grid, self.tile_overlap, self.merge_thresh = tuple(int(v) for v in tiling_grid), tile_overlap, merge_thresh
         self.model = models.YOLO.get_model(model)
         assert 0 <= conf_thresh <= 1
         self.conf_thresh = conf_thresh
@@ -316,8 +365,16 @@ class YOLODetector(Detector):
         self.ctx = get_context()
         self._announced = []                    # frames whose passes prefetch / prefetch_batch enqueued, in order
         self.graph, self.heads = self.model.build_graph(weights)
-        self.backend = HipNet(self.ctx, NET_DETECTOR, self.graph, max_batch, reuse_buffers=reuse_buffers)
+        self.backend = HipNet(self.ctx, NET_DETECTOR, self.graph, max(max_batch, self.n_tiles), reuse_buffers=reuse_buffers)
         self.roi, self.upscaled_sz, self.bbox_offset = self._create_letterbox()
+        self.tiles = self.tiling_region_sz = self.tile_bbox_offsets = None
+        self.last_tile_detections = None
+        if self.n_tiles > 1:
+            tile_wh = self.model.INPUT_SHAPE[:0:-1]
+            self.tiles, self.tiling_region_sz = generate_tiles(tile_wh, self.tiling_grid, self.tile_overlap)
+            self.upscaled_sz, self.tile_bbox_offsets = tile_box_transforms(self.size, tile_wh, self.tiles,
+                                                                           self.tiling_region_sz)
+            self.bbox_offset = self.tile_bbox_offsets[0]
         self._configure(max_candidates)
 
     def _create_letterbox(self):
@@ -364,6 +421,9 @@ class YOLODetector(Detector):
         cfg.max_candidates = max_candidates
         self._cfg = cfg
         self.ctx.detect_configure(cfg)
+        if self.n_tiles > 1:
+            self.ctx.detect_configure_tiles(self.tiles[:, :2], self.tiling_region_sz, self.tile_bbox_offsets,
+                                            self.merge_thresh)
 
     def detect_async(self, frame):
         """Detects objects asynchronously (preprocess + network + decode + NMS enqueued)."""
@@ -392,6 +452,8 @@ class YOLODetector(Detector):
         frames = list(frames)
         if len(frames) == 1:
             return self.prefetch(frames[0])
+        if self.n_tiles > 1:
+            raise ValueError('a tiled detector takes one frame per network pass')
         if not 1 <= len(frames) <= self.max_batch:
             raise ValueError(f'{len(frames)} frames for a detector of max_batch {self.max_batch}')
         prefetch_frames(self.ctx, frames, self.size)
@@ -403,6 +465,8 @@ class YOLODetector(Detector):
         returns one record array per frame, each equal to what detect_async + postprocess return for that frame."""
         self._drop_announced()
         frames = list(frames)
+        if self.n_tiles > 1:            # (one pass per frame: its batch dimension holds the tiles)
+            return [self(f) for f in frames]
         out = []
         try:
             for i in range(0, len(frames), self.max_batch):
@@ -425,6 +489,11 @@ class YOLODetector(Detector):
     def postprocess(self):
         """Synchronizes and returns a record array of detections (DET_DTYPE), sorted in ascending
         order by class ID.  This API should be called after `detect_async`."""
+        if self.n_tiles > 1:
+            self.last_tile_detections = None
+            dets = self.ctx.detect_sync()
+            self.last_tile_detections = self.ctx.detect_last_tiles()
+            return dets
         return self.ctx.detect_sync()
 
 

@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib
-from .detector import SSDDetector, YOLODetector, PublicDetector, bind_frame
+from .detector import SSDDetector, YOLODetector, PublicDetector, bind_frame, check_tiling
 from .feature_extractor import FeatureExtractor
 from .tracker import MultiTracker
 from .flow import Flow
@@ -107,6 +107,9 @@ class MOT:
                 raise ValueError('detector_lookahead > 1 needs the YOLO detector')
             if detector_frame_skip != 1:
                 raise ValueError('detector_lookahead > 1 needs detector_frame_skip == 1')
+        if self.detector_type == DetectorType.YOLO and yolo_detector_cfg is not None:
+            # (a tiled YOLO detector uses the batch dimension for its tiles: checked here, before anything is built)
+            check_tiling(getattr(yolo_detector_cfg, 'tiling_grid', (1, 1)), detector_lookahead=detector_lookahead)
         self.detector_lookahead = detector_lookahead
         self._lookahead = DetectorLookahead(detector_lookahead)
         self.detector_frame_skip = detector_frame_skip

@@ -924,6 +924,33 @@ int fm_detect_raw_candidates(fm_ctx* ctx, float* rows, int cap, int* n);
  * stream (the bench's live roofline measurement); -1 when that pass carried no events (option "net_timing").  A batch
  * pass (fm_detect_async_ahead) reports its duration on the collect of its first frame and -1 on the others. */
 int fm_detect_net_ms(fm_ctx* ctx, float* ms);
+/* Tiled detection (SSDDetector's tiling, fastmot/detector.py:77-139, for the YOLO networks): the frame is resized to a
+ * tiling region and cut into n_tiles overlapping tiles of the network's input size, which ONE network pass takes as the
+ * samples of a batch.  Call after fm_detect_configure (which returns the detector to untiled); n_tiles = 0 does the same,
+ * otherwise 2 <= n_tiles <= FM_MAX_DET_BATCH <= the detector network's max_batch.
+ *   origins  [n_tiles][2]  top-left corner of each tile in the region; every tile lies inside it.  Input pixel (x, y) of
+ *                          tile t is pixel (x + origin_x, y + origin_y) of the frame resized to region_w x region_h with
+ *                          the detector's own arithmetic (detector.py:289-300); the letterbox ROI is not applied.
+ *   offsets  [n_tiles][2]  the decode's box offset per tile (subtracted, detector.py:343): -origin * frame size / region
+ *                          size; its box scale, one for all tiles, is fm_yolo_cfg.size = tile size * frame size / region size
+ * From then on fm_detect_async and fm_detect_async_next run one batch-n_tiles pass over the tiles of the current / next
+ * frame -- decode, sort, DIoU-NMS and box filters per tile, in frame coordinates, exactly as for a sample of
+ * fm_detect_async_ahead -- and fm_detect_sync returns that frame's detections after the cross-tile merge
+ * (fm_detect_merge_tiles with merge_thresh).  A candidate-list overflow in any tile is reported by that frame's
+ * fm_detect_sync; fm_detect_last_counts returns the sums over the tiles; fm_detect_net_ms the one pass.
+ * fm_detect_async_ahead on a tiled detector is FM_ERR_STATE. */
+int fm_detect_configure_tiles(fm_ctx* ctx, int n_tiles, const int32_t* origins, int region_w, int region_h,
+                              const double* offsets, double merge_thresh);
+/* The per-tile detections of the frame fm_detect_sync collected last, before the merge: tile-major, counts[t] rows of
+ * tile t (counts: FM_MAX_DET_BATCH entries).  FM_ERR_ARG when the detector is not tiled or cap is too small. */
+int fm_detect_last_tiles(fm_ctx* ctx, fm_det48* out, int cap, int32_t* counts, int* n_tiles);
+/* SSDDetector._merge_dets (detector.py:132-139,187-217) on the host, no device call: detections of different tiles
+ * (tile_ids[i] in [0, n_tiles)) and the same class whose intersection-over-minimum is >= thresh are linked (running
+ * maxima per neighbouring tile, in index order); a connected group collapses into its first member with the enclosing
+ * box and the maximum confidence.  Survivors in the iteration order of the reference's (Numba) set, then ordered by class
+ * with a stable sort.  out: room for n rows; it may not overlap dets. */
+int fm_detect_merge_tiles(const fm_det48* dets, const int32_t* tile_ids, int n, int n_tiles, double thresh,
+                          fm_det48* out, int* n_out);
 
 /* ---------------------------------------------------------------- feature extractor --- */
 /* FeatureExtractor.extract_async (feature_extractor.py:48-60): for n boxes crop the current
