@@ -16,11 +16,12 @@ from .utils.jpeg import JPEGFrame
 from .utils.source import SourceFrame
 from .utils.yuv import PlanarFrame, I420Image
 from .utils.packed import PackedFrame
+from .utils.devarray import DeviceArrayFrame
 from .utils.bayer import BayerFrame
 from .utils.deep import DeepFrame
 from .utils.lens import LensMap
 
-__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'PackedFrame', 'BayerFrame', 'DeepFrame', 'LensMap', 'models']
+__all__ = ['VideoIO', 'MOT', 'FeatureExtractor', 'MultiTracker', 'KalmanFilter', 'MeasType', 'Flow', 'Track', 'NV12Frame', 'JPEGFrame', 'SourceFrame', 'PlanarFrame', 'I420Image', 'PackedFrame', 'BayerFrame', 'DeepFrame', 'DeviceArrayFrame', 'LensMap', 'models']
 
 
 def __getattr__(name):

@@ -7,6 +7,7 @@ RuntimeError when its plugin/engine is missing, fastmot/utils/inference.py:50-63
 import ctypes as C
 import os
 import sys
+import weakref
 from pathlib import Path
 
 import numpy as np
@@ -19,6 +20,7 @@ from .utils.yuv import PlanarFrame, frame_bytes
 from .utils.packed import PackedFrame, row_bytes
 from .utils.bayer import BayerFrame
 from .utils.deep import DeepFrame, deep_frame_bytes
+from .utils.devarray import DeviceArrayFrame
 
 LIB_PATH = Path(os.environ.get('FASTMOT_LIB_PATH', Path(__file__).parent / 'libfastmot_hip.so'))
 
@@ -129,6 +131,7 @@ class HipContext:
     """One context = one GPU = one video stream (fm_ctx)."""
 
     def __init__(self, device=0):
+        self._dev_pending = []             # (DeviceArrayFrame, ticket) of the look-ahead uploads that may still read their source
         self.lib = load()
         self._ctx = C.c_void_p()
         check(self.lib.fm_ctx_create(C.c_int(device), C.byref(self._ctx)))
@@ -137,8 +140,11 @@ class HipContext:
 
     def close(self):
         if getattr(self, '_ctx', None) is not None and self._ctx:
-            self.lib.fm_ctx_destroy(self._ctx)
+            self.lib.fm_ctx_destroy(self._ctx)     # (waits for every device frame that is still being read)
             self._ctx = C.c_void_p()
+        for frame, _ in self._dev_pending:
+            frame._pending = [(ref, t) for ref, t in frame._pending if ref() is not self]
+        self._dev_pending = []
 
     def __del__(self):
         # at interpreter shutdown the HIP runtime may already be gone: the orderly path is the atexit hook
@@ -588,7 +594,50 @@ def _bind_device_io(cls):
             return frame
         return None
 
+    def _device_of(self, frame):
+        """The DeviceArrayFrame a device call takes for `frame`, by `_planar_of`'s rules, or None for every other frame kind."""
+        if isinstance(frame, SourceFrame) and isinstance(frame.frame, DeviceArrayFrame):
+            return frame.frame
+        if isinstance(frame, DeviceArrayFrame):
+            if frame.size != tuple(self.frame_size):
+                raise ValueError(f'device frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
+                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
+            return frame
+        return None
+
+    def _device_check(self, rc):
+        """check() for the device-frame calls: a description the library refuses (FM_ERR_ARG: not device memory of this
+        device, an extent past its allocation, a misaligned plane ...) is the caller's ValueError."""
+        if rc == -2:
+            raise ValueError(f'device frame refused: {self.lib.fm_last_error().decode()}')
+        check(rc)
+
+    def device_frame_done(self, ticket, wait=False):
+        """fm_frame_device_done: the look-ahead upload `ticket` has finished reading its source (`wait`: block until then)."""
+        if not self._ctx:
+            return True                    # (close() waited for all of them)
+        rc = self.lib.fm_frame_device_done(self._ctx, C.c_uint64(ticket), C.c_int(int(wait)))
+        if rc < 0:
+            check(rc)
+        return rc == 1
+
+    def device_frames_prune(self):
+        """Drops the references to device frames whose memory has been read (every frame call does this first)."""
+        if self._dev_pending:
+            self._dev_pending = [(f, t) for f, t in self._dev_pending if not self.device_frame_done(t)]
+
+    def pending_device_frames(self):
+        """The DeviceArrayFrames this context still holds because an upload may be reading them, oldest first."""
+        self.device_frames_prune()
+        return [f for f, _ in self._dev_pending]
+
     def frame_upload(self, frame):
+        self.device_frames_prune()
+        dev = self._device_of(frame)
+        if dev is not None:
+            self._described(frame)
+            self._device_check(self.lib.fm_frame_upload_device(self._ctx, C.byref(dev.descriptor())))
+            return
         planar = self._planar_of(frame)
         if planar is not None:
             self._described(frame)
@@ -694,6 +743,12 @@ def _bind_device_io(cls):
         return [DeepFrame.from_buffer(buf[i], size, chroma, depth, matrix) for i in range(n)]
 
     def frame_ring_store(self, index, frame):
+        self.device_frames_prune()
+        dev = self._device_of(frame)
+        if dev is not None:
+            self._described(frame)
+            self._device_check(self.lib.fm_frame_ring_store_device(self._ctx, C.c_int(index), C.byref(dev.descriptor())))
+            return
         planar = self._planar_of(frame)
         if planar is not None:
             self._described(frame)
@@ -731,7 +786,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
 
     def frame_upload_next(self, frame):
-        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame, PlanarFrame, PackedFrame, BayerFrame, DeepFrame)):
+        if isinstance(frame, (NV12Frame, JPEGFrame, SourceFrame, PlanarFrame, PackedFrame, BayerFrame, DeepFrame, DeviceArrayFrame)):
             return self.frame_upload_ahead(1, frame)
         w, h = self.frame_size
         if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
@@ -750,6 +805,16 @@ def _bind_device_io(cls):
 
     def frame_upload_ahead(self, k, frame):
         """Host frame for the step k steps ahead (look-ahead slot k, 1 <= k <= FM_MAX_DET_BATCH; k = 1: frame_upload_next)."""
+        self.device_frames_prune()
+        dev = self._device_of(frame)
+        if dev is not None:
+            self._described(frame)
+            ticket = C.c_uint64(0)
+            self._device_check(self.lib.fm_frame_upload_ahead_device(self._ctx, C.c_int(k), C.byref(dev.descriptor()), C.byref(ticket)))
+            # the conversion runs behind this call: the frame (and the array it holds) stays referenced until it has run
+            dev._pending.append((weakref.ref(self), ticket.value))
+            self._dev_pending.append((dev, ticket.value))
+            return
         planar = self._planar_of(frame)
         if planar is not None:
             self._described(frame)
@@ -986,7 +1051,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, frame_set_lens, _described, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, _deep_of, pinned_deep_frames, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
+    for fn in (frame_configure, frame_set_lens, _described, _device_of, _device_check, device_frame_done, device_frames_prune, pending_device_frames, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, _deep_of, pinned_deep_frames, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
                overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,

@@ -231,6 +231,18 @@ struct fm_ctx {
     // frame_src[entry].bgr).  Freed by fm_frame_configure and fm_ctx_destroy (fm_frame_deep_free).
     SrcStage frame_deep[FM_MAX_DET_BATCH + 2];
 
+    // ---- frames that lie in device memory already (fm_frame_*_device; csrc/devsrc.hip converts from where they lie): no
+    // staging.  ev_dev_in[entry], entries as frame_nv12's: recorded on the producer's stream, waited for by the slot's.
+    // dev_ticket[t % FM_DEV_TICKETS]: the event behind the conversion kernel of look-ahead ticket t (fm_frame_device_done);
+    // events are created on first use and destroyed by fm_ctx_destroy (fm_frame_dev_free).
+    hipEvent_t ev_dev_in[FM_MAX_DET_BATCH + 2] = {};
+    struct DevTicket {
+        uint64_t ticket = 0;         // 0: the place has never been used
+        hipEvent_t ev = nullptr;
+    };
+    DevTicket dev_ticket[FM_DEV_TICKETS];
+    uint64_t dev_ticket_next = 1;
+
     // ---- the correction map of the described-source calls (fm_frame_remap_set; csrc/remap.hip gathers through it in
     // place of the resize): [frame_h][frame_w][2] int32 on the device, null = none.  Dropped by fm_frame_remap_clear,
     // fm_frame_configure and fm_ctx_destroy.
@@ -292,6 +304,18 @@ inline bool fm_deep_layout_ok(int w, int h, int chroma, int matrix, int depth, i
 }
 int fm_deep_to_bgr(const uint8_t* planes, uint8_t* bgr, int w, int h, int chroma, int matrix, int depth, int layout,
                    hipStream_t s);                                                                // deep.hip
+// devsrc.hip: the device frame `f` (checked by fm_frame_device_check) -> f->width * f->height * 3 BGR bytes at `bgr`, on `s`
+int fm_device_to_bgr(const struct fm_frame_device* f, uint8_t* bgr, hipStream_t s);
+// bytes of an element of `dtype` (FM_DEV_*); 0 for an unknown one
+inline int fm_dev_elem_bytes(int dtype) { return dtype == FM_DEV_U8 ? 1 : dtype == FM_DEV_F16 ? 2 : dtype == FM_DEV_F32 ? 4 : 0; }
+// planes a layout uses, and the rows and row bytes of plane `p` of the checked frame `f`
+inline int fm_dev_planes(int layout) { return layout == FM_DEV_HWC ? 1 : layout == FM_DEV_CHW ? 3 : layout == FM_DEV_NV12 ? 2 : 0; }
+inline int fm_dev_plane_rows(const struct fm_frame_device* f, int p) { return f->layout == FM_DEV_NV12 && p == 1 ? f->height / 2 : f->height; }
+inline size_t fm_dev_row_bytes(const struct fm_frame_device* f) {
+    if (f->layout == FM_DEV_HWC) return (size_t)f->width * (f->format <= FM_PACKED_BGR ? 3 : 4);
+    return (size_t)f->width * fm_dev_elem_bytes(f->dtype);
+}
+void fm_frame_dev_free(fm_ctx* ctx);                                                              // detect.hip
 void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
 // remap.hip: `src` through the device map `xy` ([dh][dw][2] int32, remap_pixel.h); border = b | g << 8 | r << 16

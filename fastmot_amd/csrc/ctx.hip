@@ -190,6 +190,7 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     fm_frame_src_free(ctx);
     fm_frame_deep_free(ctx);
+    fm_frame_dev_free(ctx);      // (waits for the look-ahead tickets' events)
     fm_frame_remap_free(ctx);
     fm_overlay_free(ctx);        // (before the encoder: it works on the encoder's stream)
     fm_yuv_free(ctx);            // (likewise)

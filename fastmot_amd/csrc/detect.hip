@@ -2310,6 +2310,173 @@ extern "C" int fm_frame_ring_store_deep(fm_ctx* ctx, int index, const struct fm_
     return 0;
 }
 
+// ---- frames that lie in device memory already (struct fm_frame_device: a decoder's surface, a torch / CuPy tensor, another
+// model's output): the three entry points once more, mirroring the packed ones above.  Same slots, streams, syncs, slot
+// events and flush_post, the same remap_takes check -- and no copy: a kernel of devsrc.hip reads the caller's memory and
+// writes the BGR frame, straight into `dst` on size, into ctx->frame_src[entry].bgr (and enqueue_src_tail from there)
+// off size.  What is new here is that the memory is somebody else's: every plane is checked against what the runtime
+// knows about its pointer before anything is enqueued, the slot's stream is ordered behind the producer's, and a
+// look-ahead call leaves an event behind the conversion kernel -- the last reader of the caller's memory -- for
+// fm_frame_device_done.
+
+// `f` passes fm_frame_device_check and every plane of it is device memory of the context's device, its whole extent --
+// where the runtime knows the allocation -- inside that allocation.  Nothing is enqueued.
+static int device_ok(const fm_ctx* ctx, const struct fm_frame_device* f) {
+    int rc = fm_frame_device_check(f);
+    if (rc) return rc;
+    const size_t rb = fm_dev_row_bytes(f);
+    for (int p = 0; p < fm_dev_planes(f->layout); ++p) {
+        const uint8_t* const base = static_cast<const uint8_t*>(f->plane[p]);
+        const size_t extent = (size_t)f->pitch[p] * (fm_dev_plane_rows(f, p) - 1) + rb;
+        hipPointerAttribute_t attr{};
+        const hipError_t e = hipPointerGetAttributes(&attr, base);
+        if (e != hipSuccess) (void)hipGetLastError();          // (a pointer the runtime has never seen is no sticky error)
+        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.isManaged || attr.device != ctx->device) {
+            fm_set_error("%s:%d bad argument: plane %d of the device frame (%p) is not device memory of device %d -- host, page-locked, "
+                         "managed and other-device frames go through the host calls: fm_frame_upload, _nv12, _planar, _packed, _bayer, "
+                         "_deep or _src", __FILE__, __LINE__, p, (const void*)base, ctx->device);
+            return FM_ERR_ARG;
+        }
+        hipDeviceptr_t abase = nullptr;
+        size_t asize = 0;
+        if (hipMemGetAddressRange(&abase, &asize, (hipDeviceptr_t)base) == hipSuccess) {
+            const uint8_t* const a0 = static_cast<const uint8_t*>(abase);
+            if (base < a0 || extent > asize || (size_t)(base - a0) > asize - extent) {
+                fm_set_error("%s:%d bad argument: plane %d of the device frame (%zu bytes from %p) runs past its allocation (%zu bytes from %p)",
+                             __FILE__, __LINE__, p, extent, (const void*)base, asize, (const void*)a0);
+                return FM_ERR_ARG;
+            }
+        } else {
+            (void)hipGetLastError();                           // (virtual-memory allocators: the attributes alone decide)
+        }
+    }
+    return 0;
+}
+
+// a wait for `ev` on `s` -- unless the host already sees it complete: a barrier packet that is not enqueued does not
+// park on a shared hardware queue (the rule of fm_frame_promote_next and acquire_slots)
+static int wait_unless_complete(hipStream_t s, hipEvent_t ev) {
+    if (hipEventQuery(ev) != hipSuccess) {
+        (void)hipGetLastError();                               // (hipErrorNotReady is not an error)
+        FM_HIP(hipStreamWaitEvent(s, ev, 0));
+    }
+    return 0;
+}
+
+// The conversion of the device frame `f` (device_ok) and -- off size -- the resize into `dst`, on `s`, behind the
+// producer's stream; `consumed`, when given, is recorded behind the conversion kernel.
+static int enqueue_device(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_device* f, hipStream_t s, hipEvent_t consumed) {
+    const int w = f->width, h = f->height;
+    const bool on_size = src_on_size(ctx, w, h);
+    fm_ctx::SrcStage& st = ctx->frame_src[entry];
+    int rc;
+    if (!on_size && (rc = src_reserve(st.bgr, st.bgr_cap, (size_t)w * h * 3 + FM_FRAME_SLACK, false, s))) return rc;   // (resize.hip reads 8 bytes at a pixel)
+    if (!(f->flags & FM_DEV_READY)) {
+        hipEvent_t& in = ctx->ev_dev_in[entry];
+        if (!in) FM_HIP(hipEventCreateWithFlags(&in, hipEventDisableTiming));
+        FM_HIP(hipEventRecord(in, static_cast<hipStream_t>(f->stream)));
+        if ((rc = wait_unless_complete(s, in))) return rc;
+    }
+    fm_trace_mark(ctx, s, 59);                 // (the conversion's share of the caller's 30 .. 31 interval)
+    if ((rc = fm_device_to_bgr(f, on_size ? dst : st.bgr, s))) return rc;
+    fm_trace_mark(ctx, s, 60);                 // (59 .. 60: the kernel without the event record behind it)
+    if (consumed) FM_HIP(hipEventRecord(consumed, s));
+    return on_size ? 0 : enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
+}
+
+extern "C" int fm_frame_upload_device(fm_ctx* ctx, const struct fm_frame_device* f) {
+    FM_CHECK_ARG(ctx && ctx->frame_own && f);
+    int rc = device_ok(ctx, f);
+    if (rc) return rc;
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
+    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
+    FM_HIP(hipStreamSynchronize(ctx->s_det));
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow));
+    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    if ((rc = enqueue_device(ctx, 0, ctx->frame_own, f, ctx->s_det, nullptr))) return rc;
+    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too; the caller's memory has been read
+    ctx->frame_cur = ctx->frame_own;
+    return 0;
+}
+
+extern "C" int fm_frame_upload_ahead_device(fm_ctx* ctx, int k, const struct fm_frame_device* f, uint64_t* ticket) {
+    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && f);
+    int rc = device_ok(ctx, f);
+    if (rc) return rc;
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
+    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
+    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
+        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
+        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
+    }
+    uint8_t* const buf = ahead_buf(ctx, k);
+    hipEvent_t& ev = ahead_event(ctx, k);
+    // the ticket's place in the ring: whoever held it before is consumed before it is given away
+    const uint64_t t = ctx->dev_ticket_next;
+    fm_ctx::DevTicket& place = ctx->dev_ticket[t % FM_DEV_TICKETS];
+    if (!place.ev) FM_HIP(hipEventCreateWithFlags(&place.ev, hipEventDisableTiming));
+    else if (place.ticket) FM_HIP(hipEventSynchronize(place.ev));
+    // stream, order of calls and slot event: see fm_frame_upload_ahead_packed
+    hipStream_t cs = ctx->s_ext;
+    fm_trace_mark(ctx, cs, 30);
+    if ((rc = enqueue_device(ctx, k, buf, f, cs, place.ev))) return rc;
+    place.ticket = t;
+    ctx->dev_ticket_next = t + 1;
+    if (ticket) *ticket = t;
+    fm_trace_mark(ctx, cs, 31);
+    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FM_HIP(hipEventRecord(ev, cs));
+    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
+    ahead_frame(ctx, k) = buf;
+    return 0;
+}
+
+extern "C" int fm_frame_ring_store_device(fm_ctx* ctx, int index, const struct fm_frame_device* f) {
+    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && f);
+    int rc = device_ok(ctx, f);
+    if (rc) return rc;
+    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
+    // synchronous like fm_frame_ring_store (filling the ring is set-up work): the kernels on the null stream
+    if ((rc = enqueue_device(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, nullptr)))
+        return rc;
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+extern "C" int fm_frame_device_done(fm_ctx* ctx, uint64_t ticket, int wait) {
+    if (!ctx || !ticket || ticket >= ctx->dev_ticket_next) {
+        fm_set_error("%s:%d bad argument: no such ticket", __FILE__, __LINE__);
+        return FM_ERR_ARG;
+    }
+    const fm_ctx::DevTicket& place = ctx->dev_ticket[ticket % FM_DEV_TICKETS];
+    if (place.ticket != ticket) return 1;                      // (older than the ring: consumed before its place was given away)
+    if (wait) {
+        FM_HIP(hipEventSynchronize(place.ev));
+        return 1;
+    }
+    const hipError_t e = hipEventQuery(place.ev);
+    if (e == hipSuccess) return 1;
+    (void)hipGetLastError();
+    if (e == hipErrorNotReady) return 0;
+    FM_HIP(e);
+    return 0;
+}
+
+void fm_frame_dev_free(fm_ctx* ctx) {
+    for (fm_ctx::DevTicket& place : ctx->dev_ticket) {
+        if (place.ev) {
+            (void)hipEventSynchronize(place.ev);
+            (void)hipEventDestroy(place.ev);
+        }
+        place = fm_ctx::DevTicket{};
+    }
+    for (hipEvent_t& e : ctx->ev_dev_in) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+}
+
 // ---------------------------------------------------------------------------------------- detector
 extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
     FM_CHECK_ARG(ctx && cfg);

@@ -32,7 +32,8 @@ class DeviceFrame:
 
 # Host frames come as BGR ndarrays, as utils.nv12.NV12Frame (Y + interleaved UV planes, converted on the device while
 # they are uploaded), as utils.yuv.PlanarFrame (Y, U and V planes, likewise), as utils.packed.PackedFrame (packed 4:2:2 or RGB in any channel order, likewise), as utils.bayer.BayerFrame (a raw Bayer mosaic, demosaiced likewise), as utils.deep.DeepFrame (9- to 16-bit YCbCr, planar or P010-style semi-planar, converted likewise) or as utils.jpeg.JPEGFrame (an entropy-decoded baseline JPEG; inverse DCT, upsampling and colour
-# conversion run on the device while it is uploaded), or as utils.source.SourceFrame (any of them at capture
+# conversion run on the device while it is uploaded), as utils.devarray.DeviceArrayFrame (a tensor or decoder surface in
+# GPU memory already: converted where it lies, no upload), or as utils.source.SourceFrame (any of them at capture
 # resolution, resized to the frame size on the device): the ctx frame calls below take any of them, and everything
 # behind them reads the same BGR device frame.
 

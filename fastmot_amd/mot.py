@@ -166,7 +166,9 @@ class MOT:
 
     def step(self, frame, next_frame=None, next_frames=None):
         """Runs multiple object tracker on the next frame (ndarray HxWx3 uint8 BGR, an NV12Frame, a PlanarFrame, a PackedFrame, a BayerFrame, a DeepFrame or a JPEGFrame -- converted to BGR
-        on the GPU while it is uploaded --, a SourceFrame -- any of them at capture resolution, resized to `size` on
+        on the GPU while it is uploaded --, a DeviceArrayFrame -- a torch / CuPy tensor or a decoder surface that lies in
+        GPU memory already: converted where it lies, nothing crosses PCIe; it may be dropped right after the step, not
+        overwritten before its `done()` --, a SourceFrame -- any of them at capture resolution, resized to `size` on
         the GPU --, or a detector.DeviceFrame that is already resident on the GPU).
 
         next_frame (optional, not in the reference): the frame the following `step` will receive, when

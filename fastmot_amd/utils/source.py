@@ -2,7 +2,7 @@
 
 The reference resizes every captured frame to the tracker's `size` on the host before anything else sees it
 (cv2.resize in its VideoIO; 1280 x 720 from 1920 x 1080 sources in its default configuration).  A `SourceFrame` wraps
-the frame as it was captured -- a BGR ndarray, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame, a BayerFrame or a DeepFrame -- and is uploaded at that resolution; the
+the frame as it was captured -- a BGR ndarray, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame, a BayerFrame, a DeepFrame or (already in GPU memory) a DeviceArrayFrame -- and is uploaded at that resolution; the
 kernel of csrc/resize.hip then writes the `size` BGR frame that every stage reads.  The resize is cv2.resize's 8-bit
 INTER_LINEAR arithmetic, integer and exact: the device frame equals `videoio.resize_bgr(frame, size)` bit for bit (for
 an NV12Frame / JPEGFrame / PlanarFrame / PackedFrame / BayerFrame / DeepFrame: of the BGR frame it converts / decodes to)."""
@@ -12,6 +12,7 @@ import numpy as np
 
 from .bayer import BayerFrame
 from .deep import DeepFrame
+from .devarray import DeviceArrayFrame
 from .jpeg import JPEGFrame, JpegInfo
 from .lens import LensMap
 from .nv12 import NV12Frame
@@ -38,7 +39,7 @@ class SourceFrame:
     """Host frame at capture resolution; MOT.step, the detectors, the feature extractor, the tracker and the ctx frame
     calls accept it wherever they accept a BGR ndarray, whatever the tracker's frame size is.
 
-    frame: a BGR ndarray (H, W, 3) uint8, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame, a BayerFrame or a DeepFrame, at most 16384 pixels in either direction.  It
+    frame: a BGR ndarray (H, W, 3) uint8, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame, a BayerFrame, a DeepFrame or a DeviceArrayFrame, at most 16384 pixels in either direction.  It
     is not copied (an ndarray that is not C-contiguous is, once): it must stay unmodified until the step that uses the
     frame has returned.  `size` is the SOURCE's (W, H) and `shape` its (H, W, 3); the frame every stage reads has the
     size of the context it is uploaded to.
@@ -51,7 +52,7 @@ class SourceFrame:
     def __init__(self, frame, lens=None):
         if isinstance(frame, SourceFrame):
             raise TypeError('frame is a SourceFrame already')
-        if isinstance(frame, (NV12Frame, JPEGFrame, PlanarFrame, PackedFrame, BayerFrame, DeepFrame)):
+        if isinstance(frame, (NV12Frame, JPEGFrame, PlanarFrame, PackedFrame, BayerFrame, DeepFrame, DeviceArrayFrame)):
             w, h = frame.size
         elif isinstance(frame, np.ndarray):
             if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
@@ -59,7 +60,7 @@ class SourceFrame:
             h, w = frame.shape[:2]
             frame = np.ascontiguousarray(frame)
         else:
-            raise TypeError(f'frame must be a BGR ndarray, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame, a BayerFrame or a DeepFrame, not {type(frame).__name__}')
+            raise TypeError(f'frame must be a BGR ndarray, an NV12Frame, a JPEGFrame, a PlanarFrame, a PackedFrame, a BayerFrame, a DeepFrame or a DeviceArrayFrame, not {type(frame).__name__}')
         if not (1 <= w <= MAX_DIM and 1 <= h <= MAX_DIM):
             raise ValueError(f'source size {w}x{h} outside 1..{MAX_DIM}')
         if lens is not None:
@@ -76,7 +77,7 @@ class SourceFrame:
     def describe(self):
         """The fm_frame_src that describes this frame (it points into `self.frame`, which this object keeps alive).  A
         PlanarFrame has a description of its own, `frame.describe()`: the ctx frame calls hand that one to fm_frame_*_planar,
-        which take every size; so have a PackedFrame (fm_frame_*_packed), a BayerFrame (fm_frame_*_bayer) and a DeepFrame (fm_frame_*_deep)."""
+        which take every size; so have a PackedFrame (fm_frame_*_packed), a BayerFrame (fm_frame_*_bayer), a DeepFrame (fm_frame_*_deep) and a DeviceArrayFrame (fm_frame_*_device)."""
         if isinstance(self.frame, PlanarFrame):
             raise TypeError('a planar source is described by its PlanarFrame (fm_frame_planar), not by fm_frame_src')
         if isinstance(self.frame, PackedFrame):
@@ -85,6 +86,8 @@ class SourceFrame:
             raise TypeError('a Bayer source is described by its BayerFrame (fm_frame_bayer), not by fm_frame_src')
         if isinstance(self.frame, DeepFrame):
             raise TypeError('a deep source is described by its DeepFrame (fm_frame_deep), not by fm_frame_src')
+        if isinstance(self.frame, DeviceArrayFrame):
+            raise TypeError('a source in device memory is described by its DeviceArrayFrame (fm_frame_device), not by fm_frame_src')
         d = self._desc
         if d is None:
             f = self.frame

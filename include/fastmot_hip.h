@@ -705,6 +705,79 @@ int fm_frame_upload_deep(fm_ctx* ctx, const struct fm_frame_deep* f);
 int fm_frame_upload_ahead_deep(fm_ctx* ctx, int k, const struct fm_frame_deep* f);
 int fm_frame_ring_store_deep(fm_ctx* ctx, int index, const struct fm_frame_deep* f);
 
+/* Frames that already lie in GPU memory: a hardware decoder's NV12 surface (VCN / rocDecode), the output of
+ * torchvision.io.decode_jpeg(device='cuda'), a torch / CuPy preprocessing pipeline, a GPU ISP, another model's output.
+ * Every call above takes host pointers; these three take DEVICE pointers, copy nothing across PCIe and make no host
+ * copy: a kernel of csrc/devsrc.hip reads the caller's memory where it lies and writes the BGR frame.
+ *   FM_DEV_HWC, FM_DEV_U8: plane[0] holds `height` rows, pitch[0] bytes apart, of `width` pixels of 3 or 4 bytes;
+ *     `format` is one of the RGB-family ids of fm_frame_packed (FM_PACKED_RGB .. FM_PACKED_XBGR) and the frame equals
+ *     fm_frame_upload_packed's of the same bytes.
+ *   FM_DEV_CHW: plane[0..2] hold one channel each, `height` rows of `width` elements, pitch[c] bytes apart, in the
+ *     order `format` names (FM_DEV_ORDER_RGB: R, G, B; FM_DEV_ORDER_BGR: B, G, R).  FM_DEV_U8: a channel permutation.
+ *     FM_DEV_F16 / FM_DEV_F32: v = (float)x * scale in float32 -- one multiply, not fused with anything --,
+ *     rintf(v) (half to even), NaN -> 0, clamped to 0..255; `scale` is 255.0f for values in [0, 1] and 1.0f for values
+ *     in [0, 255].
+ *   FM_DEV_NV12, FM_DEV_U8: plane[0] is the Y plane, plane[1] the interleaved UV plane of height / 2 rows, each with a
+ *     pitch of its own; fm_frame_upload_nv12's arithmetic and `matrix` ids; width and height even.
+ * Unused planes are NULL, an unused `format` (NV12) is 0; `matrix` is read for NV12 only, `scale` for the float types
+ * only.  The kernels assume nothing about the source's alignment beyond the element size -- a view of a larger tensor
+ * starts at any element and has any pitch --: they take 4- to 16-byte accesses where an address allows them and
+ * elements otherwise.  fastmot_amd/utils/devarray.py to_bgr states the four conversions in numpy; the frame equals it
+ * bit for bit.
+ * The three calls mirror fm_frame_upload_packed, fm_frame_upload_ahead_packed and fm_frame_ring_store_packed one for
+ * one: same slots, same streams, same syncs, same slot events, same rules under a correction map.  width x height equal
+ * to the configured size: the kernel writes the frame itself; any other: it writes the source-size BGR frame of
+ * fm_frame_upload_src's buffers and csrc/resize.hip (csrc/remap.hip) the frame.
+ * Checks, all before anything is enqueued (FM_ERR_ARG, nothing recorded, waited for or launched):
+ *   fm_frame_device_check (host only, no HIP call; the entry points call it first): width and height in
+ *     1..FM_SRC_MAX_DIM, even for NV12; a known layout, a dtype and a format that go with it; used planes non-null,
+ *     unused ones null; every pitch at least the row's bytes and at most 2^40; pointers and pitches multiples of the
+ *     element size; scale 1 or 255 for the float types; no flag but FM_DEV_READY.
+ *   per plane: hipPointerGetAttributes must say device memory of the context's device -- host, page-locked, managed and
+ *     other-device pointers are refused (hand those to the host calls above) --, and where hipMemGetAddressRange answers
+ *     the plane's whole extent, pitch * (rows - 1) + row bytes, must lie inside that allocation.  Where it cannot answer
+ *     (memory of a virtual-memory allocator: hipMemCreate / hipMemMap, torch's expandable segments) the attributes alone
+ *     decide, and the extent is the caller's word.
+ * Ordering: unless FM_DEV_READY is set, the call records a per-slot event on `stream` -- the stream the producer's work
+ * was enqueued on, NULL for the null stream -- and the library's stream waits for it before the kernel reads (no wait is
+ * enqueued when the host already sees the event complete).  FM_DEV_READY: the data is complete, e.g. after a
+ * synchronise; nothing is recorded.
+ * Lifetime: the caller's memory is read by the conversion kernel only, not by the resize.  fm_frame_upload_device and
+ * fm_frame_ring_store_device are synchronous like their siblings: the source is consumed on return.
+ * fm_frame_upload_ahead_device returns a ticket (> 0) in *ticket (which may be null); fm_frame_device_done(ctx, ticket,
+ * wait) says whether that frame's source has been consumed -- 1: yes, the memory may be overwritten or freed; 0: still
+ * being read (never with `wait` != 0, which blocks until it is) --, FM_ERR_ARG for a ticket never handed out.  The
+ * context keeps the last FM_DEV_TICKETS tickets' events; older ones are consumed by construction (a ticket's event is
+ * waited for before its place is reused), and fm_ctx_destroy waits for all of them. */
+#define FM_DEV_HWC 0
+#define FM_DEV_CHW 1
+#define FM_DEV_NV12 2
+#define FM_DEV_U8 0
+#define FM_DEV_F16 1
+#define FM_DEV_F32 2
+#define FM_DEV_ORDER_RGB 0
+#define FM_DEV_ORDER_BGR 1
+#define FM_DEV_READY 1
+#define FM_DEV_TICKETS 16
+struct fm_frame_device {
+    const void* plane[3];   /* device pointers; unused planes NULL */
+    int64_t     pitch[3];   /* bytes between rows of each plane */
+    int32_t     width, height;
+    int32_t     layout;     /* FM_DEV_HWC | FM_DEV_CHW | FM_DEV_NV12 */
+    int32_t     dtype;      /* FM_DEV_U8 | FM_DEV_F16 | FM_DEV_F32 (F16/F32: CHW only) */
+    int32_t     format;     /* HWC: the RGB-family ids of fm_frame_packed (bgr, rgb, bgrx, rgbx, xrgb, xbgr);
+                               CHW: FM_DEV_ORDER_RGB | FM_DEV_ORDER_BGR */
+    int32_t     matrix;     /* NV12: the matrix ids of fm_frame_upload_nv12 */
+    float       scale;      /* float dtypes: 255.0f for values in [0,1], 1.0f for values in [0,255] */
+    void*       stream;     /* producer's hipStream_t (NULL = the null stream) */
+    int32_t     flags;      /* FM_DEV_READY: the data is complete, wait for nothing */
+};
+int fm_frame_upload_device(fm_ctx* ctx, const struct fm_frame_device* f);
+int fm_frame_upload_ahead_device(fm_ctx* ctx, int k, const struct fm_frame_device* f, uint64_t* ticket);
+int fm_frame_ring_store_device(fm_ctx* ctx, int index, const struct fm_frame_device* f);
+int fm_frame_device_done(fm_ctx* ctx, uint64_t ticket, int wait);  /* 1 consumed, 0 still being read, <0 error */
+int fm_frame_device_check(const struct fm_frame_device* f);        /* host-only geometry check, no HIP call */
+
 /* Geometry between sensor and tracker: lens undistortion, or any fixed correction that is one map (a rotation by 90
  * degrees, a mirror, a perspective crop), applied by the gather that already ends every described-source call.  A map
  * holds, for every pixel of the configured width x height frame, a source coordinate in fixed point with 5 fractional
@@ -722,7 +795,7 @@ int fm_frame_ring_store_deep(fm_ctx* ctx, int index, const struct fm_frame_deep*
  * frame, src_w / src_h outside 1..FM_SRC_MAX_DIM or an entry out of range.  fm_frame_remap_clear, fm_frame_configure
  * and fm_ctx_destroy drop the map.
  * While a map is set the described-source calls -- fm_frame_upload_src / _ahead_src / _ring_store_src and their
- * _planar, _packed, _bayer and _deep forms -- take sources of src_w x src_h only (FM_ERR_ARG for any other, nothing copied or
+ * _planar, _packed, _bayer, _deep and _device forms -- take sources of src_w x src_h only (FM_ERR_ARG for any other, nothing copied or
  * launched), stage them at that size even when it is the configured one, and end in the remap kernel where they end in
  * the resize kernel without a map: same slots, streams, syncs, events and trace marks.  Every other call, and every
  * call while no map is set, is untouched.  A per-stream setting: it may change, it should not alternate per frame.
