@@ -549,61 +549,56 @@ def _bind_device_io(cls):
             raise ValueError(f'JPEG frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames {self.frame_size[0]}x{self.frame_size[1]}')
         return C.byref(frame.info), _ptr(frame.coef), _ptr(frame.qt)
 
-    def _planar_of(self, frame):
-        """The PlanarFrame a planar call takes for `frame` -- a PlanarFrame of the context's size, or a SourceFrame around
-        one of any size (fm_frame_*_planar resizes it on the device) --, or None for every other frame kind."""
-        if isinstance(frame, SourceFrame) and isinstance(frame.frame, PlanarFrame):
-            return frame.frame
-        if isinstance(frame, PlanarFrame):
-            if frame.size != tuple(self.frame_size):
-                raise ValueError(f'planar frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
-                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
-            return frame
-        return None
+    def _frame_kind(self, frame):
+        """The symbol suffix and the ctypes arguments of the fm_frame_* calls that take `frame`; ('', None) for everything
+        else, which is a BGR ndarray's business.  A planar, packed, Bayer, deep or device frame is taken at the context's
+        size, or inside a SourceFrame at any size (the call resizes it on the device).  The described kinds have the
+        context's map set to the one the frame carries."""
+        inner = frame.frame if isinstance(frame, SourceFrame) else frame
+        for cls, suffix, name in ((DeviceArrayFrame, '_device', 'device'), (PlanarFrame, '_planar', 'planar'), (PackedFrame, '_packed', 'packed'),
+                                  (BayerFrame, '_bayer', 'Bayer'), (DeepFrame, '_deep', 'deep')):
+            if isinstance(inner, cls):
+                if inner is frame and frame.size != tuple(self.frame_size):
+                    raise ValueError(f'{name} frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
+                                     f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
+                self._described(frame)
+                return suffix, (C.byref(inner.descriptor() if cls is DeviceArrayFrame else inner.describe()),)
+        if isinstance(frame, NV12Frame):
+            return '_nv12', self._nv12_args(frame)
+        if isinstance(frame, JPEGFrame):
+            return '_jpeg', self._jpeg_args(frame)
+        if isinstance(frame, SourceFrame):      # any size: resized to the frame size on the device (csrc/resize.hip)
+            self._described(frame)
+            return '_src', (C.byref(frame.describe()),)
+        return '', None
 
-    def _packed_of(self, frame):
-        """The PackedFrame a packed call takes for `frame`, by `_planar_of`'s rules, or None for every other frame kind."""
-        if isinstance(frame, SourceFrame) and isinstance(frame.frame, PackedFrame):
-            return frame.frame
-        if isinstance(frame, PackedFrame):
-            if frame.size != tuple(self.frame_size):
-                raise ValueError(f'packed frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
-                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
-            return frame
-        return None
-
-    def _bayer_of(self, frame):
-        """The BayerFrame a Bayer call takes for `frame`, by `_planar_of`'s rules, or None for every other frame kind."""
-        if isinstance(frame, SourceFrame) and isinstance(frame.frame, BayerFrame):
-            return frame.frame
-        if isinstance(frame, BayerFrame):
-            if frame.size != tuple(self.frame_size):
-                raise ValueError(f'Bayer frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
-                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
-            return frame
-        return None
-
-    def _deep_of(self, frame):
-        """The DeepFrame a deep call takes for `frame`, by `_planar_of`'s rules, or None for every other frame kind."""
-        if isinstance(frame, SourceFrame) and isinstance(frame.frame, DeepFrame):
-            return frame.frame
-        if isinstance(frame, DeepFrame):
-            if frame.size != tuple(self.frame_size):
-                raise ValueError(f'deep frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
-                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
-            return frame
-        return None
-
-    def _device_of(self, frame):
-        """The DeviceArrayFrame a device call takes for `frame`, by `_planar_of`'s rules, or None for every other frame kind."""
-        if isinstance(frame, SourceFrame) and isinstance(frame.frame, DeviceArrayFrame):
-            return frame.frame
-        if isinstance(frame, DeviceArrayFrame):
-            if frame.size != tuple(self.frame_size):
-                raise ValueError(f'device frame is {frame.size[0]}x{frame.size[1]}, the context\'s frames '
-                                 f'{self.frame_size[0]}x{self.frame_size[1]}: wrap it in a SourceFrame to have it resized')
-            return frame
-        return None
+    def _frame_call(self, stem, lead, frame):
+        """fm_frame_<stem><the frame kind's suffix>(ctx, *lead, <the frame's arguments>): stem 'upload', 'upload_ahead' or
+        'ring_store'."""
+        self.device_frames_prune()
+        suffix, args = self._frame_kind(frame)
+        fn = getattr(self.lib, f'fm_frame_{stem}{suffix}')
+        if suffix == '_device':
+            if stem != 'upload_ahead':
+                self._device_check(fn(self._ctx, *lead, *args))
+                return
+            dev = frame.frame if isinstance(frame, SourceFrame) else frame
+            ticket = C.c_uint64(0)
+            self._device_check(fn(self._ctx, *lead, *args, C.byref(ticket)))
+            # the conversion runs behind this call: the frame (and the array it holds) stays referenced until it has run
+            dev._pending.append((weakref.ref(self), ticket.value))
+            self._dev_pending.append((dev, ticket.value))
+            return
+        if args is None:
+            if stem == 'ring_store':            # (set-up work: converted, not checked)
+                f = np.ascontiguousarray(frame, np.uint8)
+            else:
+                w, h = self.frame_size
+                if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
+                    raise ValueError(f'frame must be uint8 {h}x{w}x3')
+                f = np.ascontiguousarray(frame)
+            args = (_ptr(f),)                   # (`f` lives until the call has returned)
+        check(fn(self._ctx, *lead, *args))
 
     def _device_check(self, rc):
         """check() for the device-frame calls: a description the library refuses (FM_ERR_ARG: not device memory of this
@@ -632,47 +627,7 @@ def _bind_device_io(cls):
         return [f for f, _ in self._dev_pending]
 
     def frame_upload(self, frame):
-        self.device_frames_prune()
-        dev = self._device_of(frame)
-        if dev is not None:
-            self._described(frame)
-            self._device_check(self.lib.fm_frame_upload_device(self._ctx, C.byref(dev.descriptor())))
-            return
-        planar = self._planar_of(frame)
-        if planar is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_planar(self._ctx, C.byref(planar.describe())))
-            return
-        packed = self._packed_of(frame)
-        if packed is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_packed(self._ctx, C.byref(packed.describe())))
-            return
-        bayer = self._bayer_of(frame)
-        if bayer is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_bayer(self._ctx, C.byref(bayer.describe())))
-            return
-        deep = self._deep_of(frame)
-        if deep is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_deep(self._ctx, C.byref(deep.describe())))
-            return
-        if isinstance(frame, NV12Frame):
-            check(self.lib.fm_frame_upload_nv12(self._ctx, *self._nv12_args(frame)))
-            return
-        if isinstance(frame, JPEGFrame):
-            check(self.lib.fm_frame_upload_jpeg(self._ctx, *self._jpeg_args(frame)))
-            return
-        if isinstance(frame, SourceFrame):      # any size: resized to the frame size on the device (csrc/resize.hip)
-            self._described(frame)
-            check(self.lib.fm_frame_upload_src(self._ctx, C.byref(frame.describe())))
-            return
-        w, h = self.frame_size
-        if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
-            raise ValueError(f'frame must be uint8 {h}x{w}x3')
-        f = np.ascontiguousarray(frame)
-        check(self.lib.fm_frame_upload(self._ctx, _ptr(f)))
+        self._frame_call('upload', (), frame)
 
     def pinned_frames(self, n):
         """n frames (n, H, W, 3) uint8 in page-locked host memory (fm_host_alloc): frames stored here are
@@ -743,44 +698,7 @@ def _bind_device_io(cls):
         return [DeepFrame.from_buffer(buf[i], size, chroma, depth, matrix) for i in range(n)]
 
     def frame_ring_store(self, index, frame):
-        self.device_frames_prune()
-        dev = self._device_of(frame)
-        if dev is not None:
-            self._described(frame)
-            self._device_check(self.lib.fm_frame_ring_store_device(self._ctx, C.c_int(index), C.byref(dev.descriptor())))
-            return
-        planar = self._planar_of(frame)
-        if planar is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_ring_store_planar(self._ctx, C.c_int(index), C.byref(planar.describe())))
-            return
-        packed = self._packed_of(frame)
-        if packed is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_ring_store_packed(self._ctx, C.c_int(index), C.byref(packed.describe())))
-            return
-        bayer = self._bayer_of(frame)
-        if bayer is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_ring_store_bayer(self._ctx, C.c_int(index), C.byref(bayer.describe())))
-            return
-        deep = self._deep_of(frame)
-        if deep is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_ring_store_deep(self._ctx, C.c_int(index), C.byref(deep.describe())))
-            return
-        if isinstance(frame, NV12Frame):
-            check(self.lib.fm_frame_ring_store_nv12(self._ctx, C.c_int(index), *self._nv12_args(frame)))
-            return
-        if isinstance(frame, JPEGFrame):
-            check(self.lib.fm_frame_ring_store_jpeg(self._ctx, C.c_int(index), *self._jpeg_args(frame)))
-            return
-        if isinstance(frame, SourceFrame):
-            self._described(frame)
-            check(self.lib.fm_frame_ring_store_src(self._ctx, C.c_int(index), C.byref(frame.describe())))
-            return
-        f = np.ascontiguousarray(frame, np.uint8)
-        check(self.lib.fm_frame_ring_store(self._ctx, C.c_int(index), _ptr(f)))
+        self._frame_call('ring_store', (C.c_int(index),), frame)
 
     def frame_ring_select(self, index):
         check(self.lib.fm_frame_ring_select(self._ctx, C.c_int(index)))
@@ -805,51 +723,7 @@ def _bind_device_io(cls):
 
     def frame_upload_ahead(self, k, frame):
         """Host frame for the step k steps ahead (look-ahead slot k, 1 <= k <= FM_MAX_DET_BATCH; k = 1: frame_upload_next)."""
-        self.device_frames_prune()
-        dev = self._device_of(frame)
-        if dev is not None:
-            self._described(frame)
-            ticket = C.c_uint64(0)
-            self._device_check(self.lib.fm_frame_upload_ahead_device(self._ctx, C.c_int(k), C.byref(dev.descriptor()), C.byref(ticket)))
-            # the conversion runs behind this call: the frame (and the array it holds) stays referenced until it has run
-            dev._pending.append((weakref.ref(self), ticket.value))
-            self._dev_pending.append((dev, ticket.value))
-            return
-        planar = self._planar_of(frame)
-        if planar is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_ahead_planar(self._ctx, C.c_int(k), C.byref(planar.describe())))
-            return
-        packed = self._packed_of(frame)
-        if packed is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_ahead_packed(self._ctx, C.c_int(k), C.byref(packed.describe())))
-            return
-        bayer = self._bayer_of(frame)
-        if bayer is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_ahead_bayer(self._ctx, C.c_int(k), C.byref(bayer.describe())))
-            return
-        deep = self._deep_of(frame)
-        if deep is not None:
-            self._described(frame)
-            check(self.lib.fm_frame_upload_ahead_deep(self._ctx, C.c_int(k), C.byref(deep.describe())))
-            return
-        if isinstance(frame, NV12Frame):
-            check(self.lib.fm_frame_upload_ahead_nv12(self._ctx, C.c_int(k), *self._nv12_args(frame)))
-            return
-        if isinstance(frame, JPEGFrame):
-            check(self.lib.fm_frame_upload_ahead_jpeg(self._ctx, C.c_int(k), *self._jpeg_args(frame)))
-            return
-        if isinstance(frame, SourceFrame):
-            self._described(frame)
-            check(self.lib.fm_frame_upload_ahead_src(self._ctx, C.c_int(k), C.byref(frame.describe())))
-            return
-        w, h = self.frame_size
-        if frame.shape != (h, w, 3) or frame.dtype != np.uint8:
-            raise ValueError(f'frame must be uint8 {h}x{w}x3')
-        f = np.ascontiguousarray(frame)
-        check(self.lib.fm_frame_upload_ahead(self._ctx, C.c_int(k), _ptr(f)))
+        self._frame_call('upload_ahead', (C.c_int(k),), frame)
 
     def frame_ring_select_ahead(self, k, index):
         check(self.lib.fm_frame_ring_select_ahead(self._ctx, C.c_int(k), C.c_int(index)))
@@ -1051,7 +925,7 @@ def _bind_device_io(cls):
         check(self.lib.fm_extract_read_input(self._ctx, C.c_int(n), _ptr(out)))
         return out
 
-    for fn in (frame_configure, frame_set_lens, _described, _device_of, _device_check, device_frame_done, device_frames_prune, pending_device_frames, _nv12_args, _jpeg_args, _planar_of, _packed_of, _bayer_of, _deep_of, pinned_deep_frames, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
+    for fn in (frame_configure, frame_set_lens, _described, _frame_kind, _frame_call, _device_check, device_frame_done, device_frames_prune, pending_device_frames, _nv12_args, _jpeg_args, pinned_deep_frames, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
                overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,

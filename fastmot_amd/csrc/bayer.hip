@@ -1,6 +1,6 @@
 // Bayer mosaic (one sample per pixel: 8 bits, or 10 / 12 / 14 / 16 bits in a little-endian 16-bit word) -> packed BGR u8:
-// the kernel behind fm_frame_upload_bayer / fm_frame_upload_ahead_bayer / fm_frame_ring_store_bayer (detect.hip, frame
-// section).  This is what industrial and embedded cameras hand out (GigE Vision / USB3 Vision BayerRG8 / BayerRG12, V4L2
+// the kernel behind fm_frame_upload_bayer / fm_frame_upload_ahead_bayer / fm_frame_ring_store_bayer (frames.hip).
+// This is what industrial and embedded cameras hand out (GigE Vision / USB3 Vision BayerRG8 / BayerRG12, V4L2
 // SRGGB8 / SRGGB10, CSI sensors).  The frame arrives in device staging with its rows packed to their width (W or 2 W
 // bytes) and leaves as the BGR frame every consumer reads.  fastmot_amd/utils/bayer.py states the arithmetic in numpy
 // (sample preparation, reflect-101 borders, the bilinear and the Malvar-He-Cutler filters); tests compare bit for bit.

@@ -228,7 +228,7 @@ struct fm_ctx {
     // ... and the staging of deep YCbCr frames of every size (fm_frame_*_deep; csrc/deep.hip converts out of `dev`),
     // entries as frame_nv12's: `dev` and `pinned` grow to the frame's bytes -- up to 6 per pixel, which the slots'
     // BGR-sized buffers do not hold -- by frame_src's rules; `bgr` stays unused (an off-size frame's BGR form is
-    // frame_src[entry].bgr).  Freed by fm_frame_configure and fm_ctx_destroy (fm_frame_deep_free).
+    // frame_src[entry].bgr).  Freed by fm_frame_configure and fm_ctx_destroy (fm_frame_staging_free).
     SrcStage frame_deep[FM_MAX_DET_BATCH + 2];
 
     // ---- frames that lie in device memory already (fm_frame_*_device; csrc/devsrc.hip converts from where they lie): no
@@ -315,14 +315,21 @@ inline size_t fm_dev_row_bytes(const struct fm_frame_device* f) {
     if (f->layout == FM_DEV_HWC) return (size_t)f->width * (f->format <= FM_PACKED_BGR ? 3 : 4);
     return (size_t)f->width * fm_dev_elem_bytes(f->dtype);
 }
-void fm_frame_dev_free(fm_ctx* ctx);                                                              // detect.hip
 void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
 // remap.hip: `src` through the device map `xy` ([dh][dw][2] int32, remap_pixel.h); border = b | g << 8 | r << 16
 int fm_remap_bgr(const uint8_t* src, int sw, int sh, const int32_t* xy, uint8_t* dst, int dw, int dh, uint32_t border, hipStream_t s);
-void fm_frame_src_free(fm_ctx* ctx);                                                              // detect.hip
-void fm_frame_deep_free(fm_ctx* ctx);                                                             // detect.hip
-void fm_frame_remap_free(fm_ctx* ctx);                                                            // detect.hip (no sync: the caller's)
+// frames.hip.  Look-ahead slot k, the frame the step k steps ahead receives: slot 1 is the fields of the next-frame
+// prefetch, slots 2.. those of the arrays (fm_ctx above) -- its frame, and its upload buffer with the event behind the
+// last upload into it
+inline uint8_t*& fm_ahead_frame(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_next : ctx->frame_ahead[k]; }
+inline uint8_t*& fm_ahead_buf(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_own2 : ctx->frame_up[k]; }
+inline hipEvent_t& fm_ahead_event(fm_ctx* ctx, int k) { return k == 1 ? ctx->ev_next_upload : ctx->ev_up[k]; }
+bool fm_host_is_pinned(const void* p, size_t bytes);      // frames.hip: inside a buffer from fm_host_alloc
+// frames.hip: frees every format's staging, the off-size sources' and the correction map (no sync: the caller's) ...
+void fm_frame_staging_free(fm_ctx* ctx);
+void fm_frame_dev_free(fm_ctx* ctx);     // ... and destroys the device frames' events, waiting for the tickets' (fm_ctx_destroy)
+int fm_det_flush_post(fm_ctx* ctx);      // detect.hip: enqueues the pending pass's post-processing; nothing without a detector
 int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s);   // jpeg.hip
 // fm_jpeg_info's description of a width x height frame with ncomp 1 or 3 and luma sampling hsamp0 x vsamp0 (jpeg_host.hip)
 int fm_jpeg_layout(int width, int height, int ncomp, int hsamp0, int vsamp0, struct fm_jpeg_info* out);

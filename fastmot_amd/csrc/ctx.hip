@@ -174,24 +174,10 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
         if (ctx->frame_up_pinned[k]) (void)hipHostFree(ctx->frame_up_pinned[k]);
         if (ctx->ev_up[k]) (void)hipEventDestroy(ctx->ev_up[k]);
     }
-    for (uint8_t* p : ctx->frame_nv12)
-        if (p) (void)hipFree(p);
-    for (uint8_t* p : ctx->frame_planar)
-        if (p) (void)hipFree(p);
-    for (uint8_t* p : ctx->frame_packed)
-        if (p) (void)hipFree(p);
-    for (uint8_t* p : ctx->frame_bayer)
-        if (p) (void)hipFree(p);
-    for (uint8_t* p : ctx->frame_jpeg)
-        if (p) (void)hipFree(p);
-    for (uint8_t* p : ctx->frame_jpeg_pinned)
-        if (p) (void)hipHostFree(p);
     for (hipEvent_t e : ctx->ev_jpeg)
         if (e) (void)hipEventDestroy(e);
-    fm_frame_src_free(ctx);
-    fm_frame_deep_free(ctx);
     fm_frame_dev_free(ctx);      // (waits for the look-ahead tickets' events)
-    fm_frame_remap_free(ctx);
+    fm_frame_staging_free(ctx);
     fm_overlay_free(ctx);        // (before the encoder: it works on the encoder's stream)
     fm_yuv_free(ctx);            // (likewise)
     fm_jpegenc_free(ctx);

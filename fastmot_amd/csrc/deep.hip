@@ -1,5 +1,5 @@
 // 9- to 16-bit YCbCr -> packed BGR u8: the kernel behind fm_frame_upload_deep / fm_frame_upload_ahead_deep /
-// fm_frame_ring_store_deep (detect.hip, frame section).  Two layouts of 16-bit little-endian words: planar (Y, U, V
+// fm_frame_ring_store_deep (frames.hip).  Two layouts of 16-bit little-endian words: planar (Y, U, V
 // planes, the sample in the LOW bits: libavcodec's yuv420p10le, a Y4M C420p10 frame) and semi-planar (Y plane + a plane
 // of interleaved U, V, the sample in the HIGH bits: P010 / P012 / P016, what a hardware HEVC / AV1 Main10 decoder
 // delivers).

@@ -1,5 +1,5 @@
-// Detector front/back end on the device: frame residency, preprocessing, YOLO head decode,
-// score/class filter, per-class DIoU-NMS, box filter.
+// Detector front/back end on the device: preprocessing, YOLO head decode, score/class filter,
+// per-class DIoU-NMS, box filter.  (The frames it reads are put on the device by frames.hip.)
 //
 // Replaces (reference file:line, relative to /root/reference)
 //   YOLODetector._preprocess        fastmot/detector.py:289-300  (CuPy zoom order=1 mode='opencv'
@@ -19,12 +19,9 @@
 // Roofline: HBM bound -- reads (5+C)*A*sum(HW)*4 B of head tensors (7.7 MB @608/80 classes),
 // frame 6.2 MB in, 608*608*8*2 B out.
 #include "pixel_source.h"
-#include "remap_pixel.h"
 #include <cmath>
-#include <mutex>
 #include <string>
 #include <vector>
-#include <utility>
 
 struct DetState {
     fm_yolo_cfg cfg{};
@@ -100,7 +97,7 @@ void fm_det_free(DetState* d) {
 
 namespace {
 
-// ------------------------------------------------------------------------------------ frames
+// ------------------------------------------------------------------------------------ preprocess
 // bilinear resize in uint8 with half-pixel centres and edge clamp (cupyx zoom mode='opencv',
 // grid_mode=True: src = (dst + 0.5) * (in/out) - 0.5; affine_transform order=1, mode='nearest'),
 // result rounded to uint8 (rint), then BGR->RGB, * 1/255 (fp32) and stored as fp16 NHWC with the
@@ -1182,1300 +1179,8 @@ int collect_tiles(fm_ctx* ctx, DetState* d, hipStream_t s, fm_det48* out, int ca
 
 }  // namespace
 
-// ---------------------------------------------------------------------------------------- frames
-extern "C" int fm_frame_configure(fm_ctx* ctx, int width, int height, int ring_size) {
-    FM_CHECK_ARG(ctx && width > 0 && height > 0 && ring_size >= 0);
-    FM_HIP(hipDeviceSynchronize());
-    for (void* p : {(void*)ctx->frame_own, (void*)ctx->frame_own2, (void*)ctx->frame_ring})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)ctx->frame_pinned, (void*)ctx->frame_pinned2})
-        if (p) (void)hipHostFree(p);
-    ctx->frame_own = ctx->frame_own2 = ctx->frame_ring = ctx->frame_pinned = ctx->frame_pinned2 = nullptr;
-    ctx->frame_next = nullptr;
-    for (int k = 2; k <= FM_MAX_DET_BATCH; ++k) {      // look-ahead slots: allocated again on first use at the new size
-        if (ctx->frame_up[k]) (void)hipFree(ctx->frame_up[k]);
-        if (ctx->frame_up_pinned[k]) (void)hipHostFree(ctx->frame_up_pinned[k]);
-        ctx->frame_up[k] = ctx->frame_up_pinned[k] = ctx->frame_ahead[k] = nullptr;
-    }
-    for (uint8_t*& p : ctx->frame_nv12) {              // NV12 staging: allocated again on first NV12 use
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    for (uint8_t*& p : ctx->frame_planar) {            // planar staging: allocated again on first planar use
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    for (uint8_t*& p : ctx->frame_packed) {            // packed staging: allocated again on first packed use
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    for (uint8_t*& p : ctx->frame_bayer) {             // Bayer staging: allocated again on first Bayer use
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    for (uint8_t*& p : ctx->frame_jpeg) {              // JPEG staging: allocated again on first JPEG use
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    for (uint8_t*& p : ctx->frame_jpeg_pinned) {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-    }
-    fm_frame_src_free(ctx);                            // off-size sources: allocated again on first use
-    fm_frame_deep_free(ctx);                           // deep staging: allocated again on first deep use
-    fm_frame_remap_free(ctx);                          // a correction map is for one frame size: set again by the caller
-    const size_t bytes = (size_t)width * height * 3;
-    FM_HIP(hipMalloc(&ctx->frame_own, bytes + FM_FRAME_SLACK));        // (pixel_source.h load_px2 reads 8 bytes at a pixel)
-    FM_HIP(hipMalloc(&ctx->frame_own2, bytes + FM_FRAME_SLACK));
-    FM_HIP(hipHostMalloc(&ctx->frame_pinned, bytes, hipHostMallocDefault));
-    FM_HIP(hipHostMalloc(&ctx->frame_pinned2, bytes, hipHostMallocDefault));
-    if (ring_size > 0) FM_HIP(hipMalloc(&ctx->frame_ring, bytes * ring_size + FM_FRAME_SLACK));
-    ctx->frame_w = width;
-    ctx->frame_h = height;
-    ctx->ring_size = ring_size;
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-// ---- page-locked frame buffers handed to the caller (process-wide registry of their ranges)
-namespace {
-std::mutex g_host_mu;
-std::vector<std::pair<const uint8_t*, size_t>> g_host_ranges;
-
-bool is_pinned_range(const uint8_t* p, size_t bytes) {
-    std::lock_guard<std::mutex> lk(g_host_mu);
-    for (auto& r : g_host_ranges)
-        if (p >= r.first && p + bytes <= r.first + r.second) return true;
-    return false;
-}
-}  // namespace
-
-bool fm_host_is_pinned(const void* p, size_t bytes) { return is_pinned_range((const uint8_t*)p, bytes); }   // (jpegenc.hip)
-
-extern "C" int fm_host_alloc(size_t bytes, void** out) {
-    FM_CHECK_ARG(out && bytes > 0);
-    void* p = nullptr;
-    FM_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    {
-        std::lock_guard<std::mutex> lk(g_host_mu);
-        g_host_ranges.emplace_back((const uint8_t*)p, bytes);
-    }
-    *out = p;
-    return 0;
-}
-
-extern "C" int fm_host_free(void* p) {
-    if (!p) return 0;
-    {
-        std::lock_guard<std::mutex> lk(g_host_mu);
-        for (size_t i = 0; i < g_host_ranges.size(); ++i)
-            if (g_host_ranges[i].first == (const uint8_t*)p) {
-                g_host_ranges.erase(g_host_ranges.begin() + i);
-                break;
-            }
-    }
-    FM_HIP(hipHostFree(p));
-    return 0;
-}
-
-// H2D copy of a frame from page-locked memory (the copy engine; a copy KERNEL measured no faster in round 2)
-static int enqueue_frame_copy(uint8_t* dst, const uint8_t* src_pinned, size_t bytes, hipStream_t s) {
-    FM_HIP(hipMemcpyAsync(dst, src_pinned, bytes, hipMemcpyHostToDevice, s));
-    return 0;
-}
-
-extern "C" int fm_frame_upload(fm_ctx* ctx, const uint8_t* bgr) {
-    FM_CHECK_ARG(ctx && bgr && ctx->frame_own);
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    // every consumer of the previous frame must be done before it is overwritten
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    const uint8_t* src = bgr;
-    if (!is_pinned_range(bgr, bytes)) {
-        memcpy(ctx->frame_pinned, bgr, bytes);
-        src = ctx->frame_pinned;
-    }
-    int rc_copy = enqueue_frame_copy(ctx->frame_own, src, bytes, ctx->s_det);
-    if (rc_copy) return rc_copy;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-// ---- next-frame prefetch: the detector may be started on frame t+1 while frame t is still being tracked
-// (MOT.step(frame, next_frame)).  The next frame lives in the second upload slot (or the ring) and becomes
-// the current one with fm_frame_promote_next -- no second upload.
-// Look-ahead slot k: the frame the step k steps ahead receives.  Slot 1 is the fields of the next-frame prefetch
-// (frame_next, upload slot frame_own2 / frame_pinned2 / ev_next_upload), slots 2.. those of fm_ctx::frame_ahead /
-// frame_up / frame_up_pinned / ev_up.  An upload slot's buffers move with its frame when fm_frame_promote_next shifts the
-// slots, so that slot 1's frame always lies in frame_own2 when it was uploaded.
-static uint8_t*& ahead_frame(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_next : ctx->frame_ahead[k]; }
-static uint8_t*& ahead_buf(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_own2 : ctx->frame_up[k]; }
-static uint8_t*& ahead_pinned(fm_ctx* ctx, int k) { return k == 1 ? ctx->frame_pinned2 : ctx->frame_up_pinned[k]; }
-static hipEvent_t& ahead_event(fm_ctx* ctx, int k) { return k == 1 ? ctx->ev_next_upload : ctx->ev_up[k]; }
-
-extern "C" int fm_frame_upload_next(fm_ctx* ctx, const uint8_t* bgr) { return fm_frame_upload_ahead(ctx, 1, bgr); }
-
-extern "C" int fm_frame_upload_ahead(fm_ctx* ctx, int k, const uint8_t* bgr) {
-    FM_CHECK_ARG(ctx && bgr && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH);
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    const uint8_t* src = bgr;
-    if (!is_pinned_range(bgr, bytes)) {
-        // previous H2D copy out of a staging buffer: its event, not the stream (a detector pass may be running)
-        if (ev) FM_HIP(hipEventSynchronize(ev));
-        memcpy(ahead_pinned(ctx, k), bgr, bytes);
-        src = ahead_pinned(ctx, k);
-    }
-    // The previous readers of the slot's buffer -- every stage of the step before the last promote, its detector pass
-    // included -- are done (fm_frame_promote_next synchronised the ReID / KLT streams, that pass was collected; a batched
-    // pass is complete once any of its frames was collected).  The
-    // copy goes to the ReID stream: that stream is idle at this point of a step (its network starts once this frame's
-    // detections have been collected, long after a 6 MB copy), it is a high-priority stream, and the pass on the new
-    // frame waits for the copy's event only.  On the low-priority stream that carries the post-processing the copy was
-    // held back while the KLT / ReID kernels of the running step kept the high-priority queues busy, and the detector
-    // -- the longest chain of a step -- started late every frame: 662 -> 780 frames/s for this move alone, 872 together
-    // with MOT.step enqueueing the prefetch before it starts the KLT job (config[1]; config[4] 100 -> 158;
-    // profiles/r03_pipeline_order_ab.txt holds the whole matrix, the tracker stream and a high-priority upload stream
-    // included: 550-600 and 450).
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc_copy = enqueue_frame_copy(buf, src, bytes, cs);
-    if (rc_copy) return rc_copy;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc_copy = flush_post(ctx, ctx->det))) return rc_copy;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_select_next(fm_ctx* ctx, int index) { return fm_frame_ring_select_ahead(ctx, 1, index); }
-
-extern "C" int fm_frame_ring_select_ahead(fm_ctx* ctx, int k, int index) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && k >= 1 && k <= FM_MAX_DET_BATCH);
-    ahead_frame(ctx, k) = ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index;
-    return 0;
-}
-
-extern "C" int fm_frame_promote_next(fm_ctx* ctx) {
-    FM_CHECK_ARG(ctx && ctx->frame_next);
-    if (ctx->frame_next == ctx->frame_own2) {
-        // the upload of the prefetched frame was enqueued on the ReID stream (fm_frame_upload_next); every stream that
-        // reads the frame from now on waits for that copy's event
-        FM_HIP(hipStreamSynchronize(ctx->s_ext));
-        FM_HIP(hipStreamSynchronize(ctx->s_flow));
-        FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-        // (the copy ran a step ago: when the host already sees its event complete, four barrier packets -- one in front of
-        // the next frame's copy on the ReID stream -- need not be enqueued at all)
-        if (hipEventQuery(ctx->ev_next_upload) != hipSuccess) {
-            (void)hipGetLastError();
-            FM_HIP(hipStreamWaitEvent(ctx->s_ext, ctx->ev_next_upload, 0));
-            FM_HIP(hipStreamWaitEvent(ctx->s_flow, ctx->ev_next_upload, 0));
-            FM_HIP(hipStreamWaitEvent(ctx->s_flow2, ctx->ev_next_upload, 0));
-            FM_HIP(hipStreamWaitEvent(ctx->s_main, ctx->ev_next_upload, 0));
-        }
-        std::swap(ctx->frame_own, ctx->frame_own2);
-        std::swap(ctx->frame_pinned, ctx->frame_pinned2);
-        ctx->frame_cur = ctx->frame_own;
-    } else {
-        ctx->frame_cur = ctx->frame_next;
-    }
-    ctx->frame_next = nullptr;
-    // look-ahead: slot k becomes slot k - 1; a frame in its upload slot takes that slot's buffers along (the free buffer
-    // -- the previous frame's -- moves up in exchange)
-    for (int k = 2; k <= FM_MAX_DET_BATCH; ++k) {
-        uint8_t* f = ctx->frame_ahead[k];
-        if (f && f == ctx->frame_up[k]) {
-            std::swap(ahead_buf(ctx, k - 1), ahead_buf(ctx, k));
-            std::swap(ahead_pinned(ctx, k - 1), ahead_pinned(ctx, k));
-            std::swap(ahead_event(ctx, k - 1), ahead_event(ctx, k));
-        }
-        ahead_frame(ctx, k - 1) = f;
-        ctx->frame_ahead[k] = nullptr;
-    }
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store(fm_ctx* ctx, int index, const uint8_t* bgr) {
-    FM_CHECK_ARG(ctx && bgr && index >= 0 && index < ctx->ring_size);
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    FM_HIP(hipMemcpy(ctx->frame_ring + bytes * index, bgr, bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-
-extern "C" int fm_frame_ring_select(fm_ctx* ctx, int index) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size);
-    ctx->frame_cur = ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index;
-    return 0;
-}
-
-extern "C" int fm_frame_read(fm_ctx* ctx, uint8_t* bgr) {
-    FM_CHECK_ARG(ctx && bgr && ctx->frame_cur);
-    FM_HIP(hipDeviceSynchronize());
-    FM_HIP(hipMemcpy(bgr, ctx->frame_cur, (size_t)ctx->frame_w * ctx->frame_h * 3, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// ---- NV12 ingest: the three host-frame entry points again, for a Y plane + an interleaved UV plane with a row pitch.
-// Same slots, streams, syncs and events as their BGR counterparts above; between the H2D copy (1.5 bytes per pixel, into
-// ctx->frame_nv12[entry]) and whatever followed it there, the conversion kernel of nv12.hip writes the BGR frame.
-#define FM_CHECK_NV12(ctx, y, uv, pitch, matrix)                                                                  \
-    FM_CHECK_ARG((y) && (uv) && (pitch) >= (ctx)->frame_w && ((matrix) == FM_NV12_BT601 || (matrix) == FM_NV12_BT709) && \
-                 !((ctx)->frame_w & 1) && !((ctx)->frame_h & 1))
-
-// H2D copy of an NV12 frame into the entry's device staging and its conversion into `dst`, both on `s`.  Planes that
-// cannot be copied from where they are (pageable memory, or a pitch) are packed into `pinned` first, after `reuse` --
-// the event behind the previous copy out of that staging buffer -- when one is given.
-static int enqueue_nv12(fm_ctx* ctx, int entry, uint8_t* dst, const uint8_t* y, const uint8_t* uv, int pitch, int matrix,
-                        uint8_t* pinned, hipEvent_t reuse, hipStream_t s) {
-    const int w = ctx->frame_w, h = ctx->frame_h;
-    const size_t npx = (size_t)w * h;
-    uint8_t*& stage = ctx->frame_nv12[entry];
-    if (!stage) FM_HIP(hipMalloc(&stage, npx + npx / 2));
-    if (pitch == w && is_pinned_range(y, npx) && is_pinned_range(uv, npx / 2)) {
-        if (uv == y + npx) {
-            FM_HIP(hipMemcpyAsync(stage, y, npx + npx / 2, hipMemcpyHostToDevice, s));
-        } else {
-            FM_HIP(hipMemcpyAsync(stage, y, npx, hipMemcpyHostToDevice, s));
-            FM_HIP(hipMemcpyAsync(stage + npx, uv, npx / 2, hipMemcpyHostToDevice, s));
-        }
-    } else {
-        if (reuse) FM_HIP(hipEventSynchronize(reuse));
-        for (int r = 0; r < h; ++r) memcpy(pinned + (size_t)r * w, y + (size_t)r * pitch, w);
-        for (int r = 0; r < h / 2; ++r) memcpy(pinned + npx + (size_t)r * w, uv + (size_t)r * pitch, w);
-        FM_HIP(hipMemcpyAsync(stage, pinned, npx + npx / 2, hipMemcpyHostToDevice, s));
-    }
-    fm_trace_mark(ctx, s, 36);                 // (the conversion's share of the caller's 30 .. 31 interval)
-    return fm_nv12_to_bgr(stage, dst, w, h, matrix, s);
-}
-
-extern "C" int fm_frame_upload_nv12(fm_ctx* ctx, const uint8_t* y, const uint8_t* uv, int pitch, int matrix) {
-    FM_CHECK_ARG(ctx && ctx->frame_own);
-    FM_CHECK_NV12(ctx, y, uv, pitch, matrix);
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    int rc = enqueue_nv12(ctx, 0, ctx->frame_own, y, uv, pitch, matrix, ctx->frame_pinned, nullptr, ctx->s_det);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-extern "C" int fm_frame_upload_ahead_nv12(fm_ctx* ctx, int k, const uint8_t* y, const uint8_t* uv, int pitch, int matrix) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH);
-    FM_CHECK_NV12(ctx, y, uv, pitch, matrix);
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (the BGR-sized staging holds an NV12 frame twice over)
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the KERNEL: a reader
-    // that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc = enqueue_nv12(ctx, k, buf, y, uv, pitch, matrix, ahead_pinned(ctx, k), ev, cs);
-    if (rc) return rc;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store_nv12(fm_ctx* ctx, int index, const uint8_t* y, const uint8_t* uv, int pitch, int matrix) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size);
-    FM_CHECK_NV12(ctx, y, uv, pitch, matrix);
-    const int w = ctx->frame_w, h = ctx->frame_h;
-    const size_t npx = (size_t)w * h;
-    uint8_t*& stage = ctx->frame_nv12[FM_MAX_DET_BATCH + 1];
-    if (!stage) FM_HIP(hipMalloc(&stage, npx + npx / 2));
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies that pack the rows, then
-    // the kernel on the null stream
-    FM_HIP(hipMemcpy2D(stage, w, y, pitch, w, h, hipMemcpyHostToDevice));
-    FM_HIP(hipMemcpy2D(stage + npx, w, uv, pitch, w, h / 2, hipMemcpyHostToDevice));
-    int rc = fm_nv12_to_bgr(stage, ctx->frame_ring + npx * 3 * index, w, h, matrix, nullptr);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-#undef FM_CHECK_NV12
-
-// ---- JPEG ingest: the three host-frame entry points once more, for a frame that arrives as the output of
-// fm_jpeg_entropy_decode (jpeg_host.hip).  Same slots, streams, syncs and events as their BGR counterparts; between the
-// H2D copy (coefficients + quantisation tables, into ctx->frame_jpeg[entry]) and whatever followed it there, the two
-// kernels of jpeg.hip write the BGR frame.
-
-// int16 coefficients of the largest supported layout of a w x h frame: 4:4:4 on a grid padded to 16 pixels (which bounds
-// the 8-pixel grid 4:4:4 really has, and 4:2:2 / 4:2:0 / one component at half that or less)
-static size_t jpeg_max_coefs(int w, int h) { return (size_t)3 * ((w + 15) & ~15) * ((h + 15) & ~15); }
-static size_t jpeg_stage_bytes(int w, int h) { return fm_jpeg_sample_offset((long long)jpeg_max_coefs(w, h)) + jpeg_max_coefs(w, h); }
-
-// `info` describes a supported layout of a w x h frame, every derived field as fm_jpeg_info computes it
-static bool jpeg_layout_ok_size(const struct fm_jpeg_info* info, int w, int h) {
-    if (!info || info->width != w || info->height != h) return false;
-    struct fm_jpeg_info want;
-    if (fm_jpeg_layout(info->width, info->height, info->ncomp, info->hsamp[0], info->vsamp[0], &want)) return false;
-    for (int c = 0; c < 3; ++c)
-        if (info->blocks_w[c] != want.blocks_w[c] || info->blocks_h[c] != want.blocks_h[c] || info->coef_offset[c] != want.coef_offset[c])
-            return false;
-    // (the launch grids of jpeg.hip: one lane per block row, one thread per 8 pixels of a row)
-    if (want.coef_count / 64 >= (1ll << 28) || (long long)((info->width + 7) >> 3) * info->height >= (1ll << 31)) return false;
-    return info->coef_count == want.coef_count && (size_t)want.coef_count <= jpeg_max_coefs(w, h);
-}
-// ... of the configured frame size
-static bool jpeg_layout_ok(const fm_ctx* ctx, const struct fm_jpeg_info* info) { return jpeg_layout_ok_size(info, ctx->frame_w, ctx->frame_h); }
-#define FM_CHECK_JPEG(ctx, info, coef, qt) FM_CHECK_ARG((coef) && (qt) && jpeg_layout_ok(ctx, info))
-
-// H2D copy of a frame's coefficients and tables into the entry's device staging and its decode into `dst`, both on `s`.
-// Buffers that cannot be copied from where they are (pageable memory) are packed into the entry's page-locked staging
-// first; `reuse`, when given, is the entry's event behind the previous copy out of that staging buffer: waited for
-// before the buffer is written, recorded again behind the new copy.
-static int enqueue_jpeg(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt,
-                        hipEvent_t* reuse, hipStream_t s) {
-    const size_t cbytes = (size_t)info->coef_count * 2, qbytes = 3 * 64 * 2;
-    uint8_t*& stage = ctx->frame_jpeg[entry];
-    if (!stage) FM_HIP(hipMalloc(&stage, jpeg_stage_bytes(ctx->frame_w, ctx->frame_h)));
-    const uint8_t* const c8 = reinterpret_cast<const uint8_t*>(coef);
-    const uint8_t* const q8 = reinterpret_cast<const uint8_t*>(qt);
-    if (is_pinned_range(c8, cbytes) && is_pinned_range(q8, qbytes)) {
-        if (q8 == c8 + cbytes) {
-            FM_HIP(hipMemcpyAsync(stage, c8, cbytes + qbytes, hipMemcpyHostToDevice, s));
-        } else {
-            FM_HIP(hipMemcpyAsync(stage, c8, cbytes, hipMemcpyHostToDevice, s));
-            FM_HIP(hipMemcpyAsync(stage + cbytes, q8, qbytes, hipMemcpyHostToDevice, s));
-        }
-    } else {
-        uint8_t*& pinned = ctx->frame_jpeg_pinned[entry];
-        if (!pinned) FM_HIP(hipHostMalloc(&pinned, jpeg_max_coefs(ctx->frame_w, ctx->frame_h) * 2 + qbytes, hipHostMallocDefault));
-        if (reuse && *reuse) FM_HIP(hipEventSynchronize(*reuse));
-        memcpy(pinned, c8, cbytes);
-        memcpy(pinned + cbytes, q8, qbytes);
-        FM_HIP(hipMemcpyAsync(stage, pinned, cbytes + qbytes, hipMemcpyHostToDevice, s));
-        if (reuse) {
-            if (!*reuse) FM_HIP(hipEventCreateWithFlags(reuse, hipEventDisableTiming));
-            FM_HIP(hipEventRecord(*reuse, s));
-        }
-    }
-    fm_trace_mark(ctx, s, 37);                 // (the decode's share of the caller's 30 .. 31 interval)
-    return fm_jpeg_to_bgr(stage, dst, info, s);
-}
-
-extern "C" int fm_frame_upload_jpeg(fm_ctx* ctx, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt) {
-    FM_CHECK_ARG(ctx && ctx->frame_own);
-    FM_CHECK_JPEG(ctx, info, coef, qt);
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    int rc = enqueue_jpeg(ctx, 0, ctx->frame_own, info, coef, qt, nullptr, ctx->s_det);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-extern "C" int fm_frame_upload_ahead_jpeg(fm_ctx* ctx, int k, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH);
-    FM_CHECK_JPEG(ctx, info, coef, qt);
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the KERNELS: a reader
-    // that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.  The JPEG staging
-    // buffers stay with the slot NUMBER at a promote while that event moves with the frame: the device staging needs no
-    // event (copy and kernels of a slot share one stream), the page-locked one has ev_jpeg[k], which stays as well.
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc = enqueue_jpeg(ctx, k, buf, info, coef, qt, &ctx->ev_jpeg[k], cs);
-    if (rc) return rc;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store_jpeg(fm_ctx* ctx, int index, const struct fm_jpeg_info* info, const int16_t* coef, const uint16_t* qt) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size);
-    FM_CHECK_JPEG(ctx, info, coef, qt);
-    uint8_t*& stage = ctx->frame_jpeg[FM_MAX_DET_BATCH + 1];
-    if (!stage) FM_HIP(hipMalloc(&stage, jpeg_stage_bytes(ctx->frame_w, ctx->frame_h)));
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies, then the kernels on the
-    // null stream
-    const size_t cbytes = (size_t)info->coef_count * 2;
-    FM_HIP(hipMemcpy(stage, coef, cbytes, hipMemcpyHostToDevice));
-    FM_HIP(hipMemcpy(stage + cbytes, qt, 3 * 64 * 2, hipMemcpyHostToDevice));
-    int rc = fm_jpeg_to_bgr(stage, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, info, nullptr);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-#undef FM_CHECK_JPEG
-
-// ---- frames at another size than the configured one: the three host-frame entry points for a described source
-// (struct fm_frame_src).  A source of the configured size goes to the counterpart above.  Any other is copied -- and, for
-// NV12 / JPEG, converted by the kernels above -- at ITS size into ctx->frame_src[entry].bgr, and the kernel of
-// resize.hip writes the frame the counterpart would have written.  Same slots, streams, syncs and events as the
-// counterparts; the staging is this path's own and sized by the source.
-static void src_stages_free(fm_ctx::SrcStage* stages, int n) {
-    for (int i = 0; i < n; ++i) {
-        fm_ctx::SrcStage& e = stages[i];
-        if (e.bgr) (void)hipFree(e.bgr);
-        if (e.dev) (void)hipFree(e.dev);
-        if (e.pinned) (void)hipHostFree(e.pinned);
-        if (e.ev) (void)hipEventDestroy(e.ev);
-        e = fm_ctx::SrcStage{};
-    }
-}
-void fm_frame_src_free(fm_ctx* ctx) { src_stages_free(ctx->frame_src, FM_MAX_DET_BATCH + 2); }
-void fm_frame_deep_free(fm_ctx* ctx) { src_stages_free(ctx->frame_deep, FM_MAX_DET_BATCH + 2); }     // (the fm_frame_*_deep calls' staging)
-
-static bool src_ok(const struct fm_frame_src* f) {
-    if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
-    switch (f->kind) {
-    case FM_SRC_BGR: return f->bgr != nullptr;
-    case FM_SRC_NV12:
-        return f->y && f->uv && f->pitch >= f->width && (f->matrix == FM_NV12_BT601 || f->matrix == FM_NV12_BT709) &&
-               !(f->width & 1) && !(f->height & 1);
-    case FM_SRC_JPEG: return f->coef && f->qt && jpeg_layout_ok_size(f->info, f->width, f->height);
-    }
-    return false;
-}
-
-// ---- the correction map (remap.hip): while one is set, every described-source call -- fm_frame_*_src and the planar,
-// packed, Bayer and deep families below -- takes sources of the map's size only, stages them at that size even when it is the
-// configured one, and ends in fm_remap_bgr where it ends in fm_resize_bgr without.
-void fm_frame_remap_free(fm_ctx* ctx) {
-    if (ctx->remap_xy) (void)hipFree(ctx->remap_xy);
-    ctx->remap_xy = nullptr;
-    ctx->remap_sw = ctx->remap_sh = 0;
-    ctx->remap_border = 0;
-}
-
-// the streams whose queued kernels may still read the map: the three the described-source calls launch on
-static int remap_idle(fm_ctx* ctx) {
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-extern "C" int fm_frame_remap_set(fm_ctx* ctx, int src_w, int src_h, const int32_t* xy, const uint8_t border_bgr[3]) {
-    FM_CHECK_ARG(ctx && ctx->frame_own && xy && border_bgr);
-    FM_CHECK_ARG(src_w >= 1 && src_h >= 1 && src_w <= FM_SRC_MAX_DIM && src_h <= FM_SRC_MAX_DIM);
-    const size_t n = (size_t)ctx->frame_w * ctx->frame_h;
-    for (size_t i = 0; i < n; ++i) FM_CHECK_ARG(fm_remap_entry_ok(xy[2 * i], xy[2 * i + 1], src_w, src_h));
-    int rc = remap_idle(ctx);
-    if (rc) return rc;
-    int32_t* dev = nullptr;
-    FM_HIP(hipMalloc(&dev, n * 2 * sizeof(int32_t)));
-    if (hipError_t e = hipMemcpy(dev, xy, n * 2 * sizeof(int32_t), hipMemcpyHostToDevice); e != hipSuccess) {
-        (void)hipFree(dev);
-        FM_HIP(e);
-    }
-    fm_frame_remap_free(ctx);
-    ctx->remap_xy = dev;
-    ctx->remap_sw = src_w, ctx->remap_sh = src_h;
-    ctx->remap_border = (uint32_t)border_bgr[0] | (uint32_t)border_bgr[1] << 8 | (uint32_t)border_bgr[2] << 16;
-    return 0;
-}
-
-extern "C" int fm_frame_remap_clear(fm_ctx* ctx) {
-    FM_CHECK_ARG(ctx);
-    if (!ctx->remap_xy) return 0;
-    int rc = remap_idle(ctx);
-    if (rc) return rc;
-    fm_frame_remap_free(ctx);
-    return 0;
-}
-
-// a w x h source is one the described-source calls take now: any without a map, the map's size with one
-static bool remap_takes(const fm_ctx* ctx, int w, int h) { return !ctx->remap_xy || (w == ctx->remap_sw && h == ctx->remap_sh); }
-
-// a w x h source needs no kernel of the tail below: it has the configured size and no map is set
-static bool src_on_size(const fm_ctx* ctx, int w, int h) { return !ctx->remap_xy && w == ctx->frame_w && h == ctx->frame_h; }
-static bool src_on_size(const fm_ctx* ctx, const struct fm_frame_src* f) { return src_on_size(ctx, f->width, f->height); }
-
-// The last kernel of every described-source route: the source-size BGR frame `bgr` (w x h, + FM_FRAME_SLACK) into the
-// configured-size frame `dst` on `s` -- through the correction map when one is set, resized otherwise.
-static int enqueue_src_tail(fm_ctx* ctx, const uint8_t* bgr, int w, int h, uint8_t* dst, hipStream_t s) {
-    fm_trace_mark(ctx, s, 38);                 // (the resize's / remap's share of the caller's 30 .. 31 interval)
-    if (ctx->remap_xy) return fm_remap_bgr(bgr, w, h, ctx->remap_xy, dst, ctx->frame_w, ctx->frame_h, ctx->remap_border, s);
-    return fm_resize_bgr(bgr, w, h, dst, ctx->frame_w, ctx->frame_h, s);
-}
-
-// at least `bytes` at p; a buffer that has to grow is given up once `s`, the stream whose copies and kernels use it, is idle
-static int src_reserve(uint8_t*& p, size_t& cap, size_t bytes, bool host, hipStream_t s) {
-    if (bytes <= cap) return 0;
-    if (p) {
-        FM_HIP(hipStreamSynchronize(s));
-        if (host) (void)hipHostFree(p); else (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    if (host) FM_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    else FM_HIP(hipMalloc(&p, bytes));
-    cap = bytes;
-    return 0;
-}
-
-// page-locked staging of `bytes` for the entry, free to be written: the previous H2D copy out of it is done
-static int src_pinned(fm_ctx::SrcStage& st, size_t bytes, hipStream_t s) {
-    int rc = src_reserve(st.pinned, st.pinned_cap, bytes, true, s);
-    if (rc) return rc;
-    if (st.ev) FM_HIP(hipEventSynchronize(st.ev));
-    return 0;
-}
-static int src_pinned_copied(fm_ctx::SrcStage& st, hipStream_t s) {
-    if (!st.ev) FM_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(st.ev, s));
-    return 0;
-}
-
-// The off-size source `f` (checked by the caller) into the entry's source-resolution buffers and, resized, into `dst`:
-// copies and kernels on `s`; `blocking`: blocking copies from where the source lies (fm_frame_ring_store_src).
-static int enqueue_src(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_src* f, hipStream_t s, bool blocking) {
-    fm_ctx::SrcStage& st = ctx->frame_src[entry];
-    const int w = f->width, h = f->height;
-    const size_t npx = (size_t)w * h;
-    int rc = src_reserve(st.bgr, st.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s);     // (resize.hip reads 8 bytes at a pixel)
-    if (rc) return rc;
-    if (f->kind == FM_SRC_BGR) {
-        if (blocking) {
-            FM_HIP(hipMemcpy(st.bgr, f->bgr, npx * 3, hipMemcpyHostToDevice));
-        } else if (is_pinned_range(f->bgr, npx * 3)) {
-            FM_HIP(hipMemcpyAsync(st.bgr, f->bgr, npx * 3, hipMemcpyHostToDevice, s));
-        } else {
-            if ((rc = src_pinned(st, npx * 3, s))) return rc;
-            memcpy(st.pinned, f->bgr, npx * 3);
-            FM_HIP(hipMemcpyAsync(st.bgr, st.pinned, npx * 3, hipMemcpyHostToDevice, s));
-            if ((rc = src_pinned_copied(st, s))) return rc;
-        }
-    } else if (f->kind == FM_SRC_NV12) {
-        const size_t nbytes = npx + npx / 2;
-        if ((rc = src_reserve(st.dev, st.dev_cap, nbytes, false, s))) return rc;
-        if (blocking) {
-            FM_HIP(hipMemcpy2D(st.dev, w, f->y, f->pitch, w, h, hipMemcpyHostToDevice));
-            FM_HIP(hipMemcpy2D(st.dev + npx, w, f->uv, f->pitch, w, h / 2, hipMemcpyHostToDevice));
-        } else if (f->pitch == w && is_pinned_range(f->y, npx) && is_pinned_range(f->uv, npx / 2)) {
-            FM_HIP(hipMemcpyAsync(st.dev, f->y, npx, hipMemcpyHostToDevice, s));
-            FM_HIP(hipMemcpyAsync(st.dev + npx, f->uv, npx / 2, hipMemcpyHostToDevice, s));
-        } else {
-            if ((rc = src_pinned(st, nbytes, s))) return rc;
-            for (int r = 0; r < h; ++r) memcpy(st.pinned + (size_t)r * w, f->y + (size_t)r * f->pitch, w);
-            for (int r = 0; r < h / 2; ++r) memcpy(st.pinned + npx + (size_t)r * w, f->uv + (size_t)r * f->pitch, w);
-            FM_HIP(hipMemcpyAsync(st.dev, st.pinned, nbytes, hipMemcpyHostToDevice, s));
-            if ((rc = src_pinned_copied(st, s))) return rc;
-        }
-        fm_trace_mark(ctx, s, 36);
-        if ((rc = fm_nv12_to_bgr(st.dev, st.bgr, w, h, f->matrix, s))) return rc;
-    } else {
-        const size_t cbytes = (size_t)f->info->coef_count * 2, qbytes = 3 * 64 * 2;
-        if ((rc = src_reserve(st.dev, st.dev_cap, jpeg_stage_bytes(w, h), false, s))) return rc;
-        const uint8_t* const c8 = reinterpret_cast<const uint8_t*>(f->coef);
-        const uint8_t* const q8 = reinterpret_cast<const uint8_t*>(f->qt);
-        if (blocking) {
-            FM_HIP(hipMemcpy(st.dev, c8, cbytes, hipMemcpyHostToDevice));
-            FM_HIP(hipMemcpy(st.dev + cbytes, q8, qbytes, hipMemcpyHostToDevice));
-        } else if (is_pinned_range(c8, cbytes) && is_pinned_range(q8, qbytes)) {
-            FM_HIP(hipMemcpyAsync(st.dev, c8, cbytes, hipMemcpyHostToDevice, s));
-            FM_HIP(hipMemcpyAsync(st.dev + cbytes, q8, qbytes, hipMemcpyHostToDevice, s));
-        } else {
-            if ((rc = src_pinned(st, jpeg_max_coefs(w, h) * 2 + qbytes, s))) return rc;
-            memcpy(st.pinned, c8, cbytes);
-            memcpy(st.pinned + cbytes, q8, qbytes);
-            FM_HIP(hipMemcpyAsync(st.dev, st.pinned, cbytes + qbytes, hipMemcpyHostToDevice, s));
-            if ((rc = src_pinned_copied(st, s))) return rc;
-        }
-        fm_trace_mark(ctx, s, 37);
-        if ((rc = fm_jpeg_to_bgr(st.dev, st.bgr, f->info, s))) return rc;
-    }
-    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
-}
-
-extern "C" int fm_frame_upload_src(fm_ctx* ctx, const struct fm_frame_src* src) {
-    FM_CHECK_ARG(ctx && ctx->frame_own && src_ok(src));
-    FM_CHECK_ARG(remap_takes(ctx, src->width, src->height));      // (a correction map is for one source size)
-    if (src_on_size(ctx, src)) {
-        if (src->kind == FM_SRC_BGR) return fm_frame_upload(ctx, src->bgr);
-        if (src->kind == FM_SRC_NV12) return fm_frame_upload_nv12(ctx, src->y, src->uv, src->pitch, src->matrix);
-        return fm_frame_upload_jpeg(ctx, src->info, src->coef, src->qt);
-    }
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    int rc = enqueue_src(ctx, 0, ctx->frame_own, src, ctx->s_det, false);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-extern "C" int fm_frame_upload_ahead_src(fm_ctx* ctx, int k, const struct fm_frame_src* src) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && src_ok(src));
-    FM_CHECK_ARG(remap_takes(ctx, src->width, src->height));      // (a correction map is for one source size)
-    if (src_on_size(ctx, src)) {
-        if (src->kind == FM_SRC_BGR) return fm_frame_upload_ahead(ctx, k, src->bgr);
-        if (src->kind == FM_SRC_NV12) return fm_frame_upload_ahead_nv12(ctx, k, src->y, src->uv, src->pitch, src->matrix);
-        return fm_frame_upload_ahead_jpeg(ctx, k, src->info, src->coef, src->qt);
-    }
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the LAST kernel, the
-    // resize: a reader that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.  The
-    // source staging stays with the slot NUMBER at a promote while that event moves with the frame: the device buffers
-    // need no event (copies and kernels of a slot share one stream), the page-locked one has its own.
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc = enqueue_src(ctx, k, buf, src, cs, false);
-    if (rc) return rc;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store_src(fm_ctx* ctx, int index, const struct fm_frame_src* src) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && src_ok(src));
-    FM_CHECK_ARG(remap_takes(ctx, src->width, src->height));      // (a correction map is for one source size)
-    if (src_on_size(ctx, src)) {
-        if (src->kind == FM_SRC_BGR) return fm_frame_ring_store(ctx, index, src->bgr);
-        if (src->kind == FM_SRC_NV12) return fm_frame_ring_store_nv12(ctx, index, src->y, src->uv, src->pitch, src->matrix);
-        return fm_frame_ring_store_jpeg(ctx, index, src->info, src->coef, src->qt);
-    }
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies, then the kernels on the
-    // null stream
-    int rc = enqueue_src(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, src, nullptr, true);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-// ---- planar YCbCr ingest (struct fm_frame_planar: what software decoders hand out, and a YUV4MPEG2 frame): the three
-// host-frame entry points once more.  Same slots, streams, syncs and events as their BGR counterparts.  A frame of the
-// configured size goes through ctx->frame_planar[entry] and the kernel of yuv.hip writes the BGR frame; a frame of any
-// other size takes the route of fm_frame_*_src with that path's buffers (ctx->frame_src[entry]): yuv.hip writes the
-// source-size BGR frame, resize.hip the frame.
-static bool planar_ok(const struct fm_frame_planar* f) {
-    if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
-    int cw = 0, ch = 0;
-    if (!fm_yuv_chroma_dims(f->width, f->height, f->chroma, &cw, &ch)) return false;
-    if (f->matrix != FM_NV12_BT601 && f->matrix != FM_NV12_BT709) return false;
-    if (!f->y || f->pitch_y < f->width) return false;
-    return f->chroma == FM_YUV_MONO || (f->u && f->v && f->pitch_c >= cw);
-}
-
-// H2D copy of the planes, rows packed to their width, into device staging, the conversion and -- off size -- the resize
-// into `dst`, all on `s`.  On size: planes that cannot be copied from where they are go through `pinned` (the slot's
-// BGR-sized staging) after `reuse`, the event behind the previous copy out of it, when one is given.  `blocking`:
-// blocking copies from where the planes lie (fm_frame_ring_store_planar).
-static int enqueue_planar(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_planar* f, uint8_t* pinned, hipEvent_t reuse,
-                          hipStream_t s, bool blocking) {
-    const int w = f->width, h = f->height;
-    int cw = 0, ch = 0;
-    fm_yuv_chroma_dims(w, h, f->chroma, &cw, &ch);
-    const size_t npx = (size_t)w * h, nc = (size_t)cw * ch, total = npx + 2 * nc;
-    const bool on_size = src_on_size(ctx, w, h);
-    fm_ctx::SrcStage& st = ctx->frame_src[entry];
-    uint8_t* stage = nullptr;
-    int rc;
-    if (on_size) {
-        uint8_t*& p = ctx->frame_planar[entry];
-        if (!p) FM_HIP(hipMalloc(&p, npx * 3));
-        stage = p;
-    } else {
-        if ((rc = src_reserve(st.bgr, st.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s))) return rc;     // (resize.hip reads 8 bytes at a pixel)
-        if ((rc = src_reserve(st.dev, st.dev_cap, total, false, s))) return rc;
-        stage = st.dev;
-    }
-    const bool one_surface = f->pitch_y == w && (!nc || (f->pitch_c == cw && f->u == f->y + npx && f->v == f->u + nc));
-    if (blocking) {
-        FM_HIP(hipMemcpy2D(stage, w, f->y, f->pitch_y, w, h, hipMemcpyHostToDevice));
-        if (nc) {
-            FM_HIP(hipMemcpy2D(stage + npx, cw, f->u, f->pitch_c, cw, ch, hipMemcpyHostToDevice));
-            FM_HIP(hipMemcpy2D(stage + npx + nc, cw, f->v, f->pitch_c, cw, ch, hipMemcpyHostToDevice));
-        }
-    } else if (one_surface && is_pinned_range(f->y, total)) {
-        FM_HIP(hipMemcpyAsync(stage, f->y, total, hipMemcpyHostToDevice, s));
-    } else {
-        uint8_t* pin = pinned;
-        if (on_size) {
-            if (reuse) FM_HIP(hipEventSynchronize(reuse));
-        } else {
-            if ((rc = src_pinned(st, total, s))) return rc;
-            pin = st.pinned;
-        }
-        for (int r = 0; r < h; ++r) memcpy(pin + (size_t)r * w, f->y + (size_t)r * f->pitch_y, w);
-        for (int r = 0; r < ch; ++r) {
-            memcpy(pin + npx + (size_t)r * cw, f->u + (size_t)r * f->pitch_c, cw);
-            memcpy(pin + npx + nc + (size_t)r * cw, f->v + (size_t)r * f->pitch_c, cw);
-        }
-        FM_HIP(hipMemcpyAsync(stage, pin, total, hipMemcpyHostToDevice, s));
-        if (!on_size && (rc = src_pinned_copied(st, s))) return rc;
-    }
-    fm_trace_mark(ctx, s, 39);                 // (the conversion's share of the caller's 30 .. 31 interval)
-    if (on_size) return fm_planar_to_bgr(stage, dst, w, h, f->chroma, f->matrix, s);
-    if ((rc = fm_planar_to_bgr(stage, st.bgr, w, h, f->chroma, f->matrix, s))) return rc;
-    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
-}
-
-extern "C" int fm_frame_upload_planar(fm_ctx* ctx, const struct fm_frame_planar* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own && planar_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    int rc = enqueue_planar(ctx, 0, ctx->frame_own, f, ctx->frame_pinned, nullptr, ctx->s_det, false);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-extern "C" int fm_frame_upload_ahead_planar(fm_ctx* ctx, int k, const struct fm_frame_planar* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && planar_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (the BGR-sized staging holds every planar layout)
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the LAST kernel: a reader
-    // that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc = enqueue_planar(ctx, k, buf, f, ahead_pinned(ctx, k), ev, cs, false);
-    if (rc) return rc;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store_planar(fm_ctx* ctx, int index, const struct fm_frame_planar* f) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && planar_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies that pack the rows, then
-    // the kernels on the null stream
-    int rc = enqueue_planar(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr,
-                            nullptr, nullptr, true);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-// ---- packed 4:2:2 / RGB ingest (struct fm_frame_packed: what UVC / V4L2 cameras, capture cards, image libraries and
-// `appsink` hand out): the three host-frame entry points once more, mirroring the planar ones above.  Same slots,
-// streams, syncs and events as their BGR counterparts.  A frame of the configured size goes through
-// ctx->frame_packed[entry] and a kernel of packed.hip writes the BGR frame; a frame of any other size takes the route
-// of fm_frame_*_src with that path's buffers (ctx->frame_src[entry]): packed.hip writes the source-size BGR frame,
-// resize.hip the frame.  Rows that cannot be copied from where they lie are packed into ctx->frame_src[entry].pinned
-// for both sizes (the slots' own page-locked buffers hold 3 bytes per pixel; BGRx has 4).
-static bool packed_ok(const struct fm_frame_packed* f) {
-    if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
-    const size_t rb = fm_packed_row_bytes(f->width, f->format);
-    return rb && fm_packed_matrix_ok(f->matrix) && f->data && f->pitch > 0 && (size_t)f->pitch >= rb;
-}
-
-// H2D copy of the rows, packed to their byte width, into device staging, the conversion and -- off size -- the resize
-// into `dst`, all on `s`.  `blocking`: blocking copies from where the rows lie (fm_frame_ring_store_packed).
-static int enqueue_packed(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_packed* f, hipStream_t s, bool blocking) {
-    const int w = f->width, h = f->height;
-    const size_t rb = fm_packed_row_bytes(w, f->format), total = rb * h, npx = (size_t)w * h;
-    const bool on_size = src_on_size(ctx, w, h);
-    fm_ctx::SrcStage& st = ctx->frame_src[entry];
-    uint8_t* stage = nullptr;
-    int rc;
-    if (on_size) {
-        uint8_t*& p = ctx->frame_packed[entry];
-        if (!p) FM_HIP(hipMalloc(&p, npx * 4));            // (4 * ceil(w / 2) <= 4 w: every layout fits)
-        stage = p;
-    } else {
-        if ((rc = src_reserve(st.bgr, st.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s))) return rc;     // (resize.hip reads 8 bytes at a pixel)
-        if ((rc = src_reserve(st.dev, st.dev_cap, total, false, s))) return rc;
-        stage = st.dev;
-    }
-    if (blocking) {
-        FM_HIP(hipMemcpy2D(stage, rb, f->data, f->pitch, rb, h, hipMemcpyHostToDevice));
-    } else if ((size_t)f->pitch == rb && is_pinned_range(f->data, total)) {
-        FM_HIP(hipMemcpyAsync(stage, f->data, total, hipMemcpyHostToDevice, s));
-    } else {
-        if ((rc = src_pinned(st, total, s))) return rc;
-        for (int r = 0; r < h; ++r) memcpy(st.pinned + (size_t)r * rb, f->data + (size_t)r * f->pitch, rb);
-        FM_HIP(hipMemcpyAsync(stage, st.pinned, total, hipMemcpyHostToDevice, s));
-        if ((rc = src_pinned_copied(st, s))) return rc;
-    }
-    fm_trace_mark(ctx, s, 48);                 // (the conversion's share of the caller's 30 .. 31 interval)
-    if (on_size) return fm_packed_to_bgr(stage, dst, w, h, f->format, f->matrix, s);
-    if ((rc = fm_packed_to_bgr(stage, st.bgr, w, h, f->format, f->matrix, s))) return rc;
-    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
-}
-
-extern "C" int fm_frame_upload_packed(fm_ctx* ctx, const struct fm_frame_packed* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own && packed_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    int rc = enqueue_packed(ctx, 0, ctx->frame_own, f, ctx->s_det, false);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-extern "C" int fm_frame_upload_ahead_packed(fm_ctx* ctx, int k, const struct fm_frame_packed* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && packed_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // stream and order of calls: see fm_frame_upload_ahead.  The slot's event is recorded behind the LAST kernel: a reader
-    // that waits for it (the detector pass, fm_frame_promote_next) finds the BGR frame complete.  The staging stays with
-    // the slot NUMBER at a promote while that event moves with the frame: the device buffers need no event (copy and
-    // kernels of a slot share one stream), the page-locked one has its own.
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc = enqueue_packed(ctx, k, buf, f, cs, false);
-    if (rc) return rc;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store_packed(fm_ctx* ctx, int index, const struct fm_frame_packed* f) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && packed_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): a blocking copy that packs the rows, then
-    // the kernels on the null stream
-    int rc = enqueue_packed(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-// ---- Bayer ingest (struct fm_frame_bayer: the raw mosaic of an industrial or embedded camera): the three host-frame
-// entry points once more, mirroring the packed ones above.  Same slots, streams, syncs and events as their BGR
-// counterparts.  A frame of the configured size goes through ctx->frame_bayer[entry] and the kernel of bayer.hip writes
-// the BGR frame; a frame of any other size takes the route of fm_frame_*_src with that path's buffers
-// (ctx->frame_src[entry]): bayer.hip writes the source-size BGR frame, resize.hip the frame.  Rows that cannot be copied
-// from where they lie are packed into ctx->frame_src[entry].pinned for both sizes, as packed frames' are.
-static bool bayer_ok(const struct fm_frame_bayer* f) {
-    if (!f || f->width < 2 || f->height < 2 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
-    const int bps = fm_bayer_sample_bytes(f->depth);
-    if (!bps || f->pattern < FM_BAYER_RGGB || f->pattern > FM_BAYER_BGGR) return false;
-    if (f->method != FM_BAYER_BILINEAR && f->method != FM_BAYER_MHC) return false;
-    if (f->black < 0 || f->black >= (1 << f->depth)) return false;
-    if (!fm_bayer_gain_ok(f->gain_r) || !fm_bayer_gain_ok(f->gain_g) || !fm_bayer_gain_ok(f->gain_b)) return false;
-    return f->data && f->pitch > 0 && (size_t)f->pitch >= (size_t)f->width * bps;
-}
-
-// H2D copy of the rows, packed to their byte width, into device staging, the demosaicing and -- off size -- the resize
-// into `dst`, all on `s`.  `blocking`: blocking copies from where the rows lie (fm_frame_ring_store_bayer).
-static int enqueue_bayer(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_bayer* f, hipStream_t s, bool blocking) {
-    const int w = f->width, h = f->height;
-    const size_t rb = (size_t)w * fm_bayer_sample_bytes(f->depth), total = rb * h, npx = (size_t)w * h;
-    const bool on_size = src_on_size(ctx, w, h);
-    fm_ctx::SrcStage& st = ctx->frame_src[entry];
-    uint8_t* stage = nullptr;
-    int rc;
-    if (on_size) {
-        uint8_t*& p = ctx->frame_bayer[entry];
-        if (!p) FM_HIP(hipMalloc(&p, npx * 2));            // (16-bit samples: every depth fits)
-        stage = p;
-    } else {
-        if ((rc = src_reserve(st.bgr, st.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s))) return rc;     // (resize.hip reads 8 bytes at a pixel)
-        if ((rc = src_reserve(st.dev, st.dev_cap, total, false, s))) return rc;
-        stage = st.dev;
-    }
-    if (blocking) {
-        FM_HIP(hipMemcpy2D(stage, rb, f->data, f->pitch, rb, h, hipMemcpyHostToDevice));
-    } else if ((size_t)f->pitch == rb && is_pinned_range(f->data, total)) {
-        FM_HIP(hipMemcpyAsync(stage, f->data, total, hipMemcpyHostToDevice, s));
-    } else {
-        if ((rc = src_pinned(st, total, s))) return rc;
-        for (int r = 0; r < h; ++r) memcpy(st.pinned + (size_t)r * rb, f->data + (size_t)r * f->pitch, rb);
-        FM_HIP(hipMemcpyAsync(stage, st.pinned, total, hipMemcpyHostToDevice, s));
-        if ((rc = src_pinned_copied(st, s))) return rc;
-    }
-    fm_trace_mark(ctx, s, 49);                 // (the demosaicing's share of the caller's 30 .. 31 interval)
-    uint8_t* const out = on_size ? dst : st.bgr;
-    if ((rc = fm_bayer_to_bgr(stage, out, w, h, f->pattern, f->depth, f->method, f->black, f->gain_r, f->gain_g, f->gain_b, s))) return rc;
-    if (on_size) return 0;
-    return enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
-}
-
-extern "C" int fm_frame_upload_bayer(fm_ctx* ctx, const struct fm_frame_bayer* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own && bayer_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    int rc = enqueue_bayer(ctx, 0, ctx->frame_own, f, ctx->s_det, false);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-extern "C" int fm_frame_upload_ahead_bayer(fm_ctx* ctx, int k, const struct fm_frame_bayer* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && bayer_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // stream, order of calls, event and staging: see fm_frame_upload_ahead_packed
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc = enqueue_bayer(ctx, k, buf, f, cs, false);
-    if (rc) return rc;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store_bayer(fm_ctx* ctx, int index, const struct fm_frame_bayer* f) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && bayer_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): a blocking copy that packs the rows, then
-    // the kernels on the null stream
-    int rc = enqueue_bayer(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-// ---- deep YCbCr ingest (struct fm_frame_deep: 9- to 16-bit samples in 16-bit words, planar as a software decoder or a
-// Y4M C420p10 frame holds them, semi-planar as a hardware decoder's P010 / P016 surface): the three host-frame entry
-// points once more, mirroring the planar ones above.  Same slots, streams, syncs and events as their BGR counterparts.
-// The staging is this family's own for every size, ctx->frame_deep[entry].dev and .pinned, grown by src_reserve /
-// src_pinned with their reuse ordering: a frame is up to 6 bytes per pixel, and the slots' device and page-locked
-// buffers hold 3.  The kernel of deep.hip writes the BGR frame; for a frame of another size than the configured one it
-// writes ctx->frame_src[entry].bgr and resize.hip (remap.hip) the frame, the route of fm_frame_*_src.
-static bool deep_ok(const struct fm_frame_deep* f) {
-    if (!f || f->width < 1 || f->height < 1 || f->width > FM_SRC_MAX_DIM || f->height > FM_SRC_MAX_DIM) return false;
-    if (!fm_deep_layout_ok(f->width, f->height, f->chroma, f->matrix, f->depth, f->layout)) return false;
-    int cw = 0, ch = 0;
-    fm_yuv_chroma_dims(f->width, f->height, f->chroma, &cw, &ch);
-    if (!f->y || f->pitch_y % 2 || f->pitch_y < 2 * f->width) return false;
-    if (f->chroma == FM_YUV_MONO) return true;
-    if (f->layout == FM_DEEP_SEMIPLANAR) cw = f->width;        // (U, V pairs: width words a row)
-    return f->u && (f->v || f->layout == FM_DEEP_SEMIPLANAR) && f->pitch_c % 2 == 0 && f->pitch_c >= 2 * cw;
-}
-
-// H2D copy of the planes, rows packed to their width, into the entry's device staging, the conversion and -- off size --
-// the resize into `dst`, all on `s`.  `blocking`: blocking copies from where the planes lie (fm_frame_ring_store_deep).
-static int enqueue_deep(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_deep* f, hipStream_t s, bool blocking) {
-    const int w = f->width, h = f->height;
-    const bool semi = f->layout == FM_DEEP_SEMIPLANAR;
-    int cw = 0, ch = 0;
-    fm_yuv_chroma_dims(w, h, f->chroma, &cw, &ch);
-    // the chroma planes as byte rows: two (U, V) of 2 cw bytes for planar, one (UV) of 2 w bytes for semi-planar
-    const int nplanes = !ch ? 0 : semi ? 1 : 2;
-    const size_t yrow = (size_t)w * 2, crow = semi ? yrow : (size_t)cw * 2;
-    const size_t ybytes = yrow * h, cbytes = crow * ch, total = ybytes + nplanes * cbytes, npx = (size_t)w * h;
-    const uint8_t* const cplane[2] = {f->u, f->v};
-    const bool on_size = src_on_size(ctx, w, h);
-    fm_ctx::SrcStage& st = ctx->frame_deep[entry];
-    fm_ctx::SrcStage& off = ctx->frame_src[entry];
-    int rc;
-    if (!on_size && (rc = src_reserve(off.bgr, off.bgr_cap, npx * 3 + FM_FRAME_SLACK, false, s))) return rc;     // (resize.hip reads 8 bytes at a pixel)
-    if ((rc = src_reserve(st.dev, st.dev_cap, total, false, s))) return rc;
-    bool one_surface = (size_t)f->pitch_y == yrow && (!nplanes || ((size_t)f->pitch_c == crow && f->u == f->y + ybytes));
-    if (nplanes == 2) one_surface = one_surface && f->v == f->u + cbytes;
-    if (blocking) {
-        FM_HIP(hipMemcpy2D(st.dev, yrow, f->y, f->pitch_y, yrow, h, hipMemcpyHostToDevice));
-        for (int p = 0; p < nplanes; ++p)
-            FM_HIP(hipMemcpy2D(st.dev + ybytes + p * cbytes, crow, cplane[p], f->pitch_c, crow, ch, hipMemcpyHostToDevice));
-    } else if (one_surface && is_pinned_range(f->y, total)) {
-        FM_HIP(hipMemcpyAsync(st.dev, f->y, total, hipMemcpyHostToDevice, s));
-    } else {
-        if ((rc = src_pinned(st, total, s))) return rc;
-        for (int r = 0; r < h; ++r) memcpy(st.pinned + (size_t)r * yrow, f->y + (size_t)r * f->pitch_y, yrow);
-        for (int p = 0; p < nplanes; ++p)
-            for (int r = 0; r < ch; ++r)
-                memcpy(st.pinned + ybytes + p * cbytes + (size_t)r * crow, cplane[p] + (size_t)r * f->pitch_c, crow);
-        FM_HIP(hipMemcpyAsync(st.dev, st.pinned, total, hipMemcpyHostToDevice, s));
-        if ((rc = src_pinned_copied(st, s))) return rc;
-    }
-    fm_trace_mark(ctx, s, 58);                 // (the conversion's share of the caller's 30 .. 31 interval)
-    uint8_t* const out = on_size ? dst : off.bgr;
-    if ((rc = fm_deep_to_bgr(st.dev, out, w, h, f->chroma, f->matrix, f->depth, f->layout, s))) return rc;
-    if (on_size) return 0;
-    return enqueue_src_tail(ctx, off.bgr, w, h, dst, s);
-}
-
-// replaces the host narrowing + conversion of a Main10 decoder's / a 10-bit Y4M file's frames (see fm_frame_deep)
-extern "C" int fm_frame_upload_deep(fm_ctx* ctx, const struct fm_frame_deep* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own && deep_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    int rc = enqueue_deep(ctx, 0, ctx->frame_own, f, ctx->s_det, false);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-// the same for the frame of a step ahead (fm_frame_upload_ahead's role for deep frames)
-extern "C" int fm_frame_upload_ahead_deep(fm_ctx* ctx, int k, const struct fm_frame_deep* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && deep_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // stream, order of calls, event and staging: see fm_frame_upload_ahead_packed
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    int rc = enqueue_deep(ctx, k, buf, f, cs, false);
-    if (rc) return rc;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-// the same into ring entry `index` (fm_frame_ring_store's role for deep frames)
-extern "C" int fm_frame_ring_store_deep(fm_ctx* ctx, int index, const struct fm_frame_deep* f) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && deep_ok(f));
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): blocking copies that pack the rows, then
-    // the kernels on the null stream
-    int rc = enqueue_deep(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, true);
-    if (rc) return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-// ---- frames that lie in device memory already (struct fm_frame_device: a decoder's surface, a torch / CuPy tensor, another
-// model's output): the three entry points once more, mirroring the packed ones above.  Same slots, streams, syncs, slot
-// events and flush_post, the same remap_takes check -- and no copy: a kernel of devsrc.hip reads the caller's memory and
-// writes the BGR frame, straight into `dst` on size, into ctx->frame_src[entry].bgr (and enqueue_src_tail from there)
-// off size.  What is new here is that the memory is somebody else's: every plane is checked against what the runtime
-// knows about its pointer before anything is enqueued, the slot's stream is ordered behind the producer's, and a
-// look-ahead call leaves an event behind the conversion kernel -- the last reader of the caller's memory -- for
-// fm_frame_device_done.
-
-// `f` passes fm_frame_device_check and every plane of it is device memory of the context's device, its whole extent --
-// where the runtime knows the allocation -- inside that allocation.  Nothing is enqueued.
-static int device_ok(const fm_ctx* ctx, const struct fm_frame_device* f) {
-    int rc = fm_frame_device_check(f);
-    if (rc) return rc;
-    const size_t rb = fm_dev_row_bytes(f);
-    for (int p = 0; p < fm_dev_planes(f->layout); ++p) {
-        const uint8_t* const base = static_cast<const uint8_t*>(f->plane[p]);
-        const size_t extent = (size_t)f->pitch[p] * (fm_dev_plane_rows(f, p) - 1) + rb;
-        hipPointerAttribute_t attr{};
-        const hipError_t e = hipPointerGetAttributes(&attr, base);
-        if (e != hipSuccess) (void)hipGetLastError();          // (a pointer the runtime has never seen is no sticky error)
-        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.isManaged || attr.device != ctx->device) {
-            fm_set_error("%s:%d bad argument: plane %d of the device frame (%p) is not device memory of device %d -- host, page-locked, "
-                         "managed and other-device frames go through the host calls: fm_frame_upload, _nv12, _planar, _packed, _bayer, "
-                         "_deep or _src", __FILE__, __LINE__, p, (const void*)base, ctx->device);
-            return FM_ERR_ARG;
-        }
-        hipDeviceptr_t abase = nullptr;
-        size_t asize = 0;
-        if (hipMemGetAddressRange(&abase, &asize, (hipDeviceptr_t)base) == hipSuccess) {
-            const uint8_t* const a0 = static_cast<const uint8_t*>(abase);
-            if (base < a0 || extent > asize || (size_t)(base - a0) > asize - extent) {
-                fm_set_error("%s:%d bad argument: plane %d of the device frame (%zu bytes from %p) runs past its allocation (%zu bytes from %p)",
-                             __FILE__, __LINE__, p, extent, (const void*)base, asize, (const void*)a0);
-                return FM_ERR_ARG;
-            }
-        } else {
-            (void)hipGetLastError();                           // (virtual-memory allocators: the attributes alone decide)
-        }
-    }
-    return 0;
-}
-
-// a wait for `ev` on `s` -- unless the host already sees it complete: a barrier packet that is not enqueued does not
-// park on a shared hardware queue (the rule of fm_frame_promote_next and acquire_slots)
-static int wait_unless_complete(hipStream_t s, hipEvent_t ev) {
-    if (hipEventQuery(ev) != hipSuccess) {
-        (void)hipGetLastError();                               // (hipErrorNotReady is not an error)
-        FM_HIP(hipStreamWaitEvent(s, ev, 0));
-    }
-    return 0;
-}
-
-// The conversion of the device frame `f` (device_ok) and -- off size -- the resize into `dst`, on `s`, behind the
-// producer's stream; `consumed`, when given, is recorded behind the conversion kernel.
-static int enqueue_device(fm_ctx* ctx, int entry, uint8_t* dst, const struct fm_frame_device* f, hipStream_t s, hipEvent_t consumed) {
-    const int w = f->width, h = f->height;
-    const bool on_size = src_on_size(ctx, w, h);
-    fm_ctx::SrcStage& st = ctx->frame_src[entry];
-    int rc;
-    if (!on_size && (rc = src_reserve(st.bgr, st.bgr_cap, (size_t)w * h * 3 + FM_FRAME_SLACK, false, s))) return rc;   // (resize.hip reads 8 bytes at a pixel)
-    if (!(f->flags & FM_DEV_READY)) {
-        hipEvent_t& in = ctx->ev_dev_in[entry];
-        if (!in) FM_HIP(hipEventCreateWithFlags(&in, hipEventDisableTiming));
-        FM_HIP(hipEventRecord(in, static_cast<hipStream_t>(f->stream)));
-        if ((rc = wait_unless_complete(s, in))) return rc;
-    }
-    fm_trace_mark(ctx, s, 59);                 // (the conversion's share of the caller's 30 .. 31 interval)
-    if ((rc = fm_device_to_bgr(f, on_size ? dst : st.bgr, s))) return rc;
-    fm_trace_mark(ctx, s, 60);                 // (59 .. 60: the kernel without the event record behind it)
-    if (consumed) FM_HIP(hipEventRecord(consumed, s));
-    return on_size ? 0 : enqueue_src_tail(ctx, st.bgr, w, h, dst, s);
-}
-
-extern "C" int fm_frame_upload_device(fm_ctx* ctx, const struct fm_frame_device* f) {
-    FM_CHECK_ARG(ctx && ctx->frame_own && f);
-    int rc = device_ok(ctx, f);
-    if (rc) return rc;
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // every consumer of the previous frame must be done before it is overwritten (fm_frame_upload)
-    FM_HIP(hipStreamSynchronize(ctx->s_det));
-    FM_HIP(hipStreamSynchronize(ctx->s_ext));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow));
-    FM_HIP(hipStreamSynchronize(ctx->s_flow2));
-    if ((rc = enqueue_device(ctx, 0, ctx->frame_own, f, ctx->s_det, nullptr))) return rc;
-    FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too; the caller's memory has been read
-    ctx->frame_cur = ctx->frame_own;
-    return 0;
-}
-
-extern "C" int fm_frame_upload_ahead_device(fm_ctx* ctx, int k, const struct fm_frame_device* f, uint64_t* ticket) {
-    FM_CHECK_ARG(ctx && ctx->frame_own2 && k >= 1 && k <= FM_MAX_DET_BATCH && f);
-    int rc = device_ok(ctx, f);
-    if (rc) return rc;
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    const size_t bytes = (size_t)ctx->frame_w * ctx->frame_h * 3;
-    if (!ahead_buf(ctx, k)) {       // slots k >= 2: on first use (with the staging a later plain upload into the slot expects)
-        FM_HIP(hipMalloc(&ahead_buf(ctx, k), bytes + FM_FRAME_SLACK));
-        FM_HIP(hipHostMalloc(&ahead_pinned(ctx, k), bytes, hipHostMallocDefault));
-    }
-    uint8_t* const buf = ahead_buf(ctx, k);
-    hipEvent_t& ev = ahead_event(ctx, k);
-    // the ticket's place in the ring: whoever held it before is consumed before it is given away
-    const uint64_t t = ctx->dev_ticket_next;
-    fm_ctx::DevTicket& place = ctx->dev_ticket[t % FM_DEV_TICKETS];
-    if (!place.ev) FM_HIP(hipEventCreateWithFlags(&place.ev, hipEventDisableTiming));
-    else if (place.ticket) FM_HIP(hipEventSynchronize(place.ev));
-    // stream, order of calls and slot event: see fm_frame_upload_ahead_packed
-    hipStream_t cs = ctx->s_ext;
-    fm_trace_mark(ctx, cs, 30);
-    if ((rc = enqueue_device(ctx, k, buf, f, cs, place.ev))) return rc;
-    place.ticket = t;
-    ctx->dev_ticket_next = t + 1;
-    if (ticket) *ticket = t;
-    fm_trace_mark(ctx, cs, 31);
-    if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    FM_HIP(hipEventRecord(ev, cs));
-    if (ctx->det && (rc = flush_post(ctx, ctx->det))) return rc;   // see flush_post
-    ahead_frame(ctx, k) = buf;
-    return 0;
-}
-
-extern "C" int fm_frame_ring_store_device(fm_ctx* ctx, int index, const struct fm_frame_device* f) {
-    FM_CHECK_ARG(ctx && index >= 0 && index < ctx->ring_size && f);
-    int rc = device_ok(ctx, f);
-    if (rc) return rc;
-    FM_CHECK_ARG(remap_takes(ctx, f->width, f->height));      // (a correction map is for one source size)
-    // synchronous like fm_frame_ring_store (filling the ring is set-up work): the kernels on the null stream
-    if ((rc = enqueue_device(ctx, FM_MAX_DET_BATCH + 1, ctx->frame_ring + (size_t)ctx->frame_w * ctx->frame_h * 3 * index, f, nullptr, nullptr)))
-        return rc;
-    FM_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-extern "C" int fm_frame_device_done(fm_ctx* ctx, uint64_t ticket, int wait) {
-    if (!ctx || !ticket || ticket >= ctx->dev_ticket_next) {
-        fm_set_error("%s:%d bad argument: no such ticket", __FILE__, __LINE__);
-        return FM_ERR_ARG;
-    }
-    const fm_ctx::DevTicket& place = ctx->dev_ticket[ticket % FM_DEV_TICKETS];
-    if (place.ticket != ticket) return 1;                      // (older than the ring: consumed before its place was given away)
-    if (wait) {
-        FM_HIP(hipEventSynchronize(place.ev));
-        return 1;
-    }
-    const hipError_t e = hipEventQuery(place.ev);
-    if (e == hipSuccess) return 1;
-    (void)hipGetLastError();
-    if (e == hipErrorNotReady) return 0;
-    FM_HIP(e);
-    return 0;
-}
-
-void fm_frame_dev_free(fm_ctx* ctx) {
-    for (fm_ctx::DevTicket& place : ctx->dev_ticket) {
-        if (place.ev) {
-            (void)hipEventSynchronize(place.ev);
-            (void)hipEventDestroy(place.ev);
-        }
-        place = fm_ctx::DevTicket{};
-    }
-    for (hipEvent_t& e : ctx->ev_dev_in) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-}
+// the look-ahead uploads of frames.hip call this once their copy is enqueued (see flush_post); nothing without a detector
+int fm_det_flush_post(fm_ctx* ctx) { return ctx->det ? flush_post(ctx, ctx->det) : 0; }
 
 // ---------------------------------------------------------------------------------------- detector
 extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
@@ -2620,13 +1325,13 @@ static int detect_ahead(fm_ctx* ctx, int n) {
     const uint8_t* frames[FM_MAX_DET_BATCH];
     hipEvent_t uploads[FM_MAX_DET_BATCH];
     for (int k = 1; k <= n; ++k) {
-        frames[k - 1] = ahead_frame(ctx, k);
+        frames[k - 1] = fm_ahead_frame(ctx, k);
         if (!frames[k - 1]) {
             fm_set_error("look-ahead slot %d holds no frame (fm_frame_upload_ahead / fm_frame_ring_select_ahead)", k);
             return FM_ERR_ARG;
         }
         // a frame in its upload slot: the pass waits for that copy
-        uploads[k - 1] = frames[k - 1] == ahead_buf(ctx, k) ? ahead_event(ctx, k) : nullptr;
+        uploads[k - 1] = frames[k - 1] == fm_ahead_buf(ctx, k) ? fm_ahead_event(ctx, k) : nullptr;
     }
     return detect_pass(ctx, frames, uploads, n);
 }

@@ -1,5 +1,5 @@
 // Frames that lie in device memory already -> packed BGR u8: the kernels behind fm_frame_upload_device /
-// fm_frame_upload_ahead_device / fm_frame_ring_store_device (detect.hip, frame section), and fm_frame_device_check, the
+// fm_frame_upload_ahead_device / fm_frame_ring_store_device (frames.hip), and fm_frame_device_check, the
 // host-only part of their argument check.  There is no staging and no copy: a kernel reads the producer's memory where
 // it lies -- a torch / CuPy tensor or a view of one, a decoder's NV12 surface -- and writes the BGR frame every consumer
 // reads (fastmot_amd/utils/devarray.py to_bgr states the four conversions in numpy, tests compare bit for bit):
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void dev_nv12_to_bgr_kernel(const uint8_t* __r
 }  // namespace
 
 // The geometry of a device frame's description: everything that can be said without asking the runtime about the
-// pointers (the entry points in detect.hip do that next).  Host code only.
+// pointers (the entry points in frames.hip do that next).  Host code only.
 extern "C" int fm_frame_device_check(const struct fm_frame_device* f) {
     FM_CHECK_ARG(f != nullptr);
     FM_CHECK_ARG(f->width >= 1 && f->height >= 1 && f->width <= FM_SRC_MAX_DIM && f->height <= FM_SRC_MAX_DIM);

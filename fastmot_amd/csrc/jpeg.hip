@@ -1,5 +1,5 @@
 // Entropy-decoded JPEG -> packed BGR u8: the device half of the JPEG ingest path, behind fm_frame_upload_jpeg /
-// fm_frame_upload_ahead_jpeg / fm_frame_ring_store_jpeg (detect.hip, frame section).  The frame arrives in a device
+// fm_frame_upload_ahead_jpeg / fm_frame_ring_store_jpeg (frames.hip).  The frame arrives in a device
 // staging buffer as quantised coefficients (int16, per component [block_row][block_col][64] over the MCU-padded grid,
 // row-major inside a block) plus one 64-entry quantisation table per component -- what jpeg_host.hip's Huffman decoder
 // wrote on the host -- and leaves as the BGR frame every consumer already reads, so nothing downstream knows where the
@@ -219,7 +219,7 @@ size_t fm_jpeg_sample_offset(long long coef_count) { return ((size_t)coef_count 
 
 // Decodes the frame whose coefficients lie at `stage` (int16 x coef_count, then 3 x 64 uint16 quantisation entries) into
 // w * h * 3 BGR bytes at `bgr`, on stream `s`; the sample planes go to stage + fm_jpeg_sample_offset(coef_count), coef_count
-// bytes.  `info` has been checked by the caller, grid sizes included (jpeg_layout_ok in detect.hip); `stage` is 16-byte aligned.
+// bytes.  `info` has been checked by the caller, grid sizes included (jpeg_layout_ok in frames.hip); `stage` is 16-byte aligned.
 int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s) {
     FM_CHECK_ARG(stage && bgr && info && !((uintptr_t)stage & 15));
     JpegGeo g;

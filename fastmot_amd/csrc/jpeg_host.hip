@@ -1,7 +1,7 @@
 // Host half of the JPEG ingest path: marker parsing and Huffman decoding of a baseline JPEG file, the part of the
 // format that is serial by construction.  What comes out -- the quantised coefficients, de-zigzagged, per component as
 // [block_row][block_col][64] over the MCU-padded grid, and one quantisation table per component -- is what
-// fm_frame_upload_jpeg (detect.hip) copies to the device, where jpeg.hip does everything that is parallel:
+// fm_frame_upload_jpeg (frames.hip) copies to the device, where jpeg.hip does everything that is parallel:
 // dequantisation, inverse DCT, chroma upsampling, colour conversion.  fastmot_amd/utils/jpeg.py states the same decode in
 // numpy; tests/test_jpeg_host.py compares the two entry for entry.
 //

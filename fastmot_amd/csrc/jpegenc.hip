@@ -35,8 +35,6 @@
 #include "common.h"
 #include "jpegenc.h"
 
-bool fm_host_is_pinned(const void* p, size_t bytes);      // detect.hip: inside a buffer from fm_host_alloc
-
 namespace {
 
 constexpr int BLK_STRIDE = 72;                // words of LDS per block (64 used): column reads of the six blocks spread over the banks

@@ -1,5 +1,5 @@
 // NV12 -> packed BGR u8: the conversion behind fm_frame_upload_nv12 / fm_frame_upload_ahead_nv12 /
-// fm_frame_ring_store_nv12 (detect.hip, frame section).  The frame arrives as 1.5 bytes per pixel in a device staging
+// fm_frame_ring_store_nv12 (frames.hip).  The frame arrives as 1.5 bytes per pixel in a device staging
 // buffer (Y plane W x H, then the interleaved UV plane W x H/2, both packed to rows of W bytes) and leaves as the BGR
 // frame that every consumer already reads (pixel_source.h, the ReID crop, the KLT gray conversion), so nothing
 // downstream knows where the frame came from.

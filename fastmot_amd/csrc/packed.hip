@@ -1,6 +1,6 @@
 // Packed 4:2:2 (YUY2 / UYVY / YVYU) and packed RGB (any channel order, 3 or 4 bytes per pixel) -> packed BGR u8: the
-// kernels behind fm_frame_upload_packed / fm_frame_upload_ahead_packed / fm_frame_ring_store_packed (detect.hip, frame
-// section).  Packed 4:2:2 is what UVC / V4L2 cameras and capture cards deliver, RGB what image libraries hand out, BGRx
+// kernels behind fm_frame_upload_packed / fm_frame_upload_ahead_packed / fm_frame_ring_store_packed (frames.hip).
+// Packed 4:2:2 is what UVC / V4L2 cameras and capture cards deliver, RGB what image libraries hand out, BGRx
 // what `nvvidconv` / `appsink` do.  The frame arrives in device staging with its rows packed to their byte width
 // (4 * ceil(W / 2), 3 W or 4 W) and leaves as the BGR frame every consumer reads.
 //

@@ -1,6 +1,6 @@
 // Packed BGR u8 [sh][sw][3] -> packed BGR u8 [dh][dw][3] through a per-pixel correction map: lens undistortion (or any
 // fixed geometric correction) and the frame-level resize in ONE gather.  While a map is set (fm_frame_remap_set) this
-// kernel takes the place of resize.hip's behind the described-source calls (detect.hip, frame section): the frame is
+// kernel takes the place of resize.hip's behind the described-source calls (frames.hip): the frame is
 // copied / converted at capture resolution and leaves this kernel as the W x H BGR frame every consumer reads.
 //
 // The arithmetic is remap_pixel.h's (5 fractional bits, border per tap, one rounding), shared with fm_remap_bgr_host and

@@ -1,5 +1,5 @@
 // Packed BGR u8 [sh][sw][3] -> packed BGR u8 [dh][dw][3]: the frame-level resize behind fm_frame_upload_src /
-// fm_frame_upload_ahead_src / fm_frame_ring_store_src (detect.hip, frame section).  A frame that arrives at capture
+// fm_frame_upload_ahead_src / fm_frame_ring_store_src (frames.hip).  A frame that arrives at capture
 // resolution is copied (and, for NV12 / JPEG, converted) at that resolution and leaves this kernel as the W x H BGR
 // frame that every consumer already reads, so nothing downstream knows the frame was ever larger.
 //

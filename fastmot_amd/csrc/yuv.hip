@@ -1,5 +1,5 @@
 // Planar YCbCr <-> packed BGR u8: the kernels behind fm_frame_upload_planar / fm_frame_upload_ahead_planar /
-// fm_frame_ring_store_planar (detect.hip, frame section) and the exports fm_frame_export_i420 / fm_i420_from_bgr (below).
+// fm_frame_ring_store_planar (frames.hip) and the exports fm_frame_export_i420 / fm_i420_from_bgr (below).
 // Planar I420 is what software decoders hand out and what a YUV4MPEG2 (.y4m) file holds: a Y plane W x H, then a U and a
 // V plane of ceil(W / 2) x ceil(H / 2) (4:2:0), ceil(W / 2) x H (4:2:2) or W x H (4:4:4) samples, or no chroma at all.
 //
@@ -23,7 +23,6 @@
 #include "common.h"
 #include "yuv_coef.h"
 
-bool fm_host_is_pinned(const void* p, size_t bytes);      // detect.hip: inside a buffer from fm_host_alloc
 const uint8_t* fm_overlay_buffer(fm_ctx* ctx);            // overlay.hip: the overlay picture of the current frame size, or null
 
 namespace {
