@@ -449,6 +449,19 @@ FM_EXPORT_FRAME, FM_EXPORT_OVERLAY = 0, 1     # fm_frame_export_i420's `which` (
 FM_MAX_DET_BATCH = 4         # frames of one batched detector pass (fastmot_hip.h)
 
 
+FM_MAX_SSD_TILES, FM_MAX_SSD_HEADS = 16, 6      # (fastmot_hip.h)
+
+
+class SsdCfg(C.Structure):           # fm_ssd_cfg
+    _fields_ = [('input_tensor', C.c_int32), ('in_w', C.c_int32), ('in_h', C.c_int32), ('n_heads', C.c_int32),
+                ('head_tensor', C.c_int32 * FM_MAX_SSD_HEADS), ('map_w', C.c_int32 * FM_MAX_SSD_HEADS),
+                ('map_h', C.c_int32 * FM_MAX_SSD_HEADS), ('n_anchors', C.c_int32 * FM_MAX_SSD_HEADS),
+                ('anchors', C.c_void_p), ('n_anchor_rows', C.c_int32), ('box_scales', C.c_float * 4),
+                ('num_classes', C.c_int32), ('topk', C.c_int32), ('nms_thresh', C.c_float), ('n_tiles', C.c_int32),
+                ('tile_x', C.c_int32 * FM_MAX_SSD_TILES), ('tile_y', C.c_int32 * FM_MAX_SSD_TILES),
+                ('region_w', C.c_int32), ('region_h', C.c_int32)]
+
+
 class YoloCfg(C.Structure):
     _fields_ = [('in_w', C.c_int32), ('in_h', C.c_int32),
                 ('roi_x', C.c_int32), ('roi_y', C.c_int32), ('roi_w', C.c_int32), ('roi_h', C.c_int32),
@@ -907,6 +920,61 @@ def _bind_device_io(cls):
         check(self.lib.fm_detect_raw_candidates(self._ctx, _ptr(rows), C.c_int(cap), C.byref(n)))
         return rows[:n.value]
 
+    def ssd_configure(self, map_shapes, anchors_per_cell, anchors, box_scales, num_classes, topk, nms_thresh, tile_origins,
+                      region, in_wh, input_tensor=0, head_tensors=None):
+        """fm_ssd_configure.  map_shapes [(h, w)], anchors_per_cell [A] per head; anchors float32 [n, 4] (cy, cx, h, w);
+        tile_origins [(x, y)] in the tiling region `region` = (w, h); in_wh: the network input (w, h).  head_tensors: the
+        head tensor ids of the detector network (None: only ssd_postprocess_host_heads will be used)."""
+        cfg = SsdCfg()
+        a = _as(anchors, np.float32).reshape(-1, 4)
+        cfg.input_tensor, cfg.in_w, cfg.in_h, cfg.n_heads = input_tensor, int(in_wh[0]), int(in_wh[1]), len(map_shapes)
+        for k, ((h, w), na) in enumerate(zip(map_shapes, anchors_per_cell)):
+            cfg.head_tensor[k] = head_tensors[k] if head_tensors is not None else -1
+            cfg.map_w[k], cfg.map_h[k], cfg.n_anchors[k] = int(w), int(h), int(na)
+        cfg.anchors, cfg.n_anchor_rows = a.ctypes.data, len(a)
+        cfg.box_scales[:] = [float(v) for v in box_scales]
+        cfg.num_classes, cfg.topk, cfg.nms_thresh, cfg.n_tiles = int(num_classes), int(topk), float(nms_thresh), len(tile_origins)
+        for t, (x, y) in enumerate(tile_origins):
+            cfg.tile_x[t], cfg.tile_y[t] = int(x), int(y)
+        cfg.region_w, cfg.region_h = int(region[0]), int(region[1])
+        check(self.lib.fm_ssd_configure(self._ctx, C.byref(cfg)))
+        self._ssd_n_tiles = len(tile_origins)
+        self._ssd_rows = np.zeros((len(tile_origins) * int(topk), 7), np.float32)
+        self._ssd_heads = [(int(h) * int(w), int(na) * (4 + int(num_classes))) for (h, w), na in zip(map_shapes, anchors_per_cell)]
+
+    def ssd_detect_async(self):
+        check(self.lib.fm_ssd_detect_async(self._ctx))
+
+    def ssd_stage_ms(self):
+        """(preprocess, network, decode / NMS) HIP-event times in ms of the last collected pass, or None when it was not timed
+        (option 'net_timing' > 0)."""
+        ms = (C.c_float * 3)()
+        check(self.lib.fm_ssd_stage_ms(self._ctx, ms))
+        return tuple(ms) if ms[0] >= 0 else None
+
+    def ssd_preprocess_only(self):
+        check(self.lib.fm_ssd_preprocess_only(self._ctx))
+
+    def ssd_detect_sync(self):
+        """-> float32 [n_tiles * topk, 7] rows (tile, label, conf, xmin, ymin, xmax, ymax) of the pass in flight"""
+        n = C.c_int(0)
+        check(self.lib.fm_ssd_detect_sync(self._ctx, _ptr(self._ssd_rows), C.c_int(len(self._ssd_rows)), C.byref(n)))
+        return self._ssd_rows[:n.value].copy()
+
+    def ssd_postprocess_host_heads(self, heads):
+        """Decode + NMS + top-K of host head tensors: heads[k] float32 [n_tiles, map_h * map_w, A * (4 + num_classes)]."""
+        n_tiles = self._ssd_n_tiles               # (the library reads the configured number of tiles from every pointer)
+        hs = [_as(h, np.float32) for h in heads]
+        if len(hs) != len(self._ssd_heads):
+            raise ValueError(f'{len(hs)} head tensors, the configuration has {len(self._ssd_heads)}')
+        for h, (hw, cs) in zip(hs, self._ssd_heads):
+            if h.shape != (n_tiles, hw, cs):
+                raise ValueError(f'head tensor of shape {h.shape}, the configuration needs {(n_tiles, hw, cs)}')
+        ptrs = (C.c_void_p * len(hs))(*[h.ctypes.data for h in hs])
+        n = C.c_int(0)
+        check(self.lib.fm_ssd_postprocess_host_heads(self._ctx, ptrs, _ptr(self._ssd_rows), C.c_int(len(self._ssd_rows)), C.byref(n)))
+        return self._ssd_rows[:n.value].copy()
+
     def extract_configure(self, input_tensor, in_w, in_h):
         check(self.lib.fm_extract_configure(self._ctx, C.c_int(input_tensor), C.c_int(in_w), C.c_int(in_h)))
 
@@ -932,7 +1000,9 @@ def _bind_device_io(cls):
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,
-               detect_raw_candidates, detect_last_counts, detect_configure_tiles, detect_last_tiles, extract_configure, extract_async, extract_sync, extract_read_input):
+               detect_raw_candidates, detect_last_counts, detect_configure_tiles, detect_last_tiles,
+               ssd_configure, ssd_detect_async, ssd_stage_ms, ssd_preprocess_only, ssd_detect_sync, ssd_postprocess_host_heads,
+               extract_configure, extract_async, extract_sync, extract_read_input):
         setattr(cls, fn.__name__, fn)
 
 

@@ -87,6 +87,7 @@ struct FlowState;    // KLT (flow.hip)
 struct EncState;     // JPEG output path (jpegenc.hip)
 struct OvlState;     // overlays on the device frame (overlay.hip)
 struct YuvState;     // I420 export (yuv.hip)
+struct SsdState;     // SSD detector pre/post (ssd.hip)
 struct GalleryState; // cross-stream ReID-gallery all-gather over RCCL (gallery.hip)
 constexpr int FM_GALLERY_CHANNELS = 2;
 
@@ -173,6 +174,7 @@ struct fm_ctx {
     uint8_t* frame_pinned = nullptr;
 
     DetState* det = nullptr;
+    SsdState* ssd = nullptr;             // created by fm_ssd_configure
     ExtState* ext = nullptr;
     NetState* det_net = nullptr;
     NetState* ext_net = nullptr;
@@ -315,6 +317,7 @@ inline size_t fm_dev_row_bytes(const struct fm_frame_device* f) {
     if (f->layout == FM_DEV_HWC) return (size_t)f->width * (f->format <= FM_PACKED_BGR ? 3 : 4);
     return (size_t)f->width * fm_dev_elem_bytes(f->dtype);
 }
+void fm_ssd_free(fm_ctx* ctx);                                                                    // ssd.hip
 void fm_yuv_free(fm_ctx* ctx);                                                                    // yuv.hip
 int fm_resize_bgr(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s);   // resize.hip
 // remap.hip: `src` through the device map `xy` ([dh][dw][2] int32, remap_pixel.h); border = b | g << 8 | r << 16

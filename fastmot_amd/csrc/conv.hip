@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256, MINB) void conv_igemm_kernel(const ConvParams 
         const int n = idiv_small(pix, hw, inv_hw), rem = pix - n * hw;
         const int ho = idiv_small(rem, p.Wo, inv_wo), wo = rem - ho * p.Wo;
         phi0[i] = ho * p.stride - p.pad;
-        pwi0[i] = wo * p.stride - p.pad;
+        pwi0[i] = wo * p.stride - p.pad - p.pad_dx;
         pbase[i] = p.in + (size_t)n * p.H * p.W * p.in_cs + p.in_coff;
     }
     // K walk of this thread's 8-channel chunk: k = (k_begin + step) * 64 + lchunk*8 -> (kh, kw, c)

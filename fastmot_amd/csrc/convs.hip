@@ -81,7 +81,7 @@ __global__ __launch_bounds__(NW * 64) void convs_kernel(const ConvParams p, int 
         const int pix = min(tile_p * 32 * PT + (lane >> 3) + 8 * u, p.P - 1);   // clamped; masked at the store
         const int n = idiv_small(pix, hw, inv_hw), rem = pix - n * hw, oy = idiv_small(rem, p.Wo, inv_wo), ox = rem - oy * p.Wo;
         iy0[u] = oy * p.stride - p.pad;
-        ix0[u] = ox * p.stride - p.pad;
+        ix0[u] = ox * p.stride - p.pad - p.pad_dx;
         img[u] = p.in + (size_t)n * p.H * p.W * p.in_cs + p.in_coff + seg * 8;
     }
     f16* stage = reinterpret_cast<f16*>(smem) + wave * PT * 32 * BROW;

@@ -164,6 +164,7 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx) {
     fm_gallery_free(ctx);
     (void)hipDeviceSynchronize();
     if (ctx->det) fm_det_free(ctx->det);
+    fm_ssd_free(ctx);
     if (ctx->ext) fm_ext_free(ctx->ext);
     for (void* p : {(void*)ctx->frame_own, (void*)ctx->frame_own2, (void*)ctx->frame_ring})
         if (p) (void)hipFree(p);

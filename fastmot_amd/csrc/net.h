@@ -9,7 +9,7 @@ typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum { ACT_LINEAR = 0, ACT_LEAKY = 1, ACT_MISH = 2, ACT_RELU = 3, ACT_LOGISTIC = 4, ACT_SWISH = 5 };
+enum { ACT_LINEAR = 0, ACT_LEAKY = 1, ACT_MISH = 2, ACT_RELU = 3, ACT_LOGISTIC = 4, ACT_SWISH = 5, ACT_RELU6 = 6 };
 enum { RES_NONE = 0, RES_AFTER_ACT = 1, RES_BEFORE_ACT = 2 };
 
 struct ConvParams {
@@ -24,6 +24,7 @@ struct ConvParams {
     int cout_store;                         // ceil8(Cout): channels written
     int act, res_mode;
     int grid_p, grid_c, grid_z, weight_major;   // tile grid + XCD-aware order (filled by launch_conv)
+    int pad_dx;                             // column padding minus `pad` (0 unless TF "SAME" pads the two axes differently: fm_layer.gate[0])
     int up;                                 // 2: every output pixel is stored to its 2x2 block of a (2Ho, 2Wo) view
     int batch_inv;                          // 1 (detector net): every choice that fixes an output's summation order is taken
                                             // from the batch-1 geometry (P = Ho * Wo), so that a sample of a batch-N launch
@@ -137,6 +138,7 @@ __device__ __forceinline__ void store_out(const ConvParams& p, long pix, int co,
 __device__ __forceinline__ float act_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float act_leaky(float x) { return x > 0.f ? x : 0.1f * x; }
 __device__ __forceinline__ float act_relu(float x) { return x > 0.f ? x : 0.f; }
+__device__ __forceinline__ float act_relu6(float x) { return fminf(fmaxf(x, 0.f), 6.f); }    // TF-slim MobileNet
 __device__ __forceinline__ float act_mish(float x) {   // x * tanh(softplus(x)),  tanh(log(1+e^x)) = t/(t+2), t = n^2+2n, n = e^x
     const float n = __expf(x);
     const float t = n * (n + 2.f);
@@ -152,6 +154,7 @@ __device__ __forceinline__ float apply_act(float x, int act) {
         case ACT_RELU: return act_relu(x);
         case ACT_LOGISTIC: return act_logistic(x);
         case ACT_SWISH: return act_swish(x);
+        case ACT_RELU6: return act_relu6(x);
         default: return x;
     }
 }
@@ -181,6 +184,10 @@ __device__ __forceinline__ void apply_act_n(float* v, int act) {
         case ACT_SWISH:
 #pragma unroll
             for (int e = 0; e < N; ++e) v[e] = act_swish(v[e]);
+            break;
+        case ACT_RELU6:
+#pragma unroll
+            for (int e = 0; e < N; ++e) v[e] = act_relu6(v[e]);
             break;
         default: break;
     }

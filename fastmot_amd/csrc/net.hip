@@ -8,6 +8,12 @@
 
 int launch_dwconv3(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, const f16* w,
                    const float* bias, int N, int H, int W, int C, int act, hipStream_t s);
+int launch_dwconv(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, const f16* w,
+                  const float* bias, int N, int H, int W, int Ho, int Wo, int C, int stride, int act, hipStream_t s);
+bool sepconv_supported(int cin, int cout, int stride);
+int launch_sepconv(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, const f16* wdw,
+                   const float* bdw, const f16* wpw, const float* bpw, int N, int H, int W, int Ho, int Wo, int cin,
+                   int cout, int stride, int act1, int act2, long p_choice, hipStream_t s);
 int launch_liteconv(int G, const f16* const* in, const int* in_cs, const int* in_coff, f16* out, int out_cs,
                     int out_coff, const f16* wpw, int kpad, const f16* wdw, const float* bias, int N, int H,
                     int W, int C, int act, float* gap_out, hipStream_t s);
@@ -188,7 +194,17 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             p.cout_store = (L.cout + 7) & ~7;
             p.act = L.act; p.res_mode = L.res_mode;
             p.batch_inv = net->which == FM_NET_DETECTOR ? 1 : 0;
-            FM_CHECK_ARG((ti.h + 2 * L.pad - L.k) / L.stride + 1 == p.Ho);
+            // TF "SAME" padding of a 3x3 stride-2 conv (Graph.conv(same=True)): an even axis pads (0, 1) -- pad 0 with
+            // ceil(in / 2) outputs, the taps at iy == H / ix == W read zero -- and an odd one (1, 1); when the two axes differ,
+            // gate[0] carries the column padding.  FM_OP_CONVD stays symmetric (it pads through its buffer descriptor).
+            {
+                const int pad_x = L.gate[0] >= 0 && L.op != FM_OP_CONVD ? L.gate[0] : L.pad;
+                const bool same2 = L.k == 3 && L.stride == 2 && L.op != FM_OP_CONVD;
+                FM_CHECK_ARG(pad_x <= L.k / 2 && (pad_x == L.pad || same2));
+                FM_CHECK_ARG((ti.h + 2 * L.pad - L.k) / L.stride + 1 == p.Ho || (same2 && L.pad == 0 && ti.h % 2 == 0 && p.Ho == ti.h / 2));
+                FM_CHECK_ARG((ti.w + 2 * pad_x - L.k) / L.stride + 1 == p.Wo || (same2 && pad_x == 0 && ti.w % 2 == 0 && p.Wo == ti.w / 2));
+                p.pad_dx = pad_x - L.pad;
+            }
             FM_CHECK_ARG(L.out_coff + p.cout_store <= to.c && L.in_coff[0] + L.cin <= ti.c);
             if (L.op == FM_OP_CONVS) return launch_conv_streamed(p, s);
             if (L.op == FM_OP_CONVD) return launch_convd(p, s);
@@ -198,6 +214,21 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             return launch_dwconv3(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff,
                                   (const f16*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off),
                                   B, ti.h, ti.w, L.cin, L.act, s);
+        case FM_OP_DWCONV:
+            FM_CHECK_ARG(!to.f32 && L.k == 3 && L.in_coff[0] + L.cin <= ti.c && L.out_coff + L.cin <= to.c);
+            return launch_dwconv(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff, (const f16*)(net->weights + L.w_off),
+                                 (const float*)(net->weights + L.b_off), B, ti.h, ti.w, to.h, to.w, L.cin, L.stride, L.act, s);
+        case FM_OP_SEPCONV:     // gate[0] = the depthwise stage's activation, act = the pointwise stage's
+            FM_CHECK_ARG(!to.f32 && L.k == 3 && sepconv_supported(L.cin, L.cout, L.stride) && L.in_coff[0] + L.cin <= ti.c &&
+                         L.out_coff + L.cout <= to.c && L.gate[0] >= 0);
+            FM_CHECK_ARG(L.w2_off >= 0 && L.w2_off % 16 == 0 && L.b2_off >= 0 && L.b2_off % 16 == 0 &&
+                         (size_t)L.w_off + (size_t)9 * L.cin * 2 <= net->weight_bytes && (size_t)L.b_off + (size_t)L.cin * 4 <= net->weight_bytes &&
+                         (size_t)L.w2_off + (size_t)((L.cout + 31) / 32) * ((L.cin + 15) / 16) * 1024 <= net->weight_bytes &&
+                         (size_t)L.b2_off + (size_t)((L.cout + 31) / 32) * 128 <= net->weight_bytes);
+            return launch_sepconv(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff, (const f16*)(net->weights + L.w_off),
+                                  (const float*)(net->weights + L.b_off), (const f16*)(net->weights + L.w2_off),
+                                  (const float*)(net->weights + L.b2_off), B, ti.h, ti.w, to.h, to.w, L.cin, L.cout, L.stride,
+                                  L.gate[0], L.act, net->which == FM_NET_DETECTOR ? (long)to.h * to.w : (long)B * to.h * to.w, s);
         case FM_OP_LITECONV: {
             FM_CHECK_ARG(L.cin == ((L.cout + 7) & ~7) && L.n_in >= 1 && L.n_in <= 4);
             FM_CHECK_ARG(L.out_coff + L.n_in * L.cin <= to.c);
@@ -263,12 +294,15 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
                                     (const f16*)(net->weights + L.w2_off), (const float*)(net->weights + L.b2_off),
                                     out, to.c, L.out_coff, L.gate[0] >= 0 ? parts : nullptr, tiles, s);
         }
-        case FM_OP_STEMCONV:
-            FM_CHECK_ARG(!to.f32 && (ti.h + 2 * L.pad - L.k) / L.stride + 1 == to.h &&
-                         (ti.w + 2 * L.pad - L.k) / L.stride + 1 == to.w && L.out_coff + ((L.cout + 7) & ~7) <= to.c);
+        case FM_OP_STEMCONV: {
+            const bool same01 = L.k == 3 && L.stride == 2 && L.pad == 0;     // TF "SAME" (0, 1), as for FM_OP_CONV
+            FM_CHECK_ARG(!to.f32 && L.out_coff + ((L.cout + 7) & ~7) <= to.c);
+            FM_CHECK_ARG((ti.h + 2 * L.pad - L.k) / L.stride + 1 == to.h || (same01 && ti.h % 2 == 0 && to.h == ti.h / 2));
+            FM_CHECK_ARG((ti.w + 2 * L.pad - L.k) / L.stride + 1 == to.w || (same01 && ti.w % 2 == 0 && to.w == ti.w / 2));
             return launch_stemconv(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff,
                                    (const f16*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off),
                                    B, ti.h, ti.w, to.h, to.w, L.k, L.stride, L.pad, L.cout, L.act, s);
+        }
         case FM_OP_PAIR11: {
             FM_CHECK_ARG(L.n_in == 2 && !to.f32 && pair11_supported(L.cin, L.hid, L.cin, L.cout));
             const fm_tensor& tc = net->tensors[L.in[1]];
@@ -494,6 +528,14 @@ static void layer_cost(const NetState* net, const fm_layer& L, int B, double* fl
         case FM_OP_DWCONV3:
             *flops = 2.0 * 9 * L.cin * pout;
             *bytes = (pin + pout) * L.cin * 2;
+            break;
+        case FM_OP_DWCONV:
+            *flops = 2.0 * 9 * L.cin * pout;
+            *bytes = (pin + pout) * L.cin * 2;
+            break;
+        case FM_OP_SEPCONV:
+            *flops = 2.0 * (9 + L.cout) * L.cin * pout;
+            *bytes = pin * L.cin * 2 + pout * L.cout * 2 + (double)(L.cin + 9) * L.cout * 2;
             break;
         case FM_OP_LITECONV:
             *flops = 2.0 * (L.cin + 9) * L.cout * pout * L.n_in;

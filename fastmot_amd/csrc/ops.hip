@@ -42,6 +42,43 @@ __global__ void dwconv3_kernel(const f16* __restrict__ in, int in_cs, int in_cof
     *reinterpret_cast<uint4*>(out + pix * out_cs + out_coff + c) = pack8(acc);
 }
 
+// depthwise 3x3, stride 1 or 2, TF "SAME" padding (pad_y / pad_x rows / columns before; what the window covers beyond the
+// map on either side is zero), + bias (folded BN) + activation.  w: [9][C] fp16, bias f32[C].  FM_OP_DWCONV: the unfused
+// form of the separable block (sepconv.hip computes the same fmaf chain in the same tap order)
+__global__ void dwconv_kernel(const f16* __restrict__ in, int in_cs, int in_coff, f16* __restrict__ out, int out_cs,
+                              int out_coff, const f16* __restrict__ w, const float* __restrict__ bias, int N, int H, int W,
+                              int Ho, int Wo, int C, int stride, int pad_y, int pad_x, int act) {
+    const int c8n = C / 8;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total = (long)N * Ho * Wo * c8n;
+    if (idx >= total) return;
+    const int c = (int)(idx % c8n) * 8;
+    const long pix = idx / c8n;
+    const int xo = (int)(pix % Wo), yo = (int)((pix / Wo) % Ho);
+    const long n = pix / ((long)Wo * Ho);
+    const int y0 = yo * stride - pad_y, x0 = xo * stride - pad_x;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = bias[c + e];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        const int yy = y0 + dy;
+        if (yy < 0 || yy >= H) continue;
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int xx = x0 + dx;
+            if (xx < 0 || xx >= W) continue;
+            float v[8], k[8];
+            unpack8(*reinterpret_cast<const uint4*>(in + ((n * H + yy) * W + xx) * in_cs + in_coff + c), v);
+            unpack8(*reinterpret_cast<const uint4*>(w + (dy * 3 + dx) * C + c), k);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = fmaf(v[e], k[e], acc[e]);
+        }
+    }
+    apply_act_n<8>(acc, act);
+    *reinterpret_cast<uint4*>(out + pix * out_cs + out_coff + c) = pack8(acc);
+}
+
 // darknet SPP block in one launch: stride-1 max pools k = 5, 9, 13 (window clipped at the border) of
 // one (sample, 8-channel group) per workgroup, entirely in LDS.  pool9 = pool5(pool5), pool13 =
 // pool5(pool9) and each pool5 is a row pass + a column pass: 6 passes of 5 taps instead of
@@ -506,6 +543,19 @@ int launch_dwconv3(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, 
     const long total = (long)N * H * W * (C / 8);
     hipLaunchKernelGGL(dwconv3_kernel, grid1d(total), dim3(256), 0, s, in, in_cs, in_coff, out, out_cs,
                        out_coff, w, bias, N, H, W, C, act);
+    FM_HIP(hipGetLastError());
+    return 0;
+}
+
+int tf_same_pad_before(int in, int out, int stride);
+
+int launch_dwconv(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, const f16* w,
+                  const float* bias, int N, int H, int W, int Ho, int Wo, int C, int stride, int act, hipStream_t s) {
+    FM_CHECK_ARG(C % 8 == 0 && in_cs % 8 == 0 && in_coff % 8 == 0 && out_cs % 8 == 0 && out_coff % 8 == 0);
+    FM_CHECK_ARG((stride == 1 || stride == 2) && Ho == (H + stride - 1) / stride && Wo == (W + stride - 1) / stride);
+    const long total = (long)N * Ho * Wo * (C / 8);
+    hipLaunchKernelGGL(dwconv_kernel, grid1d(total), dim3(256), 0, s, in, in_cs, in_coff, out, out_cs, out_coff, w, bias,
+                       N, H, W, Ho, Wo, C, stride, tf_same_pad_before(H, Ho, stride), tf_same_pad_before(W, Wo, stride), act);
     FM_HIP(hipGetLastError());
     return 0;
 }

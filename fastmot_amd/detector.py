@@ -4,8 +4,9 @@ YOLODetector keeps the reference's two-phase protocol (`detect_async(frame)` / `
 but every stage between the frame and the final detections runs on the GPU (detect.hip): the
 frame is uploaded once per step and shared with the ReID extractor and KLT; candidates never
 leave the device.  PublicDetector (MOTChallenge det.txt) is kept as the detector-disabled path.
-SSDDetector keeps the reference's tiling / normalisation / filtering / cross-tile merging stages around
-an inference callable (the SSD networks themselves need a TensorFlow graph reader, see models/ssd.py).
+SSDDetector runs SSD-MobileNetV1 on the GPU as well (ssd.hip: tile cut + normalisation, the network at batch = tiles,
+box decode + NMS); the reference's filtering / cross-tile merging stages follow on the host, unchanged.  For the
+models without a lowering (models/ssd.py) it keeps those stages around an inference callable.
 """
 from collections import defaultdict
 from pathlib import Path
@@ -169,14 +170,19 @@ class SSDDetector(Detector):
                  conf_thresh=0.5,
                  merge_thresh=0.6,
                  max_area=120000,
-                 backend=None):
+                 backend=None,
+                 weights=None):
         """Tiled SSD detector; parameters as fastmot/detector.py:46-75.  The frame is resized to the tiling
         region, cut into `tiling_grid` overlapping tiles of the network's input size, normalised to [-1, 1]
         (RGB, CHW) and handed to `backend(batch) -> det_out` as one batch; `det_out` is the output of the SSD
         engine with its NMS stage: TOPK rows (image id, label, conf, xmin, ymin, xmax, ymax in tile fractions)
         per tile, sorted by confidence.  `backend` (not in the reference: there it is the TensorRT engine built
-        from the model's .pb file) is required because the SSD networks cannot be built here (models/ssd.py).
-        These stages run on the host, as the reference's Numba versions do."""
+        from the model's .pb file) replaces the network; those stages then run on the host, as the reference's Numba
+        versions do, and only ndarray frames are accepted.
+        With backend=None the model's own layer table (models/ssd.py: SSDMobileNetV1 and its subclasses; `weights` as
+        for build_graph) runs on the device at max_batch = number of tiles, between the preprocess and decode / NMS
+        kernels of ssd.hip: detect_async is bind_frame + fm_ssd_detect_async, so every frame kind is accepted and a
+        frame MOT.step has bound is reused; postprocess() collects the rows and filters / merges them as above."""
         super().__init__(size)
         self.model = models.SSD.get_model(model)
         assert 0 <= tile_overlap <= 1
@@ -199,22 +205,43 @@ class SSDDetector(Detector):
         self.batch_size = int(np.prod(self.tiling_grid))
         self.tiles, self.tiling_region_sz = self._generate_tiles()
         self.scale_factor = tuple(np.array(self.size) / self.tiling_region_sz)
-        if backend is None:
-            self.model.build_graph()            # raises: explains what is missing
         self.backend = backend
-        self.inp_handle = np.empty((self.batch_size, *self.model.INPUT_SHAPE), np.float32)
         self._det_out = None
+        self._in_flight = False
+        if backend is None:
+            if self.batch_size > _lib.FM_MAX_SSD_TILES:
+                raise ValueError(f'tiling_grid {tuple(tiling_grid)}: one pass takes at most {_lib.FM_MAX_SSD_TILES} tiles')
+            self.graph, self.heads = self.model.build_graph(weights, max_batch=self.batch_size)   # raises for a model without a lowering
+            self.ctx = get_context()
+            self.net = HipNet(self.ctx, NET_DETECTOR, self.graph, self.batch_size, reuse_buffers=False)
+            m = self.model
+            self.ctx.ssd_configure([(v.h, v.w) for v in self.heads], [m.anchors_per_cell(k) for k in range(len(self.heads))],
+                                   m.anchors(), m.BOX_SCALES, m.NUM_CLASSES, m.TOPK, m.NMS_THRESH,
+                                   np.maximum(self.tiles[:, :2].astype(np.int_), 0), self.tiling_region_sz,
+                                   m.INPUT_SHAPE[:0:-1], input_tensor=self.graph.input.tid,
+                                   head_tensors=[v.tid for v in self.heads])
+            return
+        self.inp_handle = np.empty((self.batch_size, *self.model.INPUT_SHAPE), np.float32)
 
     def detect_async(self, frame):
-        """Preprocesses the frame and runs the inference callable on the batch of tiles."""
+        """Preprocesses the frame and runs the network (or the inference callable) on the batch of tiles."""
+        if self.backend is None:
+            bind_frame(self.ctx, frame, self.size)
+            self.ctx.ssd_detect_async()
+            self._in_flight = True
+            return
         from .videoio import resize_bgr
         if not isinstance(frame, np.ndarray):
-            raise TypeError('SSDDetector works on host frames (ndarray)')
+            raise TypeError('SSDDetector with a backend works on host frames (ndarray)')
         self.normalize(resize_bgr(frame, self.tiling_region_sz), self.tiles, self.inp_handle)
         self._det_out = np.asarray(self.backend(self.inp_handle), np.float32).reshape(-1)
 
     def postprocess(self):
         """Returns a record array of detections (DET_DTYPE) sorted by class ID, duplicates across tiles merged."""
+        if self.backend is None:
+            assert self._in_flight, 'postprocess() without detect_async()'
+            self._in_flight = False
+            self._det_out = self.ctx.ssd_detect_sync().reshape(-1)
         assert self._det_out is not None, 'postprocess() without detect_async()'
         dets, tile_ids = self.filter_dets(self._det_out, self.tiles, self.model.TOPK, self.label_mask,
                                           self.max_area, self.conf_thresh, self.scale_factor)

@@ -16,10 +16,10 @@ LOGGER = logging.getLogger(__name__)
 
 (OP_CONV, OP_DWCONV3, OP_MAXPOOL, OP_AVGPOOL, OP_UPSAMPLE2, OP_COPY, OP_GATE, OP_GATE_SUM, OP_HEAD,
  OP_LITECONV, OP_SPP, OP_GATED_SUM, OP_STEMCONV, OP_ADD, OP_RESBLOCK, OP_CONVS, OP_LITECHAIN, OP_CONVD, OP_STEM2, OP_PAIR11,
- OP_OSTAIL) = range(21)
+ OP_OSTAIL, OP_DWCONV, OP_SEPCONV) = range(23)
 CONV_OPS = (OP_CONV, OP_CONVS, OP_CONVD)      # the three kernels behind Graph.conv (same fields, different weight layouts)
 SPP_MAX_HW = 2048
-ACT = {'linear': 0, 'leaky': 1, 'mish': 2, 'relu': 3, 'logistic': 4, 'swish': 5}
+ACT = {'linear': 0, 'leaky': 1, 'mish': 2, 'relu': 3, 'logistic': 4, 'swish': 5, 'relu6': 6}
 RES_NONE, RES_AFTER_ACT, RES_BEFORE_ACT = 0, 1, 2
 
 
@@ -147,6 +147,8 @@ class Graph:
         self.use_pair11 = os.environ.get('FASTMOT_PAIR11', '1') != '0'
         # OSNet x0.25's 16 x 8 stage + conv5 + head as one launch, one workgroup per sample (ostail.hip, FM_OP_OSTAIL)
         self.use_ostail = os.environ.get('FASTMOT_OSTAIL', '1') != '0'
+        # MobileNet separable blocks (depthwise 3x3 + pointwise 1x1) as one launch (sepconv.hip, FM_OP_SEPCONV); 0: FM_OP_DWCONV + conv
+        self.use_sepconv = os.environ.get('FASTMOT_SEPCONV', '1') != '0'
         self.conv_params = []  # (layer index, folded fp16-rounded weight fp32, bias) for the test oracle
         h, w = in_hw
         self.input = self.new(h, w, in_c)
@@ -173,11 +175,25 @@ class Graph:
 
     # ---------------------------------------------------------------- ops
     def conv(self, name, x, cout, k=1, stride=1, act='linear', bn=True, dst=None, res=None,
-             res_mode=RES_AFTER_ACT, f32_out=False, pad=None, bias=True, up=1, wb=None):
+             res_mode=RES_AFTER_ACT, f32_out=False, pad=None, bias=True, up=1, wb=None, same=False):
+        """same=True: TensorFlow "SAME" padding, for stride 1 (any odd k: pad k // 2 on every side) and for 1x1 / 3x3 convs at
+        stride 2 (larger windows at stride 2 pad (k // 2 - 1, k // 2) over an even side, which is not implemented: refused).
+        A 3x3 stride-2 conv over an even side pads (0, 1) there: expressed as pad 0 with ceil(in / 2) outputs -- the
+        kernels treat taps at iy >= H / ix >= W as zero.  `pad` is the row padding; when the columns differ (one side
+        even, one odd) their padding travels in gates[0]."""
         cin_pad = x.cpad
         pad = k // 2 if pad is None else pad
         ho = (x.h + 2 * pad - k) // stride + 1
         wo = (x.w + 2 * pad - k) // stride + 1
+        same2, pad_x = False, pad
+        if same:
+            assert k % 2 == 1 and stride in (1, 2) and pad == k // 2 and res is None and up == 1
+            if stride == 2 and k not in (1, 3):
+                raise ValueError(f'{name}: TF SAME padding of a {k}x{k} stride-2 conv is not implemented')
+            if stride == 2 and k == 3:
+                same2, pad, pad_x = True, x.h % 2, x.w % 2
+            ho, wo = self.same_out(x.h, stride), self.same_out(x.w, stride)
+        same01 = same2 and (pad, pad_x) != (1, 1)          # (an odd x odd map: the symmetric default, any kernel)
         if dst is None:
             dst = self.new(ho * up, wo * up, cout, f32=f32_out)
         assert dst.h == ho * up and dst.w == wo * up and dst.c == cout, (name, dst.h, ho, dst.c, cout)
@@ -190,7 +206,7 @@ class Graph:
         if not bias:
             b = np.zeros_like(b)
         w16 = w.astype(np.float16)
-        prev = self._pair11_applies(x, cout, k, stride, pad, res, f32_out, up)
+        prev = None if same01 else self._pair11_applies(x, cout, k, stride, pad, res, f32_out, up)
         if prev is not None:
             # `x` is a 128-channel concat whose first 64 channels the previous layer -- a 64 -> 64 pointwise conv -- has just
             # written: both as ONE launch (pair11.hip); that half of the concat is never stored (check_fusions: nobody else
@@ -210,7 +226,7 @@ class Graph:
                         b2_off=self._push(bias2), name=name,
                         pair_ref=(w1ref, b1ref, prev['act'], w16.astype(np.float32), b))
             return dst
-        if self._stem3_applies(x, cout, k, stride, pad, res, f32_out, up):
+        if not same01 and self._stem3_applies(x, cout, k, stride, pad, res, f32_out, up):
             # a pointwise conv over the whole output of the stem pair (the first CSP stage's merged 1x1 conv): third stage of the
             # same launch (stem2.hip, C3) -- the stride-2 conv's output is never stored either
             pair = self.layers.pop()
@@ -229,7 +245,7 @@ class Graph:
                         w2_off=self._push(blob2), b2_off=self._push(b23), name=name,
                         stem2_ref=(w1ref, b1ref, a1, w2ref, b2ref), stem3_ref=(pair['act'], w16.astype(np.float32), b))
             return dst
-        if self._stem2_applies(x, cout, k, stride, pad, res, f32_out, up):
+        if not same01 and self._stem2_applies(x, cout, k, stride, pad, res, f32_out, up):     # (the fused pair pads 1 on every side)
             # second layer of the network, a 3x3 stride-2 conv over the whole output of the stem layer: both as ONE launch
             # (stem2.hip) -- the 32-channel full-resolution tensor between them (27 MB at 608 x 608) is never stored.  The
             # stem's layer entry is replaced; finish() checks that nothing else wanted its output.
@@ -246,7 +262,7 @@ class Graph:
                         stem2_ref=(w1ref, b1ref, stem['act'], w16.astype(np.float32), b))
             return dst
         if (self.use_stem and x.c <= 4 and x.coff == 0 and cout <= 32 and (k, stride) in ((3, 1), (3, 2), (7, 2))
-                and res is None and not f32_out and up == 1):
+                and res is None and not f32_out and up == 1 and pad_x == pad):
             # stem layer: input patch staged in LDS instead of 16 B gathers per tap (stemconv.hip)
             kp = ceil_to(k * k * 4, 16)
             wk = np.zeros((32, k, k, 4), np.float16)
@@ -262,7 +278,8 @@ class Graph:
         streamed = x.c == cin_pad and cin_pad % 64 == 0 and k * k * cin_pad >= 512 and ho * wo <= self.convs_max_pixels
         beats_streamed = k == 3 and stride == 2 and ho * wo >= 1024
         # (1x1: any cin % 8 == 0 -- the K range is zero-padded to whole 64-deep steps; OSNet's 16 .. 96-channel pointwise convs)
-        if ((k == 3 and cin_pad % 64 == 0) or (k == 1 and pad == 0 and cin_pad >= self.convd_min_cin1)) and \
+        # (TF SAME (0, 1) layers stay off the DMA kernel: its padding is the buffer descriptor's range check)
+        if not same01 and ((k == 3 and cin_pad % 64 == 0) or (k == 1 and pad == 0 and cin_pad >= self.convd_min_cin1)) and \
                 self.convd_level >= (1 if not streamed or beats_streamed else 2):
             wk4 = np.zeros((ceil_to(cout, 32), k, k, cin_pad), np.float16)
             wk4[:cout, :, :, :x.c] = w16.transpose(0, 2, 3, 1)
@@ -282,7 +299,8 @@ class Graph:
             bias[:cout] = b
             self._layer(op=OP_CONVS, ins=[x], out=dst, cin=cin_pad, cout=cout, k=k, stride=stride, pad=pad,
                         act=ACT[act], up=up, w_off=self._push(self._pack_frag(wp)), b_off=self._push(bias),
-                        res=res, res_mode=res_mode if res is not None else RES_NONE, name=name)
+                        res=res, res_mode=res_mode if res is not None else RES_NONE, name=name,
+                        gates=[pad_x] if pad_x != pad else [])
             self.conv_params.append((len(self.layers) - 1, w16.astype(np.float32), b))
             return dst
         # pack [cout_pad32][Kpad64], K order (kh, kw, cin_pad)
@@ -297,7 +315,8 @@ class Graph:
         bias[:cout] = b
         lay = self._layer(op=OP_CONV, ins=[x], out=dst, cin=cin_pad, cout=cout, k=k, stride=stride, pad=pad,
                           act=ACT[act], up=up, w_off=self._push(packed), b_off=self._push(bias),
-                          res=res, res_mode=res_mode if res is not None else RES_NONE, name=name)
+                          res=res, res_mode=res_mode if res is not None else RES_NONE, name=name,
+                          gates=[pad_x] if pad_x != pad else [])
         self.conv_params.append((len(self.layers) - 1, w16.astype(np.float32), b))
         return dst
 
@@ -479,6 +498,69 @@ class Graph:
         self._layer(op=OP_DWCONV3, ins=[x], out=dst, cin=x.cpad, cout=c, k=3, stride=1, pad=1, act=ACT[act],
                     w_off=self._push(wk), b_off=self._push(bias), name=name)
         self.conv_params.append((len(self.layers) - 1, w16.astype(np.float32), b))
+        return dst
+
+    @staticmethod
+    def same_out(n, stride):
+        """Output size of a TF "SAME" window op: ceil(n / stride)."""
+        return -(-n // stride)
+
+    @staticmethod
+    def sepconv_supported(cin, cout, stride):
+        """The shapes FM_OP_SEPCONV runs (sepconv.hip: sepconv_supported; tests/test_ssd_topology.py asserts they agree)."""
+        return 8 <= cin <= 2048 and cin % 8 == 0 and 8 <= cout <= 2048 and cout % 8 == 0 and stride in (1, 2)
+
+    def _dw_params(self, name, x, wb=None, eps=1e-5):
+        """-> (packed [9][cpad] fp16, bias f32[cpad], fp16-rounded weight [c, 1, 3, 3] as fp32, bias f32[c])"""
+        c = x.c
+        w, b = wb if wb is not None else fold_bn(self.wsrc.conv(name, c, c, 3, bn=True, groups=c), eps)
+        w, b = np.asarray(w, np.float32), np.asarray(b, np.float32)
+        assert w.shape == (c, 1, 3, 3) and b.shape == (c,)
+        w16 = w.astype(np.float16)
+        wk = np.zeros((9, x.cpad), np.float16)
+        wk[:, :c] = w16.reshape(c, 9).T
+        bias = np.zeros(x.cpad, np.float32)
+        bias[:c] = b
+        return wk, bias, w16.astype(np.float32), b
+
+    def dwconv(self, name, x, stride=1, act='relu6', dst=None, wb=None):
+        """Depthwise 3x3, stride 1 or 2, TF "SAME" padding (FM_OP_DWCONV; dwconv3() is the stride-1 symmetric OSNet op)."""
+        assert stride in (1, 2) and x.coff % 8 == 0
+        ho, wo = self.same_out(x.h, stride), self.same_out(x.w, stride)
+        if dst is None:
+            dst = self.new(ho, wo, x.c)
+        assert (dst.h, dst.w, dst.c) == (ho, wo, x.c)
+        wk, bias, wref, bref = self._dw_params(name, x, wb)
+        self._layer(op=OP_DWCONV, ins=[x], out=dst, cin=x.cpad, cout=x.c, k=3, stride=stride, pad=1, act=ACT[act],
+                    w_off=self._push(wk), b_off=self._push(bias), name=name)
+        self.conv_params.append((len(self.layers) - 1, wref, bref))
+        return dst
+
+    def sepconv(self, name_dw, name_pw, x, cout, stride=1, act='relu6', dst=None, wb_dw=None, wb_pw=None):
+        """MobileNet separable block act(W_pw act(dw3x3(x) + b_dw) + b_pw), TF "SAME" padding: ONE launch (FM_OP_SEPCONV,
+        sepconv.hip -- the depthwise tensor is never stored) or, with use_sepconv off / an unsupported shape, FM_OP_DWCONV
+        + a pointwise conv.  Both forms draw the parameters in layer order (depthwise, then pointwise).  The fused layer
+        keeps the reference parameters as sep_ref = (w_dw [c,1,3,3], b_dw, act, w_pw [cout,c,1,1], b_pw)."""
+        c = x.c
+        if not (self.use_sepconv and x.cpad == c and x.coff % 8 == 0 and self.sepconv_supported(c, cout, stride)):
+            y = self.dwconv(name_dw, x, stride, act, wb=wb_dw)
+            return self.conv(name_pw, y, cout, 1, 1, act, dst=dst, wb=wb_pw)
+        ho, wo = self.same_out(x.h, stride), self.same_out(x.w, stride)
+        if dst is None:
+            dst = self.new(ho, wo, cout)
+        assert (dst.h, dst.w, dst.c) == (ho, wo, cout) and not self.tensors[dst.tid][3]
+        wk, bias, wref, bref = self._dw_params(name_dw, x, wb_dw)
+        w2, b2 = wb_pw if wb_pw is not None else fold_bn(self.wsrc.conv(name_pw, cout, c, 1, bn=True))
+        w2, b2 = np.asarray(w2, np.float32), np.asarray(b2, np.float32)
+        assert w2.shape == (cout, c, 1, 1) and b2.shape == (cout,)
+        wp = np.zeros((ceil_to(cout, 32), ceil_to(c, 16), 1, 1), np.float16)
+        wp[:cout, :c] = w2.astype(np.float16)
+        bias2 = np.zeros(wp.shape[0], np.float32)
+        bias2[:cout] = b2
+        self._layer(op=OP_SEPCONV, ins=[x], out=dst, cin=c, cout=cout, k=3, stride=stride, pad=1, act=ACT[act], gates=[ACT[act]],
+                    w_off=self._push(wk), b_off=self._push(bias), w2_off=self._push(self._pack_frag(wp)),
+                    b2_off=self._push(bias2), name=name_pw,
+                    sep_ref=(wref, bref, ACT[act], w2.astype(np.float16).astype(np.float32), b2))
         return dst
 
     def lightconv_params(self, name, c):
@@ -745,6 +827,9 @@ class Graph:
             elif d['op'] == OP_RESBLOCK:
                 o = d['out']
                 total += 2 * 10 * d['cin'] * d['hid'] * o.h * o.w * batch
+            elif d['op'] == OP_SEPCONV:      # (the pointwise stage; depthwise layers are not part of this sum)
+                o = d['out']
+                total += 2 * d['cin'] * d['cout'] * o.h * o.w * batch
             elif d['op'] == OP_PAIR11:
                 o = d['out']
                 total += (2 * d['cin'] * d['hid'] + 2 * (d['hid'] + d['cin']) * d['cout']) * o.h * o.w * batch

@@ -299,12 +299,19 @@ enum {
                           * (128 -> 128) -> conv5 -> GAP -> fc (cout = 512, BN folded) -> ReLU -> L2 normalise -> ctx embeddings (as
                           * FM_OP_HEAD).  w_off: the fp16 parameters (`stride` halfs), b_off: the fp32 ones (`pad` floats) in the
                           * order ostail.hip documents (pointwise weights in MFMA fragment order)                                      */
+    FM_OP_DWCONV = 21,   /* depthwise 3x3, stride 1 or 2, TF "SAME" padding (out = ceil(in / stride); total = max((out - 1) * stride +
+                          * 3 - in, 0), before = total / 2: an even map at stride 2 pads (0, 1)) + bias + act; any cin % 8 == 0;
+                          * weights as FM_OP_DWCONV3.  The unfused form of FM_OP_SEPCONV's first stage                              */
+    FM_OP_SEPCONV = 22,  /* MobileNet separable block in one launch (sepconv.hip): out = act(W_pw act_gate[0](dw3x3(in[0]) + b_dw) + b_pw),
+                          * depthwise stage as FM_OP_DWCONV (w_off = fp16 [9][cin], b_off = f32 [cin]), rounded to fp16 in LDS and never
+                          * stored; pointwise stage cin -> cout: w2_off in MFMA fragment order [ceil32(cout)/32][ceil16(cin)/16][lane][8],
+                          * b2_off = f32 [ceil32(cout)]; cin, cout % 8 == 0 (fm_sepconv_supported)                                    */
     FM_OP_GATED_SUM = 11 /* OSNet unified aggregation gate in one launch: out = sum_i in[i] *
                           * sigmoid(fc2(relu(fc1(GAP(in[i]))))) with shared fc weights
                           * (w_off, b_off, w2_off, b2_off, hid) -- FM_OP_GATE x n_in + FM_OP_GATE_SUM */
 };
 enum { FM_ACT_LINEAR = 0, FM_ACT_LEAKY = 1, FM_ACT_MISH = 2, FM_ACT_RELU = 3, FM_ACT_LOGISTIC = 4,
-       FM_ACT_SWISH = 5 };
+       FM_ACT_SWISH = 5, FM_ACT_RELU6 = 6 /* min(max(x, 0), 6) */ };
 enum { FM_RES_NONE = 0, FM_RES_AFTER_ACT = 1, FM_RES_BEFORE_ACT = 2 };
 
 typedef struct fm_tensor {
@@ -325,7 +332,9 @@ typedef struct fm_layer {
     int32_t hid;
     int32_t up;          /* CONV: nearest-neighbour upsampling factor of the stored output (1 or 2):
                           * the [upsample] layer of yolo2onnx.py:806-836 folded into its producer */
-    int32_t gate[4];
+    int32_t gate[4];     /* gate slots / per-op extras; -1 = unused.  FM_OP_CONV / FM_OP_CONVS: gate[0] MUST be -1 unless the layer is a
+                          * 3x3 stride-2 conv whose column padding differs from `pad` (TF "SAME" over a map with one even and one odd
+                          * side), in which case it holds that column padding (0 or 1); any other value >= 0 is FM_ERR_ARG */
     int64_t w_off, b_off, w2_off, b2_off;   /* byte offsets into the weight blob (16 B aligned) */
 } fm_layer;
 
@@ -1138,11 +1147,58 @@ int fm_track_predict_async(fm_ctx* ctx, int nT, const double* inside_tlbr, const
                            const int32_t* slots, const int32_t* ages, const int32_t* sorted_idx, double age_penalty,
                            double* tlbr_out, uint8_t* lost_out);
 int fm_track_predict_wait(fm_ctx* ctx, int* status_out, int* kalman_done_out);
+/* ---------------------------------------------------------------- SSD detector --------- */
+/* The stages of the reference's SSDDetector around its TensorRT engine (fastmot/detector.py:94-120,161-185) and the
+ * engine's NMS_TRT plugin (reference models/ssd.py:136-150), on the detector stream.  The network (models/ssd.py here:
+ * SSDMobileNetV1.build_graph) is FM_NET_DETECTOR at max_batch >= n_tiles; its input is a tensor, so FM_MAX_DET_BATCH does
+ * not bind: a pass takes up to FM_MAX_SSD_TILES tiles (the default 4 x 2 grid needs 8).
+ *   preprocess   input pixel (x, y) of tile t = pixel (x + tile_x[t], y + tile_y[t]) of the current frame resized to
+ *                region_w x region_h with cv2.resize's arithmetic (INTER_LINEAR; an exact 2x decimation: INTER_AREA),
+ *                BGR -> RGB, float32(u8 * (2 / 255.) - 1.), fp16
+ *   decode       per tile and anchor (cya, cxa, ha, wa): (ty, tx, th, tw) = loc / box_scales, cy = ty ha + cya,
+ *                cx = tx wa + cxa, h = exp(th) ha, w = exp(tw) wa, corners clipped to [0, 1]; score = sigmoid(logit)
+ *   NMS          per (tile, class != 0): the topk highest scores above 1e-8, greedy NMS among them (IoU without +1; a box is
+ *                dropped when its IoU with a kept, higher-scored box is > nms_thresh)
+ *   top-K        per tile: the topk highest-scored survivors over all classes, descending, as rows (tile, label, conf,
+ *                xmin, ymin, xmax, ymax); unused rows (tile, -1, 0, 0, 0, 0, 0).  Ties in score: (class, anchor) ascending.
+ * Head tensor k: fp32 [n_tiles][map_h][map_w][>= n_anchors * (4 + num_classes)], channels [n_anchors * 4 box | n_anchors *
+ * num_classes class], anchor-major; the anchor table lists (cy, cx, h, w) in (head, row, column, anchor) order. */
+#define FM_MAX_SSD_TILES 16
+#define FM_MAX_SSD_HEADS 6
+typedef struct fm_ssd_cfg {
+    int32_t input_tensor, in_w, in_h;
+    int32_t n_heads;
+    int32_t head_tensor[FM_MAX_SSD_HEADS], map_w[FM_MAX_SSD_HEADS], map_h[FM_MAX_SSD_HEADS], n_anchors[FM_MAX_SSD_HEADS];
+    const float* anchors;        /* host, [n_anchor_rows][4]; copied by fm_ssd_configure */
+    int32_t n_anchor_rows;       /* = sum of map_w * map_h * n_anchors, at most 4096 */
+    float box_scales[4];         /* (y, x, h, w) */
+    int32_t num_classes;         /* including the background class 0; at most 256 */
+    int32_t topk;                /* at most 256 */
+    float nms_thresh;
+    int32_t n_tiles;
+    int32_t tile_x[FM_MAX_SSD_TILES], tile_y[FM_MAX_SSD_TILES];
+    int32_t region_w, region_h;
+} fm_ssd_cfg;
+int fm_ssd_configure(fm_ctx* ctx, const fm_ssd_cfg* cfg);
+/* preprocess -> fm_net_run at batch n_tiles -> decode / NMS / top-K; nothing synchronises */
+int fm_ssd_detect_async(fm_ctx* ctx);
+/* waits for the pass and copies its n_tiles * topk rows of 7 floats (cap: rows) */
+int fm_ssd_detect_sync(fm_ctx* ctx, float* rows, int cap, int* n);
+/* test hooks: the preprocess kernel alone (result in the input tensor); decode + NMS + top-K on caller-provided head tensors,
+ * heads[k] = dense [n_tiles][map_h * map_w][n_anchors * (4 + num_classes)] f32 (needs no network) */
+int fm_ssd_preprocess_only(fm_ctx* ctx);
+/* HIP-event times (ms) of the three stages -- preprocess, network, decode / NMS / top-K -- of the last collected pass that ran with
+ * option "net_timing" > 0; -1 each otherwise (measurement: scripts/ssd_timing.py) */
+int fm_ssd_stage_ms(fm_ctx* ctx, float ms[3]);
+int fm_ssd_postprocess_host_heads(fm_ctx* ctx, const float* const* heads, float* rows, int cap, int* n);
+
 /* LDS bytes FM_OP_LITECHAIN needs for c channels on h x w maps (<= 65536 to be launchable): the layer-table
  * builder decides with the same formula whether an OSNet block can use the chain kernel (no device needed) */
 size_t fm_litechain_lds_bytes(int c, int w, int h);
 /* 1 when FM_OP_RESBLOCK supports c in/out channels with mid hidden channels (no device needed) */
 int fm_resblock_supported(int c, int mid);
+/* 1 when FM_OP_SEPCONV supports a separable block cin -> cout with a depthwise stride (no device needed) */
+int fm_sepconv_supported(int cin, int cout, int stride);
 /* profiling hook: accumulated host wall time (ms) of the stages of fm_flow_predict -- out5 = {begin, prepare,
  * lk, estimate, number of calls}; reset != 0 clears the accumulators */
 int fm_flow_timing(double* out5, int reset);
