@@ -72,12 +72,14 @@ extern "C" int fm_extract_configure(fm_ctx* ctx, int input_tensor, int in_w, int
 }
 
 int fm_emb_reserve(fm_ctx* ctx, int n);
+bool fm_net_writes_mirror(const NetState* net);
 
 static int export_embeddings(fm_ctx* ctx, ExtState* e, int n, hipStream_t s) {
     const size_t bytes = sizeof(float) * (size_t)n * ctx->feat_dim;
     e->exported_n = -1;
-    if (ctx->emb_host) {
-        // round 6: the head layer wrote every row to ctx->emb_host as well (ops.hip head_kernel): nothing to launch
+    if (ctx->emb_host && fm_net_writes_mirror(ctx->ext_net)) {
+        // round 6: the head layer wrote every row to ctx->emb_host as well (ops.hip head_kernel, ostail.hip, reidhead.hip):
+        // nothing to launch.  A table that ends in any other op takes the export kernel below.
         e->exported_n = n;
         e->mirror_export = true;
         FM_HIP(hipEventRecord(ctx->ev_ext_done, s));

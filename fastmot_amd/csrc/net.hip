@@ -59,6 +59,8 @@ int launch_gate_sum(int nstreams, const f16* const* in, const int* in_cs, const 
                     hipStream_t s);
 int launch_head(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int D, const f16* w,
                 const float* b, float* out, float* raw_out, hipStream_t s, float* mirror = nullptr);
+int launch_poolhead(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int D, const float* scale, const float* shift,
+                    const f16* w, const float* b, int relu, float* out, float* mirror, hipStream_t s);
 int fm_emb_reserve(fm_ctx* ctx, int n);
 
 
@@ -316,6 +318,8 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
         }
         case FM_OP_STEM2:
             return launch_stem2_layer(L, StemSrc{}, net, B, s);
+        case FM_OP_STEMPOOL:
+            return launch_stempool_layer(L, StemSrc{}, net, B, s);
         case FM_OP_SPP:
             FM_CHECK_ARG(to.h == ti.h && to.w == ti.w && L.out_coff + 3 * L.cin <= to.c);
             return launch_spp(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff, B, ti.h, ti.w, L.cin, s);
@@ -373,10 +377,35 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             return launch_ostail(in0, ti.c, L.in_coff[0], (const f16*)(net->weights + L.w_off),
                                  (const float*)(net->weights + L.b_off), B, ctx->emb + (size_t)net->emb_offset * ctx->feat_dim,
                                  nullptr, ctx->emb_host ? ctx->emb_host + (size_t)net->emb_offset * ctx->feat_dim : nullptr, s);
+        case FM_OP_POOLHEAD: {  // gate[0] > 0: BN neck (w2_off / b2_off = f32 scale / shift [cin]); gate[1] > 0: FC (w_off fp16 [cout][cin], b_off f32 [cout])
+            const bool neck = L.gate[0] > 0, fc = L.gate[1] > 0;
+            const size_t wb = net->weight_bytes;
+            FM_CHECK_ARG(L.cout == ctx->feat_dim && net->emb_offset + B <= ctx->emb_cap && !ti.f32 && L.cin > 0 && L.cout > 0 &&
+                         L.in_coff[0] + L.cin <= ti.c && (fc || L.cout == L.cin));
+            FM_CHECK_ARG(!fc || (L.b_off >= 0 && (size_t)L.w_off + (size_t)L.cout * L.cin * 2 <= wb && (size_t)L.b_off + (size_t)L.cout * 4 <= wb));
+            FM_CHECK_ARG(!neck || (L.w2_off >= 0 && L.b2_off >= 0 && L.w2_off % 16 == 0 && L.b2_off % 16 == 0 &&
+                                   (size_t)L.w2_off + (size_t)L.cin * 4 <= wb && (size_t)L.b2_off + (size_t)L.cin * 4 <= wb));
+            return launch_poolhead(in0, ti.c, L.in_coff[0], B, ti.h * ti.w, L.cin, L.cout,
+                                   neck ? (const float*)(net->weights + L.w2_off) : nullptr,
+                                   neck ? (const float*)(net->weights + L.b2_off) : nullptr,
+                                   fc ? (const f16*)(net->weights + L.w_off) : nullptr,
+                                   fc ? (const float*)(net->weights + L.b_off) : nullptr, L.act == FM_ACT_RELU,
+                                   ctx->emb + (size_t)net->emb_offset * ctx->feat_dim,
+                                   ctx->emb_host ? ctx->emb_host + (size_t)net->emb_offset * ctx->feat_dim : nullptr, s);
+        }
         default:
             fm_set_error("unknown layer op %d", L.op);
             return FM_ERR_ARG;
     }
+}
+
+// The network's last layer writes every embedding row to ctx->emb_host as well (FM_OP_HEAD, FM_OP_OSTAIL, FM_OP_POOLHEAD):
+// only then may the extractor skip its export launch (extract.hip export_embeddings) -- a table that ends in anything else
+// would leave stale rows in the mirror.
+bool fm_net_writes_mirror(const NetState* net) {
+    if (!net || net->layers.empty()) return false;
+    const int op = net->layers.back().op;
+    return op == FM_OP_HEAD || op == FM_OP_OSTAIL || op == FM_OP_POOLHEAD;
 }
 
 // gate kernels index gate[n*C + c] with C = the gated channel count; buffers are spaced by
@@ -394,7 +423,7 @@ static int run_layers_eager(fm_ctx* ctx, NetState* net, int batch) {
 bool fm_net_stem_fusable(const NetState* net, int input_tensor) {
     if (!net || net->layers.empty()) return false;
     const fm_layer& L = net->layers[0];
-    if ((L.op != FM_OP_STEMCONV && L.op != FM_OP_STEM2) || L.n_in != 1 || L.in[0] != input_tensor || L.in_coff[0] != 0) return false;
+    if ((L.op != FM_OP_STEMCONV && L.op != FM_OP_STEM2 && L.op != FM_OP_STEMPOOL) || L.n_in != 1 || L.in[0] != input_tensor || L.in_coff[0] != 0) return false;
     for (size_t i = 1; i < net->layers.size(); ++i) {
         const fm_layer& M = net->layers[i];
         for (int k = 0; k < M.n_in; ++k)
@@ -421,18 +450,36 @@ int launch_stem2_layer(const fm_layer& L, const StemSrc& src, const NetState* ne
                         three ? (const float*)(b2 + (size_t)cout2 * 4) : nullptr, L.act);
 }
 
+// FM_OP_STEMPOOL of a layer table (stempool.hip): gate[0] = the pool's padding form (1: pads 1, 0: pads 0 + ceil_mode)
+int launch_stempool_layer(const fm_layer& L, const StemSrc& src, const NetState* net, int batch, hipStream_t s) {
+    const fm_tensor& ti = net->tensors[L.in[0]];
+    const fm_tensor& to = net->tensors[L.out];
+    FM_CHECK_ARG(!ti.f32 && !to.f32 && L.k == 7 && L.stride == 2 && L.pad == 3 && L.act == FM_ACT_RELU && L.in_coff[0] == 0 &&
+                 (L.gate[0] == 0 || L.gate[0] == 1) && stempool_supported(L.cout, L.gate[0]) && L.out_coff + ((L.cout + 7) & ~7) <= to.c);
+    FM_CHECK_ARG(L.b_off >= 0 && (size_t)L.w_off + (size_t)((L.cout + 31) & ~31) * 208 * 2 <= net->weight_bytes &&
+                 (size_t)L.b_off + (size_t)((L.cout + 31) & ~31) * 4 <= net->weight_bytes);
+    const int hc = (ti.h + 6 - 7) / 2 + 1, wc = (ti.w + 6 - 7) / 2 + 1;
+    return launch_stempool_src(src, (const f16*)net->bufs[L.in[0]], ti.c, 0, (f16*)net->bufs[L.out], to.c, L.out_coff,
+                               (const f16*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off), batch, ti.h, ti.w,
+                               hc, wc, to.h, to.w, L.gate[0], L.cout, s);
+}
+
 // Layer 0 of `net` on `src` instead of the input tensor, launched eagerly on the network's stream (its arguments -- the
 // frame, the boxes -- change from call to call: not part of the captured graph); fm_net_run then starts at layer 1
 // (net->first, which the caller sets around its fm_net_run call).
 int fm_net_run_stem_from(fm_ctx* ctx, NetState* net, const StemSrc& src, int batch) {
     FM_CHECK_ARG(ctx && net && !net->layers.empty() && batch >= 1 && batch <= net->max_batch);
     const fm_layer& L = net->layers[0];
-    FM_CHECK_ARG(L.op == FM_OP_STEMCONV || L.op == FM_OP_STEM2);
+    FM_CHECK_ARG(L.op == FM_OP_STEMCONV || L.op == FM_OP_STEM2 || L.op == FM_OP_STEMPOOL);
     const fm_tensor& ti = net->tensors[L.in[0]];
     const fm_tensor& to = net->tensors[L.out];
     if (L.op == FM_OP_STEM2) {
         FM_CHECK_ARG(src.kind != 2);
         return launch_stem2_layer(L, src, net, batch, net->stream);
+    }
+    if (L.op == FM_OP_STEMPOOL) {
+        FM_CHECK_ARG(src.kind == 2);
+        return launch_stempool_layer(L, src, net, batch, net->stream);
     }
     return launch_stemconv_src(src, (const f16*)net->bufs[L.in[0]], ti.c, 0, (f16*)net->bufs[L.out], to.c, L.out_coff,
                                (const f16*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off), batch, ti.h,
@@ -511,6 +558,16 @@ extern "C" int fm_net_read_embeddings(fm_ctx* ctx, int n, float* host) {
     return 0;
 }
 
+// the same rows from the page-locked mirror the network's last layer writes beside ctx->emb (tests: mirror == device)
+extern "C" int fm_net_read_embeddings_mirror(fm_ctx* ctx, int n, float* host) {
+    FM_CHECK_ARG(ctx && n >= 0 && n <= ctx->emb_cap);
+    if (n == 0) return 0;
+    FM_CHECK_ARG(host && ctx->emb_host);
+    FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    memcpy(host, ctx->emb_host, sizeof(float) * (size_t)n * ctx->feat_dim);
+    return 0;
+}
+
 static void layer_cost(const NetState* net, const fm_layer& L, int B, double* flops, double* bytes) {
     const fm_tensor& ti = net->tensors[L.in[0]];
     const fm_tensor& to = net->tensors[L.out];
@@ -576,6 +633,16 @@ static void layer_cost(const NetState* net, const fm_layer& L, int B, double* fl
             *flops = 2.0 * L.cin * L.cout * B;
             *bytes = pin * L.cin * 2 + (double)L.cin * L.cout * 2;
             break;
+        case FM_OP_STEMPOOL: {  // the conv it contains (at the conv map) and the bytes of the fused pair: input in, pooled tensor out
+            const double pconv = (double)B * ((ti.h - 1) / 2 + 1) * ((ti.w - 1) / 2 + 1);
+            *flops = 2.0 * 49 * 3 * L.cout * pconv;
+            *bytes = pin * 8 + pout * L.cout * 2 + 49.0 * 4 * L.cout * 2;
+            break;
+        }
+        case FM_OP_POOLHEAD:
+            *flops = (double)pin * L.cin + (L.gate[1] > 0 ? 2.0 * L.cin * L.cout * B : 0.);
+            *bytes = pin * L.cin * 2 + (L.gate[1] > 0 ? (double)L.cin * L.cout * 2 : 0.) + (double)B * L.cout * 8;
+            break;
         default: *bytes = (pin + pout) * L.cin * 2; break;
     }
 }
@@ -591,6 +658,13 @@ extern "C" int fm_net_cost(fm_ctx* ctx, int which, int batch, double* flops, dou
             layer_cost(net, L, batch, &lf, &lb);
             f += lf;
             b += lb;
+        } else if (L.op == FM_OP_STEMPOOL && L.cout > 32) {
+            // the stem as the stand-alone FM_OP_CONV it replaces (a stem of <= 32 channels is FM_OP_STEMCONV unfused, which was
+            // never part of this sum): the algorithmic work of a network does not change with the fusions of its layer table
+            const fm_tensor& ti = net->tensors[L.in[0]];
+            const double pin = (double)batch * ti.h * ti.w, pconv = (double)batch * ((ti.h - 1) / 2 + 1) * ((ti.w - 1) / 2 + 1);
+            f += 2.0 * 49 * L.cin * L.cout * pconv;
+            b += pin * L.cin * 2 + pconv * L.cout * 2 + 49.0 * L.cin * L.cout * 2;
         } else if (L.op == FM_OP_STEM2) {
             // the pair's second conv as the stand-alone layer it replaces (the stem itself was never part of this sum): the
             // algorithmic work of a network does not change with the fusions of its layer table

@@ -154,6 +154,12 @@ bool stem3_supported(int cout2, int cout3);
 // FM_OP_STEM2 of a layer table: two stages (gate[1] < 0: cout / act are the second conv's) or three (gate[1] = the second
 // conv's channels, gate[2] its activation, cout / act the pointwise conv's; its weights / bias lie behind the second conv's)
 int launch_stem2_layer(const fm_layer& L, const StemSrc& src, const NetState* net, int batch, hipStream_t s);
+// FM_OP_STEMPOOL (stempool.hip): the ResNet stem (7x7 stride-2 conv, ReLU) with its 3x3 stride-2 max pool in one launch
+bool stempool_supported(int cout, int ppad);
+int launch_stempool_src(const StemSrc& src, const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff,
+                        const f16* w, const float* bias, int N, int H, int W, int Hc, int Wc, int Hp, int Wp, int ppad,
+                        int cout, hipStream_t s);
+int launch_stempool_layer(const fm_layer& L, const StemSrc& src, const NetState* net, int batch, hipStream_t s);
 // runs layer 0 of `net` -- a stem convolution over the network's input tensor -- on `src` instead of that tensor
 bool fm_net_stem_fusable(const NetState* net, int input_tensor);
 int fm_net_run_stem_from(fm_ctx* ctx, NetState* net, const StemSrc& src, int batch);

@@ -47,6 +47,12 @@ class HipNet:
         _lib.check(self.ctx.lib.fm_net_read_embeddings(self.ctx.handle, C.c_int(n), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def read_embeddings_mirror(self, n):
+        """The rows the last layer wrote to page-locked host memory beside the device matrix."""
+        out = np.empty((n, self.ctx.feat_dim), np.float32)
+        _lib.check(self.ctx.lib.fm_net_read_embeddings_mirror(self.ctx.handle, C.c_int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def cost(self, batch):
         f, b = C.c_double(0), C.c_double(0)
         _lib.check(self.ctx.lib.fm_net_cost(self.ctx.handle, C.c_int(self.which), C.c_int(batch), C.byref(f), C.byref(b)))

@@ -16,7 +16,7 @@ LOGGER = logging.getLogger(__name__)
 
 (OP_CONV, OP_DWCONV3, OP_MAXPOOL, OP_AVGPOOL, OP_UPSAMPLE2, OP_COPY, OP_GATE, OP_GATE_SUM, OP_HEAD,
  OP_LITECONV, OP_SPP, OP_GATED_SUM, OP_STEMCONV, OP_ADD, OP_RESBLOCK, OP_CONVS, OP_LITECHAIN, OP_CONVD, OP_STEM2, OP_PAIR11,
- OP_OSTAIL, OP_DWCONV, OP_SEPCONV) = range(23)
+ OP_OSTAIL, OP_DWCONV, OP_SEPCONV, OP_POOLHEAD, OP_STEMPOOL) = range(25)
 CONV_OPS = (OP_CONV, OP_CONVS, OP_CONVD)      # the three kernels behind Graph.conv (same fields, different weight layouts)
 SPP_MAX_HW = 2048
 ACT = {'linear': 0, 'leaky': 1, 'mish': 2, 'relu': 3, 'logistic': 4, 'swish': 5, 'relu6': 6}
@@ -149,6 +149,8 @@ class Graph:
         self.use_ostail = os.environ.get('FASTMOT_OSTAIL', '1') != '0'
         # MobileNet separable blocks (depthwise 3x3 + pointwise 1x1) as one launch (sepconv.hip, FM_OP_SEPCONV); 0: FM_OP_DWCONV + conv
         self.use_sepconv = os.environ.get('FASTMOT_SEPCONV', '1') != '0'
+        # the ResNet stem (7x7 stride-2 conv, ReLU) and its max pool as one launch (stempool.hip, FM_OP_STEMPOOL); 0: conv + pool
+        self.use_stempool = os.environ.get('FASTMOT_STEMPOOL', '1') != '0'
         self.conv_params = []  # (layer index, folded fp16-rounded weight fp32, bias) for the test oracle
         h, w = in_hw
         self.input = self.new(h, w, in_c)
@@ -751,6 +753,70 @@ class Graph:
                     head_ref=(w16[:, :x.c].astype(np.float32), b))
         return dst
 
+    @staticmethod
+    def stempool_supported(cout, pool_pad):
+        """The shapes FM_OP_STEMPOOL runs (stempool.hip: stempool_supported)."""
+        return 8 <= cout <= 64 and cout % 8 == 0 and pool_pad in (0, 1)
+
+    def stempool(self, name, x, cout, wb, pool_pad=1, dst=None):
+        """The ResNet stem in one launch (FM_OP_STEMPOOL, stempool.hip): relu(conv 7x7 stride 2 pad 3 (x) + b), rounded to fp16
+        and never stored, then max pool 3x3 stride 2 -- pool_pad 1: pads 1 on every side (torchvision, torchreid), 0: pads 0
+        with ceil_mode (fast-reid; pool(pad=0, pad_end=1)).  x: the network input (<= 4 channels); wb: the folded (weight
+        [cout, x.c, 7, 7], bias).  Keeps stempool_ref = (fp16-rounded weight as fp32, bias, pool_pad)."""
+        assert x.tid == self.input.tid and x.coff == 0 and x.c <= 4 and self.stempool_supported(cout, pool_pad)
+        w, b = (np.asarray(a, np.float32) for a in wb)
+        assert w.shape == (cout, x.c, 7, 7) and b.shape == (cout,)
+        hc, wc = (x.h + 6 - 7) // 2 + 1, (x.w + 6 - 7) // 2 + 1
+        hp, wp = (hc + pool_pad + 1 - 3) // 2 + 1, (wc + pool_pad + 1 - 3) // 2 + 1
+        if dst is None:
+            dst = self.new(hp, wp, cout)
+        assert (dst.h, dst.w, dst.c) == (hp, wp, cout) and not self.tensors[dst.tid][3]
+        w16 = w.astype(np.float16)
+        rows = ceil_to(cout, 32)
+        wk = np.zeros((rows, 7, 7, 4), np.float16)
+        wk[:cout, :, :, :x.c] = w16.transpose(0, 2, 3, 1)
+        packed = np.zeros((rows, 208), np.float16)
+        packed[:, :196] = wk.reshape(rows, -1)
+        bias = np.zeros(rows, np.float32)
+        bias[:cout] = b
+        self._layer(op=OP_STEMPOOL, ins=[x], out=dst, cin=x.cpad, cout=cout, k=7, stride=2, pad=3, act=ACT['relu'],
+                    gates=[pool_pad], w_off=self._push(packed), b_off=self._push(bias), name=name,
+                    stempool_ref=(w16.astype(np.float32), b, pool_pad))
+        return dst
+
+    POOLHEAD_MAX = 4096
+
+    def poolhead(self, name, x, neck=None, fc=None, relu=False):
+        """Pooled embedding head in one launch (FM_OP_POOLHEAD, reidhead.hip): global average pool of x -> neck = (scale,
+        shift) per channel in fp32 (a BatchNorm on the pooled vector, already folded) -> fc = (weight [dim, x.c], bias
+        [dim]) with fp16 weights (+ ReLU) -> L2 normalise -> the context's embedding buffer.  Without fc the feature is
+        the pooled vector (dim == x.c).  Keeps poolhead_ref = (scale, shift, fp16-rounded weight as fp32, bias, relu)."""
+        c = x.c
+        if c % 8 or x.coff % 8 or not 8 <= c <= self.POOLHEAD_MAX:
+            raise ValueError(f'{name}: the pooled head needs 8 <= channels <= {self.POOLHEAD_MAX}, a multiple of 8 (got {c})')
+        kw, ref = {}, [None, None, None, None, bool(relu)]
+        if neck is not None:
+            scale, shift = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in neck)
+            assert scale.shape == shift.shape == (c,)
+            kw.update(w2_off=self._push(scale), b2_off=self._push(shift))
+            ref[0], ref[1] = scale, shift
+        dim = c
+        if fc is not None:
+            w, b = np.asarray(fc[0], np.float32), np.ascontiguousarray(fc[1], np.float32).reshape(-1)
+            dim = w.shape[0]
+            assert w.shape == (dim, c) and b.shape == (dim,)
+            if not 1 <= dim <= self.POOLHEAD_MAX:
+                raise ValueError(f'{name}: embedding width {dim} > {self.POOLHEAD_MAX}')
+            w16 = w.astype(np.float16)
+            kw.update(w_off=self._push(w16), b_off=self._push(b))
+            ref[2], ref[3] = w16.astype(np.float32), b
+        else:
+            assert not relu
+        dst = View(x.tid, x.coff, x.c, x.h, x.w)   # (as head(): the result goes to the ctx embedding buffer)
+        self._layer(op=OP_POOLHEAD, ins=[x], out=dst, cin=c, cout=dim, act=ACT['relu' if relu else 'linear'],
+                    gates=[int(neck is not None), int(fc is not None)], name=name, poolhead_ref=tuple(ref), **kw)
+        return dst
+
     # ---------------------------------------------------------------- C tables
     def plan_arena(self, max_batch, reuse):
         """Byte offsets of the tensors in one activation arena.  With `reuse`, tensors whose live
@@ -824,6 +890,9 @@ class Graph:
             if d['op'] in CONV_OPS + (OP_STEMCONV,):
                 o = d['out']
                 total += 2 * d['k'] * d['k'] * d['ins'][0].c * d['cout'] * o.h * o.w * batch
+            elif d['op'] == OP_STEMPOOL:
+                i = d['ins'][0]
+                total += 2 * 49 * i.c * d['cout'] * ((i.h - 1) // 2 + 1) * ((i.w - 1) // 2 + 1) * batch
             elif d['op'] == OP_RESBLOCK:
                 o = d['out']
                 total += 2 * 10 * d['cin'] * d['hid'] * o.h * o.w * batch

@@ -48,8 +48,32 @@ class ReID:
         """Weights: the explicit source, else the model file at MODEL_PATH -- the reference's ONNX export
         (models/onnx_reader.py; fastmot/models/reid.py:97,106) or, next to it with the suffix .pth / .pth.tar, the
         torchreid checkpoint it was exported from (models/torchreid_weights.py); a missing file raises
-        FileNotFoundError unless seeded random parameters were opted into (models.allow_random_weights())."""
+        FileNotFoundError unless seeded random parameters were opted into (models.allow_random_weights()).
+
+        A descriptor with CHANNELS set is an OSNet: its topology is built here (osnet_graph) and the file only supplies
+        the parameters.  A descriptor with CHANNELS = None (the reference's "Add custom ReID": MODEL_PATH, INPUT_SHAPE,
+        OUTPUT_LAYOUT, METRIC) takes topology AND parameters from its ONNX file (models/onnx_graph.py); `weights` may
+        then be the path or the bytes of such a file."""
+        onnx_src = weights if isinstance(weights, (str, Path, bytes, bytearray, memoryview)) else None
+        if cls.CHANNELS is None:
+            from .onnx_graph import lower
+            from .onnx_reader import OnnxModel
+            if weights is not None and onnx_src is None and not isinstance(weights, OnnxModel):
+                raise TypeError(f'{cls.__name__} has no CHANNELS: its topology comes from an ONNX file; weights= must be the '
+                                f'path or the bytes of one, not {type(weights).__name__}')
+            src = weights
+            if src is None:
+                src = cls.weight_file()
+                if src is None or src.suffix != '.onnx':
+                    raise FileNotFoundError(
+                        f'{cls.__name__}: ONNX file {cls.MODEL_PATH} not found.  A ReID descriptor without CHANNELS takes its '
+                        'topology from that file: put it there or pass weights=<path or bytes of the .onnx>')
+            return lower(src, cls.INPUT_SHAPE, cls.OUTPUT_LAYOUT, where=f'{cls.__name__} ({cls.MODEL_PATH if weights is None else "weights="})')
         ckpt = None
+        if onnx_src is not None:
+            from .onnx_reader import torchreid_state_dict_from_onnx
+            from .torchreid_weights import TorchreidWeights
+            weights = ckpt = TorchreidWeights(torchreid_state_dict_from_onnx(onnx_src, cls.CHANNELS, cls.OUTPUT_LAYOUT))
         if weights is None:
             path = cls.weight_file()
             if path is not None:
@@ -66,6 +90,28 @@ class ReID:
         if ckpt is not None and ckpt.unused():
             raise ValueError(f'{cls.MODEL_PATH}: parameters not used by {cls.__name__}: {ckpt.unused()[:5]} ...')
         return out
+
+    @classmethod
+    def from_onnx(cls, path, metric='euclidean', name=None):
+        """Creates and registers a descriptor for an ONNX file (models/onnx_graph.py lists what it may contain):
+        INPUT_SHAPE and OUTPUT_LAYOUT are read from the file.  The returned class's name -- `name`, by default the
+        file's stem with every other character than letters, digits and '_' replaced by '_' -- then works as
+        feature_extractor_cfgs[].model."""
+        import re
+        from .onnx_graph import lower
+        path = Path(path)
+        if not path.is_file():
+            raise FileNotFoundError(f'ReID.from_onnx: {path} not found')
+        if metric not in ('euclidean', 'cosine'):
+            raise ValueError(f'metric {metric!r}: expected euclidean or cosine')
+        g, _ = lower(path)
+        h, w, _, _ = g.tensors[g.input.tid]
+        name = name or re.sub(r'\W', '_', path.stem)
+        if not name.isidentifier():
+            raise ValueError(f'{name!r} is not a usable model name: pass name=')
+        return type(name, (cls,), dict(MODEL_PATH=path, ENGINE_PATH=path.with_suffix('.hipnet'), INPUT_SHAPE=(g.input.c, h, w),
+                                       OUTPUT_LAYOUT=g.layers[-1]['cout'], METRIC=metric, CHANNELS=None,
+                                       __doc__=f'ReID model read from {path.name}'))
 
 
 def osnet_graph(model, weights, fuse_lightconv=True):

@@ -306,6 +306,17 @@ enum {
                           * depthwise stage as FM_OP_DWCONV (w_off = fp16 [9][cin], b_off = f32 [cin]), rounded to fp16 in LDS and never
                           * stored; pointwise stage cin -> cout: w2_off in MFMA fragment order [ceil32(cout)/32][ceil16(cin)/16][lane][8],
                           * b2_off = f32 [ceil32(cout)]; cin, cout % 8 == 0 (fm_sepconv_supported)                                    */
+    FM_OP_POOLHEAD = 23, /* pooled embedding head of a classification-style ReID backbone in one launch, one workgroup per sample
+                          * (reidhead.hip): global average pool of in[0] (cin channels, cin % 8 == 0, <= 4096) in fp32 -> gate[0] > 0:
+                          * per-channel affine, the BN neck folded to w2_off = f32 scale [cin], b2_off = f32 shift [cin] -> gate[1] > 0:
+                          * FC cin -> cout (w_off = fp16 [cout][cin], b_off = f32 [cout] with any BatchNorm folded in, act = linear or
+                          * ReLU), one wavefront per output row; otherwise cout == cin -> L2 normalise -> ctx embeddings and their
+                          * page-locked mirror (as FM_OP_HEAD)                                                                    */
+    FM_OP_STEMPOOL = 24, /* the ResNet stem with its max pool in one launch (stempool.hip): conv 7x7 stride 2 pad 3 of in[0] = the network
+                          * input (<= 4 real channels) -> cout <= 64 (% 8), + bias + ReLU, rounded to fp16 in LDS and never stored, then
+                          * max pool 3x3 stride 2 with gate[0] = 1: pads 1, gate[0] = 0: pads 0 and ceil_mode (windows clipped at the far
+                          * edge); w_off = fp16 [ceil32(cout)][208] (K order kh, kw, c < 4), b_off = f32 [ceil32(cout)].  As
+                          * FM_OP_STEMCONV, the extractor front end lets it compute the crops from the frame itself            */
     FM_OP_GATED_SUM = 11 /* OSNet unified aggregation gate in one launch: out = sum_i in[i] *
                           * sigmoid(fc2(relu(fc1(GAP(in[i]))))) with shared fc weights
                           * (w_off, b_off, w2_off, b2_off, hid) -- FM_OP_GATE x n_in + FM_OP_GATE_SUM */
@@ -353,6 +364,9 @@ int fm_net_tensor_read(fm_ctx* ctx, int which, int tensor, void* host, size_t by
 /* copies the embeddings produced by FM_OP_HEAD ([n][feat_dim] f32, L2-normalised) to the host
  * after synchronising the extractor stream (FeatureExtractor.postprocess, feature_extractor.py:62-74) */
 int fm_net_read_embeddings(fm_ctx* ctx, int n, float* host);
+/* the same rows from the page-locked mirror that the network's last layer (FM_OP_HEAD, FM_OP_OSTAIL, FM_OP_POOLHEAD) writes
+ * beside the device matrix: what fm_extract_sync hands out without a copy launch */
+int fm_net_read_embeddings_mirror(fm_ctx* ctx, int n, float* host);
 /* total FLOPs (2*MAC) and minimal HBM bytes of one run at the given batch: the numbers the
  * bench's roofline uses (SURVEY.md section 8d formulas) */
 int fm_net_cost(fm_ctx* ctx, int which, int batch, double* flops, double* bytes);
