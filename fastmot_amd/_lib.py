@@ -114,6 +114,39 @@ def overlay_render_host(frame, cmds, masks=b''):
     return frame
 
 
+# fm_redact_region (32 bytes): one region of a redaction list (utils/redact.py builds them)
+REDACT_REGION_DTYPE = np.dtype([('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('mode', '<i4'), ('shape', '<i4'),
+                                ('cell', '<i4'), ('color', 'u1', (3,)), ('reserved', 'u1')])
+assert REDACT_REGION_DTYPE.itemsize == 32
+REDACT_PIXELATE, REDACT_SMOOTH, REDACT_FILL = range(3)
+REDACT_RECT, REDACT_ELLIPSE = range(2)
+FM_REDACT_MAX_REGIONS = 4096
+FM_REDACT_MAX_CELLS = 1 << 20
+FM_SRC_MAX_DIM = 16384
+
+
+def _redact_args(regions):
+    regions = np.ascontiguousarray(regions, dtype=REDACT_REGION_DTYPE).reshape(-1)
+    return regions, (_ptr(regions) if len(regions) else None, C.c_int(len(regions)))
+
+
+def redact_check(regions, width, height):
+    """fm_redact_check's return code (0: well formed) for a region list on a width x height frame."""
+    regions, args = _redact_args(regions)
+    return load().fm_redact_check(*args, C.c_int(width), C.c_int(height))
+
+
+def redact_render_host(frame, regions):
+    """Redacts host pixels [H, W, 3] uint8 BGR IN PLACE on the CPU by a region list, with the functions the kernels are
+    compiled from (csrc/redact_pixel.h); every region reads the original pixels.  No GPU."""
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or \
+            frame.strides[1:] != (3, 1) or frame.strides[0] < 3 * frame.shape[1] or not frame.flags.writeable:
+        raise ValueError('frame must be a writeable uint8 HxWx3 array with packed pixels')
+    regions, args = _redact_args(regions)
+    check(load().fm_redact_render_host(_ptr(frame), C.c_int(frame.shape[1]), C.c_int(frame.shape[0]), C.c_size_t(frame.strides[0]), *args))
+    return frame
+
+
 def device_count():
     n = load().fm_device_count()
     if n < 0:
@@ -856,6 +889,20 @@ def _bind_device_io(cls):
         check(self.lib.fm_overlay_stream_ms(self._ctx, C.byref(ms)))
         return ms.value if ms.value >= 0 else None
 
+    def frame_render_redacted(self, regions, cmds=(), masks=b''):
+        """The frame the context holds on the device, redacted by a region list (utils/redact.py) and then drawn on by an
+        overlay command list (may be empty) -> the context's overlay buffer, which overlay_read / overlay_encode_jpeg /
+        overlay_export_i420 serve; the frame itself is not written."""
+        regions, rargs = _redact_args(regions)
+        cmds, masks, args = _overlay_args(cmds if len(cmds) else np.zeros(0, OVERLAY_CMD_DTYPE), masks)
+        check(self.lib.fm_frame_render_redacted(self._ctx, *rargs, *args))
+
+    def redact_stream_ms(self):
+        """HIP-event time of the last frame_render_redacted's kernels (cell means + tile pass), or None before the first."""
+        ms = C.c_float(0)
+        check(self.lib.fm_redact_stream_ms(self._ctx, C.byref(ms)))
+        return ms.value if ms.value >= 0 else None
+
     def detect_configure(self, cfg):
         check(self.lib.fm_detect_configure(self._ctx, C.byref(cfg)))
 
@@ -996,7 +1043,7 @@ def _bind_device_io(cls):
     for fn in (frame_configure, frame_set_lens, _described, _frame_kind, _frame_call, _device_check, device_frame_done, device_frames_prune, pending_device_frames, _nv12_args, _jpeg_args, pinned_deep_frames, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
                overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
                _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
-               frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms,
+               frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms, frame_render_redacted, redact_stream_ms,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
                detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,

@@ -20,6 +20,7 @@ from .utils import Profiler
 from .utils.source import SourceFrame
 from .utils.visualization import Visualizer
 from .utils.overlay import build_commands
+from .utils.redact import Redact, build_regions, redact_bgr
 
 LOGGER = logging.getLogger(__name__)
 _NATIVE_FLOW = True      # tests flip this to compare the native prediction worker with the Python-thread path
@@ -84,7 +85,8 @@ class MOT:
                  visualizer_cfg=None,
                  draw=False,
                  detector_lookahead=1,
-                 gpu_draw=False):
+                 gpu_draw=False,
+                 redact=None):
         """Top level module that integrates detection, feature extraction and tracking
         (parameters: fastmot/mot.py:37-67).  `draw=True` renders the overlays of `visualizer_cfg` onto every
         frame handed to `step` as a host ndarray, in place, after tracking (mot.py:166-167,191-196).
@@ -92,11 +94,22 @@ class MOT:
         network pass over the next k frames handed to `step` as `next_frames` (DetectorLookahead); results unchanged.
         `gpu_draw=True` (not in the reference; excludes `draw`): the same overlays, rendered on the GPU onto a COPY of the
         frame the tracker holds there -- whatever the frame was handed over as -- when `render_frame` or `encode_frame`
-        asks for them; `step` itself draws nothing and the frame handed to it is not touched."""
+        asks for them; `step` itself draws nothing and the frame handed to it is not touched.
+        `redact` (not in the reference; None, a utils.redact.Redact, or a dictionary of its settings -- `"redact": {...}`
+        in `mot_cfg`): the tracked objects are pixelated, smoothed or painted over in EVERY picture this object hands out:
+        `render_frame()`, `encode_frame()` and `export_frame_i420()` always return the redacted picture (`overlays=False`
+        then means "redacted, nothing drawn"), made on the GPU inside the overlay pass (csrc/redact.hip, csrc/overlay.hip);
+        with `draw=True` the host frame is redacted in place before the overlays are drawn on it.  The regions are this
+        step's detections and every active track, confirmed or not (utils.redact.Redact says how boxes become regions).
+        NOT covered, by design: `tracker.ctx.frame_read()`, the caller's own frame (unless `draw=True` writes it) and
+        the ReID crops are the unredacted picture -- the tracker must see it, and its results do not change.  A region
+        list the library refuses (more than 4096 regions or 2^20 cells) raises: no picture leaves unredacted."""
         if draw and gpu_draw:
             raise ValueError('draw=True renders on the host frame, gpu_draw=True on the GPU copy: choose one')
         self.gpu_draw = gpu_draw
-        self._overlay_rendered = False
+        self.redact = Redact.coerce(redact)
+        self._overlay_rendered = False      # False, or which picture the overlay buffer holds: True (drawn) / 'bare'
+        self._redact_regions = None
         self.size = size
         self.detector_type = DetectorType[detector_type.upper()]
         assert detector_frame_skip >= 1
@@ -182,6 +195,7 @@ class MOT:
             raise ValueError('draw=True needs host pixels at the tracker\'s size: a SourceFrame is resized on the GPU')
         bind_frame(ctx, frame, self.size, begin_step=True)
         self._overlay_rendered = False
+        self._redact_regions = None
         ctx.in_step = True
         if next_frames is not None:
             next_frames = list(next_frames)
@@ -198,6 +212,10 @@ class MOT:
             self._next_frame = None
             self._next_frames = []
         if self.draw:
+            if self.redact is not None:
+                if not isinstance(frame, np.ndarray):
+                    raise TypeError('draw=True needs host frames (ndarray): overlays are rendered on the CPU')
+                redact_bgr(frame, self._regions())
             self._draw(frame, self._last_detections)
         self.frame_count += 1
 
@@ -212,8 +230,9 @@ class MOT:
             raise ValueError(f'quality {quality} outside 1..100')
         if self.frame_count == 0:
             raise RuntimeError('encode_frame needs a step before it')
-        if self.gpu_draw if overlays is None else overlays:
-            self._render_overlay()
+        drawn = self.gpu_draw if overlays is None else overlays
+        if drawn or self.redact is not None:
+            self._render_overlay(drawn)
             return self.tracker.ctx.overlay_encode_jpeg(quality)
         return self.tracker.ctx.frame_encode_jpeg(quality)
 
@@ -227,8 +246,9 @@ class MOT:
         if self.frame_count == 0:
             raise RuntimeError('export_frame_i420 needs a step before it')
         ctx = self.tracker.ctx
-        if self.gpu_draw if overlays is None else overlays:
-            self._render_overlay()
+        drawn = self.gpu_draw if overlays is None else overlays
+        if drawn or self.redact is not None:
+            self._render_overlay(drawn)
             return I420Image(ctx.overlay_export_i420(), self.size)
         return I420Image(ctx.frame_export_i420(), self.size)
 
@@ -243,15 +263,41 @@ class MOT:
         self._render_overlay()
         return self.tracker.ctx.overlay_read()
 
-    def _render_overlay(self):
-        if self._overlay_rendered:
+    def redact_frame(self, frame):
+        """Redacts a host frame of the tracker's size (HxWx3 uint8 BGR, e.g. the caller's copy of the frame of the last
+        `step`) IN PLACE with that step's regions, on the CPU (utils.redact.redact_bgr), and returns it: for a caller that
+        writes its own array instead of asking for `render_frame()` / `encode_frame()`."""
+        if self.redact is None:
+            raise RuntimeError('redact_frame needs MOT(redact=...)')
+        if self.frame_count == 0:
+            raise RuntimeError('redact_frame needs a step before it')
+        if not isinstance(frame, np.ndarray) or frame.shape[:2] != (self.size[1], self.size[0]):
+            raise ValueError(f'redact_frame needs an ndarray of the tracker\'s size {self.size[0]}x{self.size[1]}')
+        return redact_bgr(frame, self._regions())
+
+    def _regions(self):
+        """The redaction regions of the last step: built once per step, from the state the step left."""
+        if self._redact_regions is None:
+            self._redact_regions = build_regions(self.tracker.tracks.values(), self._last_detections, self.redact, self.size)
+        return self._redact_regions
+
+    def _render_overlay(self, drawn=True):
+        """Fills the context's overlay buffer: with the overlays (`drawn`), or -- only with `redact` -- with the redacted
+        frame and nothing drawn on it."""
+        want = True if drawn else 'bare'
+        if self._overlay_rendered == want:
             return
-        visible = list(self.visible_tracks())
-        cmds, masks = build_commands(self.visualizer, visible, self._last_detections, self.tracker.klt_bboxes.values(),
-                                     self.tracker.flow.prev_bg_keypoints, self.tracker.flow.bg_keypoints,
-                                     f'visible: {len(visible)}', self.size)
-        self.tracker.ctx.frame_render_overlay(cmds, masks)
-        self._overlay_rendered = True
+        cmds, masks = (), b''
+        if drawn:
+            visible = list(self.visible_tracks())
+            cmds, masks = build_commands(self.visualizer, visible, self._last_detections, self.tracker.klt_bboxes.values(),
+                                         self.tracker.flow.prev_bg_keypoints, self.tracker.flow.bg_keypoints,
+                                         f'visible: {len(visible)}', self.size)
+        if self.redact is not None:
+            self.tracker.ctx.frame_render_redacted(self._regions(), cmds, masks)
+        else:
+            self.tracker.ctx.frame_render_overlay(cmds, masks)
+        self._overlay_rendered = want
 
     def _prefetch_next(self):
         if self.detector_lookahead > 1:

@@ -14,7 +14,8 @@ def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False,
     """stream: a started VideoIO; mot: a reset MOT (None: frames are only passed through); txt: an open text file for
     MOT Challenge result rows (app.py:91-97), needs `resize_to`; write_frames: stream.write(frame) after each step
     (the frame carries the overlays when the MOT draws; a frame that lives on the GPU only -- VideoIO(gpu_encode=True) with
-    gpu_decode / gpu_resize -- is written as mot.encode_frame(), or as mot.export_frame_i420() to a '.y4m' output); lookahead: upcoming frames read ahead and handed to each step
+    gpu_decode / gpu_resize -- is written as mot.encode_frame(), or as mot.export_frame_i420() to a '.y4m' output; with
+    MOT(redact=...) a host frame that the MOT did not draw on is redacted in place, mot.redact_frame, before it is written); lookahead: upcoming frames read ahead and handed to each step
     as `next_frames` (a MOT with detector_lookahead = k batches up to k of them).  Returns the number of frames."""
     n = 0
     frame = stream.read()
@@ -35,6 +36,8 @@ def track_stream(stream, mot=None, txt=None, resize_to=None, write_frames=False,
                 i420 = getattr(stream, 'i420_output', False)
                 stream.write(mot.export_frame_i420() if i420 else mot.encode_frame(stream.jpeg_quality))
             else:
+                if mot is not None and getattr(mot, 'redact', None) is not None and not mot.draw and hasattr(frame, '__array_interface__'):
+                    mot.redact_frame(frame)          # (draw=True has redacted it in the step; this loop owns the array)
                 stream.write(frame)
         frame = upcoming.popleft()
         n += 1

@@ -949,6 +949,70 @@ int fm_overlay_read(fm_ctx* ctx, uint8_t* out);
 int fm_overlay_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size_t capacity, size_t* length);
 int fm_overlay_stream_ms(fm_ctx* ctx, float* ms);
 
+/* Redaction of the frames that leave the GPU (no counterpart in the reference): tracked persons are pixelated, smoothed
+ * or painted over in the overlay buffer, inside the pass that makes it, so that the pictures fm_overlay_read,
+ * fm_overlay_encode_jpeg and fm_frame_export_i420(FM_EXPORT_OVERLAY) hand out do not show them.  The tracker's frame is
+ * never written: fm_frame_read, the next step's KLT and the ReID crops see the unredacted picture, by design.
+ * A frame is redacted by a list of REGIONS.  A region has inclusive corners x0, y0, x1, y1 (anywhere in
+ * +-FM_OVERLAY_MAX_COORD; empty when x1 < x0 or y1 < y0; width and height at most FM_SRC_MAX_DIM), a mode, a shape, a cell
+ * side c in 2..256 and a fill colour.  Its pixels are the rectangle, cut by the frame and by the shape.  Everything is
+ * integer and exact, stated once in csrc/redact_pixel.h -- one text for the kernels and for fm_redact_render_host -- and
+ * in numpy in tests/redact_ref.py:
+ *   cells   The grid is anchored at the UNCLIPPED corner: cell (i, j) covers the columns x0 + i c .. x0 + (i + 1) c - 1
+ *           up to x1, and the rows likewise.  Its mean per channel is (sum + n / 2) / n in integer division over those n
+ *           of its pixels that lie inside the frame -- the rectangle's pixels, whatever the shape.  Only cells with n > 0
+ *           exist: indices imin..imax, jmin..jmax.
+ *   FM_REDACT_PIXELATE  the pixel takes its cell's mean.
+ *   FM_REDACT_SMOOTH    bilinear between the means of the four nearest cell centres: u = 2 (x - x0) + 1 - c,
+ *                       i0 = floor(u / 2c), fx = u - 2c i0, the same in y for j0 and fy; i0, i0 + 1, j0, j0 + 1 clamped
+ *                       into the existing range; value = ((2c - fx)(2c - fy) m00 + fx (2c - fy) m10 + (2c - fx) fy m01 +
+ *                       fx fy m11 + 2c^2) / 4c^2 (below 2^27).  Only the cell means show, without the blocks.
+ *   FM_REDACT_FILL      the colour (b, g, r).  Such a region has no cells.
+ *   FM_REDACT_RECT      every pixel of the rectangle.
+ *   FM_REDACT_ELLIPSE   a = x1 - x0 + 1, b = y1 - y0 + 1, dx = 2 (x - x0) + 1 - a, dy = 2 (y - y0) + 1 - b: inside iff
+ *                       dx^2 b^2 + dy^2 a^2 <= a^2 b^2, in 64-bit integers.
+ * Every region computes from the ORIGINAL frame, never from another region's output; a pixel that several regions cover
+ * takes the value of the LAST of them in list order.  An overlay command list is applied on top of the redacted pixels.
+ *
+ * fm_redact_check: 0 when the list is well formed for a width x height frame; FM_ERR_ARG for a null list with n > 0,
+ * n > FM_REDACT_MAX_REGIONS, a width or height outside 1..FM_SRC_MAX_DIM, an unknown mode or shape, a cell outside 2..256,
+ * a non-empty region with a side above FM_SRC_MAX_DIM, a coordinate outside +-FM_OVERLAY_MAX_COORD, a non-zero reserved
+ * field, or a list whose existing cells on that frame number more than FM_REDACT_MAX_CELLS in all (which sizes the device
+ * buffer of the means).  Reads the list only; no context, no GPU, any number of threads.  Every entry point below calls
+ * it first and does nothing else when it fails.
+ * fm_redact_render_host: redacts host pixels (width x height BGR, `pitch` >= 3 width bytes between rows) IN PLACE, every
+ * region reading a copy of the original taken first: the CPU statement of the kernels.  No context, no GPU.
+ * fm_frame_render_redacted: current device frame -> the context's overlay buffer, redacted by the regions and then drawn
+ * on by the command list (fm_frame_render_overlay's arguments and contract: the same stream, the same ordering, the same
+ * buffer, which fm_overlay_read / fm_overlay_encode_jpeg / fm_frame_export_i420 then serve unchanged).  Two kernels: the
+ * cell means of all regions in one launch (csrc/redact.hip) into a device buffer of one B, G, R, 0 word per cell behind
+ * a per-region offset table, then the overlay tile pass, whose workgroup bins the regions against its tile as it bins
+ * commands and replaces each pixel, read once, by its last covering region's value before the commands are applied.
+ * With n_regions == 0 it is fm_frame_render_overlay, byte for byte.  List, table and means follow the overlay
+ * buffers' rules: allocated on first use, regrown on demand, freed by fm_ctx_destroy.
+ * fm_redact_stream_ms: HIP-event time of the last fm_frame_render_redacted's kernels, means and tile pass together
+ * (fm_overlay_stream_ms: the tile pass alone); -1 before the first. */
+#define FM_REDACT_PIXELATE 0
+#define FM_REDACT_SMOOTH 1
+#define FM_REDACT_FILL 2
+#define FM_REDACT_RECT 0
+#define FM_REDACT_ELLIPSE 1
+#define FM_REDACT_MAX_REGIONS 4096
+#define FM_REDACT_MAX_CELLS (1 << 20)
+typedef struct fm_redact_region {   /* 32 bytes */
+    int32_t x0, y0, x1, y1;         /* inclusive corners */
+    int32_t mode;                   /* FM_REDACT_PIXELATE / SMOOTH / FILL */
+    int32_t shape;                  /* FM_REDACT_RECT / ELLIPSE */
+    int32_t cell;                   /* cell side c, 2..256 (checked for every mode) */
+    uint8_t b, g, r;                /* FM_REDACT_FILL: the colour; others: ignored */
+    uint8_t reserved;               /* 0 */
+} fm_redact_region;
+int fm_redact_check(const fm_redact_region* regions, int n, int width, int height);
+int fm_redact_render_host(uint8_t* pixels, int width, int height, size_t pitch, const fm_redact_region* regions, int n);
+int fm_frame_render_redacted(fm_ctx* ctx, const fm_redact_region* regions, int n_regions, const fm_overlay_cmd* cmds, int n_cmds,
+                             const uint8_t* masks, size_t mask_bytes);
+int fm_redact_stream_ms(fm_ctx* ctx, float* ms);
+
 /* Frames OUT as planar I420 (a '.y4m' output, or the input of a software encoder): replaces, for such an output, the
  * reference's cv2.VideoWriter with its `autovideoconvert` stage (fastmot/videoio.py:99-103,222-232), which takes host
  * BGR pixels.  Output: width * height Y bytes, then ceil(width / 2) * ceil(height / 2) U bytes, then as many V bytes --
