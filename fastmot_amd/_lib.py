@@ -56,6 +56,7 @@ def load():
     lib.fm_last_error.restype = C.c_char_p
     lib.fm_jpeg_encode_bound.restype = C.c_size_t
     lib.fm_i420_bound.restype = C.c_size_t
+    lib.fm_jpeg_encode_regions_bound.restype = C.c_size_t
     _lib = lib
     return lib
 
@@ -123,6 +124,56 @@ REDACT_RECT, REDACT_ELLIPSE = range(2)
 FM_REDACT_MAX_REGIONS = 4096
 FM_REDACT_MAX_CELLS = 1 << 20
 FM_SRC_MAX_DIM = 16384
+
+
+# fm_crop_rect / fm_crop_plan / fm_crop_totals: object crops as JPEG files, many in one pass (fm_frame_encode_regions)
+CROP_RECT_DTYPE = np.dtype([('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4')])
+CROP_PLAN_DTYPE = np.dtype([('width', '<i4'), ('height', '<i4'), ('mcus_x', '<i4'), ('mcus_y', '<i4'), ('first_mcu', '<i4'),
+                            ('first_block', '<i4'), ('first_row', '<i4'), ('reserved', '<i4'), ('raw_offset', '<u8'), ('bound', '<u8')])
+CROP_TOTALS_DTYPE = np.dtype([('mcus', '<i4'), ('blocks', '<i4'), ('rows', '<i4'), ('reserved', '<i4'), ('raw_bytes', '<u8'),
+                              ('bound', '<u8')])
+assert CROP_RECT_DTYPE.itemsize == 16 and CROP_PLAN_DTYPE.itemsize == 48 and CROP_TOTALS_DTYPE.itemsize == 32
+FM_OBJENC_MAX_REGIONS = 1024
+FM_OBJENC_MAX_MCUS = 16384
+OBJENC_SHRINKS = (1, 2, 4)
+
+
+def _crop_rects(rects):
+    """An (n, 4) integer array of inclusive corners -> the C list."""
+    arr = np.asarray(rects)
+    if arr.size and not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError('rects must be integers')
+    return np.ascontiguousarray(arr.reshape(-1, 4), dtype=np.int32)
+
+
+def encode_regions_plan(rects, shrink=1):
+    """fm_jpeg_encode_regions_plan: (plans, totals) of one call -- where every image lies in the launches' index spaces and
+    how much its file can take; FastMOTHipError, naming the limit, for a list the library refuses.  No GPU."""
+    arr = _crop_rects(rects)
+    plans = np.zeros(len(arr), CROP_PLAN_DTYPE)
+    totals = np.zeros(1, CROP_TOTALS_DTYPE)
+    check(load().fm_jpeg_encode_regions_plan(_ptr(arr) if len(arr) else None, C.c_int(len(arr)), C.c_int(int(shrink)),
+                                             _ptr(plans) if len(arr) else None, _ptr(totals)))
+    return plans, totals[0]
+
+
+def encode_regions_assemble(plans, quality, segments, capacity=None, segs_bytes=None):
+    """fm_jpeg_encode_regions_assemble: the files of a call from the byte-stuffed segments of all its MCU rows (a list of
+    bytes in row order) -> list of bytes.  No GPU."""
+    plans = np.ascontiguousarray(plans, dtype=CROP_PLAN_DTYPE)
+    lens = np.array([len(s) for s in segments], np.uint32)
+    segs = np.zeros(max(sum((len(s) + 15) & ~15 for s in segments), 16), np.uint8)
+    at = 0
+    for s in segments:
+        segs[at:at + len(s)] = np.frombuffer(s, np.uint8)
+        at += (len(s) + 15) & ~15
+    cap = int(plans['bound'].sum()) if capacity is None else capacity
+    out = np.zeros(max(cap, 1), np.uint8)
+    offsets = np.zeros(len(plans) + 1, np.uintp)
+    check(load().fm_jpeg_encode_regions_assemble(_ptr(plans), C.c_int(len(plans)), C.c_int(int(quality)), _ptr(lens), _ptr(segs),
+                                                 C.c_size_t(segs.size if segs_bytes is None else segs_bytes), _ptr(out), C.c_size_t(cap),
+                                                 _ptr(offsets)))
+    return [out[int(a):int(b)].tobytes() for a, b in zip(offsets[:-1], offsets[1:])]
 
 
 def _redact_args(regions):
@@ -817,6 +868,46 @@ def _bind_device_io(cls):
                                           _ptr(out), C.c_size_t(out.size), C.byref(n)))
         return out[:n.value].tobytes()
 
+    def frame_encode_regions(self, rects, quality=85, shrink=1, overlay=False):
+        """Rectangles of the frame the context holds (overlay=True: of the overlay buffer) as baseline JPEG files, all in
+        one pass of the encoder -> list of bytes, one per rectangle.  rects: an (n, 4) integer array of inclusive corners
+        (x0, y0, x1, y1) inside the frame (utils.redact.region_rect clips).  shrink 2 / 4: every crop reduced by that factor
+        first (block means, fastmot_hip.h).  File i equals utils.jpeg.encode_bgr(picture[y0:y1 + 1, x0:x1 + 1], quality).
+        A list beyond what one library call takes (FM_OBJENC_MAX_REGIONS rectangles, FM_OBJENC_MAX_MCUS MCUs) is split into
+        several calls; a single rectangle above the MCU limit is refused."""
+        if getattr(self, 'frame_size', None) is None:
+            raise FastMOTHipError('no frame on the device yet')
+        if not 1 <= int(quality) <= 100:
+            raise ValueError(f'quality {quality} outside 1..100')
+        if shrink not in OBJENC_SHRINKS:
+            raise ValueError(f'shrink {shrink!r}: one of {OBJENC_SHRINKS}')
+        arr = _crop_rects(rects)
+        which = FM_EXPORT_OVERLAY if overlay else FM_EXPORT_FRAME
+        files = []
+        start = 0
+        while start < len(arr):
+            # the longest run from `start` that one call takes: MCUs of a rect as the plan counts them
+            w = (arr[start:, 2] - arr[start:, 0] + int(shrink)) // int(shrink)
+            h = (arr[start:, 3] - arr[start:, 1] + int(shrink)) // int(shrink)
+            mcus = np.cumsum(np.maximum((w.astype(np.int64) + 15) // 16, 0) * np.maximum((h.astype(np.int64) + 15) // 16, 0))
+            take = max(1, min(int(np.searchsorted(mcus, self.OBJENC_CHUNK_MCUS, side='right')), self.OBJENC_CHUNK_REGIONS))
+            files += self._encode_regions_call(arr[start:start + take], which, int(quality), int(shrink))
+            start += take
+        return files
+
+    def _encode_regions_call(self, arr, which, quality, shrink):
+        n = len(arr)
+        bound = self.lib.fm_jpeg_encode_regions_bound(_ptr(arr), C.c_int(n), C.c_int(shrink))
+        if not bound:
+            raise FastMOTHipError(f'libfastmot_hip error: {self.lib.fm_last_error().decode()}')
+        out = getattr(self, '_objenc_out_buf', None)
+        if out is None or out.size < bound:
+            out = self._objenc_out_buf = np.empty(bound, np.uint8)       # (untouched pages of it cost nothing)
+        offsets = np.zeros(n + 1, np.uintp)
+        check(self.lib.fm_frame_encode_regions(self._ctx, C.c_int(which), _ptr(arr), C.c_int(n), C.c_int(shrink), C.c_int(quality),
+                                               _ptr(out), C.c_size_t(out.size), _ptr(offsets)))
+        return [out[int(a):int(b)].tobytes() for a, b in zip(offsets[:-1], offsets[1:])]
+
     def _i420_out(self, width, height):
         bound = self.lib.fm_i420_bound(C.c_int(width), C.c_int(height))
         if not bound:
@@ -1042,7 +1133,7 @@ def _bind_device_io(cls):
 
     for fn in (frame_configure, frame_set_lens, _described, _frame_kind, _frame_call, _device_check, device_frame_done, device_frames_prune, pending_device_frames, _nv12_args, _jpeg_args, pinned_deep_frames, pinned_planar_frames, pinned_packed_frames, pinned_bayer_frames, _i420_out, _export_i420, frame_export_i420,
                overlay_export_i420, i420_from_bgr, frame_upload, pinned_frames, pinned_source_frames, pinned_nv12_frames, pinned_jpeg_buffers, frame_ring_store, frame_ring_select, frame_read, frame_upload_next,
-               _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms,
+               _jpeg_out, frame_encode_jpeg, jpeg_encode_bgr, jpeg_encode_stream_ms, frame_encode_regions, _encode_regions_call,
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms, frame_render_redacted, redact_stream_ms,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
@@ -1051,6 +1142,8 @@ def _bind_device_io(cls):
                ssd_configure, ssd_detect_async, ssd_stage_ms, ssd_preprocess_only, ssd_detect_sync, ssd_postprocess_host_heads,
                extract_configure, extract_async, extract_sync, extract_read_input):
         setattr(cls, fn.__name__, fn)
+    # what frame_encode_regions hands to ONE library call at most (the library's limits)
+    cls.OBJENC_CHUNK_REGIONS, cls.OBJENC_CHUNK_MCUS = FM_OBJENC_MAX_REGIONS, FM_OBJENC_MAX_MCUS
 
 
 _bind_device_io(HipContext)

@@ -14,7 +14,13 @@
 // bits kept between the passes, output scaled by 8), division by 8 x the quantisation value rounded half away from zero;
 // a luma block that lies wholly outside the image's own block grid is a dummy: AC zero, DC that of the block before it.
 //
-// Five launches on the encoder's own stream:
+// ONE set of kernels serves the whole frame and the object crops of fm_frame_encode_regions (many images of different
+// sizes in one pass).  Each kernel is a template over a MAP that says where an index of its launch lies: FrameMap, one
+// image found by index arithmetic (no table, no upload: the code the whole-frame path always had), and TableMap, the
+// concatenation of all images' MCUs, blocks and MCU rows behind a per-row and a per-image table that
+// fm_jpeg_encode_regions_plan lays out on the host.  Everything per MCU, per block and per byte is the same text.
+//
+// Five launches on the encoder's own stream (TableMap: a sixth, tiny one, jpegenc_segoff_kernel, in front of the gather):
 //   jpegenc_fdct_kernel    one wavefront per MCU (four per workgroup): 16 x 16 pixels -> Y / Cb / Cr in LDS, chroma
 //                          averaged, 48 row passes and 48 column passes of the DCT on 48 lanes, quantisation; writes the
 //                          six blocks in coded order (Y00 Y01 Y10 Y11 Cb Cr), each in zig-zag order, 64 lanes x 2 bytes.
@@ -35,6 +41,8 @@
 #include "common.h"
 #include "jpegenc.h"
 
+const uint8_t* fm_overlay_buffer(fm_ctx* ctx);            // overlay.hip: the overlay picture of the current frame size, or null
+
 namespace {
 
 constexpr int BLK_STRIDE = 72;                // words of LDS per block (64 used): column reads of the six blocks spread over the banks
@@ -49,8 +57,88 @@ struct EncGeo {
     int W, H;
     long long pitch;          // bytes between rows of the source
     int mx, my;               // MCU grid
-    int real_bw, real_bh;     // luma blocks that hold image pixels: ceil(W / 8), ceil(H / 8)
     unsigned row_bytes;       // spacing of the rows in the unstuffed buffer (twice that in the stuffed one)
+};
+
+// Per-image and per-MCU-row tables of a call with many images (TableMap).  Rows are the unit everything but the DCT works
+// on, so a row carries what those kernels need and they never touch the image table.
+struct EncImg {
+    int32_t x0, y0;           // the crop's corner in the source picture
+    int32_t cw, ch;           // the crop's size in source pixels
+    int32_t W, H;             // the file's size: ceil(cw / shrink), ceil(ch / shrink)
+    int32_t mx;               // MCUs across
+    int32_t row0;             // its first row in the call
+};
+struct EncRow {
+    int32_t first_mcu;        // of the row in the call's MCU index space (strictly increasing: every row has an MCU)
+    int32_t img;
+    int32_t mx;               // MCUs of the row = of its image
+    uint32_t raw_off;         // of the row in the unstuffed buffer, bytes, a multiple of 16 (twice that in the stuffed one)
+};
+
+struct McuAt {                // what the DCT kernel needs to know about one MCU
+    const uint8_t* org;       // the image's first pixel in the source
+    int W, H;                 // the image's size (after `shrink`): edge replication, the chroma rule and the dummy blocks
+    int cw, ch;               // are all per IMAGE -- nothing here is the frame's
+    int mx, my;               // the MCU's place in its image
+};
+struct RowAt {                // ... and the other kernels about one MCU row
+    int nblk;                 // blocks of the row, 6 per MCU
+    size_t blk0;              // its first block in the call's block index space (coefficients, bit offsets)
+    size_t raw_off;
+};
+
+struct FrameMap {
+    static constexpr bool TABLE = false;
+    const uint8_t* src;
+    EncGeo g;
+    __device__ __forceinline__ long long pitch() const { return g.pitch; }
+    __device__ __forceinline__ int shrink() const { return 1; }
+    __device__ __forceinline__ int n_mcu() const { return g.mx * g.my; }
+    __device__ __forceinline__ long long n_blk() const { return (long long)6 * g.mx * g.my; }
+    __device__ __forceinline__ McuAt mcu_at(int mcu) const {
+        const int my = mcu / g.mx;
+        return {src, g.W, g.H, g.W, g.H, mcu - my * g.mx, my};
+    }
+    __device__ __forceinline__ RowAt row_at(int row) const { return {6 * g.mx, (size_t)row * (6 * g.mx), (size_t)row * g.row_bytes}; }
+    __device__ __forceinline__ int row_of_block(long long id) const { return (int)(id / (6 * g.mx)); }
+};
+
+struct TableMap {
+    static constexpr bool TABLE = true;
+    const uint8_t* src;
+    long long src_pitch;
+    const EncImg* imgs;
+    const EncRow* rows;
+    int n_rows, n_mcus, s;
+    __device__ __forceinline__ long long pitch() const { return src_pitch; }
+    __device__ __forceinline__ int shrink() const { return s; }
+    __device__ __forceinline__ int n_mcu() const { return n_mcus; }
+    __device__ __forceinline__ long long n_blk() const { return (long long)6 * n_mcus; }
+    // the last row that starts at or before `mcu` (mcu < n_mcus): the table is sorted, a dozen steps for thousands of rows
+    __device__ __forceinline__ int row_of_mcu(int mcu) const {
+        int lo = 0, hi = n_rows - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (rows[mid].first_mcu <= mcu)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        return lo;
+    }
+    __device__ __forceinline__ McuAt mcu_at(int mcu) const {
+        const int row = row_of_mcu(mcu);
+        const EncRow r = rows[row];
+        const EncImg im = imgs[r.img];
+        // x0 * 3 is an arbitrary byte offset: the pixels are fetched byte by byte, nothing assumes an alignment
+        return {src + (size_t)im.y0 * src_pitch + (size_t)im.x0 * 3, im.W, im.H, im.cw, im.ch, mcu - r.first_mcu, row - im.row0};
+    }
+    __device__ __forceinline__ RowAt row_at(int row) const {
+        const EncRow r = rows[row];
+        return {6 * r.mx, (size_t)6 * r.first_mcu, (size_t)r.raw_off};
+    }
+    __device__ __forceinline__ int row_of_block(long long id) const { return row_of_mcu((int)(id / 6)); }
 };
 
 struct EncQt {
@@ -90,13 +178,36 @@ __device__ __forceinline__ int quantise(int c, int q, int lim) {
     return c < 0 ? -m : m;
 }
 
-__global__ __launch_bounds__(WG) void jpegenc_fdct_kernel(const uint8_t* __restrict__ bgr, int16_t* __restrict__ coef, EncGeo g, EncQt qt) {
+// Pixel (X, Y) of an image as the DCT sees it.  shrink 1: the source pixel.  shrink s: the rounded mean (sum + n / 2) / n
+// per channel over the crop pixels [sX, sX + s) x [sY, sY + s) that lie inside the CROP (cw x ch) -- blocks at its right
+// and lower edge average fewer pixels, never the frame's beyond it.  No reduced picture is stored.
+template <class Map>
+__device__ __forceinline__ void fetch_bgr(const Map& m, const McuAt& a, int X, int Y, int& B, int& G, int& R) {
+    const int s = m.shrink();
+    if (!Map::TABLE || s == 1) {
+        const uint8_t* const p = a.org + (size_t)Y * m.pitch() + (size_t)X * 3;
+        B = p[0], G = p[1], R = p[2];
+        return;
+    }
+    const int x0 = X * s, x1 = min(x0 + s, a.cw), y0 = Y * s, y1 = min(y0 + s, a.ch);
+    int sb = 0, sg = 0, sr = 0;
+    for (int y = y0; y < y1; ++y) {
+        const uint8_t* p = a.org + (size_t)y * m.pitch() + (size_t)x0 * 3;
+        for (int x = x0; x < x1; ++x, p += 3) sb += p[0], sg += p[1], sr += p[2];
+    }
+    const int n = (x1 - x0) * (y1 - y0);
+    B = (sb + n / 2) / n, G = (sg + n / 2) / n, R = (sr + n / 2) / n;
+}
+
+template <class Map>
+__global__ __launch_bounds__(WG) void jpegenc_fdct_kernel(Map m, int16_t* __restrict__ coef, EncQt qt) {
     __shared__ int ws[(WG / 64) * MCU_WORDS];
     __shared__ int chroma[(WG / 64) * 2 * 256];
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int mcu = blockIdx.x * (WG / 64) + wave;
-    const bool active = mcu < g.mx * g.my;
-    const int my = active ? mcu / g.mx : 0, mx = active ? mcu - my * g.mx : 0;
+    const bool active = mcu < m.n_mcu();
+    const McuAt a = m.mcu_at(active ? mcu : 0);
+    const int my = a.my, mx = a.mx;
     int* const w = ws + wave * MCU_WORDS;
     int* const cbf = chroma + wave * 512;
     int* const crf = cbf + 256;
@@ -105,18 +216,16 @@ __global__ __launch_bounds__(WG) void jpegenc_fdct_kernel(const uint8_t* __restr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int p = i * 64 + l, py = p >> 4, px = p & 15;
-            const int gx = min(mx * 16 + px, g.W - 1), gy = min(my * 16 + py, g.H - 1);      // edge replication
-            const uint8_t* const s = bgr + (size_t)gy * g.pitch + (size_t)gx * 3;
-            int B = s[0], G = s[1], R = s[2];
+            // edge replication to the MCU grid: the IMAGE's last column / row (a crop's, not its neighbours in the frame)
+            const int gx = min(mx * 16 + px, a.W - 1), gy = min(my * 16 + py, a.H - 1);
+            int B, G, R;
+            fetch_bgr(m, a, gx, gy, B, G, R);
             const int Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
             w[((py >> 3) * 2 + (px >> 3)) * BLK_STRIDE + (py & 7) * 8 + (px & 7)] = Y - 128;
             // chroma rows below the image repeat the last AVERAGED row, i.e. the last PAIR of rows (libjpeg pads the
-            // chroma plane after the averaging); with an even height that is not the last row twice
-            const int gyc = min(min(my * 16 + py, ((g.H + 1) / 2 - 1) * 2 + (py & 1)), g.H - 1);
-            if (gyc != gy) {
-                const uint8_t* const sc = bgr + (size_t)gyc * g.pitch + (size_t)gx * 3;
-                B = sc[0], G = sc[1], R = sc[2];
-            }
+            // chroma plane after the averaging); with an even height that is not the last row twice.  The image's own H.
+            const int gyc = min(min(my * 16 + py, ((a.H + 1) / 2 - 1) * 2 + (py & 1)), a.H - 1);
+            if (gyc != gy) fetch_bgr(m, a, gx, gyc, B, G, R);
             cbf[p] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
             crf[p] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
         }
@@ -149,12 +258,13 @@ __global__ __launch_bounds__(WG) void jpegenc_fdct_kernel(const uint8_t* __restr
     }
     __syncthreads();
     if (!active) return;
-    // dummy luma blocks take the quantised DC of the block before them
+    // dummy luma blocks take the quantised DC of the block before them; which blocks hold pixels is the image's matter
+    const int real_bw = (a.W + 7) / 8, real_bh = (a.H + 7) / 8;
     int dc[4];
     bool dummy[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-        dummy[b] = mx * 2 + (b & 1) >= g.real_bw || my * 2 + (b >> 1) >= g.real_bh;
+        dummy[b] = mx * 2 + (b & 1) >= real_bw || my * 2 + (b >> 1) >= real_bh;
         dc[b] = dummy[b] ? dc[b > 0 ? b - 1 : 0] : quantise(w[b * BLK_STRIDE], qt.q[0], 1024);
     }
     const int n = ZIGZAG_DEV[l];
@@ -236,17 +346,22 @@ __device__ __forceinline__ unsigned wg_inclusive_scan(unsigned v, unsigned* buf)
     return buf[threadIdx.x];
 }
 
+template <class Map>
 __global__ __launch_bounds__(WG) void jpegenc_scan_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ tables,
                                                           uint32_t* __restrict__ bitoff, uint32_t* __restrict__ rowbits,
-                                                          uint8_t* __restrict__ raw, EncGeo g) {
+                                                          uint8_t* __restrict__ raw, Map m) {
     __shared__ uint32_t tab[2 * FM_JPEGENC_TABLE_WORDS];
     __shared__ unsigned sums[WG];
     load_tables(tables, tab);
-    const int row = blockIdx.x, nblk = 6 * g.mx, per = (nblk + WG - 1) / WG;
+    // A row is an MCU row of ONE image, so the DC predictors (dc_pred: zero at the row's first MCU) restart at every row
+    // of every image.  A row wider than 42 MCUs has more blocks than threads (per > 1), a 1-MCU image six blocks: the
+    // other threads carry a sum of zero through the scan.
+    const RowAt ra = m.row_at(blockIdx.x);
+    const int row = blockIdx.x, nblk = ra.nblk, per = (nblk + WG - 1) / WG;
     const int b0 = min((int)threadIdx.x * per, nblk), b1 = min(b0 + per, nblk);
-    const int16_t* const crow = coef + (size_t)row * nblk * 64;
-    uint32_t* const off = bitoff + (size_t)row * nblk;
-    uint32_t* const words = reinterpret_cast<uint32_t*>(raw + (size_t)row * g.row_bytes);
+    const int16_t* const crow = coef + ra.blk0 * 64;
+    uint32_t* const off = bitoff + ra.blk0;
+    uint32_t* const words = reinterpret_cast<uint32_t*>(raw + ra.raw_off);
     unsigned sum = 0;
     for (int b = b0; b < b1; ++b) {
         const uint32_t* const t = tab + (b % 6 >= 4 ? FM_JPEGENC_TABLE_WORDS : 0);
@@ -296,18 +411,23 @@ struct PackSink {
     }
 };
 
+template <class Map>
 __global__ __launch_bounds__(WG) void jpegenc_pack_kernel(const int16_t* __restrict__ coef, const uint32_t* __restrict__ tables,
                                                           const uint32_t* __restrict__ bitoff, const uint32_t* __restrict__ rowbits,
-                                                          uint8_t* __restrict__ raw, EncGeo g) {
+                                                          uint8_t* __restrict__ raw, Map m) {
     __shared__ uint32_t tab[2 * FM_JPEGENC_TABLE_WORDS];
     load_tables(tables, tab);
-    const int nblk = 6 * g.mx;
     const long long id = (long long)blockIdx.x * WG + threadIdx.x;
-    if (id >= (long long)nblk * g.my) return;
-    const int row = (int)(id / nblk), b = (int)(id - (long long)row * nblk);
-    const int16_t* const crow = coef + (size_t)row * nblk * 64;
+    if (id >= m.n_blk()) return;
+    // The atomicOr merges below stay inside the row's own buffer: rows never share a word, each starts on a 16-byte
+    // boundary of its own and is sized for its own width (fm_jpeg_encode_regions_plan), whichever image a neighbour
+    // thread's block belongs to.
+    const int row = m.row_of_block(id);
+    const RowAt ra = m.row_at(row);
+    const int nblk = ra.nblk, b = (int)(id - (long long)ra.blk0);
+    const int16_t* const crow = coef + ra.blk0 * 64;
     const uint32_t* const t = tab + (b % 6 >= 4 ? FM_JPEGENC_TABLE_WORDS : 0);
-    PackSink s(reinterpret_cast<uint32_t*>(raw + (size_t)row * g.row_bytes), bitoff[id]);
+    PackSink s(reinterpret_cast<uint32_t*>(raw + ra.raw_off), bitoff[id]);
     code_block(crow + (size_t)b * 64, dc_pred(crow, b), t, t + 16, s);
     if (b == nblk - 1) {
         const int pad = (int)(-rowbits[row] & 7u);
@@ -316,15 +436,17 @@ __global__ __launch_bounds__(WG) void jpegenc_pack_kernel(const int16_t* __restr
     s.finish();
 }
 
+template <class Map>
 __global__ __launch_bounds__(WG) void jpegenc_stuff_kernel(const uint8_t* __restrict__ raw, const uint32_t* __restrict__ rowbits,
                                                            uint8_t* __restrict__ stuffed, uint32_t* __restrict__ seg_len,
-                                                           uint32_t* __restrict__ seg_len_host, EncGeo g) {
+                                                           uint32_t* __restrict__ seg_len_host, Map m) {
     __shared__ unsigned sums[WG];
     const int row = blockIdx.x;
     const unsigned nbytes = (rowbits[row] + 7) >> 3, per = (nbytes + WG - 1) / WG;
     const unsigned i0 = min(threadIdx.x * per, nbytes), i1 = min(i0 + per, nbytes);
-    const uint8_t* const src = raw + (size_t)row * g.row_bytes;
-    uint8_t* const dst = stuffed + (size_t)row * g.row_bytes * 2;
+    const size_t raw_off = m.row_at(row).raw_off;
+    const uint8_t* const src = raw + raw_off;
+    uint8_t* const dst = stuffed + raw_off * 2;
     unsigned ff = 0;
     for (unsigned i = i0; i < i1; ++i) ff += src[i] == 0xFF;
     const unsigned incl = wg_inclusive_scan(ff, sums);
@@ -337,19 +459,41 @@ __global__ __launch_bounds__(WG) void jpegenc_stuff_kernel(const uint8_t* __rest
     if (threadIdx.x == WG - 1) seg_len[row] = seg_len_host[row] = nbytes + incl;
 }
 
+// Where every segment starts in page-locked memory: the exclusive prefix sum of the lengths, each rounded up to 16.  One
+// workgroup, once per call with many images, so that the thousands of rows of such a call need not each sum the
+// lengths of all rows before them as the rows of one frame do in jpegenc_gather_kernel.
+__global__ __launch_bounds__(WG) void jpegenc_segoff_kernel(const uint32_t* __restrict__ seg_len, uint32_t* __restrict__ seg_off, int n_rows) {
+    __shared__ unsigned sums[WG];
+    const int per = (n_rows + WG - 1) / WG;
+    const int r0 = min((int)threadIdx.x * per, n_rows), r1 = min(r0 + per, n_rows);
+    unsigned sum = 0;
+    for (int r = r0; r < r1; ++r) sum += (seg_len[r] + 15u) & ~15u;
+    unsigned at = wg_inclusive_scan(sum, sums) - sum;
+    for (int r = r0; r < r1; ++r) {
+        seg_off[r] = at;
+        at += (seg_len[r] + 15u) & ~15u;
+    }
+}
+
+template <class Map>
 __global__ __launch_bounds__(WG) void jpegenc_gather_kernel(const uint8_t* __restrict__ stuffed, const uint32_t* __restrict__ seg_len,
-                                                            uint8_t* __restrict__ segs_host, EncGeo g) {
+                                                            const uint32_t* __restrict__ seg_off, uint8_t* __restrict__ segs_host, Map m) {
     __shared__ unsigned long long part[WG];
     const int row = blockIdx.x;
-    unsigned long long before = 0;
-    for (int r = threadIdx.x; r < row; r += WG) before += (seg_len[r] + 15u) & ~15u;
-    part[threadIdx.x] = before;
-    __syncthreads();
-    for (int d = WG / 2; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) part[threadIdx.x] += part[threadIdx.x + d];
+    if (Map::TABLE) {
+        if (threadIdx.x == 0) part[0] = seg_off[row];
         __syncthreads();
+    } else {
+        unsigned long long before = 0;
+        for (int r = threadIdx.x; r < row; r += WG) before += (seg_len[r] + 15u) & ~15u;
+        part[threadIdx.x] = before;
+        __syncthreads();
+        for (int d = WG / 2; d > 0; d >>= 1) {
+            if ((int)threadIdx.x < d) part[threadIdx.x] += part[threadIdx.x + d];
+            __syncthreads();
+        }
     }
-    const uint4* const src = reinterpret_cast<const uint4*>(stuffed + (size_t)row * g.row_bytes * 2);
+    const uint4* const src = reinterpret_cast<const uint4*>(stuffed + m.row_at(row).raw_off * 2);
     uint4* const dst = reinterpret_cast<uint4*>(segs_host + part[0]);
     const unsigned n16 = (seg_len[row] + 15u) >> 4;
     for (unsigned i = threadIdx.x; i < n16; i += WG) dst[i] = src[i];
@@ -362,9 +506,10 @@ struct EncState {
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
     bool timed = false;
     uint32_t* tables = nullptr;
-    int cap_mx = 0, cap_my = 0;           // what the buffers below were sized for
+    // what the buffers below were sized for: MCUs (coefficients, bit offsets), MCU rows (lengths), bytes of unstuffed rows
+    size_t cap_mcus = 0, cap_rows = 0, cap_raw = 0;
     int16_t* coef = nullptr;
-    uint32_t *bitoff = nullptr, *rowbits = nullptr, *seg_len = nullptr;
+    uint32_t *bitoff = nullptr, *rowbits = nullptr, *seg_len = nullptr, *seg_off = nullptr;
     uint8_t *raw = nullptr, *stuffed = nullptr;
     uint32_t* seg_len_host = nullptr;     // page-locked
     uint8_t* segs_host = nullptr;         // page-locked
@@ -372,21 +517,25 @@ struct EncState {
     uint8_t* stage = nullptr;             // fm_jpeg_encode_bgr: the pixels on the device ...
     uint8_t* stage_host = nullptr;        // ... and page-locked on the host
     size_t stage_cap = 0;
+    DevBuf tab;                           // fm_frame_encode_regions: the image and row tables, staged page-locked
+    std::vector<fm_crop_plan> plans;
 };
 
 namespace {
 
 void free_buffers(EncState* e) {
-    for (void* p : {(void*)e->coef, (void*)e->bitoff, (void*)e->rowbits, (void*)e->seg_len, (void*)e->raw, (void*)e->stuffed})
+    for (void* p : {(void*)e->coef, (void*)e->bitoff, (void*)e->rowbits, (void*)e->seg_len, (void*)e->seg_off, (void*)e->raw, (void*)e->stuffed})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)e->seg_len_host, (void*)e->segs_host})
         if (p) (void)hipHostFree(p);
-    e->coef = nullptr, e->bitoff = e->rowbits = e->seg_len = e->seg_len_host = nullptr, e->raw = e->stuffed = e->segs_host = nullptr;
-    e->cap_mx = e->cap_my = 0;
+    e->coef = nullptr, e->bitoff = e->rowbits = e->seg_len = e->seg_off = e->seg_len_host = nullptr, e->raw = e->stuffed = e->segs_host = nullptr;
+    e->cap_mcus = e->cap_rows = e->cap_raw = 0;
     e->segs_bytes = 0;
 }
 
-int ensure(fm_ctx* ctx, int mx, int my) {
+// The encoder's stream and tables (first use), and working buffers for a call of `mcus` MCUs in `rows` MCU rows whose
+// unstuffed row buffers take `raw_bytes` together (0, 0, 0: the stream alone).  Each of the three only ever grows.
+int ensure(fm_ctx* ctx, size_t mcus, size_t rows, size_t raw_bytes) {
     if (!ctx->enc) {                    // published only once everything in it exists
         EncState* e = new EncState;
         uint32_t host[2 * FM_JPEGENC_TABLE_WORDS];
@@ -408,21 +557,52 @@ int ensure(fm_ctx* ctx, int mx, int my) {
         ctx->enc = e;
     }
     EncState* e = ctx->enc;
-    if (mx <= e->cap_mx && my <= e->cap_my) return 0;
+    if (mcus <= e->cap_mcus && rows <= e->cap_rows && raw_bytes <= e->cap_raw) return 0;
     FM_HIP(hipStreamSynchronize(e->s));
-    const int cx = mx > e->cap_mx ? mx : e->cap_mx, cy = my > e->cap_my ? my : e->cap_my;
+    const size_t cm = mcus > e->cap_mcus ? mcus : e->cap_mcus, cr = rows > e->cap_rows ? rows : e->cap_rows;
+    const size_t cb = raw_bytes > e->cap_raw ? raw_bytes : e->cap_raw;
     free_buffers(e);
-    const size_t nblk = (size_t)6 * cx * cy, row_bytes = fm_jpegenc_row_bytes(cx);
+    const size_t nblk = 6 * cm;
     FM_HIP(hipMalloc(&e->coef, nblk * 64 * sizeof(int16_t)));
     FM_HIP(hipMalloc(&e->bitoff, nblk * sizeof(uint32_t)));
-    FM_HIP(hipMalloc(&e->rowbits, (size_t)cy * sizeof(uint32_t)));
-    FM_HIP(hipMalloc(&e->seg_len, (size_t)cy * sizeof(uint32_t)));
-    FM_HIP(hipMalloc(&e->raw, row_bytes * cy));
-    FM_HIP(hipMalloc(&e->stuffed, 2 * row_bytes * cy));
-    FM_HIP(hipHostMalloc(&e->seg_len_host, (size_t)cy * sizeof(uint32_t), hipHostMallocDefault));
-    FM_HIP(hipHostMalloc(&e->segs_host, 2 * row_bytes * cy, hipHostMallocDefault));
-    e->segs_bytes = 2 * row_bytes * cy;
-    e->cap_mx = cx, e->cap_my = cy;
+    FM_HIP(hipMalloc(&e->rowbits, cr * sizeof(uint32_t)));
+    FM_HIP(hipMalloc(&e->seg_len, cr * sizeof(uint32_t)));
+    FM_HIP(hipMalloc(&e->seg_off, cr * sizeof(uint32_t)));
+    FM_HIP(hipMalloc(&e->raw, cb));
+    FM_HIP(hipMalloc(&e->stuffed, 2 * cb));
+    FM_HIP(hipHostMalloc(&e->seg_len_host, cr * sizeof(uint32_t), hipHostMallocDefault));
+    FM_HIP(hipHostMalloc(&e->segs_host, 2 * cb, hipHostMallocDefault));
+    e->segs_bytes = 2 * cb;
+    e->cap_mcus = cm, e->cap_rows = cr, e->cap_raw = cb;
+    return 0;
+}
+
+int ensure_frame(fm_ctx* ctx, int mx, int my) { return ensure(ctx, (size_t)mx * my, (size_t)my, fm_jpegenc_row_bytes(mx) * my); }
+
+// The launches of one call over `m`, between the two timing events; `rows` MCU rows in all.
+template <class Map>
+int launch_all(EncState* e, const Map& m, long long n_mcu, int rows, const EncQt& qt) {
+    const long long nblk = 6 * n_mcu;
+    hipStream_t s = e->s;
+    FM_HIP(hipEventRecord(e->ev_t0, s));
+    hipLaunchKernelGGL(jpegenc_fdct_kernel<Map>, dim3((unsigned)((n_mcu + WG / 64 - 1) / (WG / 64))), dim3(WG), 0, s, m, e->coef, qt);
+    FM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(jpegenc_scan_kernel<Map>, dim3(rows), dim3(WG), 0, s, e->coef, e->tables, e->bitoff, e->rowbits, e->raw, m);
+    FM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(jpegenc_pack_kernel<Map>, dim3((unsigned)((nblk + WG - 1) / WG)), dim3(WG), 0, s, e->coef, e->tables, e->bitoff,
+                       e->rowbits, e->raw, m);
+    FM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(jpegenc_stuff_kernel<Map>, dim3(rows), dim3(WG), 0, s, e->raw, e->rowbits, e->stuffed, e->seg_len, e->seg_len_host, m);
+    FM_HIP(hipGetLastError());
+    if (Map::TABLE) {
+        hipLaunchKernelGGL(jpegenc_segoff_kernel, dim3(1), dim3(WG), 0, s, e->seg_len, e->seg_off, rows);
+        FM_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(jpegenc_gather_kernel<Map>, dim3(rows), dim3(WG), 0, s, e->stuffed, e->seg_len, e->seg_off, e->segs_host, m);
+    FM_HIP(hipGetLastError());
+    FM_HIP(hipEventRecord(e->ev_t1, s));
+    FM_HIP(hipStreamSynchronize(s));
+    e->timed = true;
     return 0;
 }
 
@@ -430,30 +610,15 @@ int ensure(fm_ctx* ctx, int mx, int my) {
 // on the encoder's stream completes, and returns once the file is in `out`.
 int encode(fm_ctx* ctx, const uint8_t* src, int width, int height, long long pitch, int quality, uint8_t* out, size_t capacity, size_t* length) {
     EncState* e = ctx->enc;
-    EncGeo g;
+    FrameMap m;
+    m.src = src;
+    EncGeo& g = m.g;
     g.W = width, g.H = height, g.pitch = pitch;
     g.mx = (width + 15) / 16, g.my = (height + 15) / 16;
-    g.real_bw = (width + 7) / 8, g.real_bh = (height + 7) / 8;
-    g.row_bytes = (unsigned)fm_jpegenc_row_bytes(e->cap_mx);       // (rows as wide as the buffers were sized for)
+    g.row_bytes = (unsigned)fm_jpegenc_row_bytes(g.mx);
     EncQt qt;
     if (int rc = fm_jpeg_encode_tables(quality, qt.q)) return rc;
-    const long long n_mcu = (long long)g.mx * g.my, nblk = 6 * n_mcu;
-    hipStream_t s = e->s;
-    FM_HIP(hipEventRecord(e->ev_t0, s));
-    hipLaunchKernelGGL(jpegenc_fdct_kernel, dim3((unsigned)((n_mcu + WG / 64 - 1) / (WG / 64))), dim3(WG), 0, s, src, e->coef, g, qt);
-    FM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(jpegenc_scan_kernel, dim3(g.my), dim3(WG), 0, s, e->coef, e->tables, e->bitoff, e->rowbits, e->raw, g);
-    FM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(jpegenc_pack_kernel, dim3((unsigned)((nblk + WG - 1) / WG)), dim3(WG), 0, s, e->coef, e->tables, e->bitoff, e->rowbits,
-                       e->raw, g);
-    FM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(jpegenc_stuff_kernel, dim3(g.my), dim3(WG), 0, s, e->raw, e->rowbits, e->stuffed, e->seg_len, e->seg_len_host, g);
-    FM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(jpegenc_gather_kernel, dim3(g.my), dim3(WG), 0, s, e->stuffed, e->seg_len, e->segs_host, g);
-    FM_HIP(hipGetLastError());
-    FM_HIP(hipEventRecord(e->ev_t1, s));
-    FM_HIP(hipStreamSynchronize(s));
-    e->timed = true;
+    if (int rc = launch_all(e, m, (long long)g.mx * g.my, g.my, qt)) return rc;
     return fm_jpeg_encode_assemble(width, height, quality, e->seg_len_host, e->segs_host, e->segs_bytes, out, capacity, length);
 }
 
@@ -468,6 +633,7 @@ void fm_jpegenc_free(fm_ctx* ctx) {
     if (!e) return;
     if (e->s) (void)hipStreamSynchronize(e->s);
     free_buffers(e);
+    e->tab.release();
     if (e->tables) (void)hipFree(e->tables);
     if (e->stage) (void)hipFree(e->stage);
     if (e->stage_host) (void)hipHostFree(e->stage_host);
@@ -479,17 +645,17 @@ void fm_jpegenc_free(fm_ctx* ctx) {
 }
 
 // For overlay.hip, which renders on the encoder's stream and encodes its own buffer
-int fm_jpegenc_ensure(fm_ctx* ctx, int mcus_x, int mcus_y) { return ensure(ctx, mcus_x, mcus_y); }
+int fm_jpegenc_ensure(fm_ctx* ctx, int mcus_x, int mcus_y) { return ensure_frame(ctx, mcus_x, mcus_y); }
 hipStream_t fm_jpegenc_stream(fm_ctx* ctx) { return ctx->enc ? ctx->enc->s : nullptr; }
 int fm_jpegenc_encode_device(fm_ctx* ctx, const uint8_t* src, int width, int height, int quality, uint8_t* out, size_t capacity, size_t* length) {
     FM_CHECK_ARG(args_ok(width, height, quality));
-    if (int rc = ensure(ctx, (width + 15) / 16, (height + 15) / 16)) return rc;
+    if (int rc = ensure_frame(ctx, (width + 15) / 16, (height + 15) / 16)) return rc;
     return encode(ctx, src, width, height, (long long)width * 3, quality, out, capacity, length);
 }
 
 extern "C" int fm_frame_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size_t capacity, size_t* length) {
     FM_CHECK_ARG(ctx && out && length && ctx->frame_cur && args_ok(ctx->frame_w, ctx->frame_h, quality));
-    if (int rc = ensure(ctx, (ctx->frame_w + 15) / 16, (ctx->frame_h + 15) / 16)) return rc;
+    if (int rc = ensure_frame(ctx, (ctx->frame_w + 15) / 16, (ctx->frame_h + 15) / 16)) return rc;
     // No event of the pipeline is waited for: the current frame is complete on the device, as the host sees it, when
     // the call that made it current returned.  fm_frame_upload and its _nv12 / _jpeg / _src forms synchronise the stream
     // of their copy, conversion and resize; a ring frame was stored synchronously; fm_frame_promote_next synchronises
@@ -501,7 +667,7 @@ extern "C" int fm_frame_encode_jpeg(fm_ctx* ctx, int quality, uint8_t* out, size
 extern "C" int fm_jpeg_encode_bgr(fm_ctx* ctx, const uint8_t* pixels, int width, int height, size_t pitch, int quality, uint8_t* out,
                                   size_t capacity, size_t* length) {
     FM_CHECK_ARG(ctx && pixels && out && length && args_ok(width, height, quality) && pitch >= (size_t)width * 3);
-    if (int rc = ensure(ctx, (width + 15) / 16, (height + 15) / 16)) return rc;
+    if (int rc = ensure_frame(ctx, (width + 15) / 16, (height + 15) / 16)) return rc;
     EncState* e = ctx->enc;
     const size_t row = (size_t)width * 3, bytes = row * height;
     if (bytes > e->stage_cap) {
@@ -523,6 +689,69 @@ extern "C" int fm_jpeg_encode_bgr(fm_ctx* ctx, const uint8_t* pixels, int width,
     }
     FM_HIP(hipMemcpyAsync(e->stage, from, bytes, hipMemcpyHostToDevice, e->s));
     return encode(ctx, e->stage, width, height, (long long)row, quality, out, capacity, length);
+}
+
+extern "C" int fm_frame_encode_regions(fm_ctx* ctx, int which, const fm_crop_rect* rects, int n, int shrink, int quality, uint8_t* out,
+                                       size_t capacity, size_t* offsets) {
+    FM_CHECK_ARG(ctx && offsets && (which == FM_EXPORT_FRAME || which == FM_EXPORT_OVERLAY) && ctx->frame_cur &&
+                 args_ok(ctx->frame_w, ctx->frame_h, 1));
+    if (quality < 1 || quality > 100) {
+        fm_set_error("object encode: quality %d outside 1..100", quality);
+        return FM_ERR_ARG;
+    }
+    // Everything is refused here, before anything is enqueued: the list's own limits by the plan, then the frame's.
+    fm_crop_totals tot;
+    if (int rc = fm_jpeg_encode_regions_plan(rects, n, shrink, nullptr, &tot)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (rects[i].x1 >= ctx->frame_w || rects[i].y1 >= ctx->frame_h) {
+            fm_set_error("object encode: rectangle %d (%d, %d, %d, %d) reaches outside the %dx%d frame", i, rects[i].x0, rects[i].y0,
+                         rects[i].x1, rects[i].y1, ctx->frame_w, ctx->frame_h);
+            return FM_ERR_ARG;
+        }
+    const uint8_t* const src = which == FM_EXPORT_FRAME ? ctx->frame_cur : fm_overlay_buffer(ctx);
+    if (!src) {
+        fm_set_error("object encode: no overlay picture of the current frame size (fm_frame_render_overlay comes first)");
+        return FM_ERR_ARG;
+    }
+    if (n == 0) {
+        offsets[0] = 0;
+        return 0;
+    }
+    FM_CHECK_ARG(out);
+    if (capacity < tot.bound) {
+        fm_set_error("object encode: capacity %zu is below the bound of the %d files, %llu bytes (fm_jpeg_encode_regions_bound)", capacity, n,
+                     (unsigned long long)tot.bound);
+        return FM_ERR_ARG;
+    }
+    if (int rc = ensure(ctx, (size_t)tot.mcus, (size_t)tot.rows, (size_t)tot.raw_bytes)) return rc;
+    EncState* e = ctx->enc;
+    e->plans.resize(n);
+    if (int rc = fm_jpeg_encode_regions_plan(rects, n, shrink, e->plans.data(), &tot)) return rc;
+    // The tables: n images, then the rows.  The staging is free to rewrite: the call that used it last returned behind
+    // its synchronise (one that failed half way is waited for here).
+    FM_HIP(hipStreamSynchronize(e->s));
+    const size_t img_bytes = (((size_t)n * sizeof(EncImg)) + 15) & ~(size_t)15, all = img_bytes + (size_t)tot.rows * sizeof(EncRow);
+    if (int rc = e->tab.reserve(all)) return rc;
+    EncImg* const imgs = e->tab.host<EncImg>();
+    EncRow* const rows = reinterpret_cast<EncRow*>(e->tab.host<char>() + img_bytes);
+    for (int i = 0; i < n; ++i) {
+        const fm_crop_plan& p = e->plans[i];
+        imgs[i] = {rects[i].x0, rects[i].y0, rects[i].x1 - rects[i].x0 + 1, rects[i].y1 - rects[i].y0 + 1, p.width, p.height, p.mcus_x, p.first_row};
+        const uint32_t row_bytes = (uint32_t)fm_jpegenc_row_bytes(p.mcus_x);
+        for (int r = 0; r < p.mcus_y; ++r)
+            rows[p.first_row + r] = {p.first_mcu + r * p.mcus_x, i, p.mcus_x, (uint32_t)p.raw_offset + (uint32_t)r * row_bytes};
+    }
+    FM_HIP(hipMemcpyAsync(e->tab.d, e->tab.h, all, hipMemcpyHostToDevice, e->s));
+    TableMap m;
+    m.src = src, m.src_pitch = (long long)ctx->frame_w * 3;
+    m.imgs = e->tab.dev<EncImg>(), m.rows = reinterpret_cast<const EncRow*>(e->tab.dev<char>() + img_bytes);
+    m.n_rows = tot.rows, m.n_mcus = tot.mcus, m.s = shrink;
+    EncQt qt;
+    if (int rc = fm_jpeg_encode_tables(quality, qt.q)) return rc;
+    // fm_frame_encode_jpeg's argument for why the current frame is complete holds unchanged (no pipeline stream is waited
+    // for, frames prefetched for later steps lie in other slots); the overlay buffer was rendered on this very stream.
+    if (int rc = launch_all(e, m, tot.mcus, tot.rows, qt)) return rc;
+    return fm_jpeg_encode_regions_assemble(e->plans.data(), n, quality, e->seg_len_host, e->segs_host, e->segs_bytes, out, capacity, offsets);
 }
 
 extern "C" int fm_jpeg_encode_stream_ms(fm_ctx* ctx, float* ms) {

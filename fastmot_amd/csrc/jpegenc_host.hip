@@ -170,3 +170,96 @@ extern "C" int fm_jpeg_encode_assemble(int width, int height, int quality, const
     }
     return 0;
 }
+
+// ---- object crops: many images in one pass of the encoder (fm_frame_encode_regions, jpegenc.hip)
+extern "C" int fm_jpeg_encode_regions_plan(const fm_crop_rect* rects, int n, int shrink, fm_crop_plan* plans, fm_crop_totals* totals) {
+    if (n < 0 || (n > 0 && !rects) || !totals) {
+        fm_set_error("object encode: a null pointer or a negative count (n = %d)", n);
+        return FM_ERR_ARG;
+    }
+    if (shrink != 1 && shrink != 2 && shrink != 4) {
+        fm_set_error("object encode: shrink %d is not 1, 2 or 4", shrink);
+        return FM_ERR_ARG;
+    }
+    if (n > FM_OBJENC_MAX_REGIONS) {
+        fm_set_error("object encode: %d rectangles in one call, FM_OBJENC_MAX_REGIONS is %d", n, FM_OBJENC_MAX_REGIONS);
+        return FM_ERR_ARG;
+    }
+    long long mcus = 0, rows = 0;
+    uint64_t raw = 0, bound = 0;
+    for (int i = 0; i < n; ++i) {
+        const fm_crop_rect& r = rects[i];
+        if (r.x0 < 0 || r.y0 < 0 || r.x1 < r.x0 || r.y1 < r.y0 || (long long)r.x1 - r.x0 >= FM_SRC_MAX_DIM ||
+            (long long)r.y1 - r.y0 >= FM_SRC_MAX_DIM) {
+            fm_set_error("object encode: rectangle %d (%d, %d, %d, %d) is empty, negative or wider / higher than %d", i, r.x0, r.y0, r.x1,
+                         r.y1, FM_SRC_MAX_DIM);
+            return FM_ERR_ARG;
+        }
+        const int w = (r.x1 - r.x0 + shrink) / shrink, h = (r.y1 - r.y0 + shrink) / shrink;      // ceil((x1 - x0 + 1) / shrink)
+        const int mx = (w + 15) / 16, my = (h + 15) / 16;
+        if (plans) {
+            fm_crop_plan& p = plans[i];
+            p.width = w, p.height = h, p.mcus_x = mx, p.mcus_y = my;
+            p.first_mcu = (int32_t)mcus, p.first_block = (int32_t)(6 * mcus), p.first_row = (int32_t)rows, p.reserved = 0;
+            p.raw_offset = raw, p.bound = fm_jpeg_encode_bound(w, h);
+        }
+        mcus += (long long)mx * my, rows += my;
+        // every MCU row a buffer of its own, sized for ITS width and starting on a 16-byte boundary (fm_jpegenc_row_bytes
+        // is a multiple of 16): the pack kernel's atomicOr on a row's first and last word never meets another image's
+        raw += (uint64_t)fm_jpegenc_row_bytes(mx) * my;
+        bound += fm_jpeg_encode_bound(w, h);
+        if (mcus > FM_OBJENC_MAX_MCUS) {         // (checked inside the loop: the sums above stay far below 32 bits)
+            fm_set_error("object encode: the rectangles up to number %d take %lld MCUs, FM_OBJENC_MAX_MCUS is %d", i, mcus,
+                         FM_OBJENC_MAX_MCUS);
+            return FM_ERR_ARG;
+        }
+    }
+    totals->mcus = (int32_t)mcus, totals->blocks = (int32_t)(6 * mcus), totals->rows = (int32_t)rows, totals->reserved = 0;
+    totals->raw_bytes = raw, totals->bound = bound;
+    return 0;
+}
+
+extern "C" size_t fm_jpeg_encode_regions_bound(const fm_crop_rect* rects, int n, int shrink) {
+    fm_crop_totals t;
+    return fm_jpeg_encode_regions_plan(rects, n, shrink, nullptr, &t) ? 0 : (size_t)t.bound;
+}
+
+extern "C" int fm_jpeg_encode_regions_assemble(const fm_crop_plan* plans, int n, int quality, const uint32_t* seg_len, const uint8_t* segs,
+                                               size_t segs_bytes, uint8_t* out, size_t capacity, size_t* offsets) {
+    FM_CHECK_ARG(n >= 0 && offsets && (n == 0 || (plans && seg_len && segs && out)) && quality >= 1 && quality <= 100);
+    // The lengths came from device memory: fm_jpeg_encode_assemble's check, over all rows of all images, before anything
+    // is read.  The plans are checked with them -- rows numbered without gaps, sizes the header can state.
+    size_t at = 0;
+    int row = 0;
+    for (int i = 0; i < n; ++i) {
+        const fm_crop_plan& p = plans[i];
+        FM_CHECK_ARG(size_ok(p.width, p.height) && p.first_row == row && p.mcus_y == (p.height + 15) / 16);
+        for (int r = 0; r < p.mcus_y; ++r, ++row) {
+            if (!(at <= segs_bytes && seg_len[row] <= segs_bytes - at)) {
+                fm_set_error("object encode: the segment lengths do not fit the segment buffer (row %d of image %d: %u bytes at %zu of %zu)",
+                             r, i, seg_len[row], at, segs_bytes);
+                return FM_ERR_ARG;
+            }
+            at += ((size_t)seg_len[row] + 15) & ~(size_t)15;
+        }
+    }
+    Writer w{out, capacity};
+    at = 0, row = 0;
+    for (int i = 0; i < n; ++i) {
+        const fm_crop_plan& p = plans[i];
+        offsets[i] = w.n;
+        write_header(w, p.width, p.height, quality);
+        for (int r = 0; r < p.mcus_y; ++r, ++row) {
+            if (r) w.marker(0xD0 + ((r - 1) & 7));          // r counts inside the image: every file starts at RST0
+            w.put(segs + at, seg_len[row]);
+            at += ((size_t)seg_len[row] + 15) & ~(size_t)15;
+        }
+        w.marker(0xD9);
+    }
+    offsets[n] = w.n;
+    if (w.n > capacity) {
+        fm_set_error("object encode: the files need %zu bytes, the output holds %zu", w.n, capacity);
+        return FM_ERR_ARG;
+    }
+    return 0;
+}

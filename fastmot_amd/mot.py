@@ -20,9 +20,14 @@ from .utils import Profiler
 from .utils.source import SourceFrame
 from .utils.visualization import Visualizer
 from .utils.overlay import build_commands
-from .utils.redact import Redact, build_regions, redact_bgr
+from collections import namedtuple
+
+from .utils.redact import Redact, build_regions, redact_bgr, region_rect, clip_rect, part_fractions
 
 LOGGER = logging.getLogger(__name__)
+# One entry of MOT.encode_objects: the track's id and label, the clipped frame rectangle (x0, y0, x1, y1, inclusive) the
+# picture shows, the JPEG's (w, h) and the file's bytes
+ObjectImage = namedtuple('ObjectImage', 'trk_id label rect size data')
 _NATIVE_FLOW = True      # tests flip this to compare the native prediction worker with the Python-thread path
 
 
@@ -97,8 +102,9 @@ class MOT:
         asks for them; `step` itself draws nothing and the frame handed to it is not touched.
         `redact` (not in the reference; None, a utils.redact.Redact, or a dictionary of its settings -- `"redact": {...}`
         in `mot_cfg`): the tracked objects are pixelated, smoothed or painted over in EVERY picture this object hands out:
-        `render_frame()`, `encode_frame()` and `export_frame_i420()` always return the redacted picture (`overlays=False`
-        then means "redacted, nothing drawn"), made on the GPU inside the overlay pass (csrc/redact.hip, csrc/overlay.hip);
+        `render_frame()`, `encode_frame()`, `export_frame_i420()` and `encode_objects()` always return the redacted picture
+        (`overlays=False` then means "redacted, nothing drawn"; the object crops are cut from the redacted picture, never
+        from the tracker's frame), made on the GPU inside the overlay pass (csrc/redact.hip, csrc/overlay.hip);
         with `draw=True` the host frame is redacted in place before the overlays are drawn on it.  The regions are this
         step's detections and every active track, confirmed or not (utils.redact.Redact says how boxes become regions).
         NOT covered, by design: `tracker.ctx.frame_read()`, the caller's own frame (unless `draw=True` writes it) and
@@ -251,6 +257,50 @@ class MOT:
             self._render_overlay(drawn)
             return I420Image(ctx.overlay_export_i420(), self.size)
         return I420Image(ctx.frame_export_i420(), self.size)
+
+    def encode_objects(self, quality=85, part='box', margin=0.0, shrink=1, confirmed=True, classes=None, overlays=None):
+        """One small JPEG per tracked object of the last `step` -> list of ObjectImage(trk_id, label, rect, size, data), in
+        `tracker.tracks` order: an alarm thumbnail, a gallery image, a row of an event database.  All crops of the frame
+        are encoded in ONE pass of the GPU encoder from the frame the tracker holds there (ctx.frame_encode_regions;
+        csrc/jpegenc.hip): nothing is uploaded, only compressed bytes come back, the step's results and the frames
+        prefetched for the next steps are untouched.  `data` equals utils.jpeg.encode_bgr of the crop.
+
+        confirmed  True (default): the visible tracks (confirmed and active); False: every active track.
+        classes    labels to include (default None: every label).
+        part, margin  which part of a track's box is shown, as in utils.redact.Redact: 'box' (default), 'head' (the upper
+                   quarter, middle half: face-sized crops) or four fractions of the box; `margin` (default 0) widens it on
+                   every side.  The rectangle (utils.redact.region_rect) is clipped to the frame; a track whose rectangle
+                   misses the frame is omitted.
+        shrink     1 (default), 2 or 4: the crop is reduced by that factor first (block means); `size` says what came out.
+        overlays   (default: `gpu_draw`) crop the picture with the overlays of `render_frame` on it.  With
+                   MOT(redact=...) the crops are ALWAYS cut from the redacted picture, as `encode_frame` decides.
+        RuntimeError before the first step, ValueError for a bad quality, shrink, part or margin.  Valid until the next `step`."""
+        if not 1 <= int(quality) <= 100:
+            raise ValueError(f'quality {quality} outside 1..100')
+        if shrink not in _lib.OBJENC_SHRINKS:
+            raise ValueError(f'shrink {shrink!r}: one of {_lib.OBJENC_SHRINKS}')
+        fractions = part_fractions(part)
+        if not 0 <= float(margin) <= 4:
+            raise ValueError('margin outside 0..4')
+        if self.frame_count == 0:
+            raise RuntimeError('encode_objects needs a step before it')
+        classes = None if classes is None else frozenset(int(v) for v in classes)
+        picked = []
+        for track in self.tracker.tracks.values():
+            if not track.active or (confirmed and not track.confirmed) or (classes is not None and int(track.label) not in classes):
+                continue
+            rect = clip_rect(region_rect(track.tlbr, fractions, float(margin), self.size), self.size)
+            if rect is not None:
+                picked.append((track, rect))
+        drawn = self.gpu_draw if overlays is None else overlays
+        from_overlay = bool(drawn or self.redact is not None)
+        if from_overlay:
+            self._render_overlay(drawn)
+        files = self.tracker.ctx.frame_encode_regions(np.array([r for _, r in picked], np.int32).reshape(-1, 4), int(quality),
+                                                      shrink, overlay=from_overlay)
+        return [ObjectImage(track.trk_id, int(track.label), rect,
+                            (-(-(rect[2] - rect[0] + 1) // shrink), -(-(rect[3] - rect[1] + 1) // shrink)), data)
+                for (track, rect), data in zip(picked, files)]
 
     def render_frame(self):
         """The frame of the last `step` with the overlays of `visualizer_cfg` on it, as an HxWx3 uint8 BGR ndarray: what

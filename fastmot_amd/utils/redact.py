@@ -88,14 +88,19 @@ class Redact:
         raise TypeError('redact: None, a Redact, or a dictionary of its settings')
 
 
-def _region_of(tlbr, cfg, size):
+def region_rect(tlbr, fractions, margin, size):
+    """The pixel rectangle of a part of a box: `fractions` (left, top, right, bottom) of the box `tlbr` (inclusive corners),
+    widened by `margin` times the part's width / height on every side and rounded OUTWARDS (the class docstring above)
+    -> (x0, y0, x1, y1) with inclusive corners, or None for an empty or NaN box.  The rectangle may reach beyond the frame
+    of `size` (w, h); it is cut only where a side would exceed the library's limit.  One rule for what is redacted and for
+    what MOT.encode_objects crops (which then clips with `clip_rect`)."""
     x0, y0, x1, y1 = (float(v) for v in tlbr)
     w, h = x1 - x0 + 1, y1 - y0 + 1
     if not (w > 0 and h > 0):                      # (NaN as well)
         return None
-    fl, ft, fr, fb = cfg.fractions
+    fl, ft, fr, fb = fractions
     l, t, r, b = x0 + fl * w, y0 + ft * h, x0 + fr * w, y0 + fb * h
-    mx, my = cfg.margin * (r - l), cfg.margin * (b - t)
+    mx, my = margin * (r - l), margin * (b - t)
     corners = []
     for lo, hi, extent in ((l - mx, r + mx, size[0]), (t - my, b + my, size[1])):
         slack = (FM_SRC_MAX_DIM - extent) // 2     # the frame and this much on either side: a side within the limit
@@ -105,6 +110,35 @@ def _region_of(tlbr, cfg, size):
     (rx0, rx1), (ry0, ry1) = corners
     if rx1 < rx0 or ry1 < ry0:
         return None
+    return rx0, ry0, rx1, ry1
+
+
+def clip_rect(rect, size):
+    """A rectangle (inclusive corners, or None) cut to the frame of `size` (w, h) -> (x0, y0, x1, y1), or None when no pixel
+    of it lies inside the frame."""
+    if rect is None:
+        return None
+    x0, y0, x1, y1 = max(rect[0], 0), max(rect[1], 0), min(rect[2], size[0] - 1), min(rect[3], size[1] - 1)
+    return None if x1 < x0 or y1 < y0 else (x0, y0, x1, y1)
+
+
+def part_fractions(part):
+    """'box', 'head' or four fractions (left, top, right, bottom) of a box -> the fractions; ValueError otherwise."""
+    if isinstance(part, str):
+        if part not in PARTS:
+            raise ValueError(f'part {part!r}: one of {sorted(PARTS)} or four box fractions')
+        return PARTS[part]
+    fractions = tuple(float(v) for v in part)
+    if len(fractions) != 4 or not (0 <= fractions[0] < fractions[2] <= 1 and 0 <= fractions[1] < fractions[3] <= 1):
+        raise ValueError('part: (left, top, right, bottom) fractions with 0 <= left < right <= 1, 0 <= top < bottom <= 1')
+    return fractions
+
+
+def _region_of(tlbr, cfg, size):
+    rect = region_rect(tlbr, cfg.fractions, cfg.margin, size)
+    if rect is None:
+        return None
+    rx0, ry0, rx1, ry1 = rect
     side = max(rx1 - rx0 + 1, ry1 - ry0 + 1)
     cell = cfg.cell if cfg.cell is not None else min(256, max(2, -(-side // cfg.cells)))
     return rx0, ry0, rx1, ry1, cell

@@ -1038,6 +1038,70 @@ int fm_frame_export_i420(fm_ctx* ctx, int which, uint8_t* out, size_t capacity, 
 int fm_i420_from_bgr(fm_ctx* ctx, const uint8_t* pixels, int width, int height, size_t pitch, uint8_t* out, size_t capacity,
                      size_t* length);
 
+/* Tracked OBJECTS out as JPEG crops (no counterpart in the reference): many rectangles of the picture the context holds,
+ * each of its own size, become one baseline JPEG file each in ONE pass of the encoder -- the five launches of
+ * fm_frame_encode_jpeg (csrc/jpegenc.hip: the same kernels, instantiated over a table of images where the whole frame is
+ * one image found by index arithmetic), one small table upload and one prefix pass in front of the gather, one stream
+ * synchronise, and only compressed bytes cross to the host.  The number of launches does not depend on n.
+ * A rectangle has inclusive corners and lies inside the frame (the caller clips; utils/redact.py region_rect).  File i is
+ * byte for byte what fm_jpeg_encode_bgr writes for the pixels [y0, y1] x [x0, x1] of the picture: the crop's own last
+ * column / row is what pads it to the MCU grid, its own last averaged chroma row is what repeats below it, its dummy
+ * blocks follow from its own size, and its restart markers start at RST0.
+ * `shrink` s = 1, 2 or 4 reduces the crop first by an integer factor while the DCT kernel fetches its pixels (no reduced
+ * picture is stored): output pixel (X, Y) of a w x h crop is, per channel, (sum + n / 2) / n in integer division over the
+ * n crop pixels of [sX, sX + s) x [sY, sY + s) that lie inside the crop -- blocks at the right / lower edge average
+ * fewer --, and the file is ceil(w / s) x ceil(h / s).
+ * `which`: FM_EXPORT_FRAME, the current frame, or FM_EXPORT_OVERLAY, the overlay buffer after fm_frame_render_overlay /
+ * fm_frame_render_redacted.
+ *
+ * fm_jpeg_encode_regions_plan (no context, no GPU, any number of threads): the layout of one call.  The index spaces of
+ * the launches -- MCUs, 8 x 8 blocks (six per MCU) and MCU rows -- are the concatenation of all images' in list order;
+ * plans[i] says where image i starts in each, where its first row lies in the row buffer (every row on a 16-byte
+ * boundary of its own, sized for its own width, so that no two images share a word there) and what its file can take
+ * at most; *totals sums them.  plans may be null.  FM_ERR_ARG, with fm_last_error naming the limit, for n < 0, a null
+ * list with n > 0, a shrink other than 1 / 2 / 4, a rectangle with x0 < 0, y0 < 0, x1 < x0 or y1 < y0 or a side above
+ * FM_SRC_MAX_DIM, n > FM_OBJENC_MAX_REGIONS, or more than FM_OBJENC_MAX_MCUS MCUs in all.  The latter bounds the working
+ * memory of a call: about 7 KB per MCU (768 B coefficients, 24 B offsets, 1.25 KB unstuffed, 2.5 KB stuffed, 2.5 KB
+ * page-locked), 16384 MCUs -- two 1080p frames' worth -- about 75 MB of device and 41 MB of page-locked memory, 116 MB together.
+ * fm_jpeg_encode_regions_bound: the sum of the files' bounds (the capacity fm_frame_encode_regions asks for), 0 where
+ * the plan fails.
+ * fm_jpeg_encode_regions_assemble (no context, no GPU): the n files from the call's segments -- seg_len[r] bytes for
+ * global MCU row r, segment r at the sum of the lengths before it each rounded up to 16 inside segs[0, segs_bytes) --
+ * written one behind the other, file i at out[offsets[i], offsets[i + 1]).  Lengths that do not fit segs_bytes give
+ * FM_ERR_ARG before anything is read; nothing is written past out + capacity.
+ * fm_frame_encode_regions: plans, encodes and assembles.  Everything runs on the encoder's stream under
+ * fm_frame_encode_jpeg's rules: no pipeline stream waits or is waited for, frames prefetched for later steps are
+ * untouched, the call returns when the files are complete.  n == 0 succeeds with offsets[0] = 0 and enqueues nothing.
+ * FM_ERR_ARG, before anything is enqueued, for what the plan refuses, a rectangle that reaches outside the frame, a
+ * quality outside 1..100, an unknown `which`, no current frame / no overlay picture of the current frame size, a null
+ * pointer, or a capacity below fm_jpeg_encode_regions_bound.  Buffers grow on demand as fm_frame_encode_jpeg's do
+ * (they are the same buffers). */
+#define FM_OBJENC_MAX_REGIONS 1024
+#define FM_OBJENC_MAX_MCUS 16384
+typedef struct fm_crop_rect {
+    int32_t x0, y0, x1, y1;         /* inclusive corners, inside the frame */
+} fm_crop_rect;
+typedef struct fm_crop_plan {       /* 48 bytes */
+    int32_t width, height;          /* of the file: ceil(w / shrink), ceil(h / shrink) */
+    int32_t mcus_x, mcus_y;         /* its MCU grid */
+    int32_t first_mcu, first_block, first_row;   /* where it starts in the call's index spaces */
+    int32_t reserved;               /* 0 */
+    uint64_t raw_offset;            /* of its first MCU row in the row buffer, bytes (a multiple of 16) */
+    uint64_t bound;                 /* fm_jpeg_encode_bound(width, height) */
+} fm_crop_plan;
+typedef struct fm_crop_totals {     /* 32 bytes */
+    int32_t mcus, blocks, rows;
+    int32_t reserved;               /* 0 */
+    uint64_t raw_bytes;             /* of the row buffer */
+    uint64_t bound;                 /* sum of the files' bounds */
+} fm_crop_totals;
+size_t fm_jpeg_encode_regions_bound(const fm_crop_rect* rects, int n, int shrink);
+int fm_jpeg_encode_regions_plan(const fm_crop_rect* rects, int n, int shrink, fm_crop_plan* plans, fm_crop_totals* totals);
+int fm_jpeg_encode_regions_assemble(const fm_crop_plan* plans, int n, int quality, const uint32_t* seg_len, const uint8_t* segs,
+                                    size_t segs_bytes, uint8_t* out, size_t capacity, size_t* offsets);
+int fm_frame_encode_regions(fm_ctx* ctx, int which, const fm_crop_rect* rects, int n, int shrink, int quality, uint8_t* out,
+                            size_t capacity, size_t* offsets);
+
 /* ---------------------------------------------------------------- detector ------------ */
 #define FM_MAX_HEADS 4
 #define FM_MAX_ANCHORS 6   /* yolo_layer.h:11 */
