@@ -1475,7 +1475,13 @@ __device__ long long g_gftt_stamps[64][8];
 #else
 #define GFTT_STAMP(i)
 #endif
-constexpr int GFTT_MAX_CAND = 4096;      // sorted in LDS (32 KB)
+// Candidates sorted in LDS (32 KB).  A crop with more local maxima above the quality threshold (about 400 x 300 px of
+// texture and larger) keeps its GFTT_MAX_CAND strongest ones; the greedy selection then equals goodFeaturesToTrack as
+// long as it ends (maxCorners reached, or the list exhausted) before it would look at the 4097th strongest candidate.
+// A large minDistance on such a crop reaches further (640 x 360 of dense texture, minDistance 29, maxCorners 1000:
+// rank 4756) and returns fewer corners than OpenCV would.  DESIGN.md section 7.
+constexpr int GFTT_MAX_CAND = 4096;
+constexpr int GFTT_MAX_CORNERS = 1024;   // accepted corners of one crop (acc_x / acc_y in LDS): the range of maxCorners
 constexpr int GFTT_MAX_CELLS = 1536;     // x 4 slots x 4 B = 24 KB
 constexpr int GFTT_BLK = 1024;
 
@@ -1524,23 +1530,56 @@ __global__ __launch_bounds__(GFTT_BLK) FM_SGPR_CAP void gftt_select_kernel(const
     GFTT_STAMP(1)
     // candidates: local maxima with val > thr.  key = (float bits of val << 32) | raster index : descending 64-bit
     // order == (val desc, index desc), the order of std::sort(..., greaterThanPtr) in featureselect.cpp
-    for (int base = 0; base < ntiles; base += GFTT_BLK) {
-        __syncthreads();
-        s_tcnt[tid] = base + tid < ntiles ? (int)ts[base + tid].y : 0;
-        __syncthreads();
-        const int nt = min(GFTT_BLK, ntiles - base);
-        for (int q = tid; q < nt * 64; q += GFTT_BLK) {                   // 64 slots per tile and step; a tile rarely has more
-            const int tl = q >> 6, cnt = s_tcnt[tl];
-            const unsigned long long* cl = cand + (c.eig_off + base + tl) * EIG_TPX;
-            for (int e = q & 63; e < cnt; e += 64) {
-                const unsigned long long k = cl[e];
-                if (!(__uint_as_float((unsigned)(k >> 32)) > thr)) continue;
-                const int slot = atomicAdd(&s_n, 1);
-                if (slot < GFTT_MAX_CAND) keys[slot] = k;
+    auto collect = [&](float th) {
+        for (int base = 0; base < ntiles; base += GFTT_BLK) {
+            __syncthreads();
+            s_tcnt[tid] = base + tid < ntiles ? (int)ts[base + tid].y : 0;
+            __syncthreads();
+            const int nt = min(GFTT_BLK, ntiles - base);
+            for (int q = tid; q < nt * 64; q += GFTT_BLK) {               // 64 slots per tile and step; a tile rarely has more
+                const int tl = q >> 6, cnt = s_tcnt[tl];
+                const unsigned long long* cl = cand + (c.eig_off + base + tl) * EIG_TPX;
+                for (int e = q & 63; e < cnt; e += 64) {
+                    const unsigned long long k = cl[e];
+                    if (!(__uint_as_float((unsigned)(k >> 32)) > th)) continue;
+                    const int slot = atomicAdd(&s_n, 1);
+                    if (slot < GFTT_MAX_CAND) keys[slot] = k;
+                }
             }
         }
+        __syncthreads();
+    };
+    collect(thr);
+    if (s_n > GFTT_MAX_CAND) {             // (uniform)
+        // More candidates than the sort holds.  The slots above were handed out in the order the wavefronts happened to
+        // run, so which candidates got one differs from call to call: collect again above a raised threshold, the
+        // smallest value that leaves at most GFTT_MAX_CAND candidates (bisection on the float bits -- the values are
+        // positive, so their bit patterns order like the values; ~25 counting passes over the tile lists, only here).
+        // What is kept is the strongest candidates, always the same ones; a selection that would walk past them ends
+        // early (see GFTT_MAX_CAND).
+        unsigned lo = __float_as_uint(thr), hi = __float_as_uint(mx);     // count(> lo) > GFTT_MAX_CAND, count(> hi) == 0
+        while (hi - lo > 1) {
+            const unsigned mid = lo + (hi - lo) / 2;
+            int above = 0;
+            for (int q = tid; q < ntiles * 64; q += GFTT_BLK) {
+                const int tl = q >> 6, cnt = (int)ts[tl].y;
+                const unsigned long long* cl = cand + (c.eig_off + tl) * EIG_TPX;
+                for (int e = q & 63; e < cnt; e += 64) above += (unsigned)(cl[e] >> 32) > mid ? 1 : 0;
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) above += __shfl_xor(above, off);
+            if ((tid & 63) == 0) s_tcnt[tid >> 6] = above;
+            __syncthreads();
+            int total = 0;
+#pragma unroll
+            for (int q = 0; q < GFTT_BLK / 64; ++q) total += s_tcnt[q];
+            __syncthreads();
+            if (total > GFTT_MAX_CAND) lo = mid; else hi = mid;           // (uniform)
+        }
+        __syncthreads();
+        if (tid == 0) s_n = 0;
+        collect(__uint_as_float(hi));      // (starts with a barrier)
     }
-    __syncthreads();
     GFTT_STAMP(2)
     const int n = min(s_n, GFTT_MAX_CAND);
     int np2 = 1;
@@ -1585,7 +1624,7 @@ __global__ __launch_bounds__(GFTT_BLK) FM_SGPR_CAP void gftt_select_kernel(const
     const int md = min_dist[needy ? c.k : t];
     const int gw = (c.w + md - 1) / md, gh = (c.h + md - 1) / md;
     const bool use_grid = gw * gh <= GFTT_MAX_CELLS;
-    __shared__ short acc_x[1024], acc_y[1024];
+    __shared__ short acc_x[GFTT_MAX_CORNERS], acc_y[GFTT_MAX_CORNERS];
     __shared__ int s_acc;
     __shared__ int s_surv[GFTT_BLK];
     __shared__ int s_wcnt[GFTT_BLK / 64];
@@ -1598,7 +1637,7 @@ __global__ __launch_bounds__(GFTT_BLK) FM_SGPR_CAP void gftt_select_kernel(const
     __syncthreads();
     const int md2 = md * md;
     const float inv_md = 1.f / (float)md;
-    const int limit = min(max_corners, 1024);
+    const int limit = min(max_corners, GFTT_MAX_CORNERS);     // (fm_flow_configure admits 1 .. GFTT_MAX_CORNERS)
     // is an accepted corner closer than minDistance?  (grid cells; the accepted list [0, nacc) when the grid does not fit LDS)
     auto blocked = [&](int x, int y, int nacc) -> bool {
         bool hit = false;
@@ -1953,6 +1992,12 @@ extern "C" int fm_flow_configure(fm_ctx* ctx, const fm_flow_cfg* cfg) {
     FM_CHECK_ARG(ctx && cfg && ctx->frame_w > 0);
     FM_CHECK_ARG((cfg->win_size == 3 || cfg->win_size == 5) && cfg->max_level >= 0 && cfg->max_level < MAX_LEVELS);   // LK window instances
     FM_CHECK_ARG(cfg->block_size == 3 || cfg->block_size == 5);
+    if (cfg->max_corners < 1 || cfg->max_corners > GFTT_MAX_CORNERS) {
+        // (OpenCV: maxCorners <= 0 = no limit.  gftt_select_kernel keeps the accepted corners of a crop in LDS.)
+        fm_set_error("maxCorners %d: the corner selection holds 1 .. %d corners per track", cfg->max_corners,
+                     GFTT_MAX_CORNERS);
+        return FM_ERR_ARG;
+    }
     FM_CHECK_ARG(ctx->frame_w <= 16384 && ctx->frame_h <= 16384);     // corner coordinates are packed as int16 pairs (gftt_select_kernel)
     FM_CHECK_ARG(cfg->gray_coeff_bits == 0 || cfg->gray_coeff_bits == 14 || cfg->gray_coeff_bits == 15);
     FM_HIP(hipDeviceSynchronize());

@@ -32,6 +32,10 @@ class Flow:
         applied and None keeps the defaults -- identical results for cfg/mot.json, whose LK
         parameters equal the defaults.
 
+        obj_feat_params / opt_flow_params: the library has kernels for winSize (3, 3) and (5, 5), maxLevel 0 .. 7,
+        blockSize 3 and 5 and maxCorners 1 .. 1024 (OpenCV's "maxCorners <= 0 = no limit" included: refused, not
+        capped); anything else raises FastMOTHipError at `init`.
+
         gray_coeff_bits (not in the reference: there it is whatever the installed OpenCV does): fixed-point width of
         cv2.cvtColor(BGR2GRAY) -- 14 (B 1868, G 9617, R 4899: OpenCV's RGB2Gray<uchar> up to the 4.2 era, i.e. the
         4.1.1 the reference's Dockerfile pins) or 15 (3735 / 19235 / 9798: later 4.x).  The two differ by one grey

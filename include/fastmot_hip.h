@@ -1199,7 +1199,9 @@ typedef struct fm_flow_cfg {
     int32_t win_size, max_level, max_count;   /* cv2.calcOpticalFlowPyrLK winSize / maxLevel / criteria */
     double epsilon;
     int32_t fast_thresh;          /* bg_feat_thresh */
-    int32_t max_corners, block_size;
+    int32_t max_corners, block_size;   /* maxCorners 1 .. 1024 (OpenCV's "<= 0 = no limit" is refused with FM_ERR_ARG, as is
+                                        * anything above: the selection keeps a crop's accepted corners in LDS); blockSize 3 or 5.
+                                        * A crop with more than 4096 candidates keeps its 4096 strongest: DESIGN.md 7 */
     double quality_level;         /* obj_feat_params */
     int32_t gray_coeff_bits;      /* cv2.cvtColor(BGR2GRAY) fixed point: 14 = B 1868, G 9617, R 4899 (OpenCV <= 4.2-era
                                    * RGB2Gray<uchar>, what the reference's pinned 4.1.1 computes as far as it can be

@@ -102,7 +102,8 @@ class OracleFlow:
 
     def __init__(self, size, bg_scale=(0.1, 0.1), opt_scale=(0.5, 0.5), feat_density=0.005, feat_dist_factor=0.06,
                  ransac_max_iter=500, ransac_conf=0.99, max_error=100, inlier_thresh=4, bg_feat_thresh=10, cv_impl=None,
-                 gray_coeff_bits=None):
+                 gray_coeff_bits=None, max_corners=1000, quality_level=0.06, block_size=3, win=5, max_level=5,
+                 max_count=10, epsilon=0.03):
         self.cv = cv_impl if cv_impl is not None else cv      # cv_oracle (numpy) or c_baseline (compiled C)
         self.gray_bits = gray_coeff_bits                      # None = cv_oracle.GRAY_COEFF_BITS (14)
         self.size = size
@@ -114,6 +115,10 @@ class OracleFlow:
         self.bg_sz = (round(bg_scale[0] * size[0]), round(bg_scale[1] * size[1]))
         self.frame_rect = np.array([0., 0., size[0] - 1., size[1] - 1.])
         self.bg_keypoints = self.prev_bg_keypoints = np.empty((0, 2), np.float32)
+        # goodFeaturesToTrack / calcOpticalFlowPyrLK parameters (obj_feat_params / opt_flow_params of flow.py)
+        self.gftt_args = (max_corners, quality_level)
+        self.block_size = block_size
+        self.lk_args = (win, max_level, max_count, epsilon)
 
     def init(self, frame):
         self.prev_gray = self.cv.bgr2gray(frame, self.gray_bits)
@@ -134,7 +139,8 @@ class OracleFlow:
             kp = rect_filter(t.keypoints, ins, fg) if len(t.keypoints) else t.keypoints
             if len(kp) < self.feat_density * area:
                 md = feature_dist(area, self.feat_dist_factor)
-                kp = self.cv.good_features_to_track(self.prev_gray[ins[1]:ins[3] + 1, ins[0]:ins[2] + 1], tm, 1000, 0.06, md)
+                kp = self.cv.good_features_to_track(self.prev_gray[ins[1]:ins[3] + 1, ins[0]:ins[2] + 1], tm,
+                                                    *self.gftt_args, md, self.block_size)
                 if len(kp):
                     kp = ellipse_filter(kp, t.tlbr, ins[:2])
             all_prev.append(kp.astype(np.float32).reshape(-1, 2))
@@ -154,7 +160,7 @@ class OracleFlow:
         all_prev.append(kp)
         P = np.concatenate(all_prev).astype(np.float32)
         sp = P * np.array(self.opt_scale, np.float32)
-        C, st, err = self.cv.calc_optical_flow_pyr_lk(self.prev_small, small, sp)
+        C, st, err = self.cv.calc_optical_flow_pyr_lk(self.prev_small, small, sp, *self.lk_args)
         st = lk_status(st, err, self.max_error)
         C = unscale_pts(C, self.opt_scale, st)
         self.prev_gray, self.prev_small = gray, small

@@ -132,7 +132,10 @@ def _reflect(i, n):
     i = np.where(i < 0, -i, i)
     i = np.where(i >= n, 2 * n - 2 - i, i)
     i = np.where(i < 0, -i, i)
-    return i
+    # (a window that starts in [-win, n) on an axis longer than win is inside [0, n) by now.  The LK loop below evaluates all
+    # points at once, also those that have left the image and whose samples nobody uses: on a level of a few pixels
+    # their indices are still outside -- any valid index does for them)
+    return np.clip(i, 0, n - 1)
 
 
 def _descale(x, n):
