@@ -251,6 +251,19 @@ class HipContext:
         """Tunables of the context: 'zero_copy_tracks', 'host_lap_elems' (include/fastmot_hip.h)."""
         check(self.lib.fm_ctx_set_option(self._ctx, key.encode(), C.c_int(int(value))))
 
+    def get_option(self, key):
+        """The front-ahead options 'det_front_ahead', 'det_front_layers', 'det_front_stream' as they stand."""
+        v = C.c_int(0)
+        check(self.lib.fm_ctx_get_option(self._ctx, key.encode(), C.byref(v)))
+        return v.value
+
+    def front_info(self):
+        """-> (cut, bytes, passes): the detector network's front-ahead cut as prepared (0: none), the device memory it
+        costs, and the number of passes that ran a front so far (fm_net_front_info)."""
+        k, b, n = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+        check(self.lib.fm_net_front_info(self._ctx, C.byref(k), C.byref(b), C.byref(n)))
+        return k.value, b.value, n.value
+
     def trace_start(self, cap=20000):
         """Arms the library's stage-boundary event trace; -> host CLOCK_MONOTONIC ns of the trace's zero."""
         t0 = C.c_int64(0)

@@ -102,6 +102,12 @@ struct fm_ctx {
                                        // frame themselves (pixel_source.h); 0 = front-end kernel + input tensor (tests compare the two, A/B)
     int opt_net_timing = 0;            // "net_timing" = N: HIP events around the detector network on every N-th pass (fm_detect_net_ms); 0 = never
     int opt_nms_general = 0;           // "nms_path" = 1: always the three-kernel sort / bit matrix / scan path (tests, A/B)
+    // front-ahead (detect.hip detect_pass): the leading layers of a single-frame pass run on another stream beside the
+    // previous pass's tail
+    int opt_det_front_ahead = 1;       // "det_front_ahead": 0 off, 1 when a pass is still in flight on the detector stream, 2 always (tests)
+    int opt_det_front_layers = -1;     // "det_front_layers": 0 off, k the first k layers, -1 the rule (net.hip fm_net_front_prepare)
+    int opt_det_front_stream = 0;      // "det_front_stream": the stream that carries the front: 0 s_up, 1 s_ext
+    bool det_flush_deferred = false;   // a look-ahead upload left the pending post-processing to the pass that follows it
     int opt_lk_variant = 0;            // "lk_variant": diagnostic variants of the LK kernel (flow.hip lk_diag_kernel)
     void* predict_worker = nullptr;    // native KLT + Kalman worker thread of this context (flow_estimate.hip)
     hipStream_t s_main = nullptr;   // tracker kernels
@@ -332,6 +338,8 @@ bool fm_host_is_pinned(const void* p, size_t bytes);      // frames.hip: inside 
 // frames.hip: frees every format's staging, the off-size sources' and the correction map (no sync: the caller's) ...
 void fm_frame_staging_free(fm_ctx* ctx);
 void fm_frame_dev_free(fm_ctx* ctx);     // ... and destroys the device frames' events, waiting for the tickets' (fm_ctx_destroy)
+hipStream_t fm_det_front_stream(fm_ctx* ctx);   // detect.hip: the stream that carried a detector front last (nullptr: none)
+bool fm_det_defers_flush(fm_ctx* ctx);          // detect.hip: front-ahead on s_up -- the pending post-processing waits for the next pass's front
 int fm_det_flush_post(fm_ctx* ctx);      // detect.hip: enqueues the pending pass's post-processing; nothing without a detector
 int fm_jpeg_to_bgr(const uint8_t* stage, uint8_t* bgr, const struct fm_jpeg_info* info, hipStream_t s);   // jpeg.hip
 // fm_jpeg_info's description of a width x height frame with ncomp 1 or 3 and luma sampling hsamp0 x vsamp0 (jpeg_host.hip)

@@ -1,6 +1,7 @@
 // Context / device-resident track table management for libfastmot_hip.so.
 // Replaces the buffer + stream plumbing of fastmot/utils/inference.py:7-125 (HostDeviceMem,
 // TRTInference) with plain HIP: one ctx per video stream, four HIP streams, pinned mirrors.
+#include <algorithm>
 #include "common.h"
 void convd_set_cfg(int code);             // convd.hip
 #include <sched.h>
@@ -20,7 +21,7 @@ void fm_set_error(const char* fmt, ...) {
 extern "C" const char* fm_last_error(void) { return g_err; }
 
 extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* key, int value) {
-    FM_CHECK_ARG(ctx && key && value >= 0);
+    FM_CHECK_ARG(ctx && key && (value >= 0 || (value == -1 && !strcmp(key, "det_front_layers"))));
     if (!strcmp(key, "zero_copy_tracks")) ctx->opt_zero_copy_tracks = value;
     else if (!strcmp(key, "host_lap_elems")) ctx->opt_host_lap_elems = value;
     else if (!strcmp(key, "use_graphs")) ctx->opt_use_graphs = value;
@@ -30,6 +31,11 @@ extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* key, int value) {
     }
     else if (!strcmp(key, "fused_input")) ctx->opt_fused_input = value != 0;
     else if (!strcmp(key, "net_timing")) ctx->opt_net_timing = value;
+    else if (!strcmp(key, "det_front_ahead") || !strcmp(key, "det_front_stream")) {
+        FM_CHECK_ARG(value <= (key[10] == 'a' ? 2 : 1));
+        (key[10] == 'a' ? ctx->opt_det_front_ahead : ctx->opt_det_front_stream) = value;
+    }
+    else if (!strcmp(key, "det_front_layers")) ctx->opt_det_front_layers = value;
     else if (!strcmp(key, "lk_variant")) {
 #ifndef FM_DIAG
         if (value != 0) {
@@ -41,6 +47,19 @@ extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* key, int value) {
     }
     else {
         fm_set_error("unknown option '%s'", key);
+        return FM_ERR_ARG;
+    }
+    return 0;
+}
+
+// the front-ahead options as they stand (tests and A/B scripts put them back)
+extern "C" int fm_ctx_get_option(fm_ctx* ctx, const char* key, int* value) {
+    FM_CHECK_ARG(ctx && key && value);
+    if (!strcmp(key, "det_front_ahead")) *value = ctx->opt_det_front_ahead;
+    else if (!strcmp(key, "det_front_layers")) *value = ctx->opt_det_front_layers;
+    else if (!strcmp(key, "det_front_stream")) *value = ctx->opt_det_front_stream;
+    else {
+        fm_set_error("option '%s' cannot be read", key);
         return FM_ERR_ARG;
     }
     return 0;
@@ -125,6 +144,8 @@ extern "C" int fm_ctx_create(int device, fm_ctx** out) {
     if (const char* e = getenv("FASTMOT_HOST_LAP")) ctx->opt_host_lap_elems = atoi(e);
     if (const char* e = getenv("FASTMOT_GRAPHS")) ctx->opt_use_graphs = atoi(e);
     if (const char* e = getenv("FASTMOT_FUSED_INPUT")) ctx->opt_fused_input = atoi(e) != 0;
+    if (const char* e = getenv("FASTMOT_FRONT_AHEAD")) ctx->opt_det_front_ahead = std::min(std::max(atoi(e), 0), 2);
+    if (const char* e = getenv("FASTMOT_FRONT_STREAM")) ctx->opt_det_front_stream = atoi(e) == 1;
     // the detector network is the long, throughput-oriented stream; tracker / KLT / ReID launches are
     // short and latency critical (the host waits on them), so they get the higher priority
     int prio_lo = 0, prio_hi = 0;

@@ -70,6 +70,12 @@ struct DetState {
     hipStream_t s_fallback = nullptr;          // redo of a pass the greedy kernel declined (collect): NOT s_up, see there
     hipEvent_t ev0[NSLOT] = {}, ev1[NSLOT] = {};   // bracket the network launches (first slot of a pass)
     bool timed[NSLOT] = {};                        // ... of the passes that were timed (fm_ctx option "net_timing")
+    // front-ahead (detect_pass): a pass whose leading layers ran on another stream
+    hipEvent_t evf0[NSLOT] = {}, evf1[NSLOT] = {}; // bracket the front's launches on that stream (timed passes) ...
+    bool timed_front[NSLOT] = {};                  // ... when the timed pass in the slot had a front
+    hipEvent_t ev_front[2] = {};                   // front of the pass on buffer set i complete
+    int set_slot[2] = {-1, -1};                    // first slot of the pass that used buffer set i last: behind its ev_dec nothing
+                                                   // of that pass touches the set any more
     long n_passes = 0;
     int wr = 0, rd = 0, pending = 0, last = -1;   // slot written next / collected next / passes in flight / last collected
     uint8_t* label_mask = nullptr;
@@ -89,9 +95,11 @@ void fm_det_free(DetState* d) {
     for (int i = 0; i < DetState::NSLOT; ++i) {
         if (d->dets_host[i]) (void)hipHostFree(d->dets_host[i]);
         if (d->counters_host[i]) (void)hipHostFree(d->counters_host[i]);
-        for (hipEvent_t e : {d->ev_done[i], d->ev_dec[i], d->ev0[i], d->ev1[i]})
+        for (hipEvent_t e : {d->ev_done[i], d->ev_dec[i], d->ev0[i], d->ev1[i], d->evf0[i], d->evf1[i]})
             if (e) (void)hipEventDestroy(e);
     }
+    for (hipEvent_t e : d->ev_front)
+        if (e) (void)hipEventDestroy(e);
     delete d;
 }
 
@@ -861,6 +869,15 @@ __global__ __launch_bounds__(NG_T, 4) void nms_greedy_kernel(const float* __rest
     }
 }
 
+}  // namespace
+// front-ahead with the front on s_up, for a network that has a front: whoever would enqueue the pending post-processing
+// early leaves it to the next pass
+bool fm_det_defers_flush(fm_ctx* ctx) {
+    return ctx->det && ctx->det_net && ctx->det_net->front_k > 0 && ctx->opt_det_front_ahead && ctx->opt_det_front_layers &&
+           ctx->opt_det_front_stream == 0;
+}
+namespace {
+
 int ensure_det(fm_ctx* ctx) {
     if (ctx->det) return 0;
     ctx->det = new DetState();
@@ -886,6 +903,7 @@ int alloc_post(DetState* d, int cap, int nslot) {
     d->last = -1;
     d->post_pending = -1;
     d->post_pending_n = 0;
+    d->set_slot[0] = d->set_slot[1] = -1;       // (the callers left the detector's streams idle)
     for (int i = 0; i < nslot; ++i) {
         if (d->cand[i]) continue;                       // (a slot the shorter ring of the same capacity had already)
         FM_HIP(hipMalloc(&d->cand[i], sizeof(float) * 8 * cap));
@@ -902,7 +920,11 @@ int alloc_post(DetState* d, int cap, int nslot) {
         FM_HIP(hipEventCreateWithFlags(&d->ev_dec[i], hipEventDisableTiming));
         FM_HIP(hipEventCreate(&d->ev0[i]));
         FM_HIP(hipEventCreate(&d->ev1[i]));
+        FM_HIP(hipEventCreate(&d->evf0[i]));
+        FM_HIP(hipEventCreate(&d->evf1[i]));
     }
+    for (hipEvent_t& e : d->ev_front)
+        if (!e) FM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (!d->label_mask) FM_HIP(hipMalloc(&d->label_mask, 128));
     return 0;
 }
@@ -1063,8 +1085,18 @@ int collect(fm_ctx* ctx, DetState* d, hipStream_t s, fm_det48* out, int cap_out,
         return FM_ERR_STATE;
     }
     const int slot = d->rd;
-    int rc_f = flush_post(ctx, d);
-    if (rc_f) return rc_f;
+    // (With front-ahead on the post-processing stream a LATER pass's pending post-processing stays pending: it waits for
+    // that pass's decode, and the front of the pass after it, enqueued with the next look-ahead upload, belongs in front
+    // of it -- behind it the front starts when the running pass ends, which is no look-ahead at all.  Not when that later
+    // pass is complete already: the detector stream is not what bounds the step then, the next pass will not find it
+    // busy, and its post-processing should not wait for the next upload.)
+    bool later = d->post_pending >= 0 && (slot - d->post_pending + d->nslot) % d->nslot >= d->post_pending_n && fm_det_defers_flush(ctx);
+    if (later && hipEventQuery(d->ev_dec[d->post_pending]) == hipSuccess) later = false;
+    (void)hipGetLastError();                // (hipErrorNotReady is not an error)
+    if (!later) {
+        int rc_f = flush_post(ctx, d);
+        if (rc_f) return rc_f;
+    }
     FM_HIP(hipEventSynchronize(d->ev_done[slot]));
     if (d->counters_host[slot][3] != 0 && !d->counters_host[slot][1]) {
         // the greedy kernel did not take the pass -- more candidates than it was given LDS for (1), or more survivors than
@@ -1181,6 +1213,7 @@ int collect_tiles(fm_ctx* ctx, DetState* d, hipStream_t s, fm_det48* out, int ca
 
 // the look-ahead uploads of frames.hip call this once their copy is enqueued (see flush_post); nothing without a detector
 int fm_det_flush_post(fm_ctx* ctx) { return ctx->det ? flush_post(ctx, ctx->det) : 0; }
+hipStream_t fm_det_front_stream(fm_ctx* ctx) { return ctx->det_net ? ctx->det_net->front_stream : nullptr; }
 
 // ---------------------------------------------------------------------------------------- detector
 extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
@@ -1200,6 +1233,8 @@ extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
     DetState* d = ctx->det;
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_up));
+    if (int rc_n = fm_net_sync(ctx->det_net)) return rc_n;      // (a front on another stream)
+    d->set_slot[0] = d->set_slot[1] = -1;
     d->post_pending = -1;
     d->post_pending_n = 0;
     d->rd = d->wr;            // a new detector: nothing of the previous one is collected any more
@@ -1229,6 +1264,8 @@ extern "C" int fm_detect_configure_tiles(fm_ctx* ctx, int n_tiles, const int32_t
     }
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_up));
+    if (int rc_n = fm_net_sync(ctx->det_net)) return rc_n;      // (a front on another stream)
+    d->set_slot[0] = d->set_slot[1] = -1;
     d->post_pending = -1;
     d->post_pending_n = 0;
     d->rd = d->wr;            // (passes of the previous geometry are not collected any more)
@@ -1290,13 +1327,13 @@ extern "C" int fm_detect_preprocess_only(fm_ctx* ctx) {
     return enqueue_preprocess(ctx, ctx->det, ctx->det_net, det_source(ctx, ctx->det, &f, n), n);
 }
 
-static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n);
+static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n, bool look_ahead);
 
 extern "C" int fm_detect_async(fm_ctx* ctx) {
     FM_CHECK_ARG(ctx);
     const uint8_t* f = ctx->frame_cur;
     const hipEvent_t none = nullptr;
-    return detect_pass(ctx, &f, &none, 1);
+    return detect_pass(ctx, &f, &none, 1, false);     // (strictly sequential: never in two parts)
 }
 
 // detector on the prefetched next frame (fm_frame_upload_next / fm_frame_ring_select_next)
@@ -1333,13 +1370,13 @@ static int detect_ahead(fm_ctx* ctx, int n) {
         // a frame in its upload slot: the pass waits for that copy
         uploads[k - 1] = frames[k - 1] == fm_ahead_buf(ctx, k) ? fm_ahead_event(ctx, k) : nullptr;
     }
-    return detect_pass(ctx, frames, uploads, n);
+    return detect_pass(ctx, frames, uploads, n, true);
 }
 
 // One network pass at batch n over frames[0..n-1] (n = 1: the single-frame pass), decode of every image into slots
 // d->wr .. d->wr + n - 1, their post-processing left pending (flush_post).  A tiled detector takes ONE frame and runs the
 // pass at batch n_tiles over its tiles: from here on the tiles are the images of a batched pass.
-static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n) {
+static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n, bool look_ahead) {
     FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured && ctx->det_net);
     DetState* d = ctx->det;
     NetState* net = ctx->det_net;
@@ -1356,39 +1393,113 @@ static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent
     }
     FM_CHECK_ARG(n >= 1 && n <= FM_MAX_DET_BATCH && n <= net->max_batch);
     hipStream_t s = ctx->s_det;
-    fm_trace_mark(ctx, s, 10);
-    for (int i = 0; i < n_frames; ++i)
-        if (uploads[i]) FM_HIP(hipStreamWaitEvent(s, uploads[i], 0));
-    int rc = acquire_slots(ctx, d, s, n);
-    if (rc) return rc;
-    fm_trace_mark(ctx, s, 14);
-    const StemSrc src = det_source(ctx, d, frames, n);
+    int rc = 0;
     // Round 6: when the network begins with a stem convolution over its input tensor, that convolution computes the
     // resized / normalised pixels itself while it stages its patch (stemconv.hip, pixel_source.h): the preprocess launch
     // (15 us inside the pipeline, between two passes of the stream whose period is the step) and the input tensor's
     // write + read disappear.  Same functions, same values (tests/test_detect_gpu.py compares the head tensors).
     const bool fused = ctx->opt_fused_input && fm_net_stem_fusable(net, c.input_tensor);
+    // Front-ahead: nothing at the start of a pass depends on the previous pass, and the start is the part of a pass with
+    // more tiles than CUs while the end leaves most of the chip empty.  A single-frame pass that finds the
+    // previous one still in flight therefore runs its first K layers on another stream, behind its frame's copy only,
+    // and the detector stream carries the rest behind one event.  K = 0: the pass as it always was.
+    int K = 0;
+    if (ctx->det_flush_deferred && !(look_ahead && fused && n == 1 && !tiled)) {
+        ctx->det_flush_deferred = false;
+        if ((rc = flush_post(ctx, d))) return rc;
+    }
+    if (look_ahead && fused && n == 1 && !tiled && ctx->opt_det_front_ahead && ctx->opt_det_front_layers) {
+        bool busy = ctx->opt_det_front_ahead == 2;
+        if (!busy && d->pending > 0 && hipEventQuery(d->ev_dec[(d->wr + d->nslot - 1) % d->nslot]) != hipSuccess) {
+            (void)hipGetLastError();            // (hipErrorNotReady is not an error)
+            busy = true;
+        }
+        if (busy && (rc = fm_net_front_prepare(ctx, net, ctx->opt_det_front_layers, &K))) return rc;
+    }
+    if (ctx->det_flush_deferred && !K) {        // (what the upload would have done, in today's order)
+        ctx->det_flush_deferred = false;
+        if ((rc = flush_post(ctx, d))) return rc;
+    }
     // the event pair around the network is measurement, not product: two more packets on the stream whose period is the
     // step cost 1.2 % of the frame rate (profiles/r06_net_timing_events_ab.txt) -- recorded on every N-th pass only when
     // a caller asked for it (option "net_timing" = N; bench.py samples every 4th pass).  A batched pass carries them in
     // its first image's slot.
     const bool timing = ctx->opt_net_timing > 0 && d->n_passes++ % ctx->opt_net_timing == 0;
-    for (int i = 0; i < n; ++i) d->timed[(d->wr + i) % d->nslot] = timing && i == 0;
-    if (fused) {
-        if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
-        fm_trace_mark(ctx, s, 11);
-        if ((rc = fm_net_run_stem_from(ctx, net, src, n))) return rc;
-        fm_trace_mark(ctx, s, 15);
-        net->first = 1;
-        rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n);
-        net->first = 0;
-        if (rc) return rc;
-    } else {
-        if ((rc = enqueue_preprocess(ctx, d, net, src, n))) return rc;
-        if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
-        fm_trace_mark(ctx, s, 11);
-        if ((rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n))) return rc;
+    for (int i = 0; i < n; ++i) {
+        d->timed[(d->wr + i) % d->nslot] = timing && i == 0;
+        d->timed_front[(d->wr + i) % d->nslot] = timing && i == 0 && K > 0;
     }
+    struct Restore {        // whatever happens, the network is left on its own stream with its whole table
+        NetState* net;
+        ~Restore() { net->first = net->last = 0; fm_net_select(net, nullptr, net->set); }
+    } restore{net};
+    fm_trace_mark(ctx, s, 10);
+    if (K > 0) {
+        hipStream_t se = ctx->opt_det_front_stream == 1 ? ctx->s_ext : ctx->s_up;
+        const int set = net->set ^ 1;
+        if (net->front_stream && net->front_stream != se) FM_HIP(hipStreamSynchronize(net->front_stream));
+        net->front_stream = se;
+        ++net->front_passes;
+        // the frame: its copy was enqueued on s_ext (frames.hip into_ahead), in front of anything enqueued there now
+        if (uploads[0] && se != ctx->s_ext) FM_HIP(hipStreamWaitEvent(se, uploads[0], 0));
+        if ((rc = acquire_slots(ctx, d, se, 1))) return rc;    // (the first launch zeroes the slot's counters)
+        // the set's tensors: the pass that used them last -- two passes ago in a pipelined run, long complete -- is
+        // through with them behind its decode
+        if (d->set_slot[set] >= 0 && hipEventQuery(d->ev_dec[d->set_slot[set]]) != hipSuccess) {
+            (void)hipGetLastError();
+            FM_HIP(hipStreamWaitEvent(se, d->ev_dec[d->set_slot[set]], 0));
+        }
+        const StemSrc src = det_source(ctx, d, frames, n);
+        fm_net_select(net, se, set);
+        if (timing) FM_HIP(hipEventRecord(d->evf0[d->wr], se));
+        fm_trace_mark(ctx, se, 11);
+        if ((rc = fm_net_run_stem_from(ctx, net, src, n))) return rc;
+        fm_trace_mark(ctx, se, 15);
+        if (K > 1) {
+            net->first = 1;
+            net->last = K;
+            if ((rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n))) return rc;
+        }
+        if (timing) FM_HIP(hipEventRecord(d->evf1[d->wr], se));
+        fm_trace_mark(ctx, se, 16);
+        FM_HIP(hipEventRecord(d->ev_front[set], se));
+        // the previous pass's post-processing, which waits for that pass's decode, goes BEHIND the front when they share
+        // a stream (the look-ahead upload left it to this pass: frames.hip into_ahead)
+        if (ctx->det_flush_deferred) {
+            ctx->det_flush_deferred = false;
+            if ((rc = flush_post(ctx, d))) return rc;
+        }
+        fm_net_select(net, nullptr, set);
+        FM_HIP(hipStreamWaitEvent(s, d->ev_front[set], 0));     // (the only wait of the pass on the detector stream)
+        fm_trace_mark(ctx, s, 14);
+        if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
+        net->first = K;
+        net->last = 0;
+        if ((rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n))) return rc;
+        net->first = 0;
+    } else {
+        for (int i = 0; i < n_frames; ++i)
+            if (uploads[i]) FM_HIP(hipStreamWaitEvent(s, uploads[i], 0));
+        if ((rc = acquire_slots(ctx, d, s, n))) return rc;
+        fm_trace_mark(ctx, s, 14);
+        const StemSrc src = det_source(ctx, d, frames, n);
+        if (fused) {
+            if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
+            fm_trace_mark(ctx, s, 11);
+            if ((rc = fm_net_run_stem_from(ctx, net, src, n))) return rc;
+            fm_trace_mark(ctx, s, 15);
+            net->first = 1;
+            rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n);
+            net->first = 0;
+            if (rc) return rc;
+        } else {
+            if ((rc = enqueue_preprocess(ctx, d, net, src, n))) return rc;
+            if (timing) FM_HIP(hipEventRecord(d->ev0[d->wr], s));
+            fm_trace_mark(ctx, s, 11);
+            if ((rc = fm_net_run_internal(ctx, FM_NET_DETECTOR, n))) return rc;
+        }
+    }
+    d->set_slot[net->set] = d->wr;
     if (timing) FM_HIP(hipEventRecord(d->ev1[d->wr], s));
     fm_trace_mark(ctx, s, 12);
     FilterArgs fa = filter_args(d, d->wr);      // (counters were zeroed by this pass's preprocess / stem kernel)
@@ -1438,6 +1549,8 @@ extern "C" int fm_filter_dets(fm_ctx* ctx, const float* rows, int n, fm_det48* o
     hipStream_t s = ctx->s_det;
     FM_HIP(hipStreamSynchronize(s));
     FM_HIP(hipStreamSynchronize(ctx->s_up));
+    if (int rc_n = fm_net_sync(ctx->det_net)) return rc_n;      // (a front on another stream)
+    d->set_slot[0] = d->set_slot[1] = -1;
     d->post_pending = -1;
     d->post_pending_n = 0;
     d->rd = d->wr;            // (test hook: passes nobody collected are dropped; the streams are idle here)
@@ -1493,6 +1606,7 @@ extern "C" int fm_detect_raw_candidates(fm_ctx* ctx, float* rows, int cap, int* 
     if (rc_f) return rc_f;
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_up));
+    if (int rc_n = fm_net_sync(ctx->det_net)) return rc_n;
     const int slot = (d->wr + d->nslot - 1) % d->nslot;       // the pass enqueued last
     int32_t cnt[4];
     FM_HIP(hipMemcpy(cnt, d->counters[slot], sizeof(cnt), hipMemcpyDeviceToHost));
@@ -1511,5 +1625,12 @@ extern "C" int fm_detect_net_ms(fm_ctx* ctx, float* ms) {
     if (!ctx->det->timed[slot]) { *ms = -1.f; return 0; }       // (this pass was not timed: option "net_timing")
     FM_HIP(hipEventSynchronize(ctx->det->ev1[slot]));
     FM_HIP(hipEventElapsedTime(ms, ctx->det->ev0[slot], ctx->det->ev1[slot]));
+    if (ctx->det->timed_front[slot]) {
+        // a pass in two parts: the time of its launches is the sum of the two brackets -- the span from the front's first
+        // launch to the back's last would contain the wait for the previous pass
+        float front = 0.f;
+        FM_HIP(hipEventElapsedTime(&front, ctx->det->evf0[slot], ctx->det->evf1[slot]));
+        *ms += front;
+    }
     return 0;
 }

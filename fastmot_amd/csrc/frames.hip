@@ -80,6 +80,7 @@ static void remap_free(fm_ctx* ctx) {
 static int remap_idle(fm_ctx* ctx) {
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     FM_HIP(hipStreamSynchronize(ctx->s_ext));
+    if (fm_det_front_stream(ctx)) FM_HIP(hipStreamSynchronize(fm_det_front_stream(ctx)));
     FM_HIP(hipStreamSynchronize(nullptr));
     return 0;
 }
@@ -291,6 +292,7 @@ template <class Enqueue> static int into_current(fm_ctx* ctx, Enqueue enqueue) {
     FM_HIP(hipStreamSynchronize(ctx->s_ext));
     FM_HIP(hipStreamSynchronize(ctx->s_flow));
     FM_HIP(hipStreamSynchronize(ctx->s_flow2));
+    if (fm_det_front_stream(ctx)) FM_HIP(hipStreamSynchronize(fm_det_front_stream(ctx)));    // (a detector front reads its frame there)
     int rc = enqueue(Target{0, ctx->frame_own, ctx->s_det, ctx->frame_pinned, nullptr, false});
     if (rc) return rc;
     FM_HIP(hipStreamSynchronize(ctx->s_det));   // the other streams read the frame too (and a caller's memory has been read)
@@ -340,7 +342,11 @@ template <class Enqueue> static int into_ahead(fm_ctx* ctx, int k, Enqueue enque
     fm_trace_mark(ctx, cs, 31);
     if (!ev) FM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     FM_HIP(hipEventRecord(ev, cs));
-    if ((rc = fm_det_flush_post(ctx))) return rc;   // see flush_post (detect.hip)
+    // see flush_post (detect.hip).  With front-ahead on the post-processing stream the pass that follows this upload
+    // enqueues its front there first and the pending post-processing, which waits for the running pass, behind it.
+    if (k == 1 && fm_det_defers_flush(ctx))
+        ctx->det_flush_deferred = true;
+    else if ((rc = fm_det_flush_post(ctx))) return rc;
     fm_ahead_frame(ctx, k) = buf;
     return 0;
 }

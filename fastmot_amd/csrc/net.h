@@ -46,12 +46,39 @@ struct NetState {
     char* arena = nullptr;    // shared activation arena (tensors with offset >= 0)
     float* ws = nullptr;      // split-K partial sums (fp32)
     size_t ws_floats = 0;
-    std::vector<std::pair<long, hipGraphExec_t>> graphs;   // (batch, emb_offset) -> captured layer sequence
+    // what a captured layer sequence bakes in: batch and embedding offset, the layer range [first, last) and the buffer set
+    struct GraphKey {
+        long batch_emb;
+        int first, last, set;
+        bool operator==(const GraphKey& o) const { return batch_emb == o.batch_emb && first == o.first && last == o.last && set == o.set; }
+    };
+    std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;
     bool use_graphs = true;
     int emb_offset = 0;   // row offset of FM_OP_HEAD outputs in ctx->emb (batched extraction)
     int batch_offset = 0; // sample offset into the input tensor for chunked runs
     int first = 0;        // first layer fm_net_run executes: 1 when the caller has run layer 0 itself (fm_net_run_stem_from)
+    int last = 0;         // one past the last layer fm_net_run executes; 0: the end of the table
+    // ---- front-ahead (fm_net_front_prepare; detect.hip detect_pass): layers [0, front_k) of a pass may run on another
+    // stream while the previous pass still runs its tail.  Every tensor a front layer touches, the input excepted, lies
+    // outside the arena and exists twice: `bufs` holds the pointers of the selected set, `bufs_b` those of the other one
+    // (the two agree on every other tensor).  Passes alternate; a pass that is not split runs on the selected set.
+    int front_k = 0;                    // prepared cut (0: none prepared)
+    int front_req = 0;                  // the request it was prepared for (option "det_front_layers")
+    int set = 0;                        // the selected set (fm_net_select)
+    std::vector<void*> bufs_b;
+    std::vector<char> in_front;         // tensor lies in the two sets (and no longer in the arena / its own allocation)
+    std::vector<void*> front_owned;     // allocations of the two sets (freed with the network)
+    float* ws_b = nullptr;              // split-K partials of launches that do not run on `home`
+    size_t front_bytes = 0;             // what the above cost
+    hipStream_t home = nullptr;         // the stream the network was created on (`stream` is redirected for a front)
+    hipStream_t front_stream = nullptr; // stream that carried a front last (nullptr: none yet)
+    long front_passes = 0;              // passes that ran a front so far (fm_net_front_info)
 };
+
+int fm_net_front_prepare(fm_ctx* ctx, NetState* net, int request, int* k);
+// the launches that follow go to stream `s` (nullptr: the network's own) and use buffer set `set`
+void fm_net_select(NetState* net, hipStream_t s, int set);
+int fm_net_sync(NetState* net);
 
 NetState* fm_net_get(fm_ctx* ctx, int which);
 int fm_net_run_internal(fm_ctx* ctx, int which, int batch);

@@ -67,18 +67,47 @@ int fm_emb_reserve(fm_ctx* ctx, int n);
 void fm_net_free(NetState* n) {
     if (!n) return;
     for (size_t i = 0; i < n->bufs.size(); ++i)
-        if (n->bufs[i] && n->tensors[i].offset < 0) (void)hipFree(n->bufs[i]);
+        if (n->bufs[i] && n->tensors[i].offset < 0 && !(i < n->in_front.size() && n->in_front[i])) (void)hipFree(n->bufs[i]);
+    for (void* p : n->front_owned) (void)hipFree(p);
     if (n->arena) (void)hipFree(n->arena);
     if (n->weights) (void)hipFree(n->weights);
     if (n->gates) (void)hipFree(n->gates);
     if (n->ws) (void)hipFree(n->ws);
+    if (n->ws_b) (void)hipFree(n->ws_b);
     for (auto& g : n->graphs) (void)hipGraphExecDestroy(g.second);
     delete n;
+}
+
+// every launch of the network is complete: its own stream and the one that carried a front last (the back of a pass
+// waits for its front, so the network's stream alone covers every pass that was enqueued completely)
+int fm_net_sync(NetState* net) {
+    if (!net) return 0;
+    if (net->front_stream) FM_HIP(hipStreamSynchronize(net->front_stream));
+    FM_HIP(hipStreamSynchronize(net->home ? net->home : net->stream));
+    return 0;
+}
+
+void fm_net_select(NetState* net, hipStream_t s, int set) {
+    net->stream = s ? s : net->home;
+    if (set != net->set && !net->bufs_b.empty()) {
+        net->bufs.swap(net->bufs_b);
+        net->set = set;
+    }
 }
 
 static NetState*& net_slot(fm_ctx* ctx, int which) {
     return which == FM_NET_DETECTOR ? ctx->det_net : which == FM_NET_EXTRACTOR ? ctx->ext_net
                                                     : ctx->ext_net_x[which - FM_NET_EXTRACTOR_B];
+}
+// the detector network's front as it stands: the prepared cut (0: none), the device memory its two tensor sets and
+// partial-sum buffer cost, and how many passes have run a front so far
+extern "C" int fm_net_front_info(fm_ctx* ctx, int* k, long long* bytes, long long* passes) {
+    FM_CHECK_ARG(ctx && k && bytes && passes);
+    const NetState* net = ctx->det_net;
+    *k = net ? net->front_k : 0;
+    *bytes = net ? (long long)net->front_bytes : 0;
+    *passes = net ? (long long)net->front_passes : 0;
+    return 0;
 }
 NetState* fm_net_get(fm_ctx* ctx, int which) { return net_slot(ctx, which); }
 int fm_net_run_internal(fm_ctx* ctx, int which, int batch) { return fm_net_run(ctx, which, batch); }
@@ -86,9 +115,92 @@ int fm_net_run_internal(fm_ctx* ctx, int which, int batch) { return fm_net_run(c
 // captured graphs bake the pointers their layers were launched with: whoever re-allocates one of those drops the graphs
 void fm_net_drop_graphs(NetState* net) {
     if (!net) return;
-    (void)hipStreamSynchronize(net->stream);
-    for (auto& g : net->graphs) (void)hipGraphExecDestroy(g.second);
+    (void)fm_net_sync(net);
+    for (auto& g : net->graphs) (void)hipGraphExecDestroy(g.second);     // (every layer range, both buffer sets)
     net->graphs.clear();
+}
+
+static size_t elem_size(const fm_tensor& t);
+
+// Front-ahead, the network's side: the cut K for `request` (option "det_front_layers": k > 0 forced, -1 the rule -- the
+// longest prefix of the table whose layers all write maps of at least 8192 pixels, graph.py's "large map"), shortened
+// until every front layer is one whose launch keeps no state in the network besides its tensors and the split-K
+// partials, and until the second copy of the front's tensors fits the budget.  Then those tensors leave the arena (or
+// their own allocation) for two sets of their own, and the captured graphs, which bake the old pointers, are dropped.
+// Returns the cut in *k (0: this network has no front).
+constexpr size_t FRONT_BUDGET = (size_t)512 << 20;
+constexpr size_t FRONT_WS_FLOATS = (size_t)16 << 20;    // what a batch-1 launch can ask for at most (launch_conv: t < 256 tiles x 16 splits)
+int fm_net_front_prepare(fm_ctx* ctx, NetState* net, int request, int* k) {
+    FM_CHECK_ARG(ctx && net && k && request != 0);
+    if (net->front_req == request) { *k = net->front_k; return 0; }
+    const int nl = (int)net->layers.size(), nt = (int)net->tensors.size();
+    const int input = net->layers[0].in[0];
+    int K = 0;
+    if (request > 0) K = std::min(request, nl - 1);
+    else
+        while (K < nl - 1 && (long)net->tensors[net->layers[K].out].h * net->tensors[net->layers[K].out].w >= 8192) ++K;
+    auto plain = [](int op) {
+        switch (op) {
+            case FM_OP_CONV: case FM_OP_CONVS: case FM_OP_CONVD: case FM_OP_DWCONV3: case FM_OP_DWCONV: case FM_OP_SEPCONV:
+            case FM_OP_STEMCONV: case FM_OP_STEM2: case FM_OP_STEMPOOL: case FM_OP_PAIR11: case FM_OP_SPP: case FM_OP_MAXPOOL:
+            case FM_OP_AVGPOOL: case FM_OP_UPSAMPLE2: case FM_OP_RESBLOCK: case FM_OP_ADD: case FM_OP_COPY: return true;
+            default: return false;
+        }
+    };
+    std::vector<char> want;
+    size_t bytes = 0;
+    for (;; --K) {
+        want.assign(nt, 0);
+        bytes = net->ws_b ? 0 : FRONT_WS_FLOATS * sizeof(float);
+        bool ok = true;
+        for (int i = 0; i < K && ok; ++i) {
+            const fm_layer& L = net->layers[i];
+            ok = plain(L.op);
+            want[L.out] = 1;
+            for (int j = 0; j < L.n_in; ++j) want[L.in[j]] = 1;
+            if (L.res_mode != FM_RES_NONE) want[L.res] = 1;
+        }
+        want[input] = 0;
+        for (int t = 0; t < nt; ++t)
+            if (want[t] && !(t < (int)net->in_front.size() && net->in_front[t])) {
+                const fm_tensor& T = net->tensors[t];
+                bytes += 2 * (((size_t)net->max_batch * T.h * T.w * T.c * elem_size(T) + 255) & ~(size_t)255);
+            }
+        if (K == 0 || (ok && net->front_bytes + bytes <= FRONT_BUDGET)) break;
+    }
+    net->front_req = request;
+    net->front_k = K;
+    *k = K;
+    if (K == 0) return 0;
+    fm_net_drop_graphs(net);
+    if (net->in_front.empty()) {
+        net->in_front.assign(nt, 0);
+        net->bufs_b = net->bufs;
+    }
+    if (!net->ws_b) {
+        FM_HIP(hipMalloc(&net->ws_b, FRONT_WS_FLOATS * sizeof(float)));
+        net->front_bytes += FRONT_WS_FLOATS * sizeof(float);
+    }
+    for (int t = 0; t < nt; ++t) {
+        if (!want[t] || net->in_front[t]) continue;
+        const fm_tensor& T = net->tensors[t];
+        const size_t b = (size_t)net->max_batch * T.h * T.w * T.c * elem_size(T);
+        void* two[2] = {nullptr, nullptr};
+        for (void*& p : two) {
+            FM_HIP(hipMalloc(&p, b));
+            net->front_owned.push_back(p);
+            FM_HIP(hipMemset(p, 0, b));
+        }
+        if (T.offset < 0) FM_HIP(hipFree(net->bufs[t]));        // (its own allocation: one pointer in both sets so far)
+        net->bufs[t] = two[0];
+        net->bufs_b[t] = two[1];
+        net->in_front[t] = 1;
+        net->front_bytes += 2 * ((b + 255) & ~(size_t)255);
+    }
+    // (the fills above run on the null stream, which the network's non-blocking streams do not wait for: the first
+    // launches into the new buffers follow at once)
+    FM_HIP(hipStreamSynchronize(nullptr));
+    return 0;
 }
 
 static size_t elem_size(const fm_tensor& t) { return t.f32 ? 4 : 2; }
@@ -97,7 +209,8 @@ extern "C" int fm_net_destroy(fm_ctx* ctx, int which) {
     FM_CHECK_ARG(ctx && (which >= 0 && which < FM_NET_EXTRACTOR_B + FM_MAX_EXTRA_EXTRACTORS));
     NetState*& slot = net_slot(ctx, which);
     if (slot) {
-        FM_HIP(hipStreamSynchronize(slot->stream));
+        int rc = fm_net_sync(slot);
+        if (rc) return rc;
         fm_net_free(slot);
         slot = nullptr;
     }
@@ -116,6 +229,7 @@ extern "C" int fm_net_create(fm_ctx* ctx, int which, int max_batch, int n_tensor
     net->max_batch = max_batch;
     net->stream = which == FM_NET_DETECTOR ? ctx->s_det : which == FM_NET_EXTRACTOR ? ctx->s_ext
                                                         : ctx->s_ext_x[which - FM_NET_EXTRACTOR_B];
+    net->home = net->stream;
     net->tensors.assign(tensors, tensors + n_tensors);
     net->layers.assign(layers, layers + n_layers);
     if (arena_bytes) {
@@ -169,7 +283,10 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
     const fm_tensor& ti = net->tensors[L.in[0]];
     const fm_tensor& to = net->tensors[L.out];
     hipStream_t s = net->stream;
-    float* ws = net->ws;
+    // (a front on another stream runs beside the previous pass's launches on `home`: partials of its own)
+    const bool away = s != net->home && net->ws_b;
+    float* ws = away ? net->ws_b : net->ws;
+    const size_t ws_floats = away ? FRONT_WS_FLOATS : net->ws_floats;
     const f16* in0 = (const f16*)net->bufs[L.in[0]];
     f16* out = (f16*)net->bufs[L.out];
     switch (L.op) {
@@ -210,7 +327,7 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             FM_CHECK_ARG(L.out_coff + p.cout_store <= to.c && L.in_coff[0] + L.cin <= ti.c);
             if (L.op == FM_OP_CONVS) return launch_conv_streamed(p, s);
             if (L.op == FM_OP_CONVD) return launch_convd(p, s);
-            return launch_conv(p, ws, net->ws_floats, s);
+            return launch_conv(p, ws, ws_floats, s);
         }
         case FM_OP_DWCONV3:
             return launch_dwconv3(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff,
@@ -411,7 +528,8 @@ bool fm_net_writes_mirror(const NetState* net) {
 // gate kernels index gate[n*C + c] with C = the gated channel count; buffers are spaced by
 // max_batch*gate_c so any C <= gate_c fits.
 static int run_layers_eager(fm_ctx* ctx, NetState* net, int batch) {
-    for (size_t i = (size_t)net->first; i < net->layers.size(); ++i) {
+    const size_t end = net->last > 0 ? (size_t)net->last : net->layers.size();
+    for (size_t i = (size_t)net->first; i < end; ++i) {
         int rc = run_layer(ctx, net, net->layers[i], batch);
         if (rc) return rc;
     }
@@ -495,7 +613,7 @@ extern "C" int fm_net_run(fm_ctx* ctx, int which, int batch) {
     FM_CHECK_ARG(net != nullptr && batch >= 0 && batch <= net->max_batch);
     if (batch == 0) return 0;
     if (!net->use_graphs || !ctx->opt_use_graphs) return run_layers_eager(ctx, net, batch);
-    const long key = (((long)batch << 32) | (unsigned)net->emb_offset) ^ ((long)net->first << 60);
+    const NetState::GraphKey key{((long)batch << 32) | (unsigned)net->emb_offset, net->first, net->last, net->set};
     for (auto& g : net->graphs)
         if (g.first == key) {
             FM_HIP(hipGraphLaunch(g.second, net->stream));
@@ -532,8 +650,12 @@ extern "C" int fm_net_tensor_write(fm_ctx* ctx, int which, int tensor, const voi
     FM_CHECK_ARG(net && tensor >= 0 && tensor < (int)net->tensors.size());
     const fm_tensor& t = net->tensors[tensor];
     FM_CHECK_ARG(bytes <= (size_t)net->max_batch * t.h * t.w * t.c * elem_size(t));
-    FM_HIP(hipStreamSynchronize(net->stream));
+    int rc = fm_net_sync(net);
+    if (rc) return rc;
     FM_HIP(hipMemcpy(net->bufs[tensor], host, bytes, hipMemcpyHostToDevice));
+    // (a tensor of the front exists twice: the caller's values hold whichever set the next pass takes)
+    if (!net->bufs_b.empty() && net->bufs_b[tensor] != net->bufs[tensor])
+        FM_HIP(hipMemcpy(net->bufs_b[tensor], host, bytes, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -543,8 +665,9 @@ extern "C" int fm_net_tensor_read(fm_ctx* ctx, int which, int tensor, void* host
     FM_CHECK_ARG(net && tensor >= 0 && tensor < (int)net->tensors.size());
     const fm_tensor& t = net->tensors[tensor];
     FM_CHECK_ARG(bytes <= (size_t)net->max_batch * t.h * t.w * t.c * elem_size(t));
-    FM_HIP(hipStreamSynchronize(net->stream));
-    FM_HIP(hipMemcpy(host, net->bufs[tensor], bytes, hipMemcpyDeviceToHost));
+    int rc = fm_net_sync(net);
+    if (rc) return rc;
+    FM_HIP(hipMemcpy(host, net->bufs[tensor], bytes, hipMemcpyDeviceToHost));    // (the set of the pass that ran last)
     return 0;
 }
 

@@ -12,6 +12,7 @@ from collections import defaultdict
 from pathlib import Path
 import abc
 import configparser
+import os
 
 import numpy as np
 
@@ -394,6 +395,8 @@ class YOLODetector(Detector):
         self._announced = []                    # frames whose passes prefetch / prefetch_batch enqueued, in order
         self.graph, self.heads = self.model.build_graph(weights)
         self.backend = HipNet(self.ctx, NET_DETECTOR, self.graph, max(max_batch, self.n_tiles), reuse_buffers=reuse_buffers)
+        # (the cut measured best for this model; FASTMOT_FRONT_LAYERS for A/B runs)
+        self.ctx.set_option('det_front_layers', int(os.environ.get('FASTMOT_FRONT_LAYERS', self.model.FRONT_LAYERS)))
         self.roi, self.upscaled_sz, self.bbox_offset = self._create_letterbox()
         self.tiles = self.tiling_region_sz = self.tile_bbox_offsets = None
         self.last_tile_detections = None

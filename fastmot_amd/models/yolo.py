@@ -40,6 +40,7 @@ class YOLO:
     ANCHORS = None
     TOPOLOGY = 'yolov4'
     BUILTIN_CFG = None          # name of a generator in models/scaled_yolov4.py (used when no .cfg file is present)
+    FRONT_LAYERS = -1           # front-ahead cut of the layer table (fm_ctx option 'det_front_layers'): -1 the rule, 0 off, k forced
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)
@@ -285,12 +286,14 @@ class YOLOv4CSP_640(YOLOv4CSP):
     """BASELINE.json config[2]: Scaled-YOLOv4 CSP at 640x640 with the 80 COCO classes (52.9 M parameters,
     121 GFLOP), seeded random weights unless yolov4-csp.weights is present."""
     NUM_CLASSES = 80
+    FRONT_LAYERS = 0            # (no gain measured, profiles/front_ahead_ab.txt: at detector_frame_skip 5 its stream idles between passes)
 
 
 class YOLOv4P6_1280(YOLOv4P6):
     """BASELINE.json config[4]: Scaled-YOLOv4 P6 at 1280x1280, 80 classes, 4 heads x 4 anchors
     (127.5 M parameters, 722 GFLOP)."""
     NUM_CLASSES = 80
+    FRONT_LAYERS = 0            # (no gain measured, profiles/front_ahead_ab.txt; the rule's front would cost 489 MiB)
 
 
 class YOLOv4Tiny(YOLO):

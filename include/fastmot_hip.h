@@ -58,11 +58,22 @@ int fm_ctx_bind_thread(fm_ctx* ctx);
  * "fused_input" (default 1: a network that begins with a stem convolution lets that convolution compute its input pixels from the
  * frame -- detector resize / ReID crops -- instead of running the front-end kernel into the input tensor; 0 for A/B and tests),
  * "net_timing" (default 0; N > 0: every N-th detector pass carries the HIP-event pair fm_detect_net_ms reads),
+ * "det_front_ahead" / "det_front_layers" / "det_front_stream" (front-ahead: a single-frame look-ahead pass -- fm_detect_async_next,
+ * fm_detect_async_ahead(1) -- runs its first K layers on another stream, behind its frame's copy only, while the previous pass
+ * still runs; results are bit-identical.  "det_front_ahead": 0 never, 1 when the previous pass is still in flight at enqueue
+ * time, 2 always (tests).  "det_front_layers", the only option that takes -1: 0 never, k the first k layers, -1 the longest
+ * prefix of layers that write maps of >= 8192 pixels; shortened to what 512 MB of second copies allow.
+ * "det_front_stream": 0 the post-processing stream, 1 the ReID stream),
  * "use_graphs" (default 1;
  * 0 launches the network layers one by one instead of replaying hipGraphs), "lk_variant" (diagnostic builds only, include/fastmot_hip_diag.h;
  * 0 is the only value the shipped library accepts).  Initial values can be set with the environment
  * variables FASTMOT_ZERO_COPY / FASTMOT_HOST_LAP / FASTMOT_GRAPHS. */
 int fm_ctx_set_option(fm_ctx* ctx, const char* key, int value);
+/* the three front-ahead options as they stand */
+int fm_ctx_get_option(fm_ctx* ctx, const char* key, int* value);
+/* the detector network's front: the cut as prepared by the first pass that took it (0: none), the device memory its two
+ * tensor sets and partial-sum buffer cost, the number of passes that ran a front so far */
+int fm_net_front_info(fm_ctx* ctx, int* k, long long* bytes, long long* passes);
 /* Event trace of a pipelined run (diagnostics; scripts/trace_pipeline.py).  fm_trace_start arms `cap` timed events and
  * returns the host's CLOCK_MONOTONIC time (ns) that corresponds to the trace's zero; from then on the library records
  * one event per stage boundary on the stage's own stream (tags: 10-13 detector pass reached / inputs ready / network done
@@ -1146,7 +1157,8 @@ int fm_filter_dets(fm_ctx* ctx, const float* rows, int n, fm_det48* out, int cap
 int fm_detect_raw_candidates(fm_ctx* ctx, float* rows, int cap, int* n);
 /* HIP-event duration (ms) of the network launches of the pass fm_detect_sync collected last, recorded on the detector
  * stream (the bench's live roofline measurement); -1 when that pass carried no events (option "net_timing").  A batch
- * pass (fm_detect_async_ahead) reports its duration on the collect of its first frame and -1 on the others. */
+ * pass (fm_detect_async_ahead) reports its duration on the collect of its first frame and -1 on the others.  A pass in
+ * two parts (front-ahead) reports the sum of its front's and its back's brackets, not the span between them. */
 int fm_detect_net_ms(fm_ctx* ctx, float* ms);
 /* Tiled detection (SSDDetector's tiling, fastmot/detector.py:77-139, for the YOLO networks): the frame is resized to a
  * tiling region and cut into n_tiles overlapping tiles of the network's input size, which ONE network pass takes as the

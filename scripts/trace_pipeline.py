@@ -18,7 +18,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import bench  # noqa: E402
 
-NAMES = {15: 'det: first layer (input pixels computed in it) done', 10: 'det: stream reaches the pass', 11: 'det: inputs ready, preprocessed', 12: 'det: network done',
+NAMES = {15: 'det: first layer (input pixels computed in it) done', 16: 'det: front done (front-ahead: on its own stream)', 10: 'det: stream reaches the pass', 11: 'det: inputs ready, preprocessed', 12: 'det: network done',
          13: 'det: decode done', 20: 'post: begins', 21: 'post: ends', 30: 'copy(next): begins', 31: 'copy(next): ends', 36: 'copy(next): NV12 -> BGR begins', 37: 'copy(next): JPEG -> BGR begins',
          32: 'reid: begins', 33: 'reid: ends', 40: 'lk: begins', 41: 'lk: ends',
          14: 'det: preprocess begins', 22: 'post: sort done', 23: 'post: bit matrix done', 34: 'reid: crops done',
@@ -127,6 +127,21 @@ def main():
         d = pairs(a, b)[5:]
         if len(d):
             print(f'{nm:40s} {np.median(d):7.3f}  ({np.percentile(d, 10):7.3f} .. {np.percentile(d, 90):7.3f})')
+    # front-ahead: the events of a pass lie on two streams and the first traced pass has no front, so these pair by time --
+    # every b with the last a before it.  (With front-ahead the 11 -> 12 row above overlaps the previous pass.)
+    def after(a, b):
+        ta = np.array(sorted(float(m) for t, m in zip(tags, ms) if t == a))
+        tb = np.array(sorted(float(m) for t, m in zip(tags, ms) if t == b))
+        if not len(ta) or not len(tb):
+            return np.zeros(0)
+        i = np.searchsorted(ta, tb, side='right') - 1
+        return (tb - ta[np.maximum(i, 0)])[i >= 0]
+    for a, b, nm in ((11, 16, 'det: front, first layer begins -> front done'), (31, 11, 'copy of the next frame done -> first layer begins'),
+                     (16, 14, 'det: front done -> detector stream past its wait'), (14, 12, 'det: detector stream past its waits -> network done'),
+                     (13, 20, 'det: decode done -> post begins')):
+        d = after(a, b)[5:]
+        if len(d):
+            print(f'{nm:52s} {np.median(d):7.3f}  ({np.percentile(d, 10):7.3f} .. {np.percentile(d, 90):7.3f})')
     t10 = np.array([float(m) for t, m in zip(tags, ms) if t == 10])
     t13 = np.array([float(m) for t, m in zip(tags, ms) if t == 13])
     t11 = np.array([float(m) for t, m in zip(tags, ms) if t == 11])
@@ -135,6 +150,17 @@ def main():
         idle = t11[1:n] - t13[:n - 1]
         print(f'detector stream: pass-to-pass period {np.median(np.diff(t11[5:n])):7.3f} ms; decode(k) done -> network(k+1) begins '
               f'{np.median(idle[5:]):7.3f} ms  ({np.percentile(idle[5:], 10):7.3f} .. {np.percentile(idle[5:], 90):7.3f})')
+    if len(t13) > 6:     # (with front-ahead tag 11 lies on the front's stream: the period of the detector stream itself)
+        print(f'detector stream: decode-done to decode-done period {np.median(np.diff(t13[5:])):7.3f} ms')
+        # the first layer of pass k + 1 against the end of pass k's network: each 11 with the last 12 before it and the next after it
+        t12 = np.array(sorted(float(m) for t, m in zip(tags, ms) if t == 12))
+        s11 = np.array(sorted(t11))
+        i = np.searchsorted(t12, s11, side='right')
+        ok = (i > 0) & (i < len(t12))
+        since, until = (s11 - t12[np.maximum(i - 1, 0)])[ok][5:], (t12[np.minimum(i, len(t12) - 1)] - s11)[ok][5:]
+        if len(since):
+            print(f'first layer begins {np.median(since):7.3f} ms after a network ended and {np.median(until):7.3f} ms before the next one ends '
+                  f'(one pass is {np.median(np.diff(t12[5:])):.3f}: a first layer that begins late in that span runs beside the previous pass)')
     if args.show:
         lo = begins[-args.show - 1] if len(begins) > args.show else begins[0]
         print(f'# raw events of the last {args.show} steps (ms since the first of them)')
