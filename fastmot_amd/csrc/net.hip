@@ -60,7 +60,9 @@ int launch_gate_sum(int nstreams, const f16* const* in, const int* in_cs, const 
 int launch_head(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int D, const f16* w,
                 const float* b, float* out, float* raw_out, hipStream_t s, float* mirror = nullptr);
 int launch_poolhead(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int D, const float* scale, const float* shift,
-                    const f16* w, const float* b, int relu, float* out, float* mirror, hipStream_t s);
+                    const f16* w, const float* b, int relu, float* out, float* mirror, hipStream_t s, float gem_p, float gem_eps);
+int launch_instnorm(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, int N, int HW, int C, int cn,
+                    const float* gamma, const float* beta, float eps, int act, hipStream_t s);
 int fm_emb_reserve(fm_ctx* ctx, int n);
 
 
@@ -143,7 +145,7 @@ int fm_net_front_prepare(fm_ctx* ctx, NetState* net, int request, int* k) {
         switch (op) {
             case FM_OP_CONV: case FM_OP_CONVS: case FM_OP_CONVD: case FM_OP_DWCONV3: case FM_OP_DWCONV: case FM_OP_SEPCONV:
             case FM_OP_STEMCONV: case FM_OP_STEM2: case FM_OP_STEMPOOL: case FM_OP_PAIR11: case FM_OP_SPP: case FM_OP_MAXPOOL:
-            case FM_OP_AVGPOOL: case FM_OP_UPSAMPLE2: case FM_OP_RESBLOCK: case FM_OP_ADD: case FM_OP_COPY: return true;
+            case FM_OP_AVGPOOL: case FM_OP_UPSAMPLE2: case FM_OP_RESBLOCK: case FM_OP_ADD: case FM_OP_COPY: case FM_OP_INSTNORM: return true;
             default: return false;
         }
     };
@@ -494,9 +496,30 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             return launch_ostail(in0, ti.c, L.in_coff[0], (const f16*)(net->weights + L.w_off),
                                  (const float*)(net->weights + L.b_off), B, ctx->emb + (size_t)net->emb_offset * ctx->feat_dim,
                                  nullptr, ctx->emb_host ? ctx->emb_host + (size_t)net->emb_offset * ctx->feat_dim : nullptr, s);
+        case FM_OP_INSTNORM: {  // hid = cn normalised channels (w_off / b_off = f32 gamma / beta [cn]), gate[0] = the IEEE bits of eps
+            const size_t wb = net->weight_bytes;
+            float eps;
+            memcpy(&eps, &L.gate[0], sizeof eps);
+            FM_CHECK_ARG(!ti.f32 && !to.f32 && L.out != L.in[0] && to.h == ti.h && to.w == ti.w && L.cin >= 8 && L.cin % 8 == 0 &&
+                         L.cout == L.cin && L.hid >= 8 && L.hid % 8 == 0 && L.hid <= L.cin);
+            FM_CHECK_ARG(L.in_coff[0] >= 0 && L.out_coff >= 0 && L.in_coff[0] % 8 == 0 && L.out_coff % 8 == 0 &&
+                         L.in_coff[0] + L.cin <= ti.c && L.out_coff + L.cin <= to.c);
+            FM_CHECK_ARG(L.w_off >= 0 && L.b_off >= 0 && L.w_off % 16 == 0 && L.b_off % 16 == 0 &&
+                         (size_t)L.w_off + (size_t)L.hid * 4 <= wb && (size_t)L.b_off + (size_t)L.hid * 4 <= wb);
+            FM_CHECK_ARG((L.act == FM_ACT_LINEAR || L.act == FM_ACT_RELU) && eps >= 0.f && eps < 1.f);
+            return launch_instnorm(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff, B, ti.h * ti.w, L.cin, L.hid,
+                                   (const float*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off), eps, L.act, s);
+        }
         case FM_OP_POOLHEAD: {  // gate[0] > 0: BN neck (w2_off / b2_off = f32 scale / shift [cin]); gate[1] > 0: FC (w_off fp16 [cout][cin], b_off f32 [cout])
+            // gate[2] > 0: GeM pooling, the IEEE bits of p (0.5 .. 16) there and of the clamp eps in gate[3]
             const bool neck = L.gate[0] > 0, fc = L.gate[1] > 0;
             const size_t wb = net->weight_bytes;
+            float gem_p = 0.f, gem_eps = 0.f;
+            if (L.gate[2] > 0) {
+                memcpy(&gem_p, &L.gate[2], sizeof gem_p);
+                memcpy(&gem_eps, &L.gate[3], sizeof gem_eps);
+                FM_CHECK_ARG(gem_p >= 0.5f && gem_p <= 16.f && gem_eps > 0.f && gem_eps <= 1.f);
+            }
             FM_CHECK_ARG(L.cout == ctx->feat_dim && net->emb_offset + B <= ctx->emb_cap && !ti.f32 && L.cin > 0 && L.cout > 0 &&
                          L.in_coff[0] + L.cin <= ti.c && (fc || L.cout == L.cin));
             FM_CHECK_ARG(!fc || (L.b_off >= 0 && (size_t)L.w_off + (size_t)L.cout * L.cin * 2 <= wb && (size_t)L.b_off + (size_t)L.cout * 4 <= wb));
@@ -508,7 +531,7 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
                                    fc ? (const f16*)(net->weights + L.w_off) : nullptr,
                                    fc ? (const float*)(net->weights + L.b_off) : nullptr, L.act == FM_ACT_RELU,
                                    ctx->emb + (size_t)net->emb_offset * ctx->feat_dim,
-                                   ctx->emb_host ? ctx->emb_host + (size_t)net->emb_offset * ctx->feat_dim : nullptr, s);
+                                   ctx->emb_host ? ctx->emb_host + (size_t)net->emb_offset * ctx->feat_dim : nullptr, s, gem_p, gem_eps);
         }
         default:
             fm_set_error("unknown layer op %d", L.op);
@@ -762,6 +785,10 @@ static void layer_cost(const NetState* net, const fm_layer& L, int B, double* fl
             *bytes = pin * 8 + pout * L.cout * 2 + 49.0 * 4 * L.cout * 2;
             break;
         }
+        case FM_OP_INSTNORM:    // one read and one write of the view (the register path; the statistics are ~6 flops per element)
+            *flops = 6.0 * pin * L.hid;
+            *bytes = (pin + pout) * L.cin * 2;
+            break;
         case FM_OP_POOLHEAD:
             *flops = (double)pin * L.cin + (L.gate[1] > 0 ? 2.0 * L.cin * L.cout * B : 0.);
             *bytes = pin * L.cin * 2 + (L.gate[1] > 0 ? (double)L.cin * L.cout * 2 : 0.) + (double)B * L.cout * 8;
@@ -801,6 +828,11 @@ extern "C" int fm_net_cost(fm_ctx* ctx, int which, int batch, double* flops, dou
                 f += 2.0 * c2 * L.cout * pout;
                 b += pout * c2 * 2 + pout * L.cout * 2 + (double)c2 * L.cout * 2;
             }
+        } else if (L.op == FM_OP_INSTNORM) {
+            // no conv FLOPs, but bytes no fusion removes: the statistics need the whole map before the first output
+            double lf, lb;
+            layer_cost(net, L, batch, &lf, &lb);
+            b += lb;
         }
     *flops = f;
     *bytes = b;

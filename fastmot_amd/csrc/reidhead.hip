@@ -1,6 +1,8 @@
 // Pooled embedding head of a classification-style ReID backbone (FM_OP_POOLHEAD; models/onnx_graph.py): ONE launch per
 // network pass, one workgroup per sample:
 //   global average pool over HW (fp32) -> optional per-channel affine (the BN neck folded to scale / shift, fp32)
+//   (GeM pooling, a template mode of the kernel in reidhead_kernel.h: the pool sums max(x, eps)^p and the mean takes the
+//   p-th root before the neck; instantiated in reidhead_gem.hip -- this file's plain instantiation is the code without it)
 //   -> optional FC C -> D (fp16 weights, fp32 bias with any BatchNorm folded in, optional ReLU) -> L2 normalise
 //   -> the row to ctx->emb and to its page-locked mirror, where ops.hip head_kernel writes its rows (no export launch
 //   behind the network: the emb_host contract of extract.hip).
@@ -10,114 +12,13 @@
 // against the pooled vector in LDS, then a cross-lane sum -- C / 512 steps per row instead of C / 8 -- and it works on 8
 // rows at a time, so that 8 independent 16-byte loads per lane are in flight per step.
 // LDS: part[max(C, 8 * PH_T)] | pooled[C] | feat[D] (FC only) | red[PH_T / 64] floats: 48 KB at C = D = 4096, the limit.
-#include "net.h"
+#include "reidhead_kernel.h"
 
-namespace {
 
-constexpr int PH_T = 512;                    // 8 wavefronts
-constexpr int PH_R = 8;                      // output rows a wavefront works on at once
-constexpr int PH_MAX = 4096;                 // largest C and D
-constexpr size_t PH_LDS_MAX = 64 * 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__global__ __launch_bounds__(PH_T) void poolhead_kernel(const f16* __restrict__ in, int in_cs, int in_coff, int HW, int C, int D,
-                                                        const float* __restrict__ scale, const float* __restrict__ shift,
-                                                        const f16* __restrict__ w, const float* __restrict__ b, int relu,
-                                                        float* __restrict__ out, float* __restrict__ mirror) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c8n = C >> 3;
-    const int groups = c8n < PH_T ? PH_T / c8n : 1;          // pixel groups that share a column of 8 channels
-    float* part = sm;                                        // [groups][C]
-    float* pooled = part + groups * C;
-    float* feat = w ? pooled + C : pooled;                   // (no FC: the pooled vector is the feature, D == C)
-    float* red = feat + D;
-
-    // ---- 1. global average pool: 16-byte loads, fp32 sums; pixel group g takes pixels g, g + groups, ...
-    const f16* base = in + (size_t)n * HW * in_cs + in_coff;
-    for (int it = tid; it < groups * c8n; it += PH_T) {
-        const int pg = it / c8n, cg = it - pg * c8n;
-        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int px = pg; px < HW; px += groups) {
-            float v[8];
-            unpack8(*reinterpret_cast<const uint4*>(base + (size_t)px * in_cs + cg * 8), v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += v[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) part[pg * C + cg * 8 + e] = acc[e];
-    }
-    __syncthreads();
-    // ---- 2. mean, then the BN neck as one multiply and one add per channel
-    for (int c = tid; c < C; c += PH_T) {
-        float s = 0.f;
-        for (int g = 0; g < groups; ++g) s += part[g * C + c];
-        float m = s / (float)HW;
-        if (scale) m = m * scale[c] + shift[c];
-        pooled[c] = m;
-    }
-    __syncthreads();
-    // ---- 3. FC: one wavefront per output row, PH_R rows at a time -- their weight loads are independent, so PH_R x 16 B per
-    // lane are in flight per step (one row at a time is a chain of load -> wait -> 8 FMAs: latency bound)
-    if (w) {
-        for (int d0 = wave * PH_R; d0 < D; d0 += (PH_T / 64) * PH_R) {
-            float s[PH_R];
-            const f16* wr[PH_R];
-#pragma unroll
-            for (int r = 0; r < PH_R; ++r) {
-                s[r] = 0.f;
-                wr[r] = w + (size_t)min(d0 + r, D - 1) * C;        // (rows past D: the last row again, not stored)
-            }
-            for (int c = lane * 8; c < C; c += 64 * 8) {
-                uint4 wv[PH_R];
-#pragma unroll
-                for (int r = 0; r < PH_R; ++r) wv[r] = *reinterpret_cast<const uint4*>(wr[r] + c);
-                const float4 g0 = *reinterpret_cast<const float4*>(pooled + c);
-                const float4 g1 = *reinterpret_cast<const float4*>(pooled + c + 4);
-#pragma unroll
-                for (int r = 0; r < PH_R; ++r) {
-                    // (v_fma_mix_f32 extends the half inside the FMA: the value of convert + fmaf; as inline assembly it also
-                    // keeps the SLP vectoriser from pairing two rows into packed fp32 with a cross-half op_sel, the form
-                    // tests/test_isa_lint.py refuses)
-                    float a = s[r];
-                    a = fma_mix_h<0>(wv[r].x, g0.x, a); a = fma_mix_h<1>(wv[r].x, g0.y, a);
-                    a = fma_mix_h<0>(wv[r].y, g0.z, a); a = fma_mix_h<1>(wv[r].y, g0.w, a);
-                    a = fma_mix_h<0>(wv[r].z, g1.x, a); a = fma_mix_h<1>(wv[r].z, g1.y, a);
-                    a = fma_mix_h<0>(wv[r].w, g1.z, a); a = fma_mix_h<1>(wv[r].w, g1.w, a);
-                    s[r] = a;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < PH_R; ++r) {
-                const float t = wave_sum(s[r]) + b[min(d0 + r, D - 1)];
-                if (lane == 0 && d0 + r < D) feat[d0 + r] = relu ? act_relu(t) : t;
-            }
-        }
-        __syncthreads();
-    }
-    // ---- 4. L2 normalise, 5. the row to the embedding matrix and its host mirror
-    float nrm = 0.f;
-    for (int d = tid; d < D; d += PH_T) nrm = fmaf(feat[d], feat[d], nrm);
-    nrm = wave_sum(nrm);
-    if (lane == 0) red[wave] = nrm;
-    __syncthreads();
-    float total = 0.f;
-#pragma unroll
-    for (int i = 0; i < PH_T / 64; ++i) total += red[i];
-    const float inv = 1.f / sqrtf(total);
-    for (int d = tid; d < D; d += PH_T) {
-        const float v = feat[d] * inv;
-        out[(size_t)n * D + d] = v;
-        if (mirror) mirror[(size_t)n * D + d] = v;
-    }
-}
-
-}  // namespace
+// (reidhead_gem.hip; arguments checked here)
+void launch_poolhead_gem(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int D, const float* scale, const float* shift,
+                         const f16* w, const float* b, int relu, float* out, float* mirror, hipStream_t s, float gem_p, float gem_eps,
+                         size_t shmem);
 
 size_t poolhead_lds_bytes(int C, int D, bool fc) {
     const int c8n = C / 8;
@@ -125,16 +26,21 @@ size_t poolhead_lds_bytes(int C, int D, bool fc) {
     return sizeof(float) * ((size_t)groups * C + C + (fc ? D : 0) + PH_T / 64);
 }
 
-// scale / shift: both or neither; w == nullptr: no FC (then D == C)
+// scale / shift: both or neither; w == nullptr: no FC (then D == C); gem_p > 0: GeM pooling with that exponent and clamp gem_eps
 int launch_poolhead(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int D, const float* scale, const float* shift,
-                    const f16* w, const float* b, int relu, float* out, float* mirror, hipStream_t s) {
+                    const f16* w, const float* b, int relu, float* out, float* mirror, hipStream_t s, float gem_p, float gem_eps) {
     FM_CHECK_ARG(in && out && N >= 1 && HW >= 1 && C >= 8 && C % 8 == 0 && C <= PH_MAX && D >= 1 && D <= PH_MAX);
     FM_CHECK_ARG(in_cs % 8 == 0 && in_coff % 8 == 0 && in_coff + C <= in_cs && (scale == nullptr) == (shift == nullptr));
     FM_CHECK_ARG(w ? b != nullptr : D == C);
     const size_t shmem = poolhead_lds_bytes(C, D, w != nullptr);
     FM_CHECK_ARG(shmem <= PH_LDS_MAX);
-    hipLaunchKernelGGL(poolhead_kernel, dim3(N), dim3(PH_T), shmem, s, in, in_cs, in_coff, HW, C, D, scale, shift, w, b, relu,
-                       out, mirror);
+    if (gem_p > 0.f) {
+        FM_CHECK_ARG(gem_p >= 0.5f && gem_p <= 16.f && gem_eps > 0.f && gem_eps <= 1.f);
+        launch_poolhead_gem(in, in_cs, in_coff, N, HW, C, D, scale, shift, w, b, relu, out, mirror, s, gem_p, gem_eps, shmem);
+    } else {
+        hipLaunchKernelGGL(poolhead_kernel<GEM_NONE>, dim3(N), dim3(PH_T), shmem, s, in, in_cs, in_coff, HW, C, D, scale, shift, w,
+                           b, relu, out, mirror, 0.f, 0.f);
+    }
     FM_HIP(hipGetLastError());
     return 0;
 }

@@ -16,7 +16,7 @@ LOGGER = logging.getLogger(__name__)
 
 (OP_CONV, OP_DWCONV3, OP_MAXPOOL, OP_AVGPOOL, OP_UPSAMPLE2, OP_COPY, OP_GATE, OP_GATE_SUM, OP_HEAD,
  OP_LITECONV, OP_SPP, OP_GATED_SUM, OP_STEMCONV, OP_ADD, OP_RESBLOCK, OP_CONVS, OP_LITECHAIN, OP_CONVD, OP_STEM2, OP_PAIR11,
- OP_OSTAIL, OP_DWCONV, OP_SEPCONV, OP_POOLHEAD, OP_STEMPOOL) = range(25)
+ OP_OSTAIL, OP_DWCONV, OP_SEPCONV, OP_POOLHEAD, OP_STEMPOOL, OP_INSTNORM) = range(26)
 CONV_OPS = (OP_CONV, OP_CONVS, OP_CONVD)      # the three kernels behind Graph.conv (same fields, different weight layouts)
 SPP_MAX_HW = 2048
 ACT = {'linear': 0, 'leaky': 1, 'mish': 2, 'relu': 3, 'logistic': 4, 'swish': 5, 'relu6': 6}
@@ -40,6 +40,11 @@ class fm_layer(C.Structure):
 
 def ceil_to(x, m):
     return (x + m - 1) // m * m
+
+
+def f32_bits(v):
+    """The IEEE-754 bits of float32(v) as an int: how a per-op float travels in fm_layer.gate (an int32 field)."""
+    return int(np.float32(v).view(np.int32))
 
 
 class View:
@@ -786,11 +791,37 @@ class Graph:
 
     POOLHEAD_MAX = 4096
 
-    def poolhead(self, name, x, neck=None, fc=None, relu=False):
+    def instnorm(self, name, x, gamma, beta, eps=1e-5, act='linear', dst=None):
+        """Instance normalisation in one launch (FM_OP_INSTNORM, instnorm.hip): the first cn = len(gamma) channels of x are
+        normalised per sample and channel over the map (biased variance, eps, gamma / beta in fp32), channels [cn, x.c) pass
+        through; `act` ('linear' or 'relu') is applied to all of them.  cn == x.c: a plain InstanceNorm2d(affine=True); cn <
+        x.c: the IN half of an IBN-a layer behind a conv whose BatchNorm half is folded into its weights.  The result goes to
+        a new tensor (or the view dst of another one), never in place.  eps travels as its fp32 bits in gates[0].  Keeps
+        instnorm_ref = (gamma, beta, eps as the fp32 value the device uses)."""
+        gamma, beta = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (gamma, beta))
+        cn = gamma.shape[0]
+        if x.c % 8 or x.coff % 8 or cn % 8 or not 8 <= cn <= x.c or beta.shape != (cn,):
+            raise ValueError(f'{name}: instance normalisation needs channel counts that are multiples of 8 with 8 <= cn <= c '
+                             f'(got cn = {cn} of {x.c} channels at offset {x.coff})')
+        if act not in ('linear', 'relu'):
+            raise ValueError(f'{name}: activation {act!r} behind an instance normalisation (linear or relu)')
+        eps = float(np.float32(eps))
+        if not 0 <= eps < 1:
+            raise ValueError(f'{name}: epsilon {eps}')
+        if dst is None:
+            dst = self.new(x.h, x.w, x.c)
+        assert (dst.h, dst.w, dst.c) == (x.h, x.w, x.c) and dst.tid != x.tid and dst.coff % 8 == 0 and not self.tensors[dst.tid][3]
+        self._layer(op=OP_INSTNORM, ins=[x], out=dst, cin=x.c, cout=x.c, hid=cn, act=ACT[act], gates=[f32_bits(eps)],
+                    w_off=self._push(gamma), b_off=self._push(beta), name=name, instnorm_ref=(gamma, beta, eps))
+        return dst
+
+    def poolhead(self, name, x, neck=None, fc=None, relu=False, gem=None):
         """Pooled embedding head in one launch (FM_OP_POOLHEAD, reidhead.hip): global average pool of x -> neck = (scale,
         shift) per channel in fp32 (a BatchNorm on the pooled vector, already folded) -> fc = (weight [dim, x.c], bias
         [dim]) with fp16 weights (+ ReLU) -> L2 normalise -> the context's embedding buffer.  Without fc the feature is
-        the pooled vector (dim == x.c).  Keeps poolhead_ref = (scale, shift, fp16-rounded weight as fp32, bias, relu)."""
+        the pooled vector (dim == x.c).  Keeps poolhead_ref = (scale, shift, fp16-rounded weight as fp32, bias, relu).
+        gem = (p, eps): generalised-mean pooling, mean(max(x, eps)^p)^(1/p) in place of the average (0.5 <= p <= 16, 0 < eps
+        <= 1); gates grows to [neck, fc, bits of p, bits of eps] and the layer keeps gem_ref = (p, eps) as fp32 values."""
         c = x.c
         if c % 8 or x.coff % 8 or not 8 <= c <= self.POOLHEAD_MAX:
             raise ValueError(f'{name}: the pooled head needs 8 <= channels <= {self.POOLHEAD_MAX}, a multiple of 8 (got {c})')
@@ -812,9 +843,16 @@ class Graph:
             ref[2], ref[3] = w16.astype(np.float32), b
         else:
             assert not relu
+        gates = [int(neck is not None), int(fc is not None)]
+        if gem is not None:
+            p, eps = (float(np.float32(v)) for v in gem)
+            if not (0.5 <= p <= 16 and 0 < eps <= 1):
+                raise ValueError(f'{name}: GeM pooling with p = {p}, eps = {eps} (0.5 <= p <= 16, 0 < eps <= 1)')
+            gates += [f32_bits(p), f32_bits(eps)]
+            kw['gem_ref'] = (p, eps)
         dst = View(x.tid, x.coff, x.c, x.h, x.w)   # (as head(): the result goes to the ctx embedding buffer)
         self._layer(op=OP_POOLHEAD, ins=[x], out=dst, cin=c, cout=dim, act=ACT['relu' if relu else 'linear'],
-                    gates=[int(neck is not None), int(fc is not None)], name=name, poolhead_ref=tuple(ref), **kw)
+                    gates=gates, name=name, poolhead_ref=tuple(ref), **kw)
         return dst
 
     # ---------------------------------------------------------------- C tables

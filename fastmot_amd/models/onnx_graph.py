@@ -16,16 +16,30 @@ Backbone operators
                         the 7x7 stride-2 stem with at most 64 channels, stem and pool are ONE launch (FM_OP_STEMPOOL;
                         FASTMOT_STEMPOOL=0, more channels or another stem: the conv and the pool as two layers)
     Identity, Dropout   skipped
+IBN-Net layers (one FM_OP_INSTNORM launch each, Graph.instnorm, csrc/instnorm.hip)
+    IBN-a               Conv (read by the Split alone) -> Split(axis 1, [h, c - h]; opset 13: `split` as a constant input) ->
+                        InstanceNormalization on part 0, BatchNormalization on part 1 -> Concat(axis 1) in that order -> Relu:
+                        the BatchNorm is folded into rows [h:] of the conv, which is emitted without activation, then
+                        instnorm(cn = h, relu) normalises the first h channels and applies the ReLU to all of them.  h % 8 == 0
+    IBN-b, IN stem      InstanceNormalization that reads a pending Conv, or a pending Conv + Add sum, alone: the conv (with
+                        `res=` for the sum) without activation, then instnorm(cn = c); a Relu behind it becomes the op's
+                        activation.  A 7x7 stem followed by InstanceNormalization is conv + instnorm + pool: the normalisation
+                        needs the whole conv map before the pool may start, so FM_OP_STEMPOOL is not used there
 Head operators (the suffix of the graph; one FM_OP_POOLHEAD launch, Graph.poolhead)
     GlobalAveragePool | ReduceMean over axes (2, 3) | AveragePool whose kernel is the whole map
+    GeM pooling: Clip(min = a positive scalar constant, no max) -> Pow(scalar constant or initialiser p, 0.5 .. 16) -> one of
+                        the pools above -> Pow(q) on the pooled vector with |q p - 1| <= 1e-4.  A learned p arrives with its
+                        root as Reciprocal / Mul / Cast of scalars: those few scalar nodes are folded here
     Flatten, Reshape, Squeeze
     BatchNormalization on the pooled vector ([N, C] or [N, C, 1, 1]): the BN neck
     Gemm | MatMul + Add, then optionally BatchNormalization and Relu (`resnet50_fc512`, OSNet-style `fc`)
 The tracker L2-normalises whatever comes out (feature_extractor.py of the reference): the head op does.
 
-Anything else raises NotImplementedError naming the node: InstanceNormalization (IBN), Pow (GeM pooling), Sigmoid / Mul
-(SE, non-local), grouped or dilated convs, asymmetric pads, a second graph output.  Those models need kernels this
-engine does not have; silently approximating them would give embeddings that look plausible and match nothing.
+Anything else raises NotImplementedError naming the node: an InstanceNormalization of a map that is already stored and
+activated (OSNet-IBN / OSNet-AIN keep theirs inside the fused OSNet operators), a Split whose IN part is no multiple of 8 or
+does not lead, a Pow without its Clip, with a per-channel exponent or without the matching root, Sigmoid / Mul (SE,
+non-local), grouped or dilated convs, asymmetric pads, a second graph output.  Those models need kernels this engine does
+not have; silently approximating them would give embeddings that look plausible and match nothing.
 """
 import numpy as np
 
@@ -33,9 +47,12 @@ from .graph import ACT, Graph, OP_CONV, OP_STEMCONV, RES_BEFORE_ACT
 from .onnx_reader import OnnxModel
 
 SUPPORTED = ('Conv (groups 1, square k in {1, 3, 7}, stride 1 or 2, symmetric pads, dilation 1), BatchNormalization behind a '
-             'Conv, Relu, Add, MaxPool 3x3 stride 2 (pads 1, or pads 0 with ceil_mode 1), Identity, Dropout; as the head: '
-             'GlobalAveragePool / ReduceMean over (2, 3) / whole-map AveragePool, Flatten / Reshape / Squeeze, '
-             'BatchNormalization on the pooled vector, Gemm or MatMul + Add, BatchNormalization, Relu')
+             'Conv, Relu, Add, MaxPool 3x3 stride 2 (pads 1, or pads 0 with ceil_mode 1), Identity, Dropout; IBN-a: Conv -> '
+             'Split(axis 1, [h, c - h], h % 8 == 0) -> InstanceNormalization on part 0 + BatchNormalization on part 1 -> Concat '
+             '-> Relu; IBN-b: InstanceNormalization (+ Relu) behind a Conv or a Conv + Add read by it alone; as the head: '
+             'GlobalAveragePool / ReduceMean over (2, 3) / whole-map AveragePool, optionally as GeM (Clip(min > 0) -> Pow(scalar '
+             'p) -> pool -> Pow(1 / p)), Flatten / Reshape / Squeeze, BatchNormalization on the pooled vector, Gemm or '
+             'MatMul + Add, BatchNormalization, Relu')
 
 
 class _Conv:
@@ -52,11 +69,51 @@ class _Sum:
         self.conv, self.other = conv, other
 
 
+class _Normed:
+    """conv (+ other) -> instance normalisation of the first cn channels, waiting for its Relu."""
+
+    def __init__(self, conv, other, gamma, beta, eps, node):
+        self.conv, self.other, self.gamma, self.beta, self.eps, self.node = conv, other, gamma, beta, eps, node
+
+
+class _Only:
+    """A value only certain nodes may read: a part of an IBN Split, the clamped / powered map of GeM, a folded scalar."""
+    what = ''
+
+
+class _Split:
+    def __init__(self, conv, parts, node):
+        self.conv, self.parts, self.node = conv, parts, node
+        self.inorm = self.bn = None          # (gamma, beta, eps, output name) / (scale, shift, output name)
+
+
+class _Part(_Only):
+    what = 'a part of a Split: only the InstanceNormalization (part 0) and BatchNormalization (part 1) of an IBN layer may'
+
+    def __init__(self, split, index, done=False):
+        self.split, self.index, self.done = split, index, done
+
+
+class _Gem(_Only):
+    what = 'the clamped / powered map of GeM pooling: only its Pow and its global pool may'
+
+    def __init__(self, x, eps, p=None):
+        self.x, self.eps, self.p = x, eps, p
+
+
+class _Scalar(_Only):
+    what = 'a folded scalar: only the exponent of a GeM root may'
+
+    def __init__(self, value):
+        self.value = value
+
+
 class _Vec:
     """The pooled vector and what the head has applied to it so far."""
 
-    def __init__(self, x):
+    def __init__(self, x, gem=None, gem_node=None):
         self.x, self.c = x, x.c
+        self.gem, self.gem_node = gem, gem_node    # (p, eps); the root is still missing while gem_node is set
         self.neck = None            # (scale, shift) fp32
         self.fc = None              # [weight [D, C], bias [D]]
         self.bias_open = False      # a MatMul whose Add has not arrived
@@ -127,6 +184,10 @@ class _Lowering:
             v = self.emit(v, 'linear')
         elif isinstance(v, _Sum):
             v = self.g.add(self.emit(v.conv, 'linear'), v.other)
+        elif isinstance(v, _Normed):
+            v = self.emit_normed(v, 'linear')
+        elif isinstance(v, _Only):
+            self.refuse(nd, f'reads {v.what}')
         elif isinstance(v, _Vec):
             self.refuse(nd, 'reads the pooled vector: only head operators may follow the global pool')
         self.env[name] = v
@@ -134,6 +195,26 @@ class _Lowering:
 
     def sole(self, name):
         return self.readers.get(name, 0) == 1 and name != self.m.outputs[0][0]
+
+    def emit_normed(self, n, act):
+        y = self.emit(n.conv, 'linear', res=n.other)
+        return self.g.instnorm(self.name_of(n.node), y, n.gamma, n.beta, n.eps, act)
+
+    def scalar(self, name):
+        """The value of a one-element constant, initialiser or folded scalar; None for anything else."""
+        v = self.env.get(name)
+        if isinstance(v, _Scalar):
+            return v.value
+        if name and self.m.has(name):
+            a = np.asarray(self.m.tensor(name))
+            if a.size == 1:
+                self.use(name)
+                return float(a.reshape(-1)[0])
+        return None
+
+    def open_root(self, v, nd):
+        if v.gem_node is not None:
+            self.refuse(nd, f'follows GeM pooling ({self.name_of(v.gem_node)!r}) whose root Pow(1 / p) has not been applied')
 
     # ------------------------------------------------------------------------------------------ operators
     def conv(self, nd):
@@ -170,7 +251,18 @@ class _Lowering:
             w = (v.w.astype(np.float64) * scale[:, None, None, None]).astype(np.float32)
             b = (v.b.astype(np.float64) * scale + shift).astype(np.float32)
             self.env[nd.outputs[0]] = _Conv(v.node, v.x, w, b, v.k, v.stride, v.pad)
+        elif isinstance(v, _Part) and not v.done:
+            sp = v.split
+            if v.index != 1 or not self.sole(nd.inputs[0]):
+                self.refuse(nd, 'BatchNormalization on the leading part of a Split: the InstanceNormalization half of an IBN '
+                                'layer must lead (IBN-a), the BatchNormalization half trail')
+            scale, shift = _bn_affine(self.m, nd, self.use)
+            if scale.shape != (sp.parts[1],):
+                self.refuse(nd, f'{scale.shape[0]} channels on a part of {sp.parts[1]}')
+            sp.bn = (scale, shift)
+            self.env[nd.outputs[0]] = _Part(sp, 1, done=True)
         elif isinstance(v, _Vec) and not v.relu and not v.bias_open:
+            self.open_root(v, nd)
             scale, shift = _bn_affine(self.m, nd, self.use)
             if scale.shape != (v.width,):
                 self.refuse(nd, f'{scale.shape[0]} channels on a vector of {v.width}')
@@ -192,11 +284,13 @@ class _Lowering:
             self.env[nd.outputs[0]] = self.emit(v, 'relu')
         elif isinstance(v, _Sum) and self.sole(nd.inputs[0]):
             self.env[nd.outputs[0]] = self.emit(v.conv, 'relu', res=v.other)
+        elif isinstance(v, _Normed) and self.sole(nd.inputs[0]):
+            self.env[nd.outputs[0]] = self.emit_normed(v, 'relu')
         elif isinstance(v, _Vec) and v.fc is not None and not v.relu and not v.bias_open:
             v.relu = True
             self.env[nd.outputs[0]] = v
         else:
-            self.refuse(nd, 'Relu that follows neither a Conv, a Conv + residual Add (read by it alone) nor the head\'s FC')
+            self.refuse(nd, 'Relu that follows neither a Conv, a Conv + residual Add, an IBN layer (read by it alone) nor the head\'s FC')
 
     def add(self, nd):
         a, b = (self.env.get(t) for t in nd.inputs)
@@ -252,8 +346,120 @@ class _Lowering:
         else:
             self.env[nd.outputs[0]] = self.g.pool(x, 3, 2, 0, pad_end=1)
 
-    def global_pool(self, nd):
+    # ---- IBN-Net
+    def split(self, nd):
+        v = self.env.get(nd.inputs[0])
+        if not (isinstance(v, _Conv) and self.sole(nd.inputs[0])):
+            self.refuse(nd, 'Split that does not read a Conv alone (the Split of an IBN-a layer does)')
+        parts = nd.attrs.get('split')
+        if parts is None and len(nd.inputs) > 1:
+            parts = self.const(nd, 1).reshape(-1).tolist()
+        c = v.w.shape[0]
+        if nd.attrs.get('axis', 0) != 1 or parts is None or len(parts) != 2 or len(nd.outputs) != 2 or sum(parts) != c or min(parts) < 1:
+            self.refuse(nd, f'Split axis {nd.attrs.get("axis", 0)} into {parts}: two parts along the channels that tile the '
+                            f'{c} channels of the conv')
+        if parts[0] % 8:
+            self.refuse(nd, f'IBN layer whose InstanceNormalization part has {parts[0]} channels: a multiple of 8')
+        sp = _Split(v, [int(q) for q in parts], nd)
+        for i, name in enumerate(nd.outputs):
+            self.env[name] = _Part(sp, i)
+
+    def instnorm(self, nd):
+        v = self.env.get(nd.inputs[0])
+        eps = float(nd.attrs.get('epsilon', 1e-5))
+        if isinstance(v, _Part) and not v.done:
+            sp = v.split
+            if v.index != 0:
+                self.refuse(nd, 'InstanceNormalization on the trailing part of a Split: the IN half of an IBN layer must lead '
+                                '(channels [0, h)), as in IBN-a')
+            if not self.sole(nd.inputs[0]):
+                self.refuse(nd, 'a part of a Split that something else reads as well')
+            gamma, beta = (self.const(nd, i).astype(np.float32).reshape(-1) for i in (1, 2))
+            if gamma.shape != (sp.parts[0],) or beta.shape != gamma.shape:
+                self.refuse(nd, f'{gamma.shape[0]} channels on a part of {sp.parts[0]}')
+            sp.inorm = (gamma, beta, eps, nd)
+            self.env[nd.outputs[0]] = _Part(sp, 0, done=True)
+            return
+        if isinstance(v, (_Conv, _Sum)) and self.sole(nd.inputs[0]):
+            conv, other = (v, None) if isinstance(v, _Conv) else (v.conv, v.other)
+            c = conv.w.shape[0]
+            gamma, beta = (self.const(nd, i).astype(np.float32).reshape(-1) for i in (1, 2))
+            if c % 8 or gamma.shape != (c,) or beta.shape != (c,):
+                self.refuse(nd, f'{gamma.shape[0]} channels behind a conv of {c} (a multiple of 8)')
+            self.env[nd.outputs[0]] = _Normed(conv, other, gamma, beta, eps, nd)
+            return
+        self.refuse(nd, 'InstanceNormalization that reads neither part 0 of an IBN Split nor a Conv or Conv + Add alone (a map '
+                        'that is already stored and activated would need a normalisation this lowering does not place)')
+
+    def concat(self, nd):
+        vs = [self.env.get(t) for t in nd.inputs]
+        if not (len(vs) == 2 and all(isinstance(v, _Part) and v.done for v in vs) and vs[0].split is vs[1].split and
+                nd.attrs.get('axis') == 1 and all(self.sole(t) for t in nd.inputs)):
+            self.refuse(nd, 'Concat that does not join the two halves of one IBN layer along the channels')
+        if (vs[0].index, vs[1].index) != (0, 1):
+            self.refuse(nd, 'Concat of an IBN layer with its parts out of order')
+        sp = vs[0].split
+        scale, shift = sp.bn
+        gamma, beta, eps, node = sp.inorm
+        h, c = sp.parts[0], sp.conv
+        w, b = c.w.astype(np.float64), c.b.astype(np.float64)
+        w[h:] *= scale[:, None, None, None]
+        b[h:] = b[h:] * scale + shift
+        self.env[nd.outputs[0]] = _Normed(_Conv(c.node, c.x, w.astype(np.float32), b.astype(np.float32), c.k, c.stride, c.pad),
+                                          None, gamma, beta, eps, node)
+
+    # ---- GeM
+    def clip(self, nd):
+        lo = self.scalar(nd.inputs[1]) if len(nd.inputs) > 1 and nd.inputs[1] else nd.attrs.get('min')
+        has_max = (len(nd.inputs) > 2 and nd.inputs[2]) or 'max' in nd.attrs
+        if lo is None or has_max or not 0 < lo <= 1:
+            self.refuse(nd, 'Clip that is not the clamp of GeM pooling (min = a scalar constant in (0, 1], no max)')
         x = self.view(nd.inputs[0], nd)
+        if not self.sole(nd.outputs[0]):
+            self.refuse(nd, 'the clamp of GeM pooling read by more than its Pow')
+        self.env[nd.outputs[0]] = _Gem(x, float(lo))
+
+    def pow(self, nd):
+        v = self.env.get(nd.inputs[0])
+        e = self.scalar(nd.inputs[1]) if len(nd.inputs) > 1 else None
+        if isinstance(v, _Gem) and v.p is None:
+            if e is None or not 0.5 <= e <= 16:
+                self.refuse(nd, 'GeM pooling whose exponent is not one scalar constant in [0.5, 16] (a per-channel p is not supported)')
+            if not self.sole(nd.outputs[0]):
+                self.refuse(nd, 'the powered map of GeM pooling read by more than its global pool')
+            self.env[nd.outputs[0]] = _Gem(v.x, v.eps, float(e))
+        elif isinstance(v, _Vec) and v.gem_node is not None and v.neck is None and v.fc is None:
+            if e is None or abs(e * v.gem[0] - 1) > 1e-4:
+                self.refuse(nd, f'the root of GeM pooling with exponent {e}: it does not match 1 / p of {self.name_of(v.gem_node)!r} '
+                                f'(p = {v.gem[0]:g})')
+            v.gem_node = None
+            self.env[nd.outputs[0]] = v
+        else:
+            self.refuse(nd, 'Pow that is neither the power of GeM pooling (behind its Clip, scalar exponent) nor its root')
+
+    def fold_scalar(self, nd):
+        vals = [self.scalar(t) for t in nd.inputs]
+        if not vals or any(v is None for v in vals):
+            self.refuse(nd, 'operator not supported')
+        if nd.op == 'Cast':
+            if nd.attrs.get('to') not in (1, 11):
+                self.refuse(nd, f'Cast of a scalar to type {nd.attrs.get("to")}')
+            out = vals[0]
+        elif nd.op == 'Reciprocal':
+            out = 1.0 / vals[0]
+        else:
+            out = vals[0] * vals[1]
+        self.env[nd.outputs[0]] = _Scalar(float(out))
+
+    def global_pool(self, nd):
+        v = self.env.get(nd.inputs[0])
+        gem = None
+        if isinstance(v, _Gem):
+            if v.p is None:
+                self.refuse(nd, 'global pool of a clamped map without the Pow of GeM pooling')
+            x, gem = v.x, (v.p, v.eps)
+        else:
+            x = self.view(nd.inputs[0], nd)
         a = nd.attrs
         if nd.op == 'ReduceMean':
             axes = a.get('axes')
@@ -268,7 +474,7 @@ class _Lowering:
                                 '(only the whole map)')
         if x.c % 8 or x.coff % 8 or x.c > Graph.POOLHEAD_MAX:
             self.refuse(nd, f'global pool over {x.c} channels (a multiple of 8, at most {Graph.POOLHEAD_MAX})')
-        self.env[nd.outputs[0]] = _Vec(x)
+        self.env[nd.outputs[0]] = _Vec(x, gem, nd if gem is not None else None)
 
     def reshape(self, nd):
         v = self.env.get(nd.inputs[0])
@@ -285,6 +491,7 @@ class _Lowering:
         v = self.env.get(nd.inputs[0])
         if not isinstance(v, _Vec) or v.fc is not None:
             self.refuse(nd, f'{nd.op} that does not read the pooled vector (or a second FC)')
+        self.open_root(v, nd)
         w = self.const(nd, 1).astype(np.float32)
         a = nd.attrs
         if nd.op == 'Gemm':
@@ -318,7 +525,8 @@ class _Lowering:
     HANDLERS = {'Conv': conv, 'BatchNormalization': batchnorm, 'Relu': relu, 'Add': add, 'MaxPool': maxpool,
                 'GlobalAveragePool': global_pool, 'ReduceMean': global_pool, 'AveragePool': global_pool,
                 'Flatten': reshape, 'Reshape': reshape, 'Squeeze': reshape, 'Gemm': fc, 'MatMul': fc,
-                'Identity': skip, 'Dropout': skip}
+                'Identity': skip, 'Dropout': skip, 'Split': split, 'InstanceNormalization': instnorm, 'Concat': concat,
+                'Clip': clip, 'Pow': pow, 'Cast': fold_scalar, 'Reciprocal': fold_scalar, 'Mul': fold_scalar}
 
     def run(self):
         for nd in self.m.nodes:
@@ -334,12 +542,14 @@ class _Lowering:
             raise NotImplementedError(f'{self.where}: the output {out_name!r} is not a pooled embedding vector (a global pool '
                                       f'and the head operators must end the graph).  Supported: {SUPPORTED}')
         v.bias_open = False
+        if v.gem_node is not None:
+            self.refuse(v.gem_node, 'GeM pooling without its root: the pooled vector must go through Pow(1 / p)')
         if self.output_dim is not None and v.width != self.output_dim:
             raise ValueError(f'{self.where}: the file\'s embedding has {v.width} components, OUTPUT_LAYOUT is {self.output_dim}')
         unused = [n for n in self.inits if n not in self.used]
         if unused:
             raise ValueError(f'{self.where}: parameters not used by the lowering: {unused[:5]} ...')
-        out = self.g.poolhead('head', v.x, neck=v.neck, fc=tuple(v.fc) if v.fc is not None else None, relu=v.relu)
+        out = self.g.poolhead('head', v.x, neck=v.neck, fc=tuple(v.fc) if v.fc is not None else None, relu=v.relu, gem=v.gem)
         self.g.outputs = [v.x]
         return self.g, out
 

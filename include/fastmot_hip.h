@@ -322,12 +322,22 @@ enum {
                           * per-channel affine, the BN neck folded to w2_off = f32 scale [cin], b2_off = f32 shift [cin] -> gate[1] > 0:
                           * FC cin -> cout (w_off = fp16 [cout][cin], b_off = f32 [cout] with any BatchNorm folded in, act = linear or
                           * ReLU), one wavefront per output row; otherwise cout == cin -> L2 normalise -> ctx embeddings and their
-                          * page-locked mirror (as FM_OP_HEAD)                                                                    */
+                          * page-locked mirror (as FM_OP_HEAD).  gate[2] > 0: GeM pooling -- gate[2] = the IEEE-754 bits of the fp32
+                          * exponent p (0.5 <= p <= 16), gate[3] = the bits of the clamp eps (0 < eps <= 1): the pool sums
+                          * max(x, eps)^p and the mean takes the p-th root before the neck (p == 3: two multiplies and cbrtf,
+                          * otherwise powf); gate[2] <= 0 (a plain head leaves -1): the average pool                          */
     FM_OP_STEMPOOL = 24, /* the ResNet stem with its max pool in one launch (stempool.hip): conv 7x7 stride 2 pad 3 of in[0] = the network
                           * input (<= 4 real channels) -> cout <= 64 (% 8), + bias + ReLU, rounded to fp16 in LDS and never stored, then
                           * max pool 3x3 stride 2 with gate[0] = 1: pads 1, gate[0] = 0: pads 0 and ceil_mode (windows clipped at the far
                           * edge); w_off = fp16 [ceil32(cout)][208] (K order kh, kw, c < 4), b_off = f32 [ceil32(cout)].  As
                           * FM_OP_STEMCONV, the extractor front end lets it compute the crops from the frame itself            */
+    FM_OP_INSTNORM = 25, /* instance normalisation of a channel view in one launch (instnorm.hip; IBN-Net layers): the first hid = cn
+                          * channels of in[0]'s view (cin channels; cn % 8 == 0, 8 <= cn <= cin = cout) are normalised per sample and
+                          * channel over h x w with the biased variance, y = act((x - mean) * (1 / sqrt(var + eps)) * gamma + beta),
+                          * w_off / b_off = f32 gamma [cn] / beta [cn], statistics in fp32 (variance from centred squares); channels
+                          * [cn, cin) get the activation only; act = linear or ReLU; eps is a per-op extra: gate[0] = the IEEE-754
+                          * bits of the fp32 value (0 <= eps < 1; 1e-5 is 0x3727C5AC).  in_coff / out_coff % 8 == 0, any channel
+                          * strides; out is another tensor than in[0] (never in place), fp16 both                              */
     FM_OP_GATED_SUM = 11 /* OSNet unified aggregation gate in one launch: out = sum_i in[i] *
                           * sigmoid(fc2(relu(fc1(GAP(in[i]))))) with shared fc weights
                           * (w_off, b_off, w2_off, b2_off, hid) -- FM_OP_GATE x n_in + FM_OP_GATE_SUM */
