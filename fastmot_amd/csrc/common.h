@@ -108,7 +108,7 @@ struct fm_ctx {
     int opt_det_front_layers = -1;     // "det_front_layers": 0 off, k the first k layers, -1 the rule (net.hip fm_net_front_prepare)
     int opt_det_front_stream = 0;      // "det_front_stream": the stream that carries the front: 0 s_up, 1 s_ext
     bool det_flush_deferred = false;   // a look-ahead upload left the pending post-processing to the pass that follows it
-    int opt_lk_variant = 0;            // "lk_variant": diagnostic variants of the LK kernel (flow.hip lk_diag_kernel)
+    int opt_lk_variant = 0;            // "lk_variant": diagnostic variants of the LK kernel (lk_core.h lk_diag_kernel)
     void* predict_worker = nullptr;    // native KLT + Kalman worker thread of this context (flow_estimate.hip)
     hipStream_t s_main = nullptr;   // tracker kernels
     hipStream_t s_det = nullptr;    // detector network

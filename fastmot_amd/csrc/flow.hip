@@ -85,15 +85,13 @@ void fm_flow_free(FlowState* f) {
 namespace {
 
 // FM_SGPR_CAP: scalar register budget of the KLT kernels.  A round-2 measure against the LK results that differed under
-// load (their rate followed the budget); round 3 found the cause elsewhere (packed-fp32 arithmetic, see lk_wave_body
-// and build.py FILE_FLAGS) -- the cap stays because the kernels were tuned with it (occupancy 8 either way).
+// load (their rate followed the budget); round 3 found the cause elsewhere (packed-fp32 arithmetic, see the head of
+// lk_core.h and build.py FILE_FLAGS) -- the cap stays because the kernels were tuned with it.  It does not set the
+// occupancy: that follows the vector registers (lk_pair_kernel 50 VGPRs, 8 waves/SIMD; lk_pair_pre_kernel 75, 6).
 #define FM_SGPR_CAP __attribute__((amdgpu_num_sgpr(48)))
 
-__device__ __forceinline__ int reflect101(int i, int n) {
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-    return i;
-}
+// ---- pyramidal Lucas-Kanade: reflect101, the LK device code and its kernels
+#include "lk_core.h"
 
 // ---- cvtColor BGR2GRAY, 8 bit: OpenCV's RGB2Gray<uchar>, (B cb + G cg + R cr + (1 << (bits - 1))) >> bits with the
 // 14-bit coefficients 1868 / 9617 / 4899 (up to the 4.2 era: the reference pins 4.1.1) or the 15-bit ones
@@ -269,864 +267,6 @@ __global__ __launch_bounds__(1024) void pyr_tail_kernel(PyrTail t) {
         __syncthreads();
     }
 }
-
-// ---- pyramidal Lucas-Kanade (video/lkpyramid.cpp LKTrackerInvoker), one thread per point
-struct LKArgs {
-    const uint8_t* I[MAX_LEVELS];
-    const uint8_t* J[MAX_LEVELS];
-    const int16_t* D[MAX_LEVELS];
-    int w[MAX_LEVELS], h[MAX_LEVELS];
-    int levels, win, max_count;
-    float eps2, min_eig_thresh;
-};
-
-#define LK_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
-
-// one image byte.  -DFM_LK_DWORD_LOADS: through an ALIGNED 32-bit load, the byte shifted out in registers -- experiment of
-// late round 2: what the disturbed LK kernel gets wrong looks like single window samples being off (err changes by one
-// or two quanta of 1/800, positions by 1e-4 .. 0.15 px: scripts/stress_lk7.py), which pointed at the scattered sub-dword
-// loads; but the disturbance is the same with dword loads (34 vs 42 differing results in 400 calls), so they are not it.
-__device__ __forceinline__ int lk_px(const uint8_t* __restrict__ row, int c) {
-#ifndef FM_LK_DWORD_LOADS
-    return row[c];
-#else
-    const uintptr_t a = reinterpret_cast<uintptr_t>(row) + (uintptr_t)c;
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(a & ~uintptr_t(3));
-    return (int)((w >> ((a & 3) * 8)) & 0xffu);
-#endif
-}
-
-// float32 sum of lanes 0..N-1 in lane order, starting from 0.f like the scalar loops of lkpyramid.cpp.
-// Sequential inclusive scan over the lanes: every step adds the left neighbour's running value (DPP wave_shr:1,
-// lane 0 reads 0) to the lane's own term, a(s)[i] = a(s-1)[i-1] + v[i].  By induction lane i holds
-// ((v0 + v1) + ...) + vi after step i and keeps it, so N-1 steps leave the scalar-order sum in lane N-1: the
-// same N-1 dependent float32 adds as the scalar loop, one VALU instruction each (round 2's first version walked
-// the lanes with v_readlane: 2 instructions + an SGPR round trip per term).
-__device__ __forceinline__ float seq_step(float acc, float v) {
-    const int left = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-    return __builtin_bit_cast(float, left) + v;
-}
-__device__ __forceinline__ float lane_value(float v, int lane) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-template <int N>
-__device__ __forceinline__ float seq_sum(float v, float* pfx = nullptr) {
-    float acc = v;
-#pragma unroll
-    for (int k = 1; k < N; ++k) acc = seq_step(acc, v);
-    if (pfx) *pfx = acc;
-    return lane_value(acc, N - 1);
-}
-// two / three independent sums, their scans interleaved step by step (a DPP read of a VGPR written by the previous
-// VALU instruction costs wait states; the neighbouring chain fills them).  `pfx` (diagnostic builds): the lanes' running
-// sums after the scan, lane i = v0 + .. + vi.
-template <int N>
-__device__ __forceinline__ void seq_sum2(float v0, float v1, float& s0, float& s1, float* pfx = nullptr) {
-    float a0 = v0, a1 = v1;
-#pragma unroll
-    for (int k = 1; k < N; ++k) { a0 = seq_step(a0, v0); a1 = seq_step(a1, v1); }
-    if (pfx) { pfx[0] = a0; pfx[1] = a1; }
-    s0 = lane_value(a0, N - 1);
-    s1 = lane_value(a1, N - 1);
-}
-template <int N>
-__device__ __forceinline__ void seq_sum3(float v0, float v1, float v2, float& s0, float& s1, float& s2, float* pfx = nullptr) {
-    float a0 = v0, a1 = v1, a2 = v2;
-#pragma unroll
-    for (int k = 1; k < N; ++k) { a0 = seq_step(a0, v0); a1 = seq_step(a1, v1); a2 = seq_step(a2, v2); }
-    if (pfx) { pfx[0] = a0; pfx[1] = a1; pfx[2] = a2; }
-    s0 = lane_value(a0, N - 1);
-    s1 = lane_value(a1, N - 1);
-    s2 = lane_value(a2, N - 1);
-}
-
-// The same sums WITHOUT any cross-lane VALU operation: every lane parks its term in the wavefront's LDS slab, then
-// every lane reads all N terms back (same address in all lanes: broadcast reads) and adds them in scalar order in its
-// own registers -- N - 1 dependent float32 adds per sum again, the result is in every lane by construction.
-// LDS operations of one wavefront execute in order; the fences keep the compiler from moving them.
-template <int N>
-__device__ __forceinline__ float lds_seq(const float* __restrict__ slab) {
-    const float4* q = reinterpret_cast<const float4*>(slab);
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < N / 4; ++k) {
-        const float4 t = q[k];
-        acc += t.x; acc += t.y; acc += t.z; acc += t.w;
-    }
-#pragma unroll
-    for (int k = N / 4 * 4; k < N; ++k) acc += slab[k];
-    return acc;
-}
-template <int N, int K>
-__device__ __forceinline__ void lds_sums(float* slab, int lane, const float (&v)[K], float (&s)[K]) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (lane < 32) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) slab[32 * k + lane] = v[k];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = lds_seq<N>(slab + 32 * k);
-    __builtin_amdgcn_wave_barrier();
-}
-
-// One WAVEFRONT per point: lane g < win*win owns window pixel (g / win, g % win) -- the samples of a window are taken
-// in parallel, and every window sum (A11, A12, A22, b1, b2, the error) is accumulated in the sequential (y, x) order of
-// LKTrackerInvoker's scalar loops (seq_sum*: 24 dependent float32 adds): bit-identical to
-// oracle/cv_oracle.calc_optical_flow_pyr_lk.  (A butterfly reduction agrees with the scalar order to ~1e-4 px only --
-// enough to flip an inlier decision now and then and let the keypoint sets of the two implementations drift apart over
-// a clip, tests/test_e2e_parity_gpu.py.)  Everything after the sums is wave-uniform arithmetic that every lane
-// repeats; the control flow (levels skipped, iteration counts) is therefore uniform and compiled as scalar branches on
-// "any lane" conditions -- which is why ONE wrong lane changes the result of the point.
-//
-// The wrong lane (rounds 1-2: "LK results differ from call to call while the ReID network runs").  Round 3
-// captured every iteration of disturbed calls (lk_diag_kernel below, scripts/lk_bisect.py, profiles/r03_lk_bisect.txt):
-// samples, running sums and broadcast sums were always right; what was wrong was dx of the position update
-//     dx = (A12 * b2 - A22 * b1) * Dt,   dy = (A12 * b1 - A11 * b2) * Dt
-// in lanes 48..63 only.  The SLP vectoriser had packed the two expressions into v_pk_mul_f32 / v_pk_add_f32, the cross
-// terms through `v_pk_mul_f32 ... op_sel:[0,1] op_sel_hi:[1,0]` (low result from the HIGH register of a source pair);
-// on MI355X that instruction form returns a wrong low half in the last 16 lanes of the wavefront now and then while
-// wavefronts of the fused LightConv kernels (or of two streamed-conv variants) are resident on the same CU -- never
-// when idle, never with unpacked v_mul_f32 / v_sub_f32 (csrc/diag.hip reproduces it stand alone: 0 of 72 M evaluations
-// idle, ~25 k wrong lanes beside litechain_kernel, all in lanes 48..63, all in the low half).  A wrong dx in lanes
-// 48..63 then ends (or prolongs) the iteration through the any-lane branch: positions off by 1e-4 .. 6 px.
-// Consequence: this file is compiled with -fno-slp-vectorize (build.py FILE_FLAGS: no packed fp32 in the KLT kernels; 0
-// disagreeing lanes in 5.1 M iterations under the same load), tests/test_isa_lint.py refuses the instruction form in
-// every kernel of the library, and the launch needs neither whole CUs nor an ordering against the ReID network.
-template <int WINC>
-__device__ __forceinline__ void lk_wave_body(const LKArgs& a, int n, const float* __restrict__ prev_pts,
-                                                 float* __restrict__ next_pts, uint8_t* __restrict__ status,
-                                                 float* __restrict__ err) {
-    const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int pt = gidx >> 6, g = gidx & 63;
-    if (pt >= n) return;                       // the whole wavefront exits together
-    constexpr int win = WINC;
-    const bool lane_on = g < win * win;
-    const int wy = lane_on ? g / win : 0, wx = lane_on ? g % win : 0;
-    const float half = (win - 1) * 0.5f;
-    const float px0 = prev_pts[2 * pt], py0 = prev_pts[2 * pt + 1];
-    float nx = 0.f, ny = 0.f;
-    bool st = true;
-    float er = 0.f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    auto weights = [](float fa, float fb, int& iw00, int& iw01, int& iw10, int& iw11) {
-        iw00 = __float2int_rn((1.f - fa) * (1.f - fb) * (1 << 14));
-        iw01 = __float2int_rn(fa * (1.f - fb) * (1 << 14));
-        iw10 = __float2int_rn((1.f - fa) * fb * (1 << 14));
-        iw11 = (1 << 14) - iw00 - iw01 - iw10;
-    };
-    for (int level = a.levels - 1; level >= 0; --level) {
-        const int w = a.w[level], h = a.h[level];
-        const uint8_t* I = a.I[level];
-        const uint8_t* J = a.J[level];
-        const int16_t* D = a.D[level];
-        const float sc = 1.f / (float)(1 << level);
-        float ppx = px0 * sc, ppy = py0 * sc;
-        if (level == a.levels - 1) { nx = ppx; ny = ppy; }
-        else { nx *= 2.f; ny *= 2.f; }
-        ppx -= half; ppy -= half;
-        const int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
-        if (ipx < -win || ipx >= w || ipy < -win || ipy >= h) {
-            if (level == 0) { st = false; er = 0.f; }
-            continue;
-        }
-        int iw00, iw01, iw10, iw11;
-        weights(ppx - ipx, ppy - ipy, iw00, iw01, iw10, iw11);
-        int ival = 0, ixval = 0, iyval = 0;
-        if (lane_on) {
-            const int xx0 = ipx + wx, xx1 = xx0 + 1, yy0 = ipy + wy, yy1 = yy0 + 1;
-            const uint8_t* r0 = I + (size_t)reflect101(yy0, h) * w;
-            const uint8_t* r1 = I + (size_t)reflect101(yy1, h) * w;
-            const int c0 = reflect101(xx0, w), c1 = reflect101(xx1, w);
-            ival = LK_DESCALE(lk_px(r0, c0) * iw00 + lk_px(r0, c1) * iw01 + lk_px(r1, c0) * iw10 + lk_px(r1, c1) * iw11, 14 - 5);
-            // derivative image is zero outside (BORDER_CONSTANT), lkpyramid.cpp
-            auto dv = [&](int xx, int yy) -> int2 {
-                if (xx < 0 || xx >= w || yy < 0 || yy >= h) return make_int2(0, 0);
-                const int v = *reinterpret_cast<const int*>(D + ((size_t)yy * w + xx) * 2);
-                return make_int2((int)(short)(v & 0xffff), (int)(short)(v >> 16));
-            };
-            const int2 d00 = dv(xx0, yy0), d01 = dv(xx1, yy0), d10 = dv(xx0, yy1), d11 = dv(xx1, yy1);
-            ixval = LK_DESCALE(d00.x * iw00 + d01.x * iw01 + d10.x * iw10 + d11.x * iw11, 14);
-            iyval = LK_DESCALE(d00.y * iw00 + d01.y * iw01 + d10.y * iw10 + d11.y * iw11, 14);
-        }
-        float A11, A12, A22;
-        seq_sum3<WINC * WINC>((float)(ixval * ixval), (float)(ixval * iyval), (float)(iyval * iyval), A11, A12, A22);
-        A11 *= FLT_SCALE; A12 *= FLT_SCALE; A22 *= FLT_SCALE;
-        float Dt = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * win * win);
-        if (minEig < a.min_eig_thresh || Dt < 1.1920929e-07f) {
-            if (level == 0) st = false;
-            continue;
-        }
-        Dt = 1.f / Dt;
-        nx -= half; ny -= half;
-        float pdx = 0.f, pdy = 0.f;
-        float outx = nx + half, outy = ny + half;
-        bool running = true;
-        for (int j = 0; j < a.max_count; ++j) {
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-            if (running && (inx < -win || inx >= w || iny < -win || iny >= h)) {
-                if (level == 0) st = false;
-                running = false;
-            }
-            if (!running) break;                 // uniform within the 32-lane group
-            weights(nx - inx, ny - iny, iw00, iw01, iw10, iw11);
-            int diff = 0;
-            if (lane_on) {
-                const uint8_t* r0 = J + (size_t)reflect101(iny + wy, h) * w;
-                const uint8_t* r1 = J + (size_t)reflect101(iny + wy + 1, h) * w;
-                const int c0 = reflect101(inx + wx, w), c1 = reflect101(inx + wx + 1, w);
-                diff = LK_DESCALE(lk_px(r0, c0) * iw00 + lk_px(r0, c1) * iw01 + lk_px(r1, c0) * iw10 + lk_px(r1, c1) * iw11, 14 - 5) - ival;
-            }
-            float b1, b2;
-            seq_sum2<WINC * WINC>((float)(diff * ixval), (float)(diff * iyval), b1, b2);
-            b1 *= FLT_SCALE; b2 *= FLT_SCALE;
-            const float dx = (A12 * b2 - A22 * b1) * Dt, dy = (A12 * b1 - A11 * b2) * Dt;
-            nx += dx; ny += dy;
-            outx = nx + half; outy = ny + half;
-            if (dx * dx + dy * dy <= a.eps2) break;
-            if (j > 0 && fabsf(dx + pdx) < 0.01f && fabsf(dy + pdy) < 0.01f) {
-                outx -= dx * 0.5f; outy -= dy * 0.5f;
-                break;
-            }
-            pdx = dx; pdy = dy;
-        }
-        nx = outx; ny = outy;
-        if (st && level == 0) {
-            const float ex = nx - half, ey = ny - half;
-            const int inx = (int)floorf(ex), iny = (int)floorf(ey);
-            if (inx < -win || inx >= w || iny < -win || iny >= h) { st = false; continue; }
-            weights(ex - inx, ey - iny, iw00, iw01, iw10, iw11);
-            int diff = 0;
-            if (lane_on) {
-                const uint8_t* r0 = J + (size_t)reflect101(iny + wy, h) * w;
-                const uint8_t* r1 = J + (size_t)reflect101(iny + wy + 1, h) * w;
-                const int c0 = reflect101(inx + wx, w), c1 = reflect101(inx + wx + 1, w);
-                diff = LK_DESCALE(lk_px(r0, c0) * iw00 + lk_px(r0, c1) * iw01 + lk_px(r1, c0) * iw10 + lk_px(r1, c1) * iw11, 14 - 5) - ival;
-            }
-            er = seq_sum<WINC * WINC>(fabsf((float)diff)) * 1.f / (32 * win * win);
-        }
-    }
-    if (g == 0) {
-        next_pts[2 * pt] = nx;
-        next_pts[2 * pt + 1] = ny;
-        status[pt] = st ? 1 : 0;
-        err[pt] = er;
-    }
-}
-
-
-template <int WINC>
-__global__ __launch_bounds__(1024) FM_SGPR_CAP void lk_wave_kernel(LKArgs a, int n, const float* __restrict__ prev_pts,
-                                                      float* __restrict__ next_pts, uint8_t* __restrict__ status,
-                                                      float* __restrict__ err) {
-    lk_wave_body<WINC>(a, n, prev_pts, next_pts, status, err);
-}
-
-// ---- two points per wavefront.  Lanes 0..24 carry the window of point 2 w, lanes 32..56 the window of point 2 w + 1;
-// the seven lanes behind each window LEAVE the kernel at once.  That is what lets the DPP scans of the two windows run
-// in the same instructions: a lane whose left neighbour is masked off reads 0 (bound_ctrl), exactly like lane 0 whose
-// neighbour does not exist, so the scan restarts at lane 32 by itself.  The broadcast of a sum comes from lane 24 of
-// the own half (ds_bpermute instead of v_readlane), the arithmetic behind it is per lane as before, and the control
-// flow -- levels skipped, iteration counts -- is now divergent between the halves (the compiler masks; nothing is
-// wave-uniform any more except the level loop).  Same operations in the same order per point: bit-identical to the
-// one-point kernel (tests/test_flow_gpu.py).  Half the wavefronts hold the registers half as long per point: the
-// kernel's footprint beside the other streams' kernels is what the pipeline pays for.
-__device__ __forceinline__ float half_value(float v, int lane_in_half, int half_base) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((half_base + lane_in_half) << 2, __builtin_bit_cast(int, v)));
-}
-
-// PATCH (round 5): the iteration's samples of the NEW frame come from a 16 x 16 byte patch of the level
-// in LDS, filled once per (point, level) around the start position (+-5 px of travel inside a level; a window that
-// leaves the patch falls back to the global loads).  An iteration then waits for four ds_read_u8 (~100 cycles) instead
-// of four global byte loads (~500-700 cycles beside the networks); the values, and with them every result, are the same.
-// The patch is private to a half-wavefront: a wavefront's LDS operations execute in program order, no barrier is needed
-// (and none is possible: lanes leave early and the two halves diverge).
-constexpr int LK_PW = 16, LK_PR = 5;
-
-template <int WINC, bool PATCH>
-__global__ __launch_bounds__(256) FM_SGPR_CAP void lk_pair_kernel(LKArgs a, int n, const float* __restrict__ prev_pts,
-                                                                  float* __restrict__ next_pts, uint8_t* __restrict__ status,
-                                                                  float* __restrict__ err) {
-    __shared__ __attribute__((aligned(16))) uint8_t patch_all[PATCH ? 8 * LK_PW * LK_PW : 16];
-    const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = gidx & 63, g = l & 31, hb = l & 32;
-    const int pt = (gidx >> 6) * 2 + (l >> 5);
-    constexpr int win = WINC, NW = WINC * WINC;
-    if (pt >= n || g >= NW) return;
-    uint8_t* const patch = patch_all + (PATCH ? ((threadIdx.x >> 5) & 7) * (LK_PW * LK_PW) : 0);
-    int sx0 = 0, sy0 = 0;                       // top-left corner of the patch in level coordinates
-    bool have_patch = false;
-    const int wy = g / win, wx = g % win;
-    const float half = (win - 1) * 0.5f;
-    const float px0 = prev_pts[2 * pt], py0 = prev_pts[2 * pt + 1];
-    float nx = 0.f, ny = 0.f;
-    bool st = true;
-    float er = 0.f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    auto weights = [](float fa, float fb, int& iw00, int& iw01, int& iw10, int& iw11) {
-        iw00 = __float2int_rn((1.f - fa) * (1.f - fb) * (1 << 14));
-        iw01 = __float2int_rn(fa * (1.f - fb) * (1 << 14));
-        iw10 = __float2int_rn((1.f - fa) * fb * (1 << 14));
-        iw11 = (1 << 14) - iw00 - iw01 - iw10;
-    };
-    auto sample = [&](const uint8_t* img, int w, int h, int bx, int by, int iw00, int iw01, int iw10, int iw11) -> int {
-        const uint8_t* r0 = img + (size_t)reflect101(by + wy, h) * w;
-        const uint8_t* r1 = img + (size_t)reflect101(by + wy + 1, h) * w;
-        const int c0 = reflect101(bx + wx, w), c1 = reflect101(bx + wx + 1, w);
-        return LK_DESCALE(lk_px(r0, c0) * iw00 + lk_px(r0, c1) * iw01 + lk_px(r1, c0) * iw10 + lk_px(r1, c1) * iw11, 14 - 5);
-    };
-    // the same sample of the new frame J, from the patch when the (win + 1)^2 pixels of the window lie inside it
-    auto sample_j = [&](const uint8_t* img, int w, int h, int bx, int by, int iw00, int iw01, int iw10, int iw11) -> int {
-        if (PATCH && have_patch && bx >= sx0 && by >= sy0 && bx + win + 1 <= sx0 + LK_PW && by + win + 1 <= sy0 + LK_PW) {
-            const uint8_t* q = patch + (by - sy0 + wy) * LK_PW + (bx - sx0 + wx);
-            return LK_DESCALE((int)q[0] * iw00 + (int)q[1] * iw01 + (int)q[LK_PW] * iw10 + (int)q[LK_PW + 1] * iw11, 14 - 5);
-        }
-        return sample(img, w, h, bx, by, iw00, iw01, iw10, iw11);
-    };
-    // patch[r][c] = J[reflect101(y0 + r)][reflect101(x0 + c)]: 64 dwords, three per lane.  Inside the image a dword is two
-    // ALIGNED loads and a byte alignment; at the borders four byte loads with the reflection sample() applies.
-    auto fill_patch = [&](const uint8_t* img, int w, int h, int x0, int y0) {
-        sx0 = x0; sy0 = y0;
-        const bool inside = x0 >= 0 && x0 + LK_PW + 4 <= w;
-        for (int item = g; item < LK_PW * LK_PW / 4; item += NW) {
-            const int r = item >> 2, c = (item & 3) * 4;
-            const uint8_t* row = img + (size_t)reflect101(y0 + r, h) * w;
-            uint32_t v;
-            if (inside) {
-                const uintptr_t ad = reinterpret_cast<uintptr_t>(row) + (uintptr_t)(x0 + c);
-                const uint32_t* al = reinterpret_cast<const uint32_t*>(ad & ~uintptr_t(3));
-                v = __builtin_amdgcn_alignbyte(al[1], al[0], (uint32_t)(ad & 3));
-            } else {
-                v = (uint32_t)row[reflect101(x0 + c, w)] | (uint32_t)row[reflect101(x0 + c + 1, w)] << 8 |
-                    (uint32_t)row[reflect101(x0 + c + 2, w)] << 16 | (uint32_t)row[reflect101(x0 + c + 3, w)] << 24;
-            }
-            *reinterpret_cast<uint32_t*>(patch + r * LK_PW + c) = v;
-        }
-        have_patch = true;
-    };
-    for (int level = a.levels - 1; level >= 0; --level) {
-        const int w = a.w[level], h = a.h[level];
-        const uint8_t* I = a.I[level];
-        const uint8_t* J = a.J[level];
-        const int16_t* D = a.D[level];
-        have_patch = false;
-        const float sc = 1.f / (float)(1 << level);
-        float ppx = px0 * sc, ppy = py0 * sc;
-        if (level == a.levels - 1) { nx = ppx; ny = ppy; }
-        else { nx *= 2.f; ny *= 2.f; }
-        ppx -= half; ppy -= half;
-        const int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
-        if (ipx < -win || ipx >= w || ipy < -win || ipy >= h) {
-            if (level == 0) { st = false; er = 0.f; }
-            continue;
-        }
-        int iw00, iw01, iw10, iw11;
-        weights(ppx - ipx, ppy - ipy, iw00, iw01, iw10, iw11);
-        const int ival = sample(I, w, h, ipx, ipy, iw00, iw01, iw10, iw11);
-        int ixval, iyval;
-        {
-            const int xx0 = ipx + wx, xx1 = xx0 + 1, yy0 = ipy + wy, yy1 = yy0 + 1;
-            // derivative image is zero outside (BORDER_CONSTANT), lkpyramid.cpp
-            auto dv = [&](int xx, int yy) -> int2 {
-                if (xx < 0 || xx >= w || yy < 0 || yy >= h) return make_int2(0, 0);
-                const int v = *reinterpret_cast<const int*>(D + ((size_t)yy * w + xx) * 2);
-                return make_int2((int)(short)(v & 0xffff), (int)(short)(v >> 16));
-            };
-            const int2 d00 = dv(xx0, yy0), d01 = dv(xx1, yy0), d10 = dv(xx0, yy1), d11 = dv(xx1, yy1);
-            ixval = LK_DESCALE(d00.x * iw00 + d01.x * iw01 + d10.x * iw10 + d11.x * iw11, 14);
-            iyval = LK_DESCALE(d00.y * iw00 + d01.y * iw01 + d10.y * iw10 + d11.y * iw11, 14);
-        }
-        float A11, A12, A22;
-        {
-            const float v0 = (float)(ixval * ixval), v1 = (float)(ixval * iyval), v2 = (float)(iyval * iyval);
-            float a0 = v0, a1 = v1, a2 = v2;
-#pragma unroll
-            for (int k = 1; k < NW; ++k) { a0 = seq_step(a0, v0); a1 = seq_step(a1, v1); a2 = seq_step(a2, v2); }
-            A11 = half_value(a0, NW - 1, hb); A12 = half_value(a1, NW - 1, hb); A22 = half_value(a2, NW - 1, hb);
-        }
-        A11 *= FLT_SCALE; A12 *= FLT_SCALE; A22 *= FLT_SCALE;
-        float Dt = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * win * win);
-        if (minEig < a.min_eig_thresh || Dt < 1.1920929e-07f) {
-            if (level == 0) st = false;
-            continue;
-        }
-        Dt = 1.f / Dt;
-        nx -= half; ny -= half;
-        float pdx = 0.f, pdy = 0.f;
-        float outx = nx + half, outy = ny + half;
-        if (PATCH) {
-            const int fx = (int)floorf(nx), fy = (int)floorf(ny);
-            if (fx >= -win && fx < w && fy >= -win && fy < h) fill_patch(J, w, h, fx - LK_PR, fy - LK_PR);
-        }
-        for (int j = 0; j < a.max_count; ++j) {
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-            if (inx < -win || inx >= w || iny < -win || iny >= h) {
-                if (level == 0) st = false;
-                break;
-            }
-            weights(nx - inx, ny - iny, iw00, iw01, iw10, iw11);
-            const int diff = sample_j(J, w, h, inx, iny, iw00, iw01, iw10, iw11) - ival;
-            float b1, b2;
-            {
-                const float v0 = (float)(diff * ixval), v1 = (float)(diff * iyval);
-                float a0 = v0, a1 = v1;
-#pragma unroll
-                for (int k = 1; k < NW; ++k) { a0 = seq_step(a0, v0); a1 = seq_step(a1, v1); }
-                b1 = half_value(a0, NW - 1, hb); b2 = half_value(a1, NW - 1, hb);
-            }
-            b1 *= FLT_SCALE; b2 *= FLT_SCALE;
-            const float dx = (A12 * b2 - A22 * b1) * Dt, dy = (A12 * b1 - A11 * b2) * Dt;
-            nx += dx; ny += dy;
-            outx = nx + half; outy = ny + half;
-            if (dx * dx + dy * dy <= a.eps2) break;
-            if (j > 0 && fabsf(dx + pdx) < 0.01f && fabsf(dy + pdy) < 0.01f) {
-                outx -= dx * 0.5f; outy -= dy * 0.5f;
-                break;
-            }
-            pdx = dx; pdy = dy;
-        }
-        nx = outx; ny = outy;
-        if (st && level == 0) {
-            const float ex = nx - half, ey = ny - half;
-            const int inx = (int)floorf(ex), iny = (int)floorf(ey);
-            if (inx < -win || inx >= w || iny < -win || iny >= h) { st = false; continue; }
-            weights(ex - inx, ey - iny, iw00, iw01, iw10, iw11);
-            const int diff = sample_j(J, w, h, inx, iny, iw00, iw01, iw10, iw11) - ival;
-            const float v0 = fabsf((float)diff);
-            float a0 = v0;
-#pragma unroll
-            for (int k = 1; k < NW; ++k) a0 = seq_step(a0, v0);
-            er = half_value(a0, NW - 1, hb) * 1.f / (32 * win * win);
-        }
-    }
-    if (g == 0) {
-        next_pts[2 * pt] = nx;
-        next_pts[2 * pt + 1] = ny;
-        status[pt] = st ? 1 : 0;
-        err[pt] = er;
-    }
-}
-
-// ---- round 6: the same two-points-per-wavefront kernel with everything that does NOT depend on the tracked position taken
-// out of the level loop.  In calcOpticalFlowPyrLK a level's template terms -- the window's samples of the previous frame
-// I, its Scharr derivatives, the matrix sums A11 / A12 / A22 -- are functions of the ORIGINAL point and the level alone;
-// only the iterations follow the position found on the coarser level.  lk_pair_kernel fetched and summed them level by
-// level: per level two dependent trips to memory (~500-700 cycles each beside the networks) and three 24-step serial
-// scans in front of the first iteration, six times in a row.  Here all levels' loads are requested at once and the 3 x
-// levels scans run interleaved (18 independent chains: the DPP adds issue back to back instead of waiting for each other);
-// the level loop keeps the patch fill and the iterations.  Every value is computed by the same operations in the same
-// order as before: bit-identical (tests/test_flow_gpu.py, the e2e parity tests).  Up to LK_PRE levels (the reference's
-// maxLevel = 5 gives 6); deeper pyramids take lk_pair_kernel.
-constexpr int LK_PRE = 6;
-
-template <int WINC>
-__global__ __launch_bounds__(256) FM_SGPR_CAP void lk_pair_pre_kernel(LKArgs a, int n, const float* __restrict__ prev_pts,
-                                                                      float* __restrict__ next_pts, uint8_t* __restrict__ status,
-                                                                      float* __restrict__ err) {
-    __shared__ __attribute__((aligned(16))) uint8_t patch_all[8 * LK_PW * LK_PW];
-    const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = gidx & 63, g = l & 31, hb = l & 32;
-    const int pt = (gidx >> 6) * 2 + (l >> 5);
-    constexpr int win = WINC, NW = WINC * WINC;
-    if (pt >= n || g >= NW) return;
-    uint8_t* const patch = patch_all + ((threadIdx.x >> 5) & 7) * (LK_PW * LK_PW);
-    int sx0 = 0, sy0 = 0;
-    bool have_patch = false;
-    const int wy = g / win, wx = g % win;
-    const float half = (win - 1) * 0.5f;
-    const float px0 = prev_pts[2 * pt], py0 = prev_pts[2 * pt + 1];
-    float nx = 0.f, ny = 0.f;
-    bool st = true;
-    float er = 0.f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    auto weights = [](float fa, float fb, int& iw00, int& iw01, int& iw10, int& iw11) {
-        iw00 = __float2int_rn((1.f - fa) * (1.f - fb) * (1 << 14));
-        iw01 = __float2int_rn(fa * (1.f - fb) * (1 << 14));
-        iw10 = __float2int_rn((1.f - fa) * fb * (1 << 14));
-        iw11 = (1 << 14) - iw00 - iw01 - iw10;
-    };
-    auto sample = [&](const uint8_t* img, int w, int h, int bx, int by, int iw00, int iw01, int iw10, int iw11) -> int {
-        const uint8_t* r0 = img + (size_t)reflect101(by + wy, h) * w;
-        const uint8_t* r1 = img + (size_t)reflect101(by + wy + 1, h) * w;
-        const int c0 = reflect101(bx + wx, w), c1 = reflect101(bx + wx + 1, w);
-        return LK_DESCALE(lk_px(r0, c0) * iw00 + lk_px(r0, c1) * iw01 + lk_px(r1, c0) * iw10 + lk_px(r1, c1) * iw11, 14 - 5);
-    };
-    auto sample_j = [&](const uint8_t* img, int w, int h, int bx, int by, int iw00, int iw01, int iw10, int iw11) -> int {
-        if (have_patch && bx >= sx0 && by >= sy0 && bx + win + 1 <= sx0 + LK_PW && by + win + 1 <= sy0 + LK_PW) {
-            const uint8_t* q = patch + (by - sy0 + wy) * LK_PW + (bx - sx0 + wx);
-            return LK_DESCALE((int)q[0] * iw00 + (int)q[1] * iw01 + (int)q[LK_PW] * iw10 + (int)q[LK_PW + 1] * iw11, 14 - 5);
-        }
-        return sample(img, w, h, bx, by, iw00, iw01, iw10, iw11);
-    };
-    auto fill_patch = [&](const uint8_t* img, int w, int h, int x0, int y0) {
-        sx0 = x0; sy0 = y0;
-        const bool inside = x0 >= 0 && x0 + LK_PW + 4 <= w;
-        for (int item = g; item < LK_PW * LK_PW / 4; item += NW) {
-            const int r = item >> 2, c = (item & 3) * 4;
-            const uint8_t* row = img + (size_t)reflect101(y0 + r, h) * w;
-            uint32_t v;
-            if (inside) {
-                const uintptr_t ad = reinterpret_cast<uintptr_t>(row) + (uintptr_t)(x0 + c);
-                const uint32_t* al = reinterpret_cast<const uint32_t*>(ad & ~uintptr_t(3));
-                v = __builtin_amdgcn_alignbyte(al[1], al[0], (uint32_t)(ad & 3));
-            } else {
-                v = (uint32_t)row[reflect101(x0 + c, w)] | (uint32_t)row[reflect101(x0 + c + 1, w)] << 8 |
-                    (uint32_t)row[reflect101(x0 + c + 2, w)] << 16 | (uint32_t)row[reflect101(x0 + c + 3, w)] << 24;
-            }
-            *reinterpret_cast<uint32_t*>(patch + r * LK_PW + c) = v;
-        }
-        have_patch = true;
-    };
-
-    // ---- the template terms of every level
-    int ivalL[LK_PRE], ixL[LK_PRE], iyL[LK_PRE];
-    bool posok[LK_PRE];
-#pragma unroll
-    for (int lv = 0; lv < LK_PRE; ++lv) {
-        ivalL[lv] = ixL[lv] = iyL[lv] = 0;
-        posok[lv] = false;
-        if (lv < a.levels) {
-            const int w = a.w[lv], h = a.h[lv];
-            const float sc = 1.f / (float)(1 << lv);
-            const float ppx = px0 * sc - half, ppy = py0 * sc - half;
-            const int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
-            posok[lv] = !(ipx < -win || ipx >= w || ipy < -win || ipy >= h);
-            // (a position outside the level is never used: its loads go to a clamped one)
-            const int cx = min(max(ipx, -win), w - 1), cy = min(max(ipy, -win), h - 1);
-            int iw00, iw01, iw10, iw11;
-            weights(ppx - ipx, ppy - ipy, iw00, iw01, iw10, iw11);
-            ivalL[lv] = sample(a.I[lv], w, h, cx, cy, iw00, iw01, iw10, iw11);
-            const int16_t* D = a.D[lv];
-            const int xx0 = cx + wx, xx1 = xx0 + 1, yy0 = cy + wy, yy1 = yy0 + 1;
-            auto dv = [&](int xx, int yy) -> int2 {      // derivative image is zero outside (BORDER_CONSTANT), lkpyramid.cpp
-                if (xx < 0 || xx >= w || yy < 0 || yy >= h) return make_int2(0, 0);
-                const int v = *reinterpret_cast<const int*>(D + ((size_t)yy * w + xx) * 2);
-                return make_int2((int)(short)(v & 0xffff), (int)(short)(v >> 16));
-            };
-            const int2 d00 = dv(xx0, yy0), d01 = dv(xx1, yy0), d10 = dv(xx0, yy1), d11 = dv(xx1, yy1);
-            ixL[lv] = LK_DESCALE(d00.x * iw00 + d01.x * iw01 + d10.x * iw10 + d11.x * iw11, 14);
-            iyL[lv] = LK_DESCALE(d00.y * iw00 + d01.y * iw01 + d10.y * iw10 + d11.y * iw11, 14);
-        }
-    }
-    float A11L[LK_PRE], A12L[LK_PRE], A22L[LK_PRE];
-    {
-        float v0[LK_PRE], v1[LK_PRE], v2[LK_PRE], s0[LK_PRE], s1[LK_PRE], s2[LK_PRE];
-#pragma unroll
-        for (int lv = 0; lv < LK_PRE; ++lv) {
-            s0[lv] = v0[lv] = (float)(ixL[lv] * ixL[lv]);
-            s1[lv] = v1[lv] = (float)(ixL[lv] * iyL[lv]);
-            s2[lv] = v2[lv] = (float)(iyL[lv] * iyL[lv]);
-        }
-#pragma unroll
-        for (int k = 1; k < NW; ++k)
-#pragma unroll
-            for (int lv = 0; lv < LK_PRE; ++lv) {
-                s0[lv] = seq_step(s0[lv], v0[lv]); s1[lv] = seq_step(s1[lv], v1[lv]); s2[lv] = seq_step(s2[lv], v2[lv]);
-            }
-#pragma unroll
-        for (int lv = 0; lv < LK_PRE; ++lv) {
-            A11L[lv] = half_value(s0[lv], NW - 1, hb); A12L[lv] = half_value(s1[lv], NW - 1, hb); A22L[lv] = half_value(s2[lv], NW - 1, hb);
-        }
-    }
-
-    // ---- coarse to fine: what follows the position
-#pragma unroll
-    for (int lv = LK_PRE - 1; lv >= 0; --lv) {
-        if (lv >= a.levels) continue;
-        const int level = lv;
-        const int w = a.w[lv], h = a.h[lv];
-        const uint8_t* J = a.J[lv];
-        have_patch = false;
-        const float sc = 1.f / (float)(1 << level);
-        if (level == a.levels - 1) { nx = px0 * sc; ny = py0 * sc; }
-        else { nx *= 2.f; ny *= 2.f; }
-        if (!posok[lv]) {
-            if (level == 0) { st = false; er = 0.f; }
-            continue;
-        }
-        const int ival = ivalL[lv], ixval = ixL[lv], iyval = iyL[lv];
-        float A11 = A11L[lv] * FLT_SCALE, A12 = A12L[lv] * FLT_SCALE, A22 = A22L[lv] * FLT_SCALE;
-        float Dt = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * win * win);
-        if (minEig < a.min_eig_thresh || Dt < 1.1920929e-07f) {
-            if (level == 0) st = false;
-            continue;
-        }
-        Dt = 1.f / Dt;
-        nx -= half; ny -= half;
-        float pdx = 0.f, pdy = 0.f;
-        float outx = nx + half, outy = ny + half;
-        {
-            const int fx = (int)floorf(nx), fy = (int)floorf(ny);
-            if (fx >= -win && fx < w && fy >= -win && fy < h) fill_patch(J, w, h, fx - LK_PR, fy - LK_PR);
-        }
-        int iw00, iw01, iw10, iw11;
-        for (int j = 0; j < a.max_count; ++j) {
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-            if (inx < -win || inx >= w || iny < -win || iny >= h) {
-                if (level == 0) st = false;
-                break;
-            }
-            weights(nx - inx, ny - iny, iw00, iw01, iw10, iw11);
-            const int diff = sample_j(J, w, h, inx, iny, iw00, iw01, iw10, iw11) - ival;
-            float b1, b2;
-            {
-                const float v0 = (float)(diff * ixval), v1 = (float)(diff * iyval);
-                float a0 = v0, a1 = v1;
-#pragma unroll
-                for (int k = 1; k < NW; ++k) { a0 = seq_step(a0, v0); a1 = seq_step(a1, v1); }
-                b1 = half_value(a0, NW - 1, hb); b2 = half_value(a1, NW - 1, hb);
-            }
-            b1 *= FLT_SCALE; b2 *= FLT_SCALE;
-            const float dx = (A12 * b2 - A22 * b1) * Dt, dy = (A12 * b1 - A11 * b2) * Dt;
-            nx += dx; ny += dy;
-            outx = nx + half; outy = ny + half;
-            if (dx * dx + dy * dy <= a.eps2) break;
-            if (j > 0 && fabsf(dx + pdx) < 0.01f && fabsf(dy + pdy) < 0.01f) {
-                outx -= dx * 0.5f; outy -= dy * 0.5f;
-                break;
-            }
-            pdx = dx; pdy = dy;
-        }
-        nx = outx; ny = outy;
-        if (st && level == 0) {
-            const float ex = nx - half, ey = ny - half;
-            const int inx = (int)floorf(ex), iny = (int)floorf(ey);
-            if (inx < -win || inx >= w || iny < -win || iny >= h) { st = false; continue; }
-            weights(ex - inx, ey - iny, iw00, iw01, iw10, iw11);
-            const int diff = sample_j(J, w, h, inx, iny, iw00, iw01, iw10, iw11) - ival;
-            const float v0 = fabsf((float)diff);
-            float a0 = v0;
-#pragma unroll
-            for (int k = 1; k < NW; ++k) a0 = seq_step(a0, v0);
-            er = half_value(a0, NW - 1, hb) * 1.f / (32 * win * win);
-        }
-    }
-    if (g == 0) {
-        next_pts[2 * pt] = nx;
-        next_pts[2 * pt + 1] = ny;
-        status[pt] = st ? 1 : 0;
-        err[pt] = er;
-    }
-}
-
-#ifdef FM_DIAG      // diagnostic builds only (FASTMOT_EXTRA_HIPCC_FLAGS=-DFM_DIAG, include/fastmot_hip_diag.h)
-// ---- diagnostic variants of the LK kernel (round 3: bisect of the results that differ under load).
-// MODE 0: window sums as DPP scans (the production arithmetic), 1: through LDS (no cross-lane VALU operation),
-// 2: both, compared, re-evaluated on a mismatch (counters say which of the two changed its mind).
-// CHK: every image sample is loaded twice (second time through a laundered pointer the compiler cannot merge) and
-//      the wave-uniform position update is compared across the lanes.
-// CAP: every (level, iteration) appends a record of 8 rows x 64 lanes to `cap`: the lanes' samples, the lanes'
-//      running sums after the scan, the broadcast sums, every lane's copy of the position; header = HW_ID / XCC_ID.
-// diag[]: 0 sum mismatches (MODE 2), 1 DPP value changed on re-evaluation, 2 LDS value changed, 3 still different
-//      after 3 retries, 4 duplicate-load mismatches, 5 lanes disagree on the position, 6 iterations evaluated.
-constexpr int LK_CAP_ROWS = 12, LK_CAP_REC = LK_CAP_ROWS * 64, LK_CAP_MAXREC = 80;
-
-__device__ __forceinline__ const uint8_t* launder(const uint8_t* p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
-template <int WINC, int MODE, bool CHK, bool CAP>
-__global__ __launch_bounds__(1024) FM_SGPR_CAP void lk_diag_kernel(LKArgs a, int n, const float* __restrict__ prev_pts,
-                                                                   float* __restrict__ next_pts, uint8_t* __restrict__ status,
-                                                                   float* __restrict__ err, int* __restrict__ diag,
-                                                                   int* __restrict__ cap, int* __restrict__ cap_hdr) {
-    __shared__ float slab_all[MODE == 0 ? 1 : 16 * 96];
-    const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int pt = gidx >> 6, g = gidx & 63;
-    if (pt >= n) return;
-    float* slab = slab_all + (MODE == 0 ? 0 : (threadIdx.x >> 6) * 96);
-    constexpr int win = WINC;
-    constexpr int NW = WINC * WINC;
-    const bool lane_on = g < NW;
-    const int wy = lane_on ? g / win : 0, wx = lane_on ? g % win : 0;
-    const float half = (win - 1) * 0.5f;
-    const float px0 = prev_pts[2 * pt], py0 = prev_pts[2 * pt + 1];
-    float nx = 0.f, ny = 0.f;
-    bool st = true;
-    float er = 0.f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    int nrec = 0;
-    int* rec0 = CAP ? cap + (size_t)pt * LK_CAP_MAXREC * LK_CAP_REC : nullptr;
-    auto put = [&](int row, int v) { if (CAP && nrec < LK_CAP_MAXREC) rec0[(size_t)nrec * LK_CAP_REC + row * 64 + g] = v; };
-    auto putf = [&](int row, float v) { put(row, __builtin_bit_cast(int, v)); };
-    auto weights = [](float fa, float fb, int& iw00, int& iw01, int& iw10, int& iw11) {
-        iw00 = __float2int_rn((1.f - fa) * (1.f - fb) * (1 << 14));
-        iw01 = __float2int_rn(fa * (1.f - fb) * (1 << 14));
-        iw10 = __float2int_rn((1.f - fa) * fb * (1 << 14));
-        iw11 = (1 << 14) - iw00 - iw01 - iw10;
-    };
-    // bilinear sample of image `img` at window pixel (wy, wx) of the window whose corner is (bx, by)
-    auto sample = [&](const uint8_t* img, int w, int h, int bx, int by, int iw00, int iw01, int iw10, int iw11) -> int {
-        const uint8_t* r0 = img + (size_t)reflect101(by + wy, h) * w;
-        const uint8_t* r1 = img + (size_t)reflect101(by + wy + 1, h) * w;
-        const int c0 = reflect101(bx + wx, w), c1 = reflect101(bx + wx + 1, w);
-        const int v = LK_DESCALE(lk_px(r0, c0) * iw00 + lk_px(r0, c1) * iw01 + lk_px(r1, c0) * iw10 + lk_px(r1, c1) * iw11, 14 - 5);
-        if (CHK) {
-            const uint8_t* q0 = launder(r0);
-            const uint8_t* q1 = launder(r1);
-            const int v2 = LK_DESCALE(lk_px(q0, c0) * iw00 + lk_px(q0, c1) * iw01 + lk_px(q1, c0) * iw10 + lk_px(q1, c1) * iw11, 14 - 5);
-            if (v2 != v) atomicAdd(&diag[4], 1);
-        }
-        return v;
-    };
-    // K window sums in scalar order; pfx = the lanes' running sums of the DPP scan (capture)
-    auto sums2 = [&](float v0, float v1, float& s0, float& s1, float* pfx) {
-        if (MODE == 0) { seq_sum2<NW>(v0, v1, s0, s1, pfx); return; }
-        const float v[2] = {v0, v1};
-        float l[2];
-        lds_sums<NW, 2>(slab, g, v, l);
-        if (MODE == 1) { s0 = l[0]; s1 = l[1]; return; }
-        float d0, d1;
-        seq_sum2<NW>(v0, v1, d0, d1, pfx);
-        int tries = 0;
-        while ((__builtin_bit_cast(int, d0) != __builtin_bit_cast(int, l[0]) || __builtin_bit_cast(int, d1) != __builtin_bit_cast(int, l[1])) && tries < 3) {
-            if (g == 0 && tries == 0) atomicAdd(&diag[0], 1);
-            float e0, e1, m[2];
-            seq_sum2<NW>(v0, v1, e0, e1, nullptr);
-            lds_sums<NW, 2>(slab, g, v, m);
-            if (g == 0) {
-                if (__builtin_bit_cast(int, e0) != __builtin_bit_cast(int, d0) || __builtin_bit_cast(int, e1) != __builtin_bit_cast(int, d1)) atomicAdd(&diag[1], 1);
-                if (__builtin_bit_cast(int, m[0]) != __builtin_bit_cast(int, l[0]) || __builtin_bit_cast(int, m[1]) != __builtin_bit_cast(int, l[1])) atomicAdd(&diag[2], 1);
-            }
-            d0 = e0; d1 = e1; l[0] = m[0]; l[1] = m[1];
-            ++tries;
-        }
-        if (tries == 3 && g == 0) atomicAdd(&diag[3], 1);
-        s0 = l[0]; s1 = l[1];
-    };
-    for (int level = a.levels - 1; level >= 0; --level) {
-        const int w = a.w[level], h = a.h[level];
-        const uint8_t* I = a.I[level];
-        const uint8_t* J = a.J[level];
-        const int16_t* D = a.D[level];
-        const float sc = 1.f / (float)(1 << level);
-        float ppx = px0 * sc, ppy = py0 * sc;
-        if (level == a.levels - 1) { nx = ppx; ny = ppy; }
-        else { nx *= 2.f; ny *= 2.f; }
-        ppx -= half; ppy -= half;
-        const int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
-        if (ipx < -win || ipx >= w || ipy < -win || ipy >= h) {
-            if (level == 0) { st = false; er = 0.f; }
-            continue;
-        }
-        int iw00, iw01, iw10, iw11;
-        weights(ppx - ipx, ppy - ipy, iw00, iw01, iw10, iw11);
-        int ival = 0, ixval = 0, iyval = 0;
-        if (lane_on) {
-            const int xx0 = ipx + wx, xx1 = xx0 + 1, yy0 = ipy + wy, yy1 = yy0 + 1;
-            ival = sample(I, w, h, ipx, ipy, iw00, iw01, iw10, iw11);
-            auto dv = [&](int xx, int yy) -> int2 {
-                if (xx < 0 || xx >= w || yy < 0 || yy >= h) return make_int2(0, 0);
-                const int v = *reinterpret_cast<const int*>(D + ((size_t)yy * w + xx) * 2);
-                return make_int2((int)(short)(v & 0xffff), (int)(short)(v >> 16));
-            };
-            const int2 d00 = dv(xx0, yy0), d01 = dv(xx1, yy0), d10 = dv(xx0, yy1), d11 = dv(xx1, yy1);
-            ixval = LK_DESCALE(d00.x * iw00 + d01.x * iw01 + d10.x * iw10 + d11.x * iw11, 14);
-            iyval = LK_DESCALE(d00.y * iw00 + d01.y * iw01 + d10.y * iw10 + d11.y * iw11, 14);
-        }
-        float A11, A12, A22;
-        float pfx[3] = {0.f, 0.f, 0.f};
-        {
-            float s01, s02;
-            // (three sums = the two-sum helper twice in the LDS / checked modes; the DPP mode keeps the production shape)
-            if (MODE == 0) seq_sum3<NW>((float)(ixval * ixval), (float)(ixval * iyval), (float)(iyval * iyval), A11, A12, A22, CAP ? pfx : nullptr);
-            else {
-                sums2((float)(ixval * ixval), (float)(ixval * iyval), A11, A12, pfx);
-                sums2((float)(iyval * iyval), (float)(ixval * iyval), A22, s01, pfx + 1);
-                (void)s02;
-            }
-        }
-        put(0, ival); put(1, ixval); put(2, iyval); putf(3, pfx[0]); putf(4, pfx[1]); putf(5, pfx[2]);
-        putf(6, A11); put(7, (level << 8) | 1);
-        ++nrec;
-        A11 *= FLT_SCALE; A12 *= FLT_SCALE; A22 *= FLT_SCALE;
-        float Dt = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * win * win);
-        if (minEig < a.min_eig_thresh || Dt < 1.1920929e-07f) {
-            if (level == 0) st = false;
-            continue;
-        }
-        Dt = 1.f / Dt;
-        nx -= half; ny -= half;
-        float pdx = 0.f, pdy = 0.f;
-        float outx = nx + half, outy = ny + half;
-        bool running = true;
-        for (int j = 0; j < a.max_count; ++j) {
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-            if (running && (inx < -win || inx >= w || iny < -win || iny >= h)) {
-                if (level == 0) st = false;
-                running = false;
-            }
-            if (!running) break;
-            weights(nx - inx, ny - iny, iw00, iw01, iw10, iw11);
-            int diff = 0;
-            if (lane_on) diff = sample(J, w, h, inx, iny, iw00, iw01, iw10, iw11) - ival;
-            float b1, b2;
-            float pb[2] = {0.f, 0.f};
-            sums2((float)(diff * ixval), (float)(diff * iyval), b1, b2, CAP ? pb : nullptr);
-            put(0, diff); putf(1, pb[0]); putf(2, pb[1]); putf(5, b1); putf(6, b2); put(7, (level << 8) | (j << 16) | 2);
-            b1 *= FLT_SCALE; b2 *= FLT_SCALE;
-            const float dx = (A12 * b2 - A22 * b1) * Dt, dy = (A12 * b1 - A11 * b2) * Dt;
-            putf(8, nx); putf(9, b1);
-            nx += dx; ny += dy;
-            putf(3, nx); putf(4, ny); putf(10, dx); putf(11, dy);
-            ++nrec;
-            if (CHK) {
-                if (g == 0) atomicAdd(&diag[6], 1);
-                const int fx = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, nx));
-                const int fy = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ny));
-                if (__builtin_bit_cast(int, nx) != fx || __builtin_bit_cast(int, ny) != fy) {
-                    atomicAdd(&diag[5], 1);
-                    atomicAdd(&diag[8 + (g >> 4)], 1);          // which quarter of the wavefront
-                }
-            }
-            outx = nx + half; outy = ny + half;
-            if (dx * dx + dy * dy <= a.eps2) break;
-            if (j > 0 && fabsf(dx + pdx) < 0.01f && fabsf(dy + pdy) < 0.01f) {
-                outx -= dx * 0.5f; outy -= dy * 0.5f;
-                break;
-            }
-            pdx = dx; pdy = dy;
-        }
-        nx = outx; ny = outy;
-        if (st && level == 0) {
-            const float ex = nx - half, ey = ny - half;
-            const int inx = (int)floorf(ex), iny = (int)floorf(ey);
-            if (inx < -win || inx >= w || iny < -win || iny >= h) { st = false; continue; }
-            weights(ex - inx, ey - iny, iw00, iw01, iw10, iw11);
-            int diff = 0;
-            if (lane_on) diff = sample(J, w, h, inx, iny, iw00, iw01, iw10, iw11) - ival;
-            float pe = 0.f;
-            if (MODE == 0) er = seq_sum<NW>(fabsf((float)diff), CAP ? &pe : nullptr) * 1.f / (32 * win * win);
-            else {
-                float e1, e2;
-                sums2(fabsf((float)diff), 0.f, e1, e2, nullptr);
-                er = e1 * 1.f / (32 * win * win);
-            }
-            put(0, diff); putf(1, pe); putf(5, er); put(7, 3);
-            ++nrec;
-        }
-    }
-    if (g == 0) {
-        next_pts[2 * pt] = nx;
-        next_pts[2 * pt + 1] = ny;
-        status[pt] = st ? 1 : 0;
-        err[pt] = er;
-        if (CAP) {
-            cap_hdr[4 * pt] = (int)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));       // HW_REG_HW_ID
-            cap_hdr[4 * pt + 1] = (int)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-            cap_hdr[4 * pt + 2] = nrec;
-            cap_hdr[4 * pt + 3] = (int)blockIdx.x;
-        }
-    }
-}
-
-#endif  // FM_DIAG
 
 // ---- foreground-mask bookkeeping: rect k sees pixel p as foreground iff no rect j<k covers p.
 // Only earlier rects that intersect rect k can cover its pixels: the host passes that (short) list.
@@ -2279,7 +1419,7 @@ extern "C" int fm_flow_lk(fm_ctx* ctx, int n, const float* prev_pts, float* next
             float* o_errp = reinterpret_cast<float*>(o + o_err);
             const float* in_pts = f->lk_in.host<float>();
             // ordinary 4-point workgroups beside whatever the other streams run (rounds 1-2 gave this launch whole CUs
-            // or ordered the ReID network behind it; see the note at lk_wave_body for what was actually wrong)
+            // or ordered the ReID network behind it; see the head of lk_core.h for what was actually wrong)
             const int threads = 256, lds_req = 0;
             const dim3 grid((unsigned)(((size_t)n * 64 + threads - 1) / threads));
 #ifdef FM_DIAG
@@ -2298,11 +1438,8 @@ extern "C" int fm_flow_lk(fm_ctx* ctx, int n, const float* prev_pts, float* next
 #define FM_LK_DIAG_LAUNCH(MODE, CHK, CAP) \
     hipLaunchKernelGGL((lk_diag_kernel<5, MODE, CHK, CAP>), grid, dim3(threads), lds_req, s, a, n, in_pts, o_pts, o_stat, o_errp, \
                        f->lk_diag, f->lk_cap, f->lk_cap_hdr)
-                if (v == 128) {                                              // one point per wavefront (the round-2 kernel)
-                    hipLaunchKernelGGL(lk_wave_kernel<5>, grid, dim3(threads), lds_req, s, a, n, in_pts, o_pts, o_stat, o_errp);
-                } else
                 switch (v) {
-                case 1 | 64: FM_LK_DIAG_LAUNCH(0, false, false); break;      // DPP sums, diagnostic body (control)
+                case 1 | 64: FM_LK_DIAG_LAUNCH(0, false, false); break;      // DPP sums, one point per wavefront (control)
                 case 1 | 32: FM_LK_DIAG_LAUNCH(0, false, true); break;       // DPP sums + capture
                 case 1 | 16: FM_LK_DIAG_LAUNCH(0, true, false); break;       // DPP sums + duplicate loads / lane agreement
                 case 2: FM_LK_DIAG_LAUNCH(1, false, false); break;           // LDS sums
@@ -2318,8 +1455,6 @@ extern "C" int fm_flow_lk(fm_ctx* ctx, int n, const float* prev_pts, float* next
 #endif
                 const dim3 grid2((unsigned)((((size_t)n + 1) / 2 * 64 + threads - 1) / threads));     // two points per wavefront
                 fm_trace_mark(ctx, s, 40);
-                // (PATCH = false, the global-load sampling of rounds 3-4, measured equal within the spread:
-                // profiles/r05_lk_patch_and_ring_depth_ab.txt)
                 // (lk_pair_pre_kernel against lk_pair_kernel: 77 vs 90 us inside the pipeline at 1080p, config[4] 185 vs 176
                 // frames/s, profiles/r06_lk_template_terms_ab.txt)
                 if (a.levels <= LK_PRE) {      // template terms of all levels up front (bit-identical; see the kernel)
@@ -2328,9 +1463,9 @@ extern "C" int fm_flow_lk(fm_ctx* ctx, int n, const float* prev_pts, float* next
                     else
                         hipLaunchKernelGGL((lk_pair_pre_kernel<3>), grid2, dim3(threads), 0, s, a, n, in_pts, o_pts, o_stat, o_errp);
                 } else if (a.win == 5)
-                    hipLaunchKernelGGL((lk_pair_kernel<5, true>), grid2, dim3(threads), 0, s, a, n, in_pts, o_pts, o_stat, o_errp);
+                    hipLaunchKernelGGL((lk_pair_kernel<5>), grid2, dim3(threads), 0, s, a, n, in_pts, o_pts, o_stat, o_errp);
                 else
-                    hipLaunchKernelGGL((lk_pair_kernel<3, true>), grid2, dim3(threads), 0, s, a, n, in_pts, o_pts, o_stat, o_errp);
+                    hipLaunchKernelGGL((lk_pair_kernel<3>), grid2, dim3(threads), 0, s, a, n, in_pts, o_pts, o_stat, o_errp);
                 fm_trace_mark(ctx, s, 41);
             }
         }

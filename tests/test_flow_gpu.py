@@ -315,7 +315,7 @@ def test_lk_deterministic_while_other_streams_are_busy(ctx, hammer):
     History: rounds 1-2 saw single points change by 1e-5 .. 6 px in up to 70 % of such calls, traced it to the two
     fused LightConv kernels being resident on the same CU, and shipped isolation / ordering around an unknown cause.
     Round 3 captured disturbed calls (scripts/lk_bisect.py): the packed-fp32 form the compiler had chosen for the
-    position update returned a wrong low half in lanes 48..63 (csrc/flow.hip lk_wave_body, csrc/diag.hip); without
+    position update returned a wrong low half in lanes 48..63 (the head of csrc/lk_core.h, csrc/diag.hip); without
     packed fp32 in the KLT kernels 0 of 5.1 M iterations disagree under the same load."""
     import threading
     from fastmot_amd.detector import DeviceFrame

@@ -152,8 +152,8 @@ LK_CASES = {
 @pytest.mark.parametrize('case', list(LK_CASES))
 def test_lk_windows_levels_criteria(ctx, case):
     """fm_flow_lk at the window sizes, pyramid depths and termination criteria the default configuration never runs:
-    `lk_pair_pre_kernel<3>` (winSize 3, at most LK_PRE = 6 levels), `lk_pair_kernel<5, true>` and
-    `lk_pair_kernel<3, true>` (a pyramid deeper than LK_PRE: 7 levels of a 640 x 360 optical-flow image, scale 1, which
+    `lk_pair_pre_kernel<3>` (winSize 3, at most LK_PRE = 6 levels), `lk_pair_kernel<5>` and
+    `lk_pair_kernel<3>` (a pyramid deeper than LK_PRE: 7 levels of a 640 x 360 optical-flow image, scale 1, which
     also takes the plain pyramid path), one and three levels (`pyr_level_kernel` with has_next == false, no tail launch),
     the window-dependent pyramid depth (flow.hip: buildOpticalFlowPyramid's stop rule in fm_flow_configure), criteria
     with other counts / epsilons and with COUNT or EPS alone (Flow._configure: epsilon 0.01, 30 iterations).
@@ -175,9 +175,60 @@ def test_lk_windows_levels_criteria(ctx, case):
     check_lk(ctx, small0, small1, np.float32([[w * 0.4, h * 0.55]]), win, max_level, max_count, eps, floor=None)
 
 
+LK_KERNEL_CASES = {
+    # the four production instantiations: lk_pair_pre_kernel<5> / <3> (at most LK_PRE = 6 levels: the default configuration
+    # and 'win3'), lk_pair_kernel<5> / <3> (7 levels)
+    'win5': ((0.5, 0.5), 5, 5, (3, 10, 0.03), (10, 0.03), 6),
+    **{name: LK_CASES[name] for name in ('win3', 'win5_7levels', 'win3_7levels')},
+}
+
+
+@pytest.mark.parametrize('case', list(LK_KERNEL_CASES))
+def test_lk_point_counts(ctx, case):
+    """Every production LK kernel with 1, 2, 3 and 65 points: two points share a wavefront, so an odd count leaves the
+    second half of the last wavefront without a point (n = 1: of the first), and 65 points are 33 wavefronts, 8 per
+    256-thread workgroup -- a ninth workgroup with one half-filled wavefront.
+
+    The first points are chosen so that the small counts meet the branches a point can take: [0] an ordinary point,
+    [1] one that lies inside the TOP level only (x = w + 3 half 2^(levels - 3): its window starts right of every finer
+    level, `posok` false there, status 0 -- beside a point that iterates in the other half of the wavefront), [2] the
+    corner pixel (0, 0), whose window starts outside level 0 at (-half, -half) (reflected samples, zero derivatives),
+    [3], [4] points just right of / above the image that miss level 0 alone; then seam_points and random ones."""
+    scale, win, max_level, criteria, (max_count, eps), levels = LK_KERNEL_CASES[case]
+    size = (640, 360)
+    f0, f1, small0, small1 = frame_pair(size, scale, 1, (4, 2))
+    h, w = small0.shape
+    flow = make_flow(size, scale=scale, win=win, max_level=max_level, criteria=criteria)
+    start_pair(ctx, flow, f0, f1)
+    assert check_levels(ctx, small0, win, max_level) == levels
+    seams = seam_points(w, h, levels)
+    assert tuple(seams[51]) == (0, 0)
+    half = (win - 1) * 0.5
+    top_only = w + half * 3 * (1 << (levels - 3))       # between where the two coarsest levels' windows may start
+    special = np.float32([[w * 0.4, h * 0.55], [top_only, h * 0.5], seams[51], [w + half + 0.5, h * 0.3],
+                          [w * 0.6, -3.5]])
+    shapes = [img.shape for img in cv.build_pyramid(small0, win, max_level)]
+    start_ok = [[-win <= np.floor(x / (1 << l) - half) < lw and -win <= np.floor(y / (1 << l) - half) < lh
+                 for l, (lh, lw) in enumerate(shapes)] for x, y in special]
+    assert all(start_ok[0]) and all(start_ok[2])
+    assert start_ok[1] == [False] * (levels - 1) + [True]
+    assert start_ok[3] == [False] + [True] * (levels - 1) and start_ok[4] == start_ok[3]
+    pts = np.concatenate([special, seams[:51], seams[52:], random_points(w, h, 1, seed=5)])
+    assert len(pts) == 65
+    prev, nxt = small0, small1
+    for n in (1, 2, 3, 65):
+        en, es = check_lk(ctx, prev, nxt, pts[:n], win, max_level, max_count, eps, floor=None)
+        prev, nxt = nxt, prev                          # (fm_flow_lk swaps the two frames)
+        # (the oracle's own: the ordinary point is tracked, the ones that start outside level 0 are lost)
+        assert es[0] == 1 and not es[[i for i in (1, 3, 4) if i < n]].any()
+    # (60 of the 65 lie on borders and seams: the oracle tracks 0.78 / 0.68 of them with winSize 5, 0.58 / 0.48 with 3; the
+    # floor only has to show that a good part of the points iterates to the end, as in test_pyramid_paths)
+    assert es.mean() > 0.3, es.mean()
+
+
 def test_lk_window_leaves_the_patch(ctx):
-    """`sample_j`'s fallback to global loads (flow.hip, both LK kernels): the kernel stages a patch of the next image
-    around the start position and leaves it when the window travels more than LK_PR = 5 px inside one level.  With ONE
+    """`LKPatch::sample`'s fallback to global loads (lk_core.h, both LK kernels): the kernel stages a patch of the next
+    image around the start position and leaves it when the window travels more than LK_PR = 5 px inside one level.  With ONE
     level a point's displacement is its travel inside that level: the frames are (16, 8) apart, (8, 4) in the
     optical-flow image, and 30 iterations with epsilon 0.01 let the points get there."""
     size, scale = (640, 360), (0.5, 0.5)

@@ -54,11 +54,12 @@ def test_klt_kernels_have_no_modified_packed_fp32(tmp_path):
     seen = set()
     for line in text.splitlines():
         if line.startswith('_Z'):
-            in_lk = any(k in line for k in ('lk_pair_kernel', 'lk_wave_kernel', 'lk_diag_kernel'))
+            in_lk = any(k in line for k in ('lk_pair_kernel', 'lk_pair_pre_kernel', 'lk_diag_kernel'))
             if in_lk:
                 seen.add(line.split(':')[0])
         m = PACKED.match(line)
         if m:
             assert not in_lk, line
             assert 'op_sel' not in m.group(2), line
-    assert any('lk_pair_kernel' in k for k in seen), 'the production LK kernel was not found in the listing'
+    for name in ('lk_pair_kernel', 'lk_pair_pre_kernel'):
+        assert any(name in k for k in seen), f'the production LK kernel {name} was not found in the listing'
