@@ -1,13 +1,15 @@
 """TEST INFRASTRUCTURE -- generates tests/golden/*.npz by running the UNMODIFIED reference
 (/root/reference, via oracle/ref_shim.py) on seeded inputs.  Run here (build container) only:
 
-    python oracle/make_golden.py
+    python oracle/make_golden.py [kalman] [kalman_offdefault] [assoc] [nms] [tracker]     (none named: all of them)
 
 Outputs (committed):
   tests/golden/tracker_<scene>.npz   per-frame track ids / rounded boxes / lifecycle flags /
                                       history order + final Kalman states of the reference
                                       MultiTracker (tracker.py:18-422) on tests/scenes.py scenes
   tests/golden/kalman_kat.npz        KalmanFilter create/warp/predict/update/motion_distance
+  tests/golden/kalman_kat_offdefault.npz   the same stages with non-default filter parameters, a perspective
+                                      homography, fast tracks and covariances evolved over three frames
   tests/golden/assoc_kat.npz         cdist / iou_dist / find_occluded / fuse+gate / LAP / greedy
   tests/golden/nms_kat.npz           diou_nms + YOLODetector._filter_dets
 """
@@ -82,6 +84,70 @@ def golden_kalman(ns):
                     f'{tag}_det': det, f'{tag}_dt': np.array(dt)})
     np.savez_compressed(GOLDEN / 'kalman_kat.npz', **out)
     print('kalman_kat: ok')
+
+
+KF_OFFDEFAULT = dict(std_factor_acc=1.7, std_offset_acc=40.0, std_factor_det=(0.05, 0.11),
+                     std_factor_klt=(0.2, 0.09), min_std_det=(3.0, 6.5), min_std_klt=(7.0, 4.0),
+                     init_pos_weight=3, init_vel_weight=9, vel_coupling=0.35, vel_half_life=0.7)
+
+
+def golden_kalman_offdefault(ns):
+    """The stages of kalman_kat at an operating point no default reaches: width and height factors that differ, a
+    velocity coupling away from 0.6 / 0.4, a homography with a real perspective row, fast tracks, small boxes on which
+    the min_std floors bind, and covariances evolved over three frames.  n = 23: the last block of the batched kernels
+    (four tracks each) is not full."""
+    rng = np.random.default_rng(56)     # (a seed at which the assertions at the end hold)
+    kf = ns.kalman_filter.KalmanFilter(**KF_OFFDEFAULT)
+    MeasType = ns.kalman_filter.MeasType
+    out = {}
+    for tag, dt in (('od30', 1 / 30.), ('od7', 1 / 7.)):
+        kf.reset_dt(dt)
+        n = 23
+        tl = np.stack([rng.uniform(-40, 1700, n), rng.uniform(-40, 800, n)], 1)
+        boxes = np.rint(np.concatenate([tl, tl + rng.uniform(8, 300, (n, 2)) - 1], 1))
+        H = np.eye(3) + rng.normal(0, 2e-2, (3, 3))
+        H[:2, 2] = rng.normal(0, 15, 2)
+        H[2, :2] = rng.normal(0, 1e-4, 2)
+        H[2, 2] = 1.
+        vel = rng.normal(0, 120, (n, 4))
+        mult = rng.uniform(1, 8, n)
+        stages = {k: [] for k in ('create_m', 'create_c', 'start_m', 'start_c', 'warp_m', 'warp_c', 'pred_m', 'pred_c',
+                                  'klt_m', 'klt_c', 'det_m', 'det_c', 'maha')}
+        klt = np.empty((n, 4))
+        for i in range(n):
+            m, c = kf.create(boxes[i])
+            stages['create_m'].append(m.copy()); stages['create_c'].append(c.copy())
+            m = m.copy(); m[4:] = vel[i]
+            for _ in range(3):       # evolved, well off-diagonal covariances before the recorded chain
+                m, c = kf.warp(m, c, H)
+                m, c = kf.predict(m, c)
+                m, c = kf.update(m, c, m[:4] + rng.normal(0, 1.5, 4), MeasType.FLOW, rng.uniform(1, 8))
+            stages['start_m'].append(m.copy()); stages['start_c'].append(c.copy())
+            m, c = kf.warp(m, c, H)
+            stages['warp_m'].append(m.copy()); stages['warp_c'].append(c.copy())
+            m, c = kf.predict(m, c)
+            stages['pred_m'].append(m.copy()); stages['pred_c'].append(c.copy())
+            klt[i] = m[:4] + rng.normal(0, 1.5, 4)
+            m, c = kf.update(m, c, klt[i], MeasType.FLOW, mult[i])
+            stages['klt_m'].append(m.copy()); stages['klt_c'].append(c.copy())
+        det = np.array(stages['klt_m'])[:, :4] + rng.normal(0, 3, (n, 4))
+        for i in range(n):
+            m, c = stages['klt_m'][i], stages['klt_c'][i]
+            stages['maha'].append(kf.motion_distance(m, c, det))
+            m, c = kf.update(m, c, det[i], MeasType.DETECTOR)
+            stages['det_m'].append(m.copy()); stages['det_c'].append(c.copy())
+        out.update({f'{tag}_{k}': np.array(v) for k, v in stages.items()})
+        out.update({f'{tag}_boxes': boxes, f'{tag}_H': H, f'{tag}_klt': klt, f'{tag}_mult': mult,
+                    f'{tag}_det': det, f'{tag}_dt': np.array(dt)})
+        # the operating point stays a sound one: the perspective divisor stays away from 0 and the covariances stay
+        # positive definite.  (The shear of this H turns a few narrow, tall boxes inside out; the filter's arithmetic
+        # does not care, and their noise floors bind.)
+        a =np.concatenate([out[f'{tag}_start_m'][:, c:c + 2] @ H[2, :2] + 1. for c in (0, 2)])
+        eig = min(np.linalg.eigvalsh(out[f'{tag}_{k}']).min() for k in ('start_c', 'warp_c', 'pred_c', 'klt_c', 'det_c'))
+        print(f'{tag}: divisor a in [{a.min():.3f}, {a.max():.3f}], smallest covariance eigenvalue {eig:.3g}')
+        assert 0.75 < a.min() and a.max() < 1.15 and eig > 5.
+    np.savez_compressed(GOLDEN / 'kalman_kat_offdefault.npz', **out)
+    print('kalman_kat_offdefault: ok')
 
 
 def golden_assoc(ns):
@@ -176,7 +242,7 @@ def golden_nms(ns):
 if __name__ == '__main__':
     GOLDEN.mkdir(parents=True, exist_ok=True)
     ns = ref_shim.load_reference()
-    golden_kalman(ns)
-    golden_assoc(ns)
-    golden_nms(ns)
-    golden_tracker(ns)
+    entries = {'kalman': golden_kalman, 'kalman_offdefault': golden_kalman_offdefault, 'assoc': golden_assoc,
+               'nms': golden_nms, 'tracker': golden_tracker}
+    for name in sys.argv[1:] or entries:      # every generator seeds its own stream: each is selectable on its own
+        entries[name](ns)
