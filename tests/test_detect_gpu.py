@@ -5,6 +5,8 @@
     tolerance 2e-6 relative (fast-exp intrinsics differ between vendors)
   * preprocessing: oracle=restated (np_oracle.yolo_preprocess / cv_oracle.reid_preprocess),
     identical uint8 pixels -> fp16 input within 1e-3"""
+import functools
+
 import numpy as np
 import pytest
 
@@ -102,6 +104,122 @@ def test_filter_dets_chunk_boundaries(ctx, n):
         np.testing.assert_allclose(out.conf, cf, rtol=1e-7)
     finally:
         ctx.set_option('nms_path', 0)
+
+
+SIZE, ALL3 = [1920, 1080], np.array([True, True, True])
+
+
+def _post_detector():
+    """A fresh detector for a case of the two tests below (fm_detect_configure also clears a sticky switch to the general
+    route that an earlier case may have left)."""
+    return YOLODetector((1920, 1080), (0, 1, 2), model='TinyYOLO', conf_thresh=0.3, nms_thresh=0.45,
+                        max_area=800000, min_aspect_ratio=0.0, max_candidates=8192)
+
+
+def _assert_equals_oracle(out, ref):
+    tl, lb, cf = ref
+    np.testing.assert_array_equal(out.tlbr, tl)
+    np.testing.assert_array_equal(out.label, lb)
+    np.testing.assert_allclose(out.conf, cf, rtol=1e-7)
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_case(n):
+    """Rows like test_filter_dets_chunk_boundaries, in 8 tight clusters: (rows, candidates over the threshold, NMS
+    survivors summed over the classes, oracle result) -- computed once for both routes."""
+    rng = np.random.default_rng(n)
+    centres = rng.uniform(0.1, 0.8, (8, 2))
+    pick = rng.integers(0, 8, n)
+    rows = np.stack([centres[pick, 0] + rng.normal(0, 0.004, n), centres[pick, 1] + rng.normal(0, 0.004, n),
+                     rng.uniform(0.05, 0.08, n), rng.uniform(0.1, 0.16, n), rng.uniform(0.6, 1, n),
+                     rng.integers(0, 3, n), rng.uniform(0.6, 1, n)], 1).astype(np.float32)
+    d, _ = o.filter_scale(rows, SIZE, [0, 0], ALL3, 0.3)
+    survivors = sum(len(o.diou_nms(d[d[:, 5] == c, :4], d[d[:, 5] == c, 4], 0.45)) for c in np.unique(d[:, 5]))
+    return rows, len(d), survivors, o.filter_dets(rows, SIZE, [0, 0], ALL3, 0.3, 0.45, 800000, 0.0)
+
+
+@pytest.mark.parametrize('n', [511, 512, 513, 1500, 2049, 4095, 4096])
+def test_filter_dets_greedy_kernel_seams(ctx, n, nms_path):
+    """Candidate counts at the seams of the greedy kernel, with few enough survivors that under 'fused' the greedy kernel
+    itself resolves the pass (it hands a pass of more than 96 survivors to the general route): the second candidate of a
+    thread from 512 on, the steps of its LDS sizing, its capacity of 4096.  The first call may be declined for LDS (the
+    size adapts to the counts seen by the context), the second cannot.  (At 513 the one candidate that is a thread's
+    second is no survivor: the kernel's final filter beyond a thread's first candidate is checked from 1500 on.)"""
+    rows, k, survivors, ref = _seam_case(n)
+    assert k == n
+    assert survivors <= 80
+    det = _post_detector()
+    for _ in range(2):
+        out = ctx.filter_dets(rows, cap=8192)
+        assert ctx.detect_last_counts()[0] == n
+        _assert_equals_oracle(out, ref)
+
+
+def _est32(a, b):
+    """float32 restatement of the second-stage estimate of the device's pair test (diou_pretest, nms_core.h)."""
+    f32 = np.float32
+    a, b = a.astype(f32), b.astype(f32)
+    ax1, ay1, bx1, by1 = a[0] + a[2], a[1] + a[3], b[0] + b[2], b[1] + b[3]
+    iw, ih = min(ax1, bx1) - max(a[0], b[0]), min(ay1, by1) - max(a[1], b[1])
+    inter = f32(iw * ih)
+    uni = f32(a[2] * a[3] + b[2] * b[3] - inter)
+    ew, eh = max(ax1, bx1) - min(a[0], b[0]), max(ay1, by1) - min(a[1], b[1])
+    dx, dy = f32(0.5) * ((a[0] + ax1) - (b[0] + bx1)), f32(0.5) * ((a[1] + ay1) - (b[1] + by1))
+    q = f32((dx * dx + dy * dy) / (ew * ew + eh * eh))
+    return float(inter / uni - (np.exp2(f32(0.6) * np.log2(q)) if q > 0 else 0))
+
+
+@functools.lru_cache(maxsize=None)
+def _threshold_pairs():
+    """40 well-separated pairs (A, B = A shifted in x) on a grid, the shift bisected in float32 on the oracle's verdict
+    for that pair alone down to two adjacent float32 values, one suppressed and one kept: odd pairs take the suppressed
+    side, even pairs the kept side.  Returns (rows, pairs suppressed, largest |estimate - threshold|, oracle result)."""
+    f32 = np.float32
+    rng = np.random.default_rng(1)
+
+    def scaled(r):
+        return o.filter_scale(np.array([[*r, 1, 0, 1]], f32), SIZE, [0, 0], [True], 0.3)[0][0, :4]
+
+    def suppressed(a, b):
+        return len(o.diou_nms(np.array([scaled(a), scaled(b)], f32), np.array([1.0, 0.5]), 0.45)) == 1
+
+    rows, n_suppressed, far = [], 0, 0.
+    for p in range(40):
+        w, h = rng.uniform(0.03, 0.05), rng.uniform(0.05, 0.08)
+        a = np.array([(p % 8) * 0.12 + 0.01, (p // 8) * 0.12 + 0.01, w, h], f32)
+        lo, hi = f32(0), f32(w)             # shift 0: identical boxes, suppressed; shift w: disjoint, kept
+        while True:
+            mid = f32((lo + hi) / 2)
+            if mid == lo or mid == hi:
+                break
+            b = a.copy()
+            b[0] = a[0] + mid
+            if suppressed(a, b):
+                lo = mid
+            else:
+                hi = mid
+        b = a.copy()
+        b[0] = a[0] + (lo if p % 2 else hi)
+        n_suppressed += suppressed(a, b)
+        far = max(far, abs(_est32(scaled(a), scaled(b)) - 0.45))
+        rows += [[*a, 0.9, p % 3, 0.9], [*b, 0.8, p % 3, 0.9]]
+    rows = np.array(rows, f32)
+    return rows, n_suppressed, far, o.filter_dets(rows, SIZE, [0, 0], ALL3, 0.3, 0.45, 800000, 0.0)
+
+
+def test_filter_dets_pairs_at_the_threshold(ctx, nms_path):
+    """Pairs whose DIoU lies one float32 step of the shift on either side of the threshold: the float32 estimate of
+    every pair is inside the band in which the device leaves the decision to the reference's float64 arithmetic (band
+    1e-4; the restated estimate stays within 5e-5, the device's own a few 1e-6 from that), and that arithmetic must
+    decide all 40 as the oracle does -- 20 suppressed, 20 kept."""
+    rows, n_suppressed, far, ref = _threshold_pairs()
+    assert n_suppressed == 20
+    assert len(ref[0]) == 60
+    assert far <= 5e-5
+    det = _post_detector()
+    out = ctx.filter_dets(rows, cap=8192)
+    assert ctx.detect_last_counts()[0] == 80
+    _assert_equals_oracle(out, ref)
 
 
 def test_filter_dets_more_candidates_than_the_fused_kernel_holds(ctx):
