@@ -4,15 +4,22 @@ reference of the same layer table (tests/torch_ref.py) with the same seeded weig
 Tolerance (fp16 storage, fp32 accumulate -- the reference enables TensorRT FP16 the same way,
 models/yolo.py:130-131): per tensor  max|gpu - ref| <= 2e-2 * max|ref| + 2e-3  when the torch
 reference also rounds stored activations to fp16; the statement for detections / embeddings is in
-DESIGN.md."""
+DESIGN.md.
+
+Beside every such whole-tensor assertion, tests/layer_check.py holds every layer of the same finished run to the derived
+per-element bound of DESIGN.md section 7 (float64 reference from the device's own input tensors: check_net /
+close_and_check), and, where a layer writes into a channel slice of a wider tensor, requires that the run changed no byte
+outside the channels its layers write (fill_sentinel / check_sentinel)."""
 import numpy as np
 import pytest
 import torch
 
 import torch_ref
+from conv_cases import CONVD_CFGS, CONVD_SHAPES, SINGLE_CONV, STEM_CONV, STREAMED_CONV
 from fastmot_amd.engine import HipNet, NET_DETECTOR, NET_EXTRACTOR
 from fastmot_amd.models import YOLO, ReID
 from fastmot_amd.models.graph import Graph, RandomWeights, RES_BEFORE_ACT
+from layer_check import SENT16, check_net, check_pair, check_sentinel, close_and_check, fill_sentinel, write_raw
 
 pytestmark = pytest.mark.gpu
 
@@ -32,17 +39,7 @@ def nhwc(t):
     return t.numpy().transpose(0, 2, 3, 1)
 
 
-@pytest.mark.parametrize('cin,cout,k,stride,act,h,w,n', [
-    (8, 32, 3, 1, 'mish', 20, 24, 1),       # stem-like
-    (64, 64, 1, 1, 'leaky', 19, 19, 1),
-    (32, 64, 3, 2, 'mish', 38, 38, 1),      # downsample
-    (128, 255, 1, 1, 'linear', 13, 13, 1),  # head-like, ragged cout
-    (256, 512, 3, 1, 'leaky', 19, 19, 1),   # big K
-    (16, 16, 1, 1, 'relu', 64, 32, 5),      # OSNet x0.25 pointwise, batch
-    (24, 96, 1, 1, 'relu', 16, 8, 7),
-    (8, 16, 7, 2, 'relu', 64, 32, 3),       # OSNet conv1 (7x7 s2 p3)
-    (512, 128, 1, 1, 'swish', 9, 11, 2),
-])
+@pytest.mark.parametrize('cin,cout,k,stride,act,h,w,n', SINGLE_CONV)
 def test_single_conv(ctx, cin, cout, k, stride, act, h, w, n):
     rng = np.random.default_rng(cin * 1000 + cout)
     g = Graph(RandomWeights(seed=cin + cout + k), (h, w), cin)
@@ -55,24 +52,16 @@ def test_single_conv(ctx, cin, cout, k, stride, act, h, w, n):
     out = net.read(y, n)
     bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
     close(out, nhwc(bufs[y.tid][:, :cout]), what=f'conv {cin}->{cout} k{k}')
+    check_net(net, n, f'single {cin}->{cout} k{k}s{stride}')
     net.close()
 
 
-@pytest.mark.parametrize('cin,cout,k,stride,act,h,w,n,extra', [
-    (512, 1024, 3, 1, 'leaky', 19, 19, 1, ''),      # 2 cout tiles per workgroup, 8 waves
-    (1024, 255, 1, 1, 'linear', 19, 19, 2, 'f32'),  # YOLO head: ragged cout, fp32 output, batch
-    (256, 512, 3, 2, 'leaky', 38, 38, 1, ''),       # stride-2 downsample into the 19 x 19 level
-    (512, 512, 1, 1, 'mish', 19, 19, 1, 'res'),     # shortcut after the activation
-    (512, 256, 1, 1, 'leaky', 19, 19, 1, 'up'),     # fused nearest x2 upsample into a concat slice
-    (128, 64, 3, 1, 'relu', 7, 5, 3, 'res'),        # 1 cout tile per workgroup, ragged pixel tile, batch
-    (64, 40, 3, 1, 'swish', 9, 9, 1, ''),           # 4 waves (K = 576: 9 chunks), cout padded to 64
-    (2048, 512, 1, 1, 'leaky', 19, 19, 1, ''),
-])
+@pytest.mark.parametrize('cin,cout,k,stride,act,h,w,n,extra', STREAMED_CONV)
 def test_streamed_conv(ctx, cin, cout, k, stride, act, h, w, n, extra):
     """Streamed conv (K split inside the workgroup, convs.hip) == LDS-tiled conv + split-K reduce == torch."""
     rng = np.random.default_rng(cin + cout)
     x = rng.normal(0, 1, (n, h, w, cin)).astype(np.float16)
-    outs = []
+    outs, kept = [], []
     for maxp in (10 ** 6, 0):
         g = Graph(RandomWeights(seed=cin + 3 * cout + k), (h, w), cin)
         g.convs_max_pixels = maxp
@@ -85,28 +74,29 @@ def test_streamed_conv(ctx, cin, cout, k, stride, act, h, w, n, extra):
         y = g.conv('c', g.input, cout, k, stride, act, dst=wide.slice(16, cout), res=res, up=up, f32_out=extra == 'f32')
         assert g.layers[-1]['op'] == (15 if maxp else 0)
         net = HipNet(ctx, NET_DETECTOR, g, n)
+        fill_sentinel(net)
         net.write(g.input, x)
         net.run(n)
         outs.append(net.read(wide, n)[..., 16:16 + cout])
         bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
         close(outs[-1], nhwc(bufs[wide.tid][:, 16:16 + cout]), what=f'conv maxp={maxp}')
+        label = f'{"streamed" if maxp else "tiled"} {cin}->{cout} k{k}s{stride} {extra}'
+        kept.append((g, {}, len(g.layers) - 1))
+        check_net(net, n, label, keep=kept[-1][1])
+        check_sentinel(net, n, label)
         net.close()
     close(outs[0], outs[1], rel=1e-2, abs_=2e-3, what='streamed vs tiled')
+    if extra != 'res':              # ('res': the shortcut tensor is itself the product of the path under test)
+        check_pair(kept[0], kept[1], 'streamed vs tiled')
 
 
-@pytest.mark.parametrize('cin,cout,k,stride,act,h,w,n', [
-    (3, 32, 3, 1, 'mish', 40, 37, 1),        # YOLOv4 layer 0
-    (3, 16, 7, 2, 'relu', 64, 32, 3),        # OSNet conv1
-    (3, 64, 7, 2, 'relu', 32, 16, 1),        # OSNet x1.0 conv1: cout > 32 -> generic kernel
-    (4, 24, 3, 2, 'leaky', 33, 18, 2),
-    (1, 8, 3, 1, 'linear', 16, 16, 1),
-])
+@pytest.mark.parametrize('cin,cout,k,stride,act,h,w,n', STEM_CONV)
 def test_stem_conv(ctx, cin, cout, k, stride, act, h, w, n):
     """LDS-patch stem kernel == generic implicit-GEMM kernel (same fp16 weights; different summation
     order) == torch."""
     rng = np.random.default_rng(cin + cout)
     x = rng.normal(0, 1, (n, h, w, cin)).astype(np.float16)
-    outs = []
+    outs, kept = [], []
     for stem in (True, False):
         g = Graph(RandomWeights(seed=k + cout), (h, w), cin)
         g.use_stem = stem
@@ -118,8 +108,11 @@ def test_stem_conv(ctx, cin, cout, k, stride, act, h, w, n):
         outs.append(net.read(y, n))
         bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
         close(outs[-1], nhwc(bufs[y.tid][:, :cout]), what=f'stem conv {cin}->{cout} k{k} stem={stem}')
+        kept.append((g, {}, 0))
+        check_net(net, n, f'stem {cin}->{cout} k{k}s{stride} stem={stem}', keep=kept[-1][1])
         net.close()
     assert np.abs(outs[0] - outs[1]).max() <= 4e-3 * max(np.abs(outs[1]).max(), 1.0)
+    check_pair(kept[0], kept[1], 'stem kernel vs generic kernel')
 
 
 def test_splitk_repeated_runs(ctx):
@@ -139,6 +132,7 @@ def test_splitk_repeated_runs(ctx):
         first = net.read(c, 1)
         bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
         close(first, nhwc(bufs[c.tid][:, :512]), what=f'split-K run {it}')
+        check_net(net, 1, f'split-K run {it}')
         net.run(1)
         np.testing.assert_array_equal(first, net.read(c, 1))
     net.close()
@@ -154,12 +148,15 @@ def test_conv_residual_concat_fp32_out(ctx):
     g.conv('b3', b2, 64, 1, 1, 'relu', dst=cat.slice(0, 64), res=b, res_mode=RES_BEFORE_ACT)
     o = g.conv('o', cat, 21, 1, 1, 'linear', bn=False, f32_out=True)
     net = HipNet(ctx, NET_DETECTOR, g, 2)
+    fill_sentinel(net)
     x = rng.normal(0, 1, (2, 24, 24, 32)).astype(np.float16)
     net.write(g.input, x)
     net.run(2)
     bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
     close(net.read(cat, 2), nhwc(bufs[cat.tid][:, :96]), what='concat')
     close(net.read(o, 2), nhwc(bufs[o.tid][:, :21]), what='fp32 head')
+    check_net(net, 2, 'residual concat fp32')
+    check_sentinel(net, 2, 'residual concat fp32')
     net.close()
 
 
@@ -179,12 +176,15 @@ def test_pool_upsample_dw_gate_ops(ctx):
     gid2, _ = g.gate('gate', mp, 2, gp)
     gs = g.gate_sum([dw, mp], [gid1, gid2])
     net = HipNet(ctx, NET_DETECTOR, g, 3)
+    fill_sentinel(net)
     x = rng.normal(0, 1, (3, 16, 12, 32)).astype(np.float16)
     net.write(g.input, x)
     net.run(3)
     bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
     for name, v in (('spp', spp), ('up', up), ('maxpool', mp), ('avgpool', ap), ('dwconv', dw), ('gate_sum', gs)):
         close(net.read(v, 3), nhwc(bufs[v.tid][:, v.coff:v.coff + v.c]), what=name)
+    check_net(net, 3, 'pool upsample dw gate')
+    check_sentinel(net, 3, 'pool upsample dw gate')
     net.close()
 
 
@@ -226,6 +226,7 @@ def test_resblock_fused(ctx, c, mid, h, w, n):
     t = g.conv('a2', xin, mid, 1, 1, 'mish', wb=(w1, b1))
     plain = g.conv('b2', t, c, 3, 1, 'mish', res=xin, wb=(w2, b2))
     net = HipNet(ctx, NET_DETECTOR, g, n)
+    fill_sentinel(net)
     xi = np.zeros((n, h, w, c + 8), np.float16)
     xi[..., 8:] = x
     net.write(g.input, xi)
@@ -234,6 +235,8 @@ def test_resblock_fused(ctx, c, mid, h, w, n):
     close(a, b, what='fused vs unfused')
     bufs, _ = torch_ref.run_graph(g, nchw(xi.astype(np.float32)))
     close(a, nhwc(bufs[wide.tid][:, 16:16 + c]), what='fused vs torch')
+    check_net(net, n, f'resblock {c}/{mid} {h}x{w}')
+    check_sentinel(net, n, f'resblock {c}/{mid} {h}x{w}')
     net.close()
 
 
@@ -251,9 +254,12 @@ def test_conv_fused_upsample(ctx, cin, cout, h, w, n):
     outs = []
     for gg, v in ((g, cat), (g2, u)):
         net = HipNet(ctx, NET_DETECTOR, gg, n)
+        fill_sentinel(net)
         net.write(gg.input, x)
         net.run(n)
         outs.append(net.read(v, n))
+        check_net(net, n, f'conv up2 {cin}->{cout} {"fused" if gg is g else "conv + upsample"}')
+        check_sentinel(net, n, f'conv up2 {cin}->{cout}')
         net.close()
     np.testing.assert_array_equal(outs[0][..., 8:8 + cout], outs[1][..., :cout])
     bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
@@ -279,6 +285,7 @@ def test_lightconv_fused(ctx, c, h, w, n):
         outs.append(net.read(y, n))
         bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
         close(outs[-1], nhwc(bufs[y.tid][:, :c]), what=f'lightconv c{c} fuse={fuse}')
+        check_net(net, n, f'lightconv c{c} {h}x{w} fuse={fuse}')
         net.close()
     np.testing.assert_array_equal(outs[0], outs[1])
 
@@ -298,11 +305,16 @@ def test_osnet_fused_and_arena_reuse_identical(ctx):
         g, _ = Small.build_graph(RandomWeights(seed=5), fuse_lightconv=fuse)
         assert len(g.layers) == (32 if fuse else 173)   # 50 with one launch per stream depth (next test)
         net = HipNet(ctx, NET_EXTRACTOR, g, 6, reuse_buffers=reuse)
+        if (fuse, reuse) == (True, False):
+            fill_sentinel(net)
         for _ in range(2):                      # second run: stale arena contents must not matter
             net.write(g.input, x)
             net.run(6)
         embs[fuse, reuse] = net.read_embeddings(6)
-        net.close()
+        if (fuse, reuse) == (True, False):      # the fused table with every tensor readable: each layer on its own
+            close_and_check(net, 6, x, 'OSNet025 128x64 fused', sentinel=True)
+        else:
+            net.close()
     np.testing.assert_array_equal(embs[True, False], embs[True, True])
     assert np.abs(embs[True, True] - embs[False, False]).max() < 2e-3
     assert (np.sum(embs[True, True] * embs[False, False], axis=1) > 0.9999).all()
@@ -314,7 +326,7 @@ def test_gated_sum_fused(ctx, c, hid, h, w, n, k):
     """FM_OP_GATED_SUM == k gate launches + gate_sum (up to the average-pool grouping) == torch."""
     rng = np.random.default_rng(c)
     x = rng.normal(0, 1, (n, h, w, k * c)).astype(np.float16)
-    outs = []
+    outs, kept = [], []
     for fused in (True, False):
         g = Graph(RandomWeights(seed=c), (h, w), k * c)
         xs = [g.input.slice(i * c, c) for i in range(k)]
@@ -332,8 +344,11 @@ def test_gated_sum_fused(ctx, c, hid, h, w, n, k):
         outs.append(net.read(y, n))
         bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
         close(outs[-1], nhwc(bufs[y.tid][:, :c]), what=f'gated_sum fused={fused}')
+        kept.append((g, {}, len(g.layers) - 1))
+        check_net(net, n, f'gated_sum c{c} k{k} fused={fused}', keep=kept[-1][1])
         net.close()
     assert np.abs(outs[0] - outs[1]).max() <= 4e-3 * np.abs(outs[1]).max()
+    check_pair(kept[0], kept[1], 'fused gated sum vs gate launches + gate_sum')
 
 
 @pytest.mark.parametrize('c,h,w,n', [(16, 64, 32, 3), (24, 32, 16, 5), (32, 16, 8, 4), (16, 21, 19, 2), (8, 9, 40, 1),
@@ -367,6 +382,7 @@ def test_lightconv_chain(ctx, c, h, w, n):
         net.write(g.input, x)
         net.run(n)
         outs.append([net.read(v, n) for v in streams] + [net.read(z, n)])
+        check_net(net, n, f'lightconv chain c{c} {h}x{w} n{n} chain={chain}')
         if chain:
             bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
             for t, v in enumerate(streams):
@@ -417,6 +433,7 @@ def test_lightconv_grouped(ctx):
     for i, s in enumerate(singles):
         np.testing.assert_array_equal(full[..., i * c:(i + 1) * c], net.read(s, n))
     close(full, nhwc(bufs[grouped.tid][:, :3 * c]), what='grouped lightconv')
+    check_net(net, n, 'grouped lightconv')
     net.close()
 
 
@@ -458,7 +475,7 @@ def test_osnet_embeddings(ctx, model, size, batch):
     # embeddings: unit vectors; tolerance 2e-2 absolute per component, cosine similarity > 0.999
     assert np.abs(emb - ref.numpy()).max() < 2e-2
     assert (np.sum(emb * ref.numpy(), axis=1) > 0.999).all()
-    net.close()
+    close_and_check(net, batch, x, f'{model} {size[0]}x{size[1]} x{batch}')
 
 
 @pytest.mark.parametrize('batch', [1, 3])
@@ -480,7 +497,7 @@ def test_osnet_tail_fused(ctx, monkeypatch, batch):
             net.write(g.input, x)
             net.run(batch)
         embs.append(net.read_embeddings(batch))
-        net.close()
+        close_and_check(net, batch, x, f'OSNet025 x{batch} ostail={fused}')
         _, ref = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
         assert np.abs(embs[-1] - ref.numpy()).max() < 4e-3, (fused, np.abs(embs[-1] - ref.numpy()).max())
     np.testing.assert_allclose(np.linalg.norm(embs[0], axis=1), 1.0, atol=1e-5)
@@ -507,6 +524,7 @@ def test_yolov4_small_input(ctx, monkeypatch, resblock):
     assert n_convs == 110 - 5
     assert g.layers[0]['op'] == 18 and len(g.layers[0]['gates']) == 3
     net = HipNet(ctx, NET_DETECTOR, g, 1)
+    fill_sentinel(net)
     rng = np.random.default_rng(22)
     x = rng.uniform(0, 1, (1, 96, 96, 3)).astype(np.float16)
     net.write(g.input, x)
@@ -518,40 +536,15 @@ def test_yolov4_small_input(ctx, monkeypatch, resblock):
     bufs32, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)), emulate_fp16_storage=False)
     for i, hd in enumerate(heads):
         close(net.read(hd, 1), nhwc(bufs32[hd.tid][:, :hd.c]), rel=5e-2, abs_=1e-2, what=f'head {i} vs fp32')
-    net.close()
+    close_and_check(net, 1, x, f'YOLOv4 96x96 resblock={resblock}', sentinel=True)
 
 
 def _convd_code(bm, bn, kg, ns=0, role=0, spb=1):
     return bm | bn << 8 | kg << 16 | ns << 20 | role << 24 | (spb - 1) << 25
 
 
-_CONVD_SHAPES = [
-    (64, 128, 1, 1, 'mish', 76, 76, 1, ''),            # CSP stage entry
-    (64, 64, 1, 1, 'mish', 48, 40, 1, 'slice'),        # reads a channel slice, writes a concat slice
-    (128, 64, 1, 1, 'mish', 35, 35, 1, ''),            # ragged last pixel tile
-    (128, 128, 1, 1, 'leaky', 32, 32, 2, ''),          # batch 2
-    (256, 255, 1, 1, 'linear', 38, 38, 1, 'f32'),      # head: ragged cout, fp32 output
-    (128, 255, 1, 1, 'logistic', 20, 20, 1, 'f32'),    # NEW_COORDS head
-    (512, 256, 1, 1, 'leaky', 19, 19, 1, 'up'),        # fused nearest x2 upsample into a concat slice
-    (512, 512, 1, 1, 'mish', 19, 19, 1, 'res'),        # shortcut after the activation
-    (2048, 512, 1, 1, 'leaky', 19, 19, 1, ''),         # 32 K steps
-    (128, 256, 3, 1, 'leaky', 38, 38, 1, ''),          # 3x3, padding on every border
-    (64, 128, 3, 2, 'mish', 76, 76, 1, ''),            # stride-2 downsample, 9 K steps (odd: two steps per barrier repeat one)
-    (256, 512, 3, 2, 'leaky', 38, 38, 1, ''),
-    (512, 1024, 3, 1, 'leaky', 19, 19, 1, ''),         # 72 K steps
-    (128, 64, 3, 1, 'relu', 7, 5, 3, 'res'),           # tiny maps, batch, shortcut
-    (64, 40, 3, 1, 'swish', 9, 9, 1, ''),              # cout padded to 64
-    (192, 96, 3, 1, 'relu', 16, 8, 4, 'resb'),         # cin = 3 * 64: a tap is three K steps; shortcut BEFORE the activation
-    (16, 64, 1, 1, 'relu', 64, 32, 5, ''),             # OSNet x0.25 pointwise convs: cin % 64 != 0 (K zero-padded to a step,
-    (96, 24, 1, 1, 'relu', 16, 8, 7, 'resb'),          #   chunks beyond the pixel's channels not fetched), batch
-    (24, 96, 1, 1, 'linear', 32, 16, 3, 'slice'),
-]
-# forced configurations (bm, bn, K groups, ring slots, loader waves, steps per barrier); every shape runs the launcher's own
-# choice and three of them (a different three per shape: every pairing of a shape class with a code path occurs)
-_CONVD_CFGS = [(128, 128, 1, 0, 1), (128, 64, 2, 0, 1), (128, 64, 1, 2, 0), (64, 64, 4), (64, 64, 1, 3, 1), (64, 64, 2, 0, 0),
-               (128, 128, 2, 2, 1), (64, 64, 2, 2, 1, 2), (128, 64, 1, 3, 1, 2), (64, 64, 1, 0, 0, 2)]
-_CONVD_CASES = [(*sh, cfg) for i, sh in enumerate(_CONVD_SHAPES)
-                for cfg in ['auto'] + [_CONVD_CFGS[(3 * i + j) % len(_CONVD_CFGS)] for j in range(3)]]
+_CONVD_CASES = [(*sh, cfg) for i, sh in enumerate(CONVD_SHAPES)
+                for cfg in ['auto'] + [CONVD_CFGS[(3 * i + j) % len(CONVD_CFGS)] for j in range(3)]]
 
 
 @pytest.mark.parametrize('cin,cout,k,stride,act,h,w,n,extra,cfg', _CONVD_CASES)
@@ -562,7 +555,7 @@ def test_convd_conv(ctx, cin, cout, k, stride, act, h, w, n, extra, cfg):
     rng = np.random.default_rng(cin + cout + h)
     sl = extra == 'slice'
     x = rng.normal(0, 1, (n, h, w, cin + (64 if sl else 0))).astype(np.float16)
-    outs = []
+    outs, kept = [], []
     for level in (2, 0):
         ctx.set_option('convd_cfg', 0 if cfg == 'auto' or not level else _convd_code(*cfg))
         g = Graph(RandomWeights(seed=cin + 3 * cout + k), (h, w), x.shape[-1])
@@ -578,6 +571,7 @@ def test_convd_conv(ctx, cin, cout, k, stride, act, h, w, n, extra, cfg):
                    res_mode=RES_BEFORE_ACT if extra == 'resb' else 1, bn=extra != 'f32')
         assert g.layers[-1]['op'] == (17 if level else 0)
         net = HipNet(ctx, NET_DETECTOR, g, n)
+        fill_sentinel(net)
         for xi in (x[:, ::-1].copy(), x):           # eager validation + capture, then a graph replay -- on another input, so
             net.write(g.input, xi)                  # that a replay which did nothing could not pass on the first launch's output
             net.run(n)
@@ -585,10 +579,19 @@ def test_convd_conv(ctx, cin, cout, k, stride, act, h, w, n, extra, cfg):
         if level:
             bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
             close(outs[-1], nhwc(bufs[wide.tid][:, 64:64 + cout]), what=f'convd {cin}->{cout} k{k}s{stride} {cfg}')
+        label = f'{"convd" if level else "tiled"} {cin}->{cout} k{k}s{stride} {h}x{w} {extra} {cfg if level else ""}'
+        kept.append((g, {}, len(g.layers) - 1))
+        try:
+            check_net(net, n, label, keep=kept[-1][1])
+            check_sentinel(net, n, label)
+        finally:
+            ctx.set_option('convd_cfg', 0)
         net.close()
     ctx.set_option('convd_cfg', 0)
     assert np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 0
     close(outs[0], outs[1], rel=1e-2, abs_=2e-3, what='convd vs tiled')
+    if extra not in ('res', 'resb'):        # (there the shortcut tensor is itself produced under the forced configuration)
+        check_pair(kept[0], kept[1], 'convd vs tiled')
 
 
 @pytest.mark.parametrize('cout,act1,act2,h,w,n,c3', [(64, 'mish', 'mish', 64, 96, 1, 0), (64, 'leaky', 'mish', 37, 51, 2, 0),
@@ -618,6 +621,8 @@ def test_stem_pair_fused(ctx, cout, act1, act2, h, w, n, c3):
         net.write(g.input, x)
         net.run(n)
         outs.append(net.read(y, n))
+        if fuse:
+            check_net(net, n, f'stem pair {cout}/{c3} {h}x{w} n{n}')
         net.close()
         if fuse:
             bufs, _ = torch_ref.run_graph(g, nchw(x[..., :3].astype(np.float32)))
@@ -645,11 +650,46 @@ def test_pointwise_pair_fused(ctx, cout, act1, act2, h, w, n):
         g.outputs.append(y)
         assert (g.layers[-1]['op'] == 19) == fuse and len(g.layers) == (3 if fuse else 4)
         net = HipNet(ctx, NET_DETECTOR, g, n)
+        fill_sentinel(net)
         net.write(g.input, x)
         net.run(n)
         outs.append(net.read(y, n))
+        if fuse:
+            check_net(net, n, f'pointwise pair {cout} {h}x{w} n{n}')
+        check_sentinel(net, n, f'pointwise pair {cout} {h}x{w} n{n} fuse={fuse}')       # (fused: the concat's first half stays unwritten)
         net.close()
         if fuse:
             bufs, _ = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
             close(outs[0], nhwc(bufs[y.tid][:, :cout]), what='fused pointwise pair vs torch')
     np.testing.assert_array_equal(outs[0], outs[1])
+
+
+@pytest.mark.parametrize('case', ['tiled 3x3', 'streamed 3x3', 'convd 3x3', 'convd 1x1', 'resblock', 'lightconv'])
+def test_ragged_tile_stays_inside_the_batch(ctx, case):
+    """Shapes whose last pixel tile is ragged, in a network created for one sample more than it runs: sample n of the input
+    and of every tensor a layer writes holds the sentinel before the run and has to hold it afterwards -- a tile that runs
+    on past the batch lands there --, as do the guard channels beside the output slice; the n samples meet the per-element
+    bound."""
+    n, h, w, cin = {'convd 1x1': (1, 35, 35, 128), 'resblock': (3, 9, 5, 128), 'lightconv': (1, 5, 3, 8)}.get(case, (3, 7, 5, 128))
+    g = Graph(RandomWeights(seed=7), (h, w), cin)
+    if case == 'resblock':
+        g.resblock('a', 'b', g.input, 64, dst=g.new(h, w, cin + 16).slice(16, cin))
+        assert g.layers[-1]['op'] == 14
+    elif case == 'lightconv':
+        g.lightconv('lc', g.input, cin, 'relu', fuse=True)
+        assert len(g.layers) == 1
+    else:
+        g.convs_max_pixels = 10 ** 6 if case.startswith('streamed') else 0
+        g.convd_level = 2 if case.startswith('convd') else 0
+        k = int(case[-1])
+        g.conv('c', g.input, 64, k, 1, 'relu' if k == 3 else 'mish', dst=g.new(h, w, 64 + 16).slice(16, 64))
+        assert g.layers[-1]['op'] == {'tiled': 0, 'streamed': 15, 'convd': 17}[case.split()[0]]
+    net = HipNet(ctx, NET_DETECTOR, g, n + 1)
+    fill_sentinel(net)
+    x = np.full((n + 1, h, w, cin), SENT16)
+    x[:n] = np.random.default_rng(cin + h).normal(0, 1, (n, h, w, cin))
+    write_raw(net, g.input.tid, x)
+    net.run(n)
+    check_net(net, n, f'ragged {case}')
+    check_sentinel(net, n, f'ragged {case}', also=[g.input.tid])
+    net.close()

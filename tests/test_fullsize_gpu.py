@@ -11,8 +11,6 @@ to fp16 at the same points as the engine stores them).  Tolerances (stated in DE
 KLT oracle: oracle/cv_oracle.py (OpenCV algorithms restated): keypoints (GFTT, FAST and the LK-tracked points),
 status / inlier flags, per-track result codes and rounded boxes IDENTICAL; homography rtol 1e-6 (double precision
 Jacobi / Levenberg-Marquardt on the host vs numpy)."""
-import copy
-
 import numpy as np
 import pytest
 import torch
@@ -23,7 +21,8 @@ import scenes
 import torch_ref
 from fastmot_amd.engine import HipNet, NET_DETECTOR, NET_EXTRACTOR
 from fastmot_amd.models import YOLO, ReID
-from fastmot_amd.models.graph import CONV_OPS, RandomWeights, View
+from fastmot_amd.models.graph import CONV_OPS, RandomWeights
+from layer_check import _device_tensors, check_layers, clobber_snapshots
 
 pytestmark = pytest.mark.gpu
 
@@ -46,28 +45,6 @@ def check_tensor(gpu, ref, what):
     return err.max() / max(np.abs(ref).max(), 1e-12), rms_err / max(rms_ref, 1e-12)
 
 
-def _device_tensors(net, g, batch, tids=None):
-    """tid -> torch view [N, cpad, h, w] of what the device holds (fp16 tensors stay fp16: lossless, half the host memory)."""
-    out = {}
-    for tid, (h, w, c, f32) in enumerate(g.tensors):
-        if tids is None or tid in tids:
-            a = net.read(_whole(g, tid), batch)
-            out[tid] = torch.from_numpy(a if f32 else a.astype(np.float16)).permute(0, 3, 1, 2)
-    return out
-
-
-class _Forced:
-    """The tensors layer `i` of a finished run saw: the final state, except for tensors a later layer overwrote in place
-    (torch_ref.clobbers: the merged CSP stages) -- those come from a run of the table cut before the overwriting layer."""
-
-    def __init__(self, final, snaps):
-        self.final, self.snaps, self.i = final, snaps, 0       # snaps: [(layer index L, tid, tensor before layer L ran)]
-
-    def __getitem__(self, tid):
-        later = [(L, t) for L, st, t in self.snaps if st == tid and L > self.i]
-        return min(later, key=lambda p: p[0])[1] if later else self.final[tid]
-
-
 def _every_tensor_and_every_layer(ctx, which, g, x, batch, label, heads=()):
     """(1) the whole table against torch_ref.run_graph, every written tensor and every head view, with the whole-tensor
     bar; (2) every layer against torch_ref.run_layer (float64, S in float64 too) fed with the tensors THE DEVICE produced
@@ -80,15 +57,7 @@ def _every_tensor_and_every_layer(ctx, which, g, x, batch, label, heads=()):
     emb = net.read_embeddings(batch) if which != NET_DETECTOR else None
     head_views = [net.read(hd, batch) for hd in heads]
     net.close()
-    snaps = []
-    for L, tid in torch_ref.clobbers(g):
-        cut = copy.copy(g)
-        cut.layers = g.layers[:L]
-        net = HipNet(ctx, which, cut, batch, reuse_buffers=False)
-        net.write(g.input, x)
-        net.run(batch)
-        snaps.append((L, tid, _device_tensors(net, g, batch, {tid})[tid]))
-        net.close()
+    snaps = clobber_snapshots(ctx, which, g, x, batch)
     # (1) whole network, whole-tensor bar
     bufs, ref_emb = torch_ref.run_graph(g, nchw(x.astype(np.float32)))
     # the conv kernels write ceil8(cout) channels (net.h: cout_store), the padding ones from zero weights and zero bias:
@@ -110,20 +79,7 @@ def _every_tensor_and_every_layer(ctx, which, g, x, batch, label, heads=()):
     del bufs
     print(f'{label}: {len(written)} tensors, worst max-err/max {worst[0]:.2e} (tensor {worst[1]})')
     # (2) layer by layer on the device's own inputs, per-element bound
-    forced, gates, ratios = _Forced(final, snaps), {}, {}
-    for i, d in enumerate(g.layers):
-        forced.i = i
-        kind, ref, bound = torch_ref.run_layer(g, i, forced, gates=gates)
-        if kind == 'gate':
-            continue
-        o = d['out']
-        got = emb if kind == 'emb' else forced[o.tid][:, o.coff:o.coff + o.c]
-        op = torch_ref.OP_NAMES[d['op']] + ('/3' if 'stem3_ref' in d else '')
-        r = torch_ref.check_layer(got, ref, bound, f'{label} layer {i} {op} {d.get("name", "")} k{d["k"]} s{d["stride"]} '
-                                                   f'cin {d["cin"]} cout {d["cout"]}')
-        ratios[op] = max(ratios.get(op, 0.0), r)
-    for op, r in sorted(ratios.items()):
-        print(f'LAYERBOUND {label:24s} {op:14s} worst err/bound {r:.3g}')
+    check_layers(g, final, snaps, emb, label)
     return emb, ref_emb
 
 
@@ -159,12 +115,6 @@ def test_yolov4_608_unmerged_csp_every_tensor(ctx, monkeypatch):
     g = _detector_every_tensor(ctx, 'YOLOv4_608')
     # one more layer per CSP stage, and the first stage's pointwise conv no longer is the stem launch's third stage
     assert len(g.layers) == merged + 6, (len(g.layers), merged)
-
-
-def _whole(g, tid):
-    """View of a whole tensor (all stored channels)."""
-    h, w, c, _ = g.tensors[tid]
-    return View(tid, 0, c, h, w)
 
 
 @pytest.mark.parametrize('model,batch', [('OSNet025', 50), ('OSNet10', 16), ('OSNet10', 50)])

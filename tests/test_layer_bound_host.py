@@ -18,13 +18,23 @@ summation order than the float64 reference) and every activation rounded to fp16
     two fused stages skipped on one intermediate channel; (e) a residual added on the other side of the activation;
     (f) SPP slices written in the order (5, 9, 13).  For (a) the factor by which the whole-tensor bar of
     test_fullsize_gpu.py (6e-3 * max|ref| + 2e-3) is exceeded is printed next to the per-element one.
+  * at the shapes of the unit tests (tests/conv_cases.py, every plain conv table of tests/test_conv_gpu.py with the same
+    seeds): the clean stand-in stays within the bound, and one 16-byte chunk of one tap lost by the last output channel
+    exceeds it -- at the largest K of that file, 4608, by 1.5x, where that file's whole-tensor bar passes it at 0.39.
+  * the sentinel check of tests/layer_check.py refuses a store past the written channels, one into the sample behind the
+    batch and a non-finite value (host memory in place of the device's).
 
 A kernel author who nearly made some other mistake adds it to MUTATIONS."""
+import ctypes
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases
+import layer_check
 import torch_ref as T
 from fastmot_amd.models import YOLO, ReID
 from fastmot_amd.models import graph as G
@@ -213,6 +223,85 @@ def test_clean_stand_in_stays_within_the_bound(walked):
         assert r <= 0.6, key
     # the bound is not vacuous where it is meant to bite: a correctly rounded store alone reaches most of it
     assert min(r for (t, c), r in walked['clean'].items() if c in PLAIN) >= 0.5
+
+
+def _lose_a_chunk(w):
+    """The last output channel loses the first min(8, cin) input channels of the bottom-right tap: one 16-byte chunk of
+    the weight image, what a DMA-fed kernel drops when it miscounts the chunks of a pixel."""
+    w = w.clone()
+    w[-1, :min(8, w.shape[1]), -1, -1] = 0
+    return w
+
+
+@pytest.mark.parametrize('kind,case', conv_cases.PLAIN_CASES, ids=[f'{k}-' + '-'.join(map(str, c)) for k, c in conv_cases.PLAIN_CASES])
+def test_bound_bites_at_the_unit_test_shapes(kind, case):
+    """Every plain conv shape of tests/test_conv_gpu.py (conv_cases: the same one-layer table, the same seeds): (a) the
+    clean stand-in stays within the bound, (b) the stand-in with one lost chunk exceeds it.  Printed beside (b), recorded
+    only: the same defect against that file's whole-tensor bar, max err / (2e-2 * max|ref| + 2e-3)."""
+    g, x, idx = conv_cases.table(kind, case)
+    seen = {}
+
+    def around(i, bufs):
+        if i != idx:
+            return None
+        _, ref, bound = T.run_layer(g, i, bufs)
+        bad = T.run_layer(g, i, bufs, dtype=torch.float32, emulate_fp16_storage=True, channels_last=True, mut=_at(0, 'w', _lose_a_chunk))[1]
+        seen.update(defect=_exceeds(bad, ref, bound),
+                    close=float((bad.double() - ref).abs().max() / (2e-2 * ref.abs().max() + 2e-3)))
+
+        def after(bufs, emb):
+            o = g.layers[i]['out']
+            seen['clean'] = T.check_layer(bufs[o.tid][:, o.coff:o.coff + o.c], ref, bound, f'clean stand-in, {kind} {case}')
+        return after
+    T.run_graph(g, conv_cases.nchw(x), channels_last=True, around=around)
+    print(f"{kind} {case}: clean err / bound {seen['clean']:.3g}; one lost chunk: err / bound {seen['defect']:.4g}, "
+          f"err / whole-tensor bar {seen['close']:.3g}")
+    assert seen['clean'] <= 1.0, (kind, case, seen)
+    assert seen['defect'] > 1.0, (kind, case, seen)
+    assert np.isfinite(seen['close']), (kind, case, seen)
+
+
+class _HostNet:
+    """What layer_check's sentinel functions use of a HipNet, with host memory behind the library's raw tensor write."""
+
+    def __init__(self, graph, max_batch):
+        self.graph, self.max_batch, self.which, self.mem = graph, max_batch, 0, {}
+        self.ctx = SimpleNamespace(handle=None, lib=self)
+
+    def fm_net_tensor_write(self, handle, which, tid, host, nbytes):
+        h, w, c, f32 = self.graph.tensors[tid.value]
+        a = np.frombuffer(ctypes.string_at(host, nbytes.value), np.float32 if f32 else np.float16)
+        self.mem[tid.value] = a.reshape(-1, h, w, c).copy()
+        return 0
+
+    def read(self, view, batch):
+        return self.mem[view.tid][:batch, ..., view.coff:view.coff + view.c].astype(np.float32)
+
+
+@pytest.mark.parametrize('f32', [False, True])
+def test_sentinel_check_fails_for_the_overruns_it_is_there_for(f32):
+    """20 channels written at offset 16 of a 48-channel tensor, batch 2 of 3: the ceil8 padding [36, 40) may be stored;
+    a store one channel past it, a store into sample 2 and a non-finite value in the slice are each refused."""
+    g = G.Graph(RandomWeights(seed=1), (4, 3), 16)
+    wide = g.new(4, 3, 48, f32=f32)
+    g.conv('c', g.input, 20, 1, 1, 'linear', dst=wide.slice(16, 20), f32_out=f32)
+    net = _HostNet(g, 3)
+    layer_check.fill_sentinel(net)
+    filled = net.mem[wide.tid].copy()
+    assert filled.shape == (3, 4, 3, 48) and np.isfinite(filled).all()
+    with pytest.raises(AssertionError, match='outside the written channels'):
+        net.mem[wide.tid][:2, ..., 16:40] = 1.0
+        net.mem[wide.tid][1, 3, 2, 40] = 0.0
+        layer_check.check_sentinel(net, 2, 'one channel too far')
+    net.mem[wide.tid][1, 3, 2, 40] = filled[1, 3, 2, 40]
+    layer_check.check_sentinel(net, 2, 'clean')
+    net.mem[wide.tid][2, 0, 0, 16] = 1.0
+    with pytest.raises(AssertionError, match='beyond batch 2'):
+        layer_check.check_sentinel(net, 2, 'into the next sample')
+    net.mem[wide.tid][2, 0, 0, 16] = filled[2, 0, 0, 16]
+    net.mem[wide.tid][0, 0, 0, 17] = np.inf
+    with pytest.raises(AssertionError, match='non-finite'):
+        layer_check.check_sentinel(net, 2, 'overflow')
 
 
 @pytest.mark.parametrize('cls,letter', sorted((c, m) for c, ms in MUTATIONS.items() for m in ms))
