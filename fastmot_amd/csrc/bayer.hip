@@ -18,10 +18,11 @@
 //   8-byte LDS reads (the 12 samples it needs lie in 16), bytes picked with constant shifts.  The rows of one wavefront
 //   share their parity (a wavefront takes every other row of 8), so which of a run's pixels are colour sites and which
 //   green sites is the same in all 64 lanes: the one branch on it is wave-uniform, everything else is straight-line.
-//   The 24 BGR bytes leave by packed.hip's store rule: three 8-byte stores where the run is whole and its first byte
-//   8-byte aligned, six 4-byte stores where it is 4-byte aligned, bytes otherwise -- decided per thread from the address.
+//   The 24 BGR bytes leave by bgr_run.h's StoreRule::BY_ADDRESS: three 8-byte stores where the run is whole and its first
+//   byte 8-byte aligned, six 4-byte stores where it is 4-byte aligned, bytes otherwise -- decided per thread.
 // No address depends on a sample's value.  LDS: 2720 bytes.
 #include "common.h"
+#include "bgr_run.h"
 
 namespace {
 
@@ -42,32 +43,8 @@ __device__ __forceinline__ uint32_t prep(uint32_t s, int black, uint32_t gain, i
     return min(255u, (v * gain + (1u << (depth - 1))) >> depth);
 }
 
-// the 3 n <= 24 BGR bytes of a thread's run (byte k: word k >> 2, bits 8 * (k & 3)) to `out` (packed.hip's rule)
-__device__ __forceinline__ void store_run(uint8_t* __restrict__ out, int n, const uint32_t (&o)[6]) {
-    if (n == 8 && !((uintptr_t)out & 7)) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) reinterpret_cast<uint2*>(out)[q] = make_uint2(o[2 * q], o[2 * q + 1]);
-    } else if (n == 8 && !((uintptr_t)out & 3)) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) reinterpret_cast<uint32_t*>(out)[q] = o[q];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 24; ++k)
-            if (k < 3 * n) out[k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
-    }
-}
-
-__device__ __forceinline__ void put_px(uint32_t (&o)[6], int i, uint32_t b, uint32_t g, uint32_t r) {
-    const uint32_t px[3] = {b, g, r};
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const int k = 3 * i + ch;                          // byte of the 24-byte row segment
-        o[k >> 2] |= px[ch] << ((k & 3) * 8);
-    }
-}
-
 // byte k of the 16 staged samples of one row
-__device__ __forceinline__ int bt(const uint32_t (&w)[4], int k) { return (int)((w[k >> 2] >> ((k & 3) * 8)) & 0xffu); }
+__device__ __forceinline__ int bt(const uint32_t (&w)[4], int k) { return (int)run_byte(w, k); }
 
 __device__ __forceinline__ int fin(int sum) { return min(max((sum + 8) >> 4, 0), 255); }
 
@@ -163,7 +140,7 @@ __global__ __launch_bounds__(256) void bayer_to_bgr_kernel(const uint8_t* __rest
     uint32_t o[6] = {};
     if (site0) demosaic_run<METHOD, true>(r, r_row, o);
     else demosaic_run<METHOD, false>(r, r_row, o);
-    store_run(bgr + ((size_t)y * W + x0) * 3, n, o);
+    store_run<StoreRule::BY_ADDRESS>(bgr + ((size_t)y * W + x0) * 3, n, o);
 }
 
 }  // namespace

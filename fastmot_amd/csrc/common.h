@@ -275,6 +275,9 @@ inline void fm_trace_mark(fm_ctx* ctx, hipStream_t s, int tag) {
 
 int fm_ensure_slots(fm_ctx* ctx, int max_slot_plus_1);
 int fm_nv12_to_bgr(const uint8_t* nv12, uint8_t* bgr, int w, int h, int matrix, hipStream_t s);   // nv12.hip
+// nv12.hip: the same for planes that lie anywhere in device memory, rows sy / suv bytes apart
+int fm_nv12_planes_to_bgr(const uint8_t* y, const uint8_t* uv, long long sy, long long suv, uint8_t* bgr, int w, int h, int matrix,
+                          hipStream_t s);
 // width x height of the U and V planes of a w x h frame (0 x 0 for FM_YUV_MONO); false for an unknown `chroma`
 inline bool fm_yuv_chroma_dims(int w, int h, int chroma, int* cw, int* ch) {
     switch (chroma) {
@@ -296,6 +299,9 @@ inline bool fm_packed_matrix_ok(int matrix) {
     return matrix == FM_PACKED_BT601 || matrix == FM_PACKED_BT709 || matrix == FM_PACKED_BT601_FULL || matrix == FM_PACKED_BT709_FULL;
 }
 int fm_packed_to_bgr(const uint8_t* src, uint8_t* bgr, int w, int h, int format, int matrix, hipStream_t s);   // packed.hip
+// hwc.hip: h rows of w 3- or 4-byte pixels (format: FM_PACKED_RGB .. FM_PACKED_XBGR), `pitch` bytes apart, anywhere in
+// device memory -> w * h * 3 BGR bytes at `bgr`, on `s`
+int fm_hwc_to_bgr(const uint8_t* src, long long pitch, uint8_t* bgr, int w, int h, int format, hipStream_t s);
 // bytes of one Bayer sample of `depth` bits (FM_BAYER frames); 0 for an unknown depth
 inline int fm_bayer_sample_bytes(int depth) {
     return depth == 8 ? 1 : depth == 10 || depth == 12 || depth == 14 || depth == 16 ? 2 : 0;

@@ -7,58 +7,28 @@
 // Arithmetic (fastmot_amd/utils/deep.py states it in numpy, tests compare bit for bit), d the depth, s = d - 8:
 //     y = max(Y - (16 << s), 0) * CY, u = U - (128 << s), v = V - (128 << s), h = 1 << (19 + s)
 //     R = sat8((y + h + CVR v) >> (20 + s))   G = sat8((y + h + CVG v + CUG u) >> (20 + s))   B = sat8((y + h + CUB u) >> (20 + s))
-// i.e. yuv_coef.h's with every sample kept at full precision.  The sums reach 2^37.2 at d = 16, so they are 64-bit:
-// one mad per term (v_mad_i64_i32).  A sum is below 2^(29.2 + s) in magnitude, so (sum >> s) fits an int and
-// sat8(sum >> (20 + s)) = sat8((int)(sum >> s) >> 20) exactly (two floors of a division by powers of two compose): the
-// 64-bit part ends with one shift and yuv_coef.h's 32-bit sat8 does the rest.
+// i.e. the 8-bit pixel with every sample kept at full precision: yuv_coef.h's 64-bit form (one v_mad_i64_i32 per term,
+// one shift, and the 32-bit sat8).
 //
 // Shape: planar_to_bgr_kernel's (yuv.hip).  One thread owns 8 pixels of a row and, for 4:2:0, the same 8 columns of the
 // row below it, so every chroma sample is loaded once: 16 (32) Y bytes and 2 x 8 chroma bytes (2 x 16 for 4:4:4; one
 // 16-byte run of U, V pairs for semi-planar) in, 24 (48) BGR bytes out.  Threads are numbered along a row first: a
-// wavefront reads 1024 contiguous Y bytes per row and writes 1536 contiguous BGR bytes per row.  A run is one 16-byte
-// (8-byte) load when it is whole and its address aligned to it, two 8-byte loads when a 16-byte run is aligned to 8
-// only, 2-byte loads otherwise -- decided per thread from the address, so odd widths and planes that begin at odd
-// sample offsets cost only the threads they touch.  Stores: three 8-byte stores per row when W % 8 == 0 and the frame
-// is 8-byte aligned, bytes otherwise.  Depth, the alignment shift and the mask are kernel arguments, the same for every
+// wavefront reads 1024 contiguous Y bytes per row and writes 1536 contiguous BGR bytes per row.  Loads are bgr_run.h's
+// load_run: a run is one 16-byte (8-byte) load when it is whole and its address aligned to it, narrower ones otherwise
+// -- decided per thread from the address, so odd widths and planes that begin at odd sample offsets cost only the
+// threads they touch.  Stores: StoreRule::ALIGNED8 when W % 8 == 0 and the frame is 8-byte aligned, StoreRule::BYTES
+// otherwise.  Depth, the alignment shift and the mask are kernel arguments, the same for every
 // lane.  A streaming kernel (6 bytes per pixel for 4:2:0): no LDS, no reuse beyond what a thread holds in registers.
 #include "common.h"
+#include "bgr_run.h"
 #include "yuv_coef.h"
 
 namespace {
 
-// FM_DEEP_BT601 / _BT709: yuv_coef.h's constants.  FM_DEEP_BT2020: non-constant luminance, Kr = 0.2627, Kb = 0.0593,
-// round(c * 2^20) of 255 / 219, 2 (1 - Kr) 255 / 224, 2 (1 - Kb) 255 / 224, -2 (1 - Kb) Kb / Kg 255 / 224, -2 (1 - Kr) Kr / Kg 255 / 224
-constexpr Nv12Coef DEEP_COEF[3] = {NV12_COEF[0], NV12_COEF[1], {1220945, 1760217, 2245811, -196426, -682019}};
-
-#define DEEP_WORD(w, i) ((int)(((w)[(i) >> 1] >> (((i) & 1) * 16)) & 0xffffu))
-
 // the n <= N samples of a run at p into w (sample i: word i >> 1, bits 16 * (i & 1)); N = 4: 8 bytes, N = 8: 16 bytes
 template <int N>
 __device__ __forceinline__ void load_run16(const uint16_t* __restrict__ p, int n, uint32_t (&w)[N / 2]) {
-#pragma unroll
-    for (int i = 0; i < N / 2; ++i) w[i] = 0;
-    const uintptr_t a = (uintptr_t)p;
-    if constexpr (N == 4) {
-        if (n == N && !(a & 7)) {
-            const uint2 v = *reinterpret_cast<const uint2*>(p);
-            w[0] = v.x, w[1] = v.y;
-            return;
-        }
-    } else {
-        if (n == N && !(a & 15)) {
-            const uint4 v = *reinterpret_cast<const uint4*>(p);
-            w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-            return;
-        }
-        if (n == N && !(a & 7)) {
-            const uint2 v0 = reinterpret_cast<const uint2*>(p)[0], v1 = reinterpret_cast<const uint2*>(p)[1];
-            w[0] = v0.x, w[1] = v0.y, w[2] = v1.x, w[3] = v1.y;
-            return;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        if (i < n) w[i >> 1] |= (uint32_t)p[i] << ((i & 1) * 16);
+    load_run<N / 2>(reinterpret_cast<const uint8_t*>(p), 2 * n, n == N, w);
 }
 
 // SEMI: FM_DEEP_SEMIPLANAR (4:2:0 only; `up` is the UV plane).  CHROMA: FM_YUV_*.  ST8: W % 8 == 0 and an 8-byte aligned
@@ -71,13 +41,9 @@ __global__ __launch_bounds__(256) void deep_to_bgr_kernel(const uint16_t* __rest
     constexpr int SH = (CHROMA == FM_YUV_420 || CHROMA == FM_YUV_422) ? 1 : 0;   // columns per chroma sample, log2
     constexpr int ROWS = PAIR ? 2 : 1;
     constexpr int NC = SEMI ? 8 : 8 >> SH;                                   // samples of a chroma run
-    const int nbx = (W + 7) >> 3;
-    const int nby = PAIR ? (H + 1) >> 1 : H;
-    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (id >= (long long)nbx * nby) return;
-    const int by = (int)(id / nbx), x0 = (int)(id - (long long)by * nbx) * 8;
+    int by, x0, n;                                         // n: pixels of this thread's run
+    if (!run_of(W, PAIR ? (H + 1) >> 1 : H, by, x0, n)) return;
     const int y0 = PAIR ? 2 * by : by;
-    const int n = min(8, W - x0);                          // pixels of this thread's run
     const int rows = min(ROWS, H - y0);
 
     uint32_t yw[ROWS][4], uw[NC / 2], vw[NC / 2];
@@ -102,46 +68,31 @@ __global__ __launch_bounds__(256) void deep_to_bgr_kernel(const uint16_t* __rest
 
     uint32_t o[ROWS][6] = {};
     const int yoff = 16 << s, coff = 128 << s;
-    const long long half = 1ll << (NV12_SHIFT - 1 + s);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         int u = 0, v = 0;
         if (CHROMA != FM_YUV_MONO) {
-            const int U = SEMI ? DEEP_WORD(uw, 2 * (i >> 1)) : DEEP_WORD(uw, i >> SH);
-            const int V = SEMI ? DEEP_WORD(uw, 2 * (i >> 1) + 1) : DEEP_WORD(vw, i >> SH);
-            u = (int)(((uint32_t)U >> rs) & mask) - coff;
-            v = (int)(((uint32_t)V >> rs) & mask) - coff;
+            const uint32_t U = SEMI ? run_word16(uw, 2 * (i >> 1)) : run_word16(uw, i >> SH);
+            const uint32_t V = SEMI ? run_word16(uw, 2 * (i >> 1) + 1) : run_word16(vw, i >> SH);
+            u = (int)((U >> rs) & mask) - coff;
+            v = (int)((V >> rs) & mask) - coff;
         }
-        const long long cb = half + (long long)c.cub * u, cg = half + (long long)c.cvg * v + (long long)c.cug * u,
-                        cr = half + (long long)c.cvr * v;
+        long long cb, cg, cr;
+        ycc_chroma(c, u, v, s, cb, cg, cr);
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
-            const int Y = (int)(((uint32_t)DEEP_WORD(yw[r], i) >> rs) & mask);
-            const long long y = (long long)max(Y - yoff, 0) * c.cy;
-            const uint32_t px[3] = {sat8((int)((y + cb) >> s)), sat8((int)((y + cg) >> s)), sat8((int)((y + cr) >> s))};
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const int k = 3 * i + ch;                  // byte of the 24-byte row segment
-                o[r][k >> 2] |= px[ch] << ((k & 3) * 8);
-            }
+            uint32_t b, g, d;
+            ycc_px(c, (int)((run_word16(yw[r], i) >> rs) & mask), yoff, s, cb, cg, cr, b, g, d);
+            put_px(o[r], i, b, g, d);
         }
     }
 
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
         if (r >= rows) break;
-        uint8_t* const out = bgr + ((size_t)(y0 + r) * W + x0) * 3;
-        if (ST8) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) reinterpret_cast<uint2*>(out)[q] = make_uint2(o[r][2 * q], o[r][2 * q + 1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 24; ++k)
-                if (k < 3 * n) out[k] = (uint8_t)(o[r][k >> 2] >> ((k & 3) * 8));
-        }
+        store_run<ST8 ? StoreRule::ALIGNED8 : StoreRule::BYTES>(bgr + ((size_t)(y0 + r) * W + x0) * 3, n, o[r]);
     }
 }
-#undef DEEP_WORD
 
 struct DeepArgs {
     const uint16_t *y, *u, *v;

@@ -4,7 +4,7 @@
 // slot k, into a ring entry.  Each protocol is written once (into_current, into_ahead, into_ring below) and takes the
 // family's part as a callable.  A family brings its argument check (*_ok) and its enqueue_* function: the copies into its
 // staging and the kernels that write the BGR frame (nv12.hip, jpeg.hip, resize.hip, remap.hip, yuv.hip, packed.hip,
-// bayer.hip, deep.hip, devsrc.hip).  Its three extern "C" entry points are that check and the protocol.
+// hwc.hip, bayer.hip, deep.hip, devsrc.hip; bgr_run.h is what they share).  Its three extern "C" entry points are that check and the protocol.
 // Host code only: no kernel lives here.
 #include "pixel_source.h"
 #include "remap_pixel.h"

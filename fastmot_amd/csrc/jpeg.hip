@@ -20,14 +20,16 @@
 //                         the next block's, which spreads the four blocks of a 32-lane ds_read_b32 group over all banks.
 //   jpeg_to_bgr_kernel    sample planes -> BGR.  One thread owns 8 pixels of one row: 8 Y bytes, the chroma samples under
 //                         them with one neighbour on either side (and the nearer chroma row above / below for 4:2:0), the
-//                         triangle filter, the colour conversion, 24 BGR bytes out as three 8-byte stores (frames whose
-//                         width is a multiple of 8; 4-byte stores for multiples of 4, bytes otherwise).
+//                         triangle filter, the colour conversion, 24 BGR bytes out (bgr_run.h): three 8-byte stores for
+//                         frames whose width is a multiple of 8, 4-byte stores for multiples of 4, bytes otherwise.
 // The one-launch form (a workgroup's chroma blocks plus a recomputed halo kept in LDS) would save the sample planes'
 // round trip, 1.5 bytes per pixel written and read again out of L2.  The two launches together measure 17 us for a
 // 1080p 4:2:0 frame, 13 % of the copy they follow (profiles/jpeg_ingest.txt), so the simpler form was kept.
 //
 // No load or store address depends on a coefficient's value, so no coefficient values can make the kernels fault.
 #include "common.h"
+#include "bgr_run.h"
+#include "yuv_coef.h"      // clamp8
 
 namespace {
 
@@ -68,7 +70,7 @@ __device__ __forceinline__ void idct_1d(int (&v)[8]) {
 
 // clamp(((x + 2^17) >> 18) + 128, 0, 255), written as a clamp followed by the shift (the same value for every x that
 // does not overflow): in the order shift - clamp - pack this compiler forms v_ashr_pk_u8_i32 and mishandles the
-// destination's upper half (see nv12.hip).
+// destination's upper half (see yuv_coef.h sat8).
 __device__ __forceinline__ uint32_t descale_sample(int x) {
     constexpr int S = 18;
     return (uint32_t)min(max(x + (1 << (S - 1)) + (128 << S), 0), (256 << S) - 1) >> S;
@@ -120,21 +122,20 @@ __global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_kernel(const int16_t* 
         idct_1d(v);
         uint32_t o[2] = {0, 0};
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k >> 2] |= descale_sample(v[k]) << ((k & 3) * 8);
+        for (int k = 0; k < 8; ++k) put_byte(o, k, descale_sample(v[k]));
         const long long brow = (int)local / bw, bcol = local - brow * bw;
         uint8_t* const out = samples + plane + ((brow * 8 + j) * bw + bcol) * 8;
         *reinterpret_cast<uint2*>(out) = make_uint2(o[0], o[1]);
     }
 }
 
-__device__ __forceinline__ uint32_t sat8(int v) { return (uint32_t)min(max(v, 0), 255); }
-
 // The 8 chroma values under pixels x0 .. x0 + 7 of row y, from one chroma plane.
 __device__ __forceinline__ void chroma8(const uint8_t* __restrict__ plane, const JpegGeo& g, int pitch, int x0, int y, int (&out)[8]) {
     if (g.hs == 1) {
         const uint2 a = *reinterpret_cast<const uint2*>(plane + (size_t)y * pitch + x0);
+        const uint32_t w[2] = {a.x, a.y};
 #pragma unroll
-        for (int i = 0; i < 8; ++i) out[i] = (int)(((i < 4 ? a.x : a.y) >> ((i & 3) * 8)) & 0xffu);
+        for (int i = 0; i < 8; ++i) out[i] = (int)run_byte(w, i);
         return;
     }
     const bool v2 = g.vs == 2, tri2 = v2 && g.fancy;
@@ -164,17 +165,16 @@ __device__ __forceinline__ void chroma8(const uint8_t* __restrict__ plane, const
     }
 }
 
-// ALIGN: what the frame's rows allow -- 8: width % 8 == 0 and an 8-byte aligned frame, three 8-byte stores; 4: width % 4
-// == 0, 4-byte stores; 1: bytes.  Pixels past the row's end are computed from the planes' padding and not stored.
+// ALIGN: what the frame's rows allow -- 8: width % 8 == 0 and an 8-byte aligned frame, StoreRule::ALIGNED8; 4: width % 4
+// == 0, 4-byte stores; 1: StoreRule::BYTES.  Pixels past the row's end are computed from the planes' padding and not stored.
 template <int ALIGN>
 __global__ __launch_bounds__(256) void jpeg_to_bgr_kernel(const uint8_t* __restrict__ samples, uint8_t* __restrict__ bgr, JpegGeo g) {
-    const int nbx = (g.W + 7) >> 3;
-    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (id >= (long long)nbx * g.H) return;
-    const int y = (int)(id / nbx), x0 = (int)(id - (long long)y * nbx) * 8;
+    int y, x0, n;
+    if (!run_of(g.W, g.H, y, x0, n)) return;
     const int pitch0 = g.bw0 * 8, pitch1 = g.bw1 * 8;
 
     const uint2 yy = *reinterpret_cast<const uint2*>(samples + (size_t)y * pitch0 + x0);
+    const uint32_t yw[2] = {yy.x, yy.y};
     int cb[8], cr[8];
     if (g.ncomp == 3) {
         chroma8(samples + g.off1, g, pitch1, x0, y, cb);
@@ -187,29 +187,19 @@ __global__ __launch_bounds__(256) void jpeg_to_bgr_kernel(const uint8_t* __restr
     uint32_t o[6] = {};
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int Y = (int)(((i < 4 ? yy.x : yy.y) >> ((i & 3) * 8)) & 0xffu);
+        const int Y = (int)run_byte(yw, i);
         const int b = cb[i] - 128, r = cr[i] - 128;
-        const uint32_t px[3] = {sat8(Y + ((116130 * b + 32768) >> 16)), sat8(Y + ((-22554 * b - 46802 * r + 32768) >> 16)),
-                                sat8(Y + ((91881 * r + 32768) >> 16))};
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const int k = 3 * i + ch;
-            o[k >> 2] |= px[ch] << ((k & 3) * 8);
-        }
+        put_px(o, i, clamp8(Y + ((116130 * b + 32768) >> 16)), clamp8(Y + ((-22554 * b - 46802 * r + 32768) >> 16)),
+               clamp8(Y + ((91881 * r + 32768) >> 16)));
     }
 
     uint8_t* const out = bgr + ((size_t)y * g.W + x0) * 3;
-    if (ALIGN == 8) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) reinterpret_cast<uint2*>(out)[q] = make_uint2(o[2 * q], o[2 * q + 1]);
-    } else if (ALIGN == 4) {
+    if (ALIGN == 4) {                                      // (a run of 4 pixels is whole words: W % 4 == 0)
 #pragma unroll
         for (int q = 0; q < 6; ++q)
             if (x0 + (4 * q + 3) / 3 < g.W) reinterpret_cast<uint32_t*>(out)[q] = o[q];
     } else {
-#pragma unroll
-        for (int k = 0; k < 24; ++k)
-            if (x0 + k / 3 < g.W) out[k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
+        store_run<ALIGN == 8 ? StoreRule::ALIGNED8 : StoreRule::BYTES>(out, n, o);
     }
 }
 

@@ -11,102 +11,67 @@
 // 32 bits: 239 * 1220945 + 127 * 2215014 + h < 2^31.
 //
 // One thread owns 8 pixels x 2 rows: 2 x 8 Y bytes and 8 UV bytes in, 2 x 24 BGR bytes out.  Threads are numbered along
-// a row first, so a wavefront reads 512 contiguous Y bytes per row and writes 1536 contiguous BGR bytes per row (three
-// 8-byte stores per thread, 24 bytes apart: the three together fill every cache line they touch).  A streaming
-// kernel at 4.5 bytes per pixel: no LDS, no reuse beyond the chroma pair a thread holds in registers.
+// a row first, so a wavefront reads 512 contiguous Y bytes per row and writes 1536 contiguous BGR bytes per row.  The one
+// kernel serves the staged frame (both pitches W) and a decoder's surface in device memory (devsrc.hip: a pitch per
+// plane, planes that begin anywhere), so nothing but the address itself is known about a run: loads and stores are
+// chosen per thread by bgr_run.h's rules (load_run, StoreRule::BY_ADDRESS) -- for a frame whose width is a multiple
+// of 8, staged and written at 8-byte aligned addresses, every thread takes the 8-byte ones.  A streaming kernel at 4.5
+// bytes per pixel: no LDS, no reuse beyond the chroma pair a thread holds in registers.
 #include "common.h"
-#include "yuv_coef.h"      // Nv12Coef, NV12_COEF, NV12_SHIFT, sat8 (shared with yuv.hip)
+#include "bgr_run.h"
+#include "yuv_coef.h"
 
 namespace {
 
-// VEC: W % 8 == 0 -- every access is an aligned 8-byte load / store.  Otherwise bytes, with the row's end checked per
-// pixel pair (W is even, so a chroma pair is never split).
-template <bool VEC>
-__global__ __launch_bounds__(256) void nv12_to_bgr_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp,
-                                                          uint8_t* __restrict__ bgr, int W, int H, Nv12Coef c) {
-    const int nbx = (W + 7) >> 3;
-    const int id = blockIdx.x * 256 + threadIdx.x;
-    if (id >= nbx * (H >> 1)) return;
-    const int by = id / nbx, bx = id - by * nbx;
-    const int x0 = bx * 8;
-    const size_t row0 = (size_t)(2 * by) * W + x0;          // first Y byte of the block; the BGR block starts at 3 * row0
-    const uint8_t* const uvrow = uvp + (size_t)by * W + x0;
-
-    uint32_t yw[2][2] = {}, uvw[2] = {};                    // bytes i of the block: word i >> 2, bits 8 * (i & 3)
-    if (VEC) {
-        const uint2 a = *reinterpret_cast<const uint2*>(yp + row0);
-        const uint2 b = *reinterpret_cast<const uint2*>(yp + row0 + W);
-        const uint2 q = *reinterpret_cast<const uint2*>(uvrow);
-        yw[0][0] = a.x, yw[0][1] = a.y, yw[1][0] = b.x, yw[1][1] = b.y, uvw[0] = q.x, uvw[1] = q.y;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (x0 + i < W) {
-                const int sh = (i & 3) * 8;
-                yw[0][i >> 2] |= (uint32_t)yp[row0 + i] << sh;
-                yw[1][i >> 2] |= (uint32_t)yp[row0 + W + i] << sh;
-                uvw[i >> 2] |= (uint32_t)uvrow[i] << sh;
-            }
-    }
-#define NV12_BYTE(w, i) ((int)(((w)[(i) >> 2] >> (((i) & 3) * 8)) & 0xffu))
+// yp: H rows of W luma bytes, sy apart; uvp: H / 2 rows of W interleaved U, V bytes, suv apart; W and H even (so a chroma
+// pair is never split).
+__global__ __launch_bounds__(256) void nv12_to_bgr_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, long long sy,
+                                                          long long suv, uint8_t* __restrict__ bgr, int W, int H, Nv12Coef c) {
+    int by, x0, n;
+    if (!run_of(W, H >> 1, by, x0, n)) return;
+    uint32_t yw[2][2], uvw[2];
+    const uint8_t* const y0 = yp + (long long)(2 * by) * sy + x0;
+    load_run<2>(y0, n, n == 8, yw[0]);
+    load_run<2>(y0 + sy, n, n == 8, yw[1]);
+    load_run<2>(uvp + (long long)by * suv + x0, n, n == 8, uvw);
 
     uint32_t o[2][6] = {};
-    constexpr int half = 1 << (NV12_SHIFT - 1);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {                           // chroma pair p: pixels 2p, 2p + 1 of both rows
-        const int u = NV12_BYTE(uvw, 2 * p) - 128, v = NV12_BYTE(uvw, 2 * p + 1) - 128;
-        const int cb = half + c.cub * u, cg = half + c.cvg * v + c.cug * u, cr = half + c.cvr * v;
+        int cb, cg, cr;
+        ycc_chroma(c, (int)run_byte(uvw, 2 * p) - 128, (int)run_byte(uvw, 2 * p + 1) - 128, cb, cg, cr);
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int i = 2 * p + j;
-                const int y = max(NV12_BYTE(yw[r], i) - 16, 0) * c.cy;
-                const uint32_t px[3] = {sat8(y + cb), sat8(y + cg), sat8(y + cr)};
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const int k = 3 * i + ch;               // byte of the 24-byte row segment
-                    o[r][k >> 2] |= px[ch] << ((k & 3) * 8);
-                }
+                uint32_t b, g, d;
+                ycc_px(c, (int)run_byte(yw[r], i), 16, cb, cg, cr, b, g, d);
+                put_px(o[r], i, b, g, d);
             }
     }
-
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        uint8_t* const out = bgr + 3 * (row0 + (size_t)r * W);
-        if (VEC) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) reinterpret_cast<uint2*>(out)[q] = make_uint2(o[r][2 * q], o[r][2 * q + 1]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (x0 + i < W) {
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) {
-                        const int k = 3 * i + ch;
-                        out[k] = (uint8_t)(o[r][k >> 2] >> ((k & 3) * 8));
-                    }
-                }
-        }
-    }
+    for (int r = 0; r < 2; ++r) store_run<StoreRule::BY_ADDRESS>(bgr + ((size_t)(2 * by + r) * W + x0) * 3, n, o[r]);
 }
-#undef NV12_BYTE
 
 }  // namespace
 
-// Converts the packed NV12 frame at `nv12` (Y: w * h bytes, then UV: w * h / 2 bytes) to w * h * 3 BGR bytes at `bgr`,
-// on stream `s`.  w and h even, matrix FM_NV12_BT601 / FM_NV12_BT709 (the callers have checked); `nv12` and `bgr`
-// 8-byte aligned (hipMalloc'ed buffers and whole frames of the ring are).
-int fm_nv12_to_bgr(const uint8_t* nv12, uint8_t* bgr, int w, int h, int matrix, hipStream_t s) {
-    FM_CHECK_ARG(nv12 && bgr && w > 0 && h > 0 && !(w & 1) && !(h & 1) && (matrix == FM_NV12_BT601 || matrix == FM_NV12_BT709));
+// Converts the NV12 frame whose Y rows lie `sy` bytes apart from `y` and whose UV rows `suv` bytes apart from `uv` (device
+// memory, any alignment) to w * h * 3 BGR bytes at `bgr`, on stream `s`.  w and h even, matrix FM_NV12_BT601 / FM_NV12_BT709.
+int fm_nv12_planes_to_bgr(const uint8_t* y, const uint8_t* uv, long long sy, long long suv, uint8_t* bgr, int w, int h, int matrix,
+                          hipStream_t s) {
+    FM_CHECK_ARG(y && uv && bgr && w > 0 && h > 0 && !(w & 1) && !(h & 1) && (matrix == FM_NV12_BT601 || matrix == FM_NV12_BT709));
     const long long blocks = (long long)((w + 7) >> 3) * (h >> 1);
     FM_CHECK_ARG(blocks < (1ll << 31) - 256);
-    const uint8_t* const uv = nv12 + (size_t)w * h;
     const dim3 grid((unsigned)((blocks + 255) / 256));
-    if (w % 8 == 0)
-        hipLaunchKernelGGL(nv12_to_bgr_kernel<true>, grid, dim3(256), 0, s, nv12, uv, bgr, w, h, NV12_COEF[matrix]);
-    else
-        hipLaunchKernelGGL(nv12_to_bgr_kernel<false>, grid, dim3(256), 0, s, nv12, uv, bgr, w, h, NV12_COEF[matrix]);
+    hipLaunchKernelGGL(nv12_to_bgr_kernel, grid, dim3(256), 0, s, y, uv, sy, suv, bgr, w, h, NV12_COEF[matrix]);
     FM_HIP(hipGetLastError());
     return 0;
+}
+
+// Converts the packed NV12 frame at `nv12` (Y: w * h bytes, then UV: w * h / 2 bytes) to w * h * 3 BGR bytes at `bgr`,
+// on stream `s`.  w and h even, matrix FM_NV12_BT601 / FM_NV12_BT709 (the callers have checked).
+int fm_nv12_to_bgr(const uint8_t* nv12, uint8_t* bgr, int w, int h, int matrix, hipStream_t s) {
+    FM_CHECK_ARG(nv12 && w > 0 && h > 0);
+    return fm_nv12_planes_to_bgr(nv12, nv12 + (size_t)w * h, w, w, bgr, w, h, matrix, s);
 }

@@ -15,22 +15,21 @@
 // holds.  The 8-byte load at the source's last pixel reaches 5 bytes past it: FM_FRAME_SLACK, as for the resize.  A
 // streaming kernel: no LDS; no address depends on a pixel's value.
 #include "common.h"
+#include "bgr_run.h"
 #include "pixel_source.h"
 #include "remap_pixel.h"
 
 namespace {
 
-// VEC: dw % 8 == 0, an 8-byte aligned destination and a 16-byte aligned map -- 16-byte map loads and three aligned 8-byte
-// stores.  Otherwise 8-byte map loads and bytes out, with the row's end checked (a pixel past the end is computed from
+// VEC: dw % 8 == 0, an 8-byte aligned destination and a 16-byte aligned map -- 16-byte map loads and
+// StoreRule::ALIGNED8.  Otherwise 8-byte map loads and StoreRule::BYTES (a pixel past the row's end is computed from
 // the row's last entry and not stored).
 template <bool VEC>
 __global__ __launch_bounds__(256) void remap_bgr_kernel(const uint8_t* __restrict__ src, int sw, int sh,
                                                         const int32_t* __restrict__ xy, uint8_t* __restrict__ dst, int dw,
                                                         int dh, uint32_t border) {
-    const int nbx = (dw + 7) >> 3;
-    const int id = blockIdx.x * 256 + threadIdx.x;
-    if (id >= nbx * dh) return;
-    const int y = id / nbx, x0 = (id - y * nbx) * 8;
+    int y, x0, n;
+    if (!run_of(dw, dh, y, x0, n)) return;
 
     int32_t m[16];
     if (VEC) {
@@ -62,22 +61,9 @@ __global__ __launch_bounds__(256) void remap_bgr_kernel(const uint8_t* __restric
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const uint32_t px = fm_remap_blend(q0[i], q1[i], t[i], border);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int k = 3 * i + c;                    // byte of the 24-byte row segment
-            o[k >> 2] |= ((px >> (8 * c)) & 255u) << ((k & 3) * 8);
-        }
+        put_px(o, i, px & 255u, (px >> 8) & 255u, (px >> 16) & 255u);
     }
-
-    uint8_t* const out = dst + ((size_t)y * dw + x0) * 3;
-    if (VEC) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) reinterpret_cast<uint2*>(out)[q] = make_uint2(o[2 * q], o[2 * q + 1]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 24; ++k)
-            if (x0 + k / 3 < dw) out[k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
-    }
+    store_run<VEC ? StoreRule::ALIGNED8 : StoreRule::BYTES>(dst + ((size_t)y * dw + x0) * 3, n, o);
 }
 
 }  // namespace

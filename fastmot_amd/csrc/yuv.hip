@@ -3,15 +3,15 @@
 // Planar I420 is what software decoders hand out and what a YUV4MPEG2 (.y4m) file holds: a Y plane W x H, then a U and a
 // V plane of ceil(W / 2) x ceil(H / 2) (4:2:0), ceil(W / 2) x H (4:2:2) or W x H (4:4:4) samples, or no chroma at all.
 //
-// In: nv12.hip's arithmetic per pixel (yuv_coef.h; fastmot_amd/utils/yuv.py states both directions in numpy, tests compare
-// bit for bit), pixel (r, c) using chroma sample (r >> sv, c >> sh).  One thread owns 8 pixels of a row and, for 4:2:0,
+// In: yuv_coef.h's limited-range arithmetic per pixel (fastmot_amd/utils/yuv.py states both directions in numpy, tests
+// compare bit for bit), pixel (r, c) using chroma sample (r >> sv, c >> sh).  One thread owns 8 pixels of a row and, for 4:2:0,
 // the same 8 columns of the row below it, so every chroma sample is loaded once: 8 (16) Y bytes and 2 x 4 (2 x 8 for
 // 4:4:4) chroma bytes in, 24 (48) BGR bytes out.  Threads are numbered along a row first: a wavefront reads 512 contiguous
-// Y bytes per row and writes 1536 contiguous BGR bytes per row.  A load is one 8-byte (4-byte for four chroma samples)
-// access when the thread's run is whole and its address aligned, bytes otherwise -- decided per thread from the address,
-// so odd widths, odd pitches and planes that begin at odd offsets (the U plane of an odd-sized frame) cost only the
-// threads they touch.  Stores: three 8-byte stores per row when W % 8 == 0 and the frame is 8-byte aligned
-// (jpeg_to_bgr_kernel's rule), bytes otherwise.
+// Y bytes per row and writes 1536 contiguous BGR bytes per row.  Loads are bgr_run.h's load_run: one 8-byte (4-byte for four
+// chroma samples) access when the thread's run is whole and its address aligned, narrower ones otherwise -- decided per
+// thread from the address, so odd widths, odd pitches and planes that begin at odd offsets (the U plane of an odd-sized
+// frame) cost only the threads they touch.  Stores: StoreRule::ALIGNED8 when W % 8 == 0 and the frame is 8-byte
+// aligned, StoreRule::BYTES otherwise.
 //
 // Out: BGR -> I420 with the 8-bit BT.601 integer form of utils.nv12.bgr_to_nv12,
 //     Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16, U = ((-38 R - 74 G + 112 B + 128) >> 8) + 128,
@@ -21,33 +21,12 @@
 //
 // Both are streaming kernels (4.5 bytes per pixel for 4:2:0): no LDS, no reuse beyond what a thread holds in registers.
 #include "common.h"
+#include "bgr_run.h"
 #include "yuv_coef.h"
 
 const uint8_t* fm_overlay_buffer(fm_ctx* ctx);            // overlay.hip: the overlay picture of the current frame size, or null
 
 namespace {
-
-#define YUV_BYTE(w, i) ((int)(((w)[(i) >> 2] >> (((i) & 3) * 8)) & 0xffu))
-
-// the n <= 8 (FOUR: <= 4) bytes of a run at p into w (byte i: word i >> 2, bits 8 * (i & 3)): one load when the run is whole
-// and p aligned to it, bytes otherwise
-template <bool FOUR>
-__device__ __forceinline__ void load_run(const uint8_t* __restrict__ p, int n, uint32_t (&w)[2]) {
-    w[0] = w[1] = 0;
-    constexpr int FULL = FOUR ? 4 : 8;
-    if (n == FULL && !((uintptr_t)p & (FULL - 1))) {
-        if (FOUR) {
-            w[0] = *reinterpret_cast<const uint32_t*>(p);
-        } else {
-            const uint2 a = *reinterpret_cast<const uint2*>(p);
-            w[0] = a.x, w[1] = a.y;
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < FULL; ++i)
-        if (i < n) w[i >> 2] |= (uint32_t)p[i] << ((i & 3) * 8);
-}
 
 // CHROMA: FM_YUV_*.  ST8: W % 8 == 0 and an 8-byte aligned frame -- every thread's run is whole and its stores aligned.
 template <int CHROMA, bool ST8>
@@ -57,70 +36,53 @@ __global__ __launch_bounds__(256) void planar_to_bgr_kernel(const uint8_t* __res
     constexpr bool PAIR = CHROMA == FM_YUV_420;                              // two rows share a chroma row
     constexpr int SH = (CHROMA == FM_YUV_420 || CHROMA == FM_YUV_422) ? 1 : 0;   // columns per chroma sample, log2
     constexpr int ROWS = PAIR ? 2 : 1;
-    const int nbx = (W + 7) >> 3;
-    const int nby = PAIR ? (H + 1) >> 1 : H;
-    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (id >= (long long)nbx * nby) return;
-    const int by = (int)(id / nbx), x0 = (int)(id - (long long)by * nbx) * 8;
+    constexpr int NCW = 2 >> SH;                                             // words of a chroma run: 8 or 4 samples
+    int by, x0, n;                                         // n: pixels of this thread's run
+    if (!run_of(W, PAIR ? (H + 1) >> 1 : H, by, x0, n)) return;
     const int y0 = PAIR ? 2 * by : by;
-    const int n = min(8, W - x0);                          // pixels of this thread's run
     const int rows = min(ROWS, H - y0);
 
-    uint32_t yw[ROWS][2], uw[2] = {0, 0}, vw[2] = {0, 0};
+    uint32_t yw[ROWS][2], uw[NCW] = {}, vw[NCW] = {};
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
         yw[r][0] = yw[r][1] = 0;
-        if (r < rows) load_run<false>(yp + (size_t)(y0 + r) * pitch_y + x0, n, yw[r]);
+        if (r < rows) load_run<2>(yp + (size_t)(y0 + r) * pitch_y + x0, n, n == 8, yw[r]);
     }
     if (CHROMA != FM_YUV_MONO) {
         const size_t at = (size_t)by * pitch_c + (x0 >> SH);
         const int nc = (n + SH) >> SH;                     // chroma samples under the run
-        load_run<SH == 1>(up + at, nc, uw);
-        load_run<SH == 1>(vp + at, nc, vw);
+        load_run<NCW>(up + at, nc, nc == 4 * NCW, uw);
+        load_run<NCW>(vp + at, nc, nc == 4 * NCW, vw);
     }
 
     uint32_t o[ROWS][6] = {};
-    constexpr int half = 1 << (NV12_SHIFT - 1);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int u = CHROMA == FM_YUV_MONO ? 0 : YUV_BYTE(uw, i >> SH) - 128;
-        const int v = CHROMA == FM_YUV_MONO ? 0 : YUV_BYTE(vw, i >> SH) - 128;
-        const int cb = half + c.cub * u, cg = half + c.cvg * v + c.cug * u, cr = half + c.cvr * v;
+        const int u = CHROMA == FM_YUV_MONO ? 0 : (int)run_byte(uw, i >> SH) - 128;
+        const int v = CHROMA == FM_YUV_MONO ? 0 : (int)run_byte(vw, i >> SH) - 128;
+        int cb, cg, cr;
+        ycc_chroma(c, u, v, cb, cg, cr);
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
-            const int y = max(YUV_BYTE(yw[r], i) - 16, 0) * c.cy;
-            const uint32_t px[3] = {sat8(y + cb), sat8(y + cg), sat8(y + cr)};
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const int k = 3 * i + ch;                  // byte of the 24-byte row segment
-                o[r][k >> 2] |= px[ch] << ((k & 3) * 8);
-            }
+            uint32_t b, g, d;
+            ycc_px(c, (int)run_byte(yw[r], i), 16, cb, cg, cr, b, g, d);
+            put_px(o[r], i, b, g, d);
         }
     }
 
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
         if (r >= rows) break;
-        uint8_t* const out = bgr + ((size_t)(y0 + r) * W + x0) * 3;
-        if (ST8) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) reinterpret_cast<uint2*>(out)[q] = make_uint2(o[r][2 * q], o[r][2 * q + 1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 24; ++k)
-                if (k < 3 * n) out[k] = (uint8_t)(o[r][k >> 2] >> ((k & 3) * 8));
-        }
+        store_run<ST8 ? StoreRule::ALIGNED8 : StoreRule::BYTES>(bgr + ((size_t)(y0 + r) * W + x0) * 3, n, o[r]);
     }
 }
 
 __global__ __launch_bounds__(256) void bgr_to_i420_kernel(const uint8_t* __restrict__ bgr, long long pitch, uint8_t* __restrict__ yo,
                                                           uint8_t* __restrict__ uo, uint8_t* __restrict__ vo, int W, int H) {
-    const int nbx = (W + 7) >> 3, nby = (H + 1) >> 1, CW = (W + 1) >> 1;
-    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (id >= (long long)nbx * nby) return;
-    const int by = (int)(id / nbx), x0 = (int)(id - (long long)by * nbx) * 8;
+    const int CW = (W + 1) >> 1;
+    int by, x0, n;
+    if (!run_of(W, (H + 1) >> 1, by, x0, n)) return;
     const int y0 = 2 * by;
-    const int n = min(8, W - x0);
 
     int us[4] = {0, 0, 0, 0}, vs[4] = {0, 0, 0, 0};
     uint32_t yw[2][2] = {};
@@ -137,13 +99,13 @@ __global__ __launch_bounds__(256) void bgr_to_i420_kernel(const uint8_t* __restr
         } else {
 #pragma unroll
             for (int k = 0; k < 24; ++k)                   // (a column right of the last: that column again)
-                w[k >> 2] |= (uint32_t)row[min(k / 3, n - 1) * 3 + k % 3] << ((k & 3) * 8);
+                put_byte(w, k, row[min(k / 3, n - 1) * 3 + k % 3]);
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const int B = YUV_BYTE(w, 3 * i), G = YUV_BYTE(w, 3 * i + 1), R = YUV_BYTE(w, 3 * i + 2);
+            const int B = (int)run_byte(w, 3 * i), G = (int)run_byte(w, 3 * i + 1), R = (int)run_byte(w, 3 * i + 2);
             const uint32_t Y = (uint32_t)(((66 * R + 129 * G + 25 * B + 128) >> 8) + 16);
-            yw[r][i >> 2] |= Y << ((i & 3) * 8);
+            put_byte(yw[r], i, Y);
             us[i >> 1] += ((-38 * R - 74 * G + 112 * B + 128) >> 8) + 128;
             vs[i >> 1] += ((112 * R - 94 * G - 18 * B + 128) >> 8) + 128;
         }
@@ -178,7 +140,6 @@ __global__ __launch_bounds__(256) void bgr_to_i420_kernel(const uint8_t* __restr
             if (p < nc) uo[at + p] = (uint8_t)(u4 >> (p * 8)), vo[at + p] = (uint8_t)(v4 >> (p * 8));
     }
 }
-#undef YUV_BYTE
 
 template <int CHROMA>
 void launch_planar(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* bgr, int w, int h, int py, int pc, const Nv12Coef& c,

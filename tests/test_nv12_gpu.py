@@ -130,6 +130,44 @@ def test_every_ingest_path(ctx, size):
         assert np.array_equal(ctx.frame_read(), want), i
 
 
+@pytest.mark.parametrize('size', [(2, 2), (6, 2), (8, 2), (10, 4), (24, 2)], ids=lambda s: f'{s[0]}x{s[1]}')
+def test_staged_frames_at_every_ring_address(ctx, size):
+    """One kernel converts staged frames and device surfaces, choosing its loads and stores by address.  A ring of three
+    frames lies w * h * 3 bytes apart in one allocation: 6x2 puts frame 1 at byte 36 (4-byte aligned only) with runs of six
+    pixels, which store bytes; 10x4 (120 bytes a frame) has rows 30 bytes apart, so its whole runs begin 8-byte aligned,
+    2 mod 4 and 4-byte aligned in turn and take all three store branches; 8x2 and 24x2 take the 8-byte stores throughout.
+    Each destination holds a sentinel first; the converter writes its frame, w * h * 3 bytes, and leaves the ring frames
+    on either side of it as they were."""
+    w, h = size
+    rng = np.random.default_rng(w * 16 + h)
+    ring = 3
+    configure(ctx, w, h, ring)
+    sentinel = np.full((h, w, 3), 0xA5, np.uint8)
+    for index in range(ring):
+        for i in range(ring):
+            ctx.frame_ring_store(i, sentinel)
+        f = pitched(rng, w, h, (w, w + 2)[index & 1], ('bt601', 'bt709')[index & 1])
+        ctx.frame_ring_store(index, f)
+        for i in range(ring):
+            ctx.frame_ring_select(i)
+            assert np.array_equal(ctx.frame_read(), ref_of(f) if i == index else sentinel), (index, i)
+    in_ring = ref_of(f)
+    for matrix in ('bt601', 'bt709'):
+        f = pitched(rng, w, h, w, matrix)
+        ctx.frame_upload(sentinel)
+        ctx.frame_upload(f)
+        assert np.array_equal(ctx.frame_read(), ref_of(f)), (matrix, 'upload')
+        g = pitched(rng, w, h, w + 2, matrix)
+        ctx.frame_upload_ahead(1, sentinel)
+        ctx.frame_upload_ahead(1, g)
+        ctx.frame_promote_next()
+        assert np.array_equal(ctx.frame_read(), ref_of(g)), (matrix, 'ahead')
+    for i in range(ring):                                    # the uploads went to buffers of their own
+        ctx.frame_ring_select(i)
+        assert np.array_equal(ctx.frame_read(), in_ring if i == ring - 1 else sentinel), i
+    configure(ctx, 16, 16)
+
+
 def test_errors(ctx):
     lib = ctx.lib
     w, h = 16, 4

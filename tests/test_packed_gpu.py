@@ -86,6 +86,40 @@ def test_other_entry_points(ctx, size):
             assert np.array_equal(ctx.frame_read(), f.to_bgr()), (fmt, matrix, 'ring', k)
 
 
+@pytest.mark.parametrize('size', [(1, 1), (5, 1), (8, 1), (9, 3), (11, 2)], ids=ids)
+def test_staged_rgb_at_every_ring_address(ctx, size):
+    """One kernel converts staged RGB frames and device tensors, choosing loads and stores by address.  A ring of three
+    frames of w * h * 3 bytes puts frames 1 and 2, and with widths of 5, 9 and 11 the rows inside them, at every residue
+    mod 8; the 3-byte sources' rows lie at the same residues in their staging.  Each destination holds a sentinel first;
+    the converter writes its frame, w * h * 3 bytes, and leaves the ring frames on either side of it as they were."""
+    w, h = size
+    rng = np.random.default_rng(w * 139 + h)
+    ring = 3
+    configure(ctx, w, h, ring)
+    sentinel = np.full((h, w, 3), 0xA5, np.uint8)
+    for fmt in ('rgb', 'bgr', 'rgbx', 'xbgr'):
+        for index in range(ring):
+            for i in range(ring):
+                ctx.frame_ring_store(i, sentinel)
+            f = make(ctx, rng, w, h, fmt, (0, 3)[index & 1], pinned=bool(index & 2))
+            ctx.frame_ring_store(index, f)
+            for i in range(ring):
+                ctx.frame_ring_select(i)
+                assert np.array_equal(ctx.frame_read(), f.to_bgr() if i == index else sentinel), (fmt, index, i)
+        in_ring = f.to_bgr()
+        a, b = make(ctx, rng, w, h, fmt, 0), make(ctx, rng, w, h, fmt, 5, pinned=True)
+        ctx.frame_upload(sentinel)
+        ctx.frame_upload(a)
+        assert np.array_equal(ctx.frame_read(), a.to_bgr()), (fmt, 'upload')
+        ctx.frame_upload_ahead(1, sentinel)
+        ctx.frame_upload_ahead(1, b)
+        ctx.frame_promote_next()
+        assert np.array_equal(ctx.frame_read(), b.to_bgr()), (fmt, 'ahead')
+        for i in range(ring):                                    # the uploads went to buffers of their own
+            ctx.frame_ring_select(i)
+            assert np.array_equal(ctx.frame_read(), in_ring if i == ring - 1 else sentinel), (fmt, i)
+
+
 @pytest.mark.parametrize('src,dst', [((40, 24), (20, 12)), ((37, 21), (34, 18))], ids=['exact2x', 'linear'])
 def test_source_frame_of_another_size(ctx, src, dst):
     rng = np.random.default_rng(src[0])
