@@ -43,19 +43,15 @@ struct FlowState {
     uint8_t* bg_img = nullptr;
     int prev = 0;                                   // index of the "previous" set
     // targets of the current predict
-    int nT = 0, rect_cap = 0;
-    int32_t* rects = nullptr;                       // [nT][4] inclusive integer rects
+    int nT = 0;
     DevBuf tgt_in, tgt_out, det_in, det_out, lk_in, lk_out, bg_out;
     unsigned long long* eig = nullptr;              // GFTT scratch: local-maximum keys, 1024 slots per tile (eig_cap tiles)
     uint2* tile_stat = nullptr;                     // per tile: maximum bits, key count (eig_cap entries)
     size_t eig_cap = 0;                             // capacity in tiles
-    int32_t* ov_idx = nullptr;                      // overlap lists (earlier rects intersecting rect k)
-    int32_t* ov_off = nullptr;
-    int ov_cap = 0;
-    // what the kernels read: the owned buffers above (staged calls) or the packed upload of fm_flow_prepare
-    const int32_t* v_rects = nullptr;
-    const int32_t* v_ov_idx = nullptr;
-    const int32_t* v_ov_off = nullptr;
+    // views into the packed upload in tgt_in (upload_targets): what the kernels read
+    const int32_t* rects = nullptr;                 // [nT][4] inclusive integer rects
+    const int32_t* ov_idx = nullptr;                // overlap lists (earlier rects intersecting rect k)
+    const int32_t* ov_off = nullptr;
     int32_t* bg_flags = nullptr;                    // FAST score / flags
     // diagnostic LK variants (ctx option "lk_variant"): counters, capture records + per-point header
     int* lk_diag = nullptr;
@@ -74,7 +70,7 @@ void fm_flow_free(FlowState* f) {
     for (int st = 0; st < 2; ++st)
         for (int l = 0; l < MAX_LEVELS; ++l)
             if (f->deriv[st][l]) (void)hipFree(f->deriv[st][l]);
-    for (void* p : {(void*)f->bg_img, (void*)f->rects, (void*)f->eig, (void*)f->tile_stat, (void*)f->ov_idx, (void*)f->ov_off, (void*)f->bg_flags,
+    for (void* p : {(void*)f->bg_img, (void*)f->eig, (void*)f->tile_stat, (void*)f->bg_flags,
                     (void*)f->lk_diag, (void*)f->lk_cap, (void*)f->lk_cap_hdr})
         if (p) (void)hipFree(p);
     for (DevBuf* b : {&f->tgt_in, &f->tgt_out, &f->det_in, &f->det_out, &f->lk_in, &f->lk_out, &f->bg_out})
@@ -145,43 +141,9 @@ __global__ void resize_linear_kernel(const uint8_t* __restrict__ src, int sw, in
     dst[(size_t)y * dw + x] = (uint8_t)min(max(v, 0), 255);
 }
 
-// ---- cv::pyrDown 8UC1: separable [1 4 6 4 1]/16, BORDER_REFLECT_101, (sum + 128) >> 8
-__global__ void pyrdown_kernel(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst,
-                               int dw, int dh) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= dw || y >= dh) return;
-    const int wk[5] = {1, 4, 6, 4, 1};
-    int sum = 0;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const uint8_t* row = src + (size_t)reflect101(2 * y + j - 2, sh) * sw;
-        int rs = 0;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) rs += wk[i] * row[reflect101(2 * x + i - 2, sw)];
-        sum += wk[j] * rs;
-    }
-    dst[(size_t)y * dw + x] = (uint8_t)((sum + 128) >> 8);
-}
-
-// ---- calcSharrDeriv (video/lkpyramid.cpp): int16 (dx, dy), borders mirror row/col 1 and n-2
-__global__ void scharr_kernel(const uint8_t* __restrict__ src, int w, int h, int16_t* __restrict__ d) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= w || y >= h) return;
-    const int y0 = y > 0 ? y - 1 : (h > 1 ? 1 : 0), y2 = y < h - 1 ? y + 1 : (h > 1 ? h - 2 : 0);
-    const int xm = x > 0 ? x - 1 : (w > 1 ? 1 : 0), xp = x < w - 1 ? x + 1 : (w > 1 ? w - 2 : 0);
-    const uint8_t* r0 = src + (size_t)y0 * w;
-    const uint8_t* r1 = src + (size_t)y * w;
-    const uint8_t* r2 = src + (size_t)y2 * w;
-    auto t0 = [&](int c) { return (r0[c] + r2[c]) * 3 + r1[c] * 10; };   // vertical smoothing
-    auto t1 = [&](int c) { return r2[c] - r0[c]; };                       // vertical difference
-    const int dx = t0(xp) - t0(xm);
-    const int dy = (t1(xp) + t1(xm)) * 3 + t1(x) * 10;
-    d[((size_t)y * w + x) * 2] = (int16_t)dx;
-    d[((size_t)y * w + x) * 2 + 1] = (int16_t)dy;
-}
-
-// ---- fused pyramid build (4 launches instead of 13).  Same arithmetic, pixel for pixel, as the stand-alone
-// kernels above (which stay for the general-scale path and the image tests).
+// ---- the pyramid below level 0: a pixel of cv::pyrDown and of calcSharrDeriv, and the kernels that run them
+// (pyr_level_kernel, pyr_tail_kernel: 3 launches for a 1080p frame instead of one pyrDown and one Scharr launch per level)
+// cv::pyrDown 8UC1: separable [1 4 6 4 1]/16, BORDER_REFLECT_101, (sum + 128) >> 8
 __device__ __forceinline__ uint8_t pyrdown_px(const uint8_t* __restrict__ src, int sw, int sh, int x, int y) {
     const int wk[5] = {1, 4, 6, 4, 1};
     int sum = 0;
@@ -196,14 +158,15 @@ __device__ __forceinline__ uint8_t pyrdown_px(const uint8_t* __restrict__ src, i
     return (uint8_t)((sum + 128) >> 8);
 }
 
+// calcSharrDeriv (video/lkpyramid.cpp): int16 (dx, dy), borders mirror row/col 1 and n-2
 __device__ __forceinline__ int scharr_px(const uint8_t* __restrict__ src, int w, int h, int x, int y) {
     const int y0 = y > 0 ? y - 1 : (h > 1 ? 1 : 0), y2 = y < h - 1 ? y + 1 : (h > 1 ? h - 2 : 0);
     const int xm = x > 0 ? x - 1 : (w > 1 ? 1 : 0), xp = x < w - 1 ? x + 1 : (w > 1 ? w - 2 : 0);
     const uint8_t* r0 = src + (size_t)y0 * w;
     const uint8_t* r1 = src + (size_t)y * w;
     const uint8_t* r2 = src + (size_t)y2 * w;
-    auto t0 = [&](int c) { return (r0[c] + r2[c]) * 3 + r1[c] * 10; };
-    auto t1 = [&](int c) { return r2[c] - r0[c]; };
+    auto t0 = [&](int c) { return (r0[c] + r2[c]) * 3 + r1[c] * 10; };   // vertical smoothing
+    auto t1 = [&](int c) { return r2[c] - r0[c]; };                       // vertical difference
     const int dx = t0(xp) - t0(xm);
     const int dy = (t1(xp) + t1(xm)) * 3 + t1(x) * 10;
     return (int)(((unsigned)dx & 0xffffu) | ((unsigned)dy << 16));   // int16 pair (dx, dy) as one 32-bit store
@@ -311,44 +274,9 @@ __device__ __forceinline__ bool covered_lds(const int* s_ov, int cnt, int x, int
     return c;
 }
 
-__global__ __launch_bounds__(256) void target_area_kernel(const int32_t* __restrict__ rects, Overlaps ov,
-                                                          int32_t* __restrict__ area) {
-    const int k = blockIdx.x;
-    const int32_t* r = rects + 4 * k;
-    const int w = r[2] - r[0] + 1, h = r[3] - r[1] + 1;
-    const int32_t* list = ov.idx + ov.off[k];
-    const int cnt = ov.off[k + 1] - ov.off[k];
-    int c = 0;
-    if (cnt == 0) {
-        c = threadIdx.x == 0 ? w * h : 0;
-    } else {
-        for (int i = threadIdx.x; i < w * h; i += 256)
-            c += covered_by(rects, list, cnt, r[0] + i % w, r[1] + i / w) ? 0 : 1;
-    }
-    __shared__ int red[256];
-    red[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) area[k] = red[0];
-}
-
-// _rect_filter (flow.py:282-295): rounded point inside rect k and still foreground
-__global__ void kp_filter_kernel(const int32_t* __restrict__ rects, Overlaps ov, const float* __restrict__ kps,
-                                 const int32_t* __restrict__ kp_track, int n, uint8_t* __restrict__ keep) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int k = kp_track[i];
-    const int32_t* r = rects + 4 * k;
-    const int x = (int)rintf(kps[2 * i]), y = (int)rintf(kps[2 * i + 1]);
-    const bool inside = x >= r[0] && x <= r[2] && y >= r[1] && y <= r[3];
-    keep[i] = (inside && !covered_by(rects, ov.idx + ov.off[k], ov.off[k + 1] - ov.off[k], x, y)) ? 1 : 0;
-}
-
-// fused bookkeeping of flow.py:163-169 for one track per block: mask area, _rect_filter of the
-// propagated keypoints, the "too few keypoints" decision and the GFTT minDistance (flow.py:267-271)
+// bookkeeping of flow.py:163-169 for one track per block: mask area, _rect_filter (flow.py:282-295: rounded point
+// inside rect k and still foreground) of the propagated keypoints, the "too few keypoints" decision and the GFTT
+// minDistance (flow.py:267-271)
 // (1024 threads per track: a lone wavefront per SIMD issues one instruction every ~8 cycles; 256 threads took 49 us on the
 // benchmark's crops)
 constexpr int PREP_BLK = 1024;
@@ -1075,54 +1003,172 @@ int flow_stream(fm_ctx* ctx, hipStream_t* out) {
     *out = ctx->s_flow;
     return 0;
 }
+#define FM_FLOW_STREAM(s)                      \
+    hipStream_t s;                             \
+    do {                                       \
+        int rc_s_ = flow_stream(ctx, &s);      \
+        if (rc_s_) return rc_s_;               \
+    } while (0)
 
 int build_pyramid(fm_ctx* ctx, FlowState* f, int set, hipStream_t s) {
-    const int n = ctx->frame_w * ctx->frame_h;
+    fm_trace_mark(ctx, s, 42);
     if (f->W == 2 * f->lw[0] && f->H == 2 * f->lh[0] && (f->W & 1) == 0) {
-        // gray + half-resolution image in one pass over the frame; the large levels as one launch each
-        // (derivatives + next level); the small ones in one workgroup
-        fm_trace_mark(ctx, s, 42);
+        // gray + half-resolution image in one pass over the frame
         hipLaunchKernelGGL(gray_half_kernel, dim3((f->lw[0] + 255) / 256, f->lh[0]), dim3(256), 0, s, ctx->frame_cur,
                            f->W, f->H, f->gray[set], f->pyr[set][0], gray_coeffs(f->cfg.gray_coeff_bits));
-        // the levels of at most ~10 k pixels share one workgroup (1080p: from level 3; 4K: from level 4 -- level 3 of a
-        // 4K frame, 32 k pixels, in the tail made it 53 us long), the larger ones get a launch each
-        int tail = 0;
-        while (tail < f->levels && f->lw[tail] * f->lh[tail] > 10000) ++tail;
-        for (int l = 0; l < tail; ++l) {
-            const bool has_next = l + 1 < f->levels;
-            hipLaunchKernelGGL(pyr_level_kernel, dim3((f->lw[l] + 255) / 256, f->lh[l] + (has_next ? f->lh[l + 1] : 0)),
-                               dim3(256), 0, s, f->pyr[set][l], f->lw[l], f->lh[l],
-                               reinterpret_cast<int*>(f->deriv[set][l]), has_next ? f->pyr[set][l + 1] : nullptr,
-                               has_next ? f->lw[l + 1] : 0, has_next ? f->lh[l + 1] : 0);
-        }
-        if (f->levels > tail) {
-            PyrTail t{};
-            for (int l = 0; l < f->levels; ++l) {
-                t.img[l] = f->pyr[set][l];
-                t.deriv[l] = reinterpret_cast<int*>(f->deriv[set][l]);
-                t.w[l] = f->lw[l];
-                t.h[l] = f->lh[l];
-            }
-            t.first = tail;
-            t.levels = f->levels;
-            hipLaunchKernelGGL(pyr_tail_kernel, dim3(1), dim3(1024), 0, s, t);
-        }
-        FM_HIP(hipGetLastError());
-        fm_trace_mark(ctx, s, 43);
-        return 0;
+    } else {
+        const int n = ctx->frame_w * ctx->frame_h;
+        hipLaunchKernelGGL(gray_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ctx->frame_cur, f->gray[set], n,
+                           gray_coeffs(f->cfg.gray_coeff_bits));
+        hipLaunchKernelGGL(resize_linear_kernel, dim3((f->lw[0] + 255) / 256, f->lh[0]), dim3(256), 0, s,
+                           f->gray[set], f->W, f->H, f->pyr[set][0], f->lw[0], f->lh[0]);
     }
-    hipLaunchKernelGGL(gray_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ctx->frame_cur, f->gray[set], n,
-                       gray_coeffs(f->cfg.gray_coeff_bits));
-    hipLaunchKernelGGL(resize_linear_kernel, dim3((f->lw[0] + 255) / 256, f->lh[0]), dim3(256), 0, s,
-                       f->gray[set], f->W, f->H, f->pyr[set][0], f->lw[0], f->lh[0]);
-    for (int l = 1; l < f->levels; ++l)
-        hipLaunchKernelGGL(pyrdown_kernel, dim3((f->lw[l] + 255) / 256, f->lh[l]), dim3(256), 0, s,
-                           f->pyr[set][l - 1], f->lw[l - 1], f->lh[l - 1], f->pyr[set][l], f->lw[l], f->lh[l]);
-    // Scharr derivatives of this pyramid: consumed when it has become the "previous" one
-    for (int l = 0; l < f->levels; ++l)
-        hipLaunchKernelGGL(scharr_kernel, dim3((f->lw[l] + 255) / 256, f->lh[l]), dim3(256), 0, s, f->pyr[set][l],
-                           f->lw[l], f->lh[l], f->deriv[set][l]);
+    // The large levels as one launch each (Scharr derivatives + next level; the derivatives are consumed when this
+    // pyramid has become the "previous" one), the small ones in one workgroup: the levels of at most ~10 k pixels
+    // (1080p: from level 3; 4K: from level 4 -- level 3 of a 4K frame, 32 k pixels, in the tail made it 53 us long).
+    int tail = 0;
+    while (tail < f->levels && f->lw[tail] * f->lh[tail] > 10000) ++tail;
+    for (int l = 0; l < tail; ++l) {
+        const bool has_next = l + 1 < f->levels;
+        hipLaunchKernelGGL(pyr_level_kernel, dim3((f->lw[l] + 255) / 256, f->lh[l] + (has_next ? f->lh[l + 1] : 0)),
+                           dim3(256), 0, s, f->pyr[set][l], f->lw[l], f->lh[l],
+                           reinterpret_cast<int*>(f->deriv[set][l]), has_next ? f->pyr[set][l + 1] : nullptr,
+                           has_next ? f->lw[l + 1] : 0, has_next ? f->lh[l + 1] : 0);
+    }
+    if (f->levels > tail) {
+        PyrTail t{};
+        for (int l = 0; l < f->levels; ++l) {
+            t.img[l] = f->pyr[set][l];
+            t.deriv[l] = reinterpret_cast<int*>(f->deriv[set][l]);
+            t.w[l] = f->lw[l];
+            t.h[l] = f->lh[l];
+        }
+        t.first = tail;
+        t.levels = f->levels;
+        hipLaunchKernelGGL(pyr_tail_kernel, dim3(1), dim3(1024), 0, s, t);
+    }
     FM_HIP(hipGetLastError());
+    fm_trace_mark(ctx, s, 43);
+    return 0;
+}
+
+// the eig / tile_stat arena holds `tiles` tiles (the caller guarantees an idle stream when it has to grow)
+int ensure_eig(FlowState* f, size_t tiles) {
+    if (tiles <= f->eig_cap) return 0;
+    f->eig_cap = 0;             // (a failing allocation below must not leave a capacity behind null pointers)
+    FM_HIP(hipFree(f->eig));
+    f->eig = nullptr;
+    FM_HIP(hipFree(f->tile_stat));
+    f->tile_stat = nullptr;
+    FM_HIP(hipMalloc(&f->eig, sizeof(unsigned long long) * EIG_TPX * tiles * 2));
+    FM_HIP(hipMalloc(&f->tile_stat, sizeof(uint2) * tiles * 2));
+    f->eig_cap = tiles * 2;
+    return 0;
+}
+
+CropArgs make_crop(const int32_t* r, int k, size_t eig_off) {
+    CropArgs c;
+    c.x0 = r[0]; c.y0 = r[1]; c.w = r[2] - r[0] + 1; c.h = r[3] - r[1] + 1; c.k = k; c.eig_off = eig_off;
+    return c;
+}
+
+// ---- the targets of one call (fm_flow_targets, fm_flow_prepare): marshalled on the host by marshal_targets, sent to
+// the device as ONE packed block by upload_targets.  Byte offsets into FlowState::tgt_in, 16-byte aligned:
+//   uploaded   rects i32[nT][4] (offset 0) | kp_off i32[nT+1] | kps f32[nk][2] | ov_off i32[nT+1] | ov_idx i32[n_ov] |
+//              crops CropArgs[nT] | full boxes f64[nT][4] | two zeroed counters
+//   scratch    needy u8[nT] | min distances i32[nT]    (device only, behind the upload: prepare_kernel -> eig / select)
+inline size_t al16(size_t v) { return (v + 15) & ~size_t(15); }
+struct Targets {
+    std::vector<int32_t> irect, ov_off, ov_idx;
+    std::vector<CropArgs> crops;             // every track's crop, tiles numbered through (eig_tiles in all)
+    size_t eig_tiles = 0;
+    size_t o_kpoff, o_kps, o_ovoff, o_ovidx, o_crop, o_box, o_tot, in_bytes, o_dneedy, o_dmd, dev_bytes;
+};
+
+Targets marshal_targets(int nT, const double* inside_tlbr, int nk) {
+    Targets t;
+    t.irect.resize(4 * (size_t)nT);
+    t.ov_off.assign(nT + 1, 0);
+    t.crops.resize(nT);
+    for (int k = 0; k < nT; ++k) {
+        for (int e = 0; e < 4; ++e) t.irect[4 * k + e] = (int32_t)inside_tlbr[4 * k + e];   // crop(): int() truncation
+        const int32_t* a = &t.irect[4 * k];
+        for (int j = 0; j < k; ++j) {        // earlier rects (closer tracks) that intersect rect k
+            const int32_t* b = &t.irect[4 * j];
+            if (b[0] <= a[2] && b[2] >= a[0] && b[1] <= a[3] && b[3] >= a[1]) t.ov_idx.push_back(j);
+        }
+        t.ov_off[k + 1] = (int32_t)t.ov_idx.size();
+        t.crops[k] = make_crop(a, k, t.eig_tiles);
+        t.eig_tiles += (size_t)eig_tiles(t.crops[k]);
+    }
+    t.o_kpoff = al16(sizeof(int32_t) * 4 * nT);
+    t.o_kps = al16(t.o_kpoff + sizeof(int32_t) * (nT + 1));
+    t.o_ovoff = al16(t.o_kps + sizeof(float) * 2 * nk);
+    t.o_ovidx = al16(t.o_ovoff + sizeof(int32_t) * (nT + 1));
+    t.o_crop = al16(t.o_ovidx + sizeof(int32_t) * t.ov_idx.size());
+    t.o_box = al16(t.o_crop + sizeof(CropArgs) * nT);
+    t.o_tot = al16(t.o_box + sizeof(double) * 4 * nT);
+    t.in_bytes = t.o_tot + 16;
+    t.o_dneedy = t.in_bytes;
+    t.o_dmd = al16(t.o_dneedy + nT);
+    t.dev_bytes = al16(t.o_dmd + sizeof(int32_t) * nT);
+    return t;
+}
+
+// Fills the pinned staging block and issues the one H2D copy; the kernels read rects / overlap lists / counters
+// straight from the uploaded block (no device-to-device copies, no memset).  The previous consumer of the staging
+// block must have finished, and the stream must be idle if the block has to grow (t.dev_bytes > f->tgt_in.cap).
+int upload_targets(FlowState* f, const Targets& t, const double* full_tlbr, const float* kps, const int32_t* kp_off,
+                   hipStream_t s) {
+    int rc = f->tgt_in.reserve(t.dev_bytes);
+    if (rc) return rc;
+    const int nT = (int)t.crops.size(), nk = nT ? kp_off[nT] : 0;
+    char* hb = f->tgt_in.host<char>();
+    char* db = f->tgt_in.dev<char>();
+    if (nT) {
+        memcpy(hb, t.irect.data(), sizeof(int32_t) * 4 * nT);
+        memcpy(hb + t.o_kpoff, kp_off, sizeof(int32_t) * (nT + 1));
+        if (nk) memcpy(hb + t.o_kps, kps, sizeof(float) * 2 * nk);
+        memcpy(hb + t.o_ovoff, t.ov_off.data(), sizeof(int32_t) * (nT + 1));
+        if (!t.ov_idx.empty()) memcpy(hb + t.o_ovidx, t.ov_idx.data(), sizeof(int32_t) * t.ov_idx.size());
+        memcpy(hb + t.o_crop, t.crops.data(), sizeof(CropArgs) * nT);
+        if (full_tlbr) memcpy(hb + t.o_box, full_tlbr, sizeof(double) * 4 * nT);
+    }
+    memset(hb + t.o_tot, 0, 16);
+    FM_HIP(hipMemcpyAsync(db, hb, t.in_bytes, hipMemcpyHostToDevice, s));
+    f->rects = reinterpret_cast<const int32_t*>(db);
+    f->ov_off = reinterpret_cast<const int32_t*>(db + t.o_ovoff);
+    f->ov_idx = reinterpret_cast<const int32_t*>(db + t.o_ovidx);
+    return 0;
+}
+
+// prepare_kernel over the uploaded targets: area and keep flags to `area` / `keep`, needy flags and min distances to
+// the scratch behind the upload (and the needy flags to `needy_host` if given)
+void launch_prepare(FlowState* f, const Targets& t, hipStream_t s, double feat_density, double feat_dist_factor,
+                    int32_t* area, uint8_t* keep, uint8_t* needy_host) {
+    char* db = f->tgt_in.dev<char>();
+    hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)t.crops.size()), dim3(PREP_BLK), 0, s, f->rects,
+                       Overlaps{f->ov_idx, f->ov_off}, reinterpret_cast<const float*>(db + t.o_kps),
+                       reinterpret_cast<const int32_t*>(db + t.o_kpoff), feat_density, feat_dist_factor, area, keep,
+                       reinterpret_cast<uint8_t*>(db + t.o_dneedy), reinterpret_cast<int32_t*>(db + t.o_dmd), needy_host);
+}
+
+// Background FAST keypoints under the final mask (the uploaded rects): resize, score, flags, raster-order compaction
+// into `pts` (capacity `cap`), their number to `counter` and -- if given -- the totals to `totals_host` (see
+// fast_compact_kernel).  Only the last two kernels read the rects: they wait for `rects_ready` if one is given.
+int enqueue_background(FlowState* f, hipStream_t s, hipEvent_t rects_ready, float* pts, int cap, int32_t* counter,
+                       int32_t* totals_host) {
+    const int bw = f->cfg.bg_w, bh = f->cfg.bg_h;
+    hipLaunchKernelGGL(resize_linear_kernel, dim3((bw + 255) / 256, bh), dim3(256), 0, s, f->gray[f->prev], f->W,
+                       f->H, f->bg_img, bw, bh);
+    hipLaunchKernelGGL(fast_score_kernel, dim3((bw + 63) / 64, bh), dim3(64), 0, s, f->bg_img, bw, bh,
+                       f->cfg.fast_thresh, f->bg_flags);
+    const FastBufs fb = fast_bufs(f->bg_flags, bw, bh);
+    if (rects_ready) FM_HIP(hipStreamWaitEvent(s, rects_ready, 0));
+    hipLaunchKernelGGL(fast_flag_kernel, dim3(fb.nseg), dim3(FAST_SEG), 0, s, fb.score, bw, bh, f->rects, f->nT, f->W,
+                       f->H, fb.flag, fb.seg_cnt);
+    hipLaunchKernelGGL(fast_compact_kernel, dim3(fb.nseg), dim3(FAST_SEG), 0, s, fb.flag, bw, bh, fb.seg_cnt, pts, cap,
+                       counter, nullptr, totals_host);
     return 0;
 }
 
@@ -1210,80 +1256,26 @@ extern "C" int fm_flow_targets(fm_ctx* ctx, int nT, const double* inside_tlbr, c
                                const int32_t* kp_off, int32_t* area_out, uint8_t* keep_out) {
     FM_CHECK_ARG(ctx && ctx->flow && nT >= 0);
     FlowState* f = ctx->flow;
-    hipStream_t s;
-    { int rc_s_ = flow_stream(ctx, &s); if (rc_s_) return rc_s_; }
+    FM_FLOW_STREAM(s);
     f->nT = nT;
     if (nT == 0) return 0;
     FM_CHECK_ARG(inside_tlbr && kp_off && area_out);
     const int nk = kp_off[nT];
     FM_CHECK_ARG(nk == 0 || (kps && keep_out));
-    if (nT > f->rect_cap) {
-        FM_HIP(hipStreamSynchronize(s));
-        if (f->rects) FM_HIP(hipFree(f->rects));
-        f->rects = nullptr;
-        int cap = f->rect_cap ? f->rect_cap : 64;
-        while (cap < nT) cap *= 2;
-        FM_HIP(hipMalloc(&f->rects, sizeof(int32_t) * 4 * cap));
-        f->rect_cap = cap;
-    }
-    // overlap lists: earlier rects (closer tracks) that intersect rect k
-    std::vector<int32_t> irect(4 * (size_t)nT), ov_off(nT + 1, 0), ov_idx;
-    for (int k = 0; k < nT; ++k)
-        for (int e = 0; e < 4; ++e) irect[4 * k + e] = (int32_t)inside_tlbr[4 * k + e];   // crop(): int() truncation
-    for (int k = 0; k < nT; ++k) {
-        const int32_t* a = &irect[4 * k];
-        for (int j = 0; j < k; ++j) {
-            const int32_t* b = &irect[4 * j];
-            if (b[0] <= a[2] && b[2] >= a[0] && b[1] <= a[3] && b[3] >= a[1]) ov_idx.push_back(j);
-        }
-        ov_off[k + 1] = (int32_t)ov_idx.size();
-    }
-    const int n_ov = (int)ov_idx.size();
-    if (nT + 1 > f->ov_cap || n_ov > f->ov_cap * 8) {
-        FM_HIP(hipStreamSynchronize(s));
-        if (f->ov_idx) FM_HIP(hipFree(f->ov_idx));
-        if (f->ov_off) FM_HIP(hipFree(f->ov_off));
-        f->ov_idx = f->ov_off = nullptr;
-        int cap = f->ov_cap ? f->ov_cap : 64;
-        while (cap < nT + 1 || cap * 8 < n_ov) cap *= 2;
-        FM_HIP(hipMalloc(&f->ov_off, sizeof(int32_t) * cap));
-        FM_HIP(hipMalloc(&f->ov_idx, sizeof(int32_t) * cap * 8));
-        f->ov_cap = cap;
-    }
-    // packed upload: rects i32[nT][4] | kp_track i32[nk] | kps f32[nk][2] | ov_off i32[nT+1] | ov_idx i32[n_ov]
-    const size_t o_rect = 0, o_trk = sizeof(int32_t) * 4 * nT, o_kps = o_trk + sizeof(int32_t) * nk;
-    const size_t o_ovoff = o_kps + sizeof(float) * 2 * nk, o_ovidx = o_ovoff + sizeof(int32_t) * (nT + 1);
-    const size_t in_bytes = o_ovidx + sizeof(int32_t) * n_ov;
-    int rc = f->tgt_in.reserve(in_bytes + 16);
+    const Targets t = marshal_targets(nT, inside_tlbr, nk);
+    FM_HIP(hipStreamSynchronize(s));        // (the staging block may still be read, and the blocks may have to grow)
+    int rc = upload_targets(f, t, nullptr, kps, kp_off, s);
     if (rc) return rc;
-    if ((rc = f->tgt_out.reserve(sizeof(int32_t) * nT + nk + 16))) return rc;
-    FM_HIP(hipStreamSynchronize(s));
-    char* hbuf = f->tgt_in.host<char>();
-    memcpy(hbuf + o_rect, irect.data(), sizeof(int32_t) * 4 * nT);
-    memcpy(hbuf + o_ovoff, ov_off.data(), sizeof(int32_t) * (nT + 1));
-    if (n_ov) memcpy(hbuf + o_ovidx, ov_idx.data(), sizeof(int32_t) * n_ov);
-    int32_t* ht = reinterpret_cast<int32_t*>(hbuf + o_trk);
-    for (int k = 0; k < nT; ++k)
-        for (int i = kp_off[k]; i < kp_off[k + 1]; ++i) ht[i] = k;
-    if (nk) memcpy(hbuf + o_kps, kps, sizeof(float) * 2 * nk);
-    FM_HIP(hipMemcpyAsync(f->tgt_in.d, hbuf, in_bytes, hipMemcpyHostToDevice, s));
-    FM_HIP(hipMemcpyAsync(f->rects, f->tgt_in.dev<char>() + o_rect, sizeof(int32_t) * 4 * nT, hipMemcpyDeviceToDevice, s));
-    FM_HIP(hipMemcpyAsync(f->ov_off, f->tgt_in.dev<char>() + o_ovoff, sizeof(int32_t) * (nT + 1), hipMemcpyDeviceToDevice, s));
-    if (n_ov) FM_HIP(hipMemcpyAsync(f->ov_idx, f->tgt_in.dev<char>() + o_ovidx, sizeof(int32_t) * n_ov, hipMemcpyDeviceToDevice, s));
-    f->v_rects = f->rects; f->v_ov_idx = f->ov_idx; f->v_ov_off = f->ov_off;
-    const Overlaps ov{f->ov_idx, f->ov_off};
-    int32_t* d_area = f->tgt_out.dev<int32_t>();
-    uint8_t* d_keep = reinterpret_cast<uint8_t*>(d_area + nT);
-    hipLaunchKernelGGL(target_area_kernel, dim3(nT), dim3(256), 0, s, f->rects, ov, d_area);
-    if (nk)
-        hipLaunchKernelGGL(kp_filter_kernel, dim3((nk + 255) / 256), dim3(256), 0, s, f->rects, ov,
-                           reinterpret_cast<const float*>(f->tgt_in.dev<char>() + o_kps),
-                           reinterpret_cast<const int32_t*>(f->tgt_in.dev<char>() + o_trk), nk, d_keep);
+    if ((rc = f->tgt_out.reserve(sizeof(int32_t) * nT + nk))) return rc;
+    // the bookkeeping kernel of fm_flow_prepare; its needy flags and min distances stay in the scratch behind the
+    // upload (the density parameters do not touch area and keep), the results land in the pinned block as they do there
+    int32_t* area = f->tgt_out.host<int32_t>();
+    uint8_t* keep = reinterpret_cast<uint8_t*>(area + nT);
+    launch_prepare(f, t, s, 0., 0., area, keep, nullptr);
     FM_HIP(hipGetLastError());
-    FM_HIP(hipMemcpyAsync(f->tgt_out.h, f->tgt_out.d, sizeof(int32_t) * nT + nk, hipMemcpyDeviceToHost, s));
     FM_HIP(hipStreamSynchronize(s));
-    memcpy(area_out, f->tgt_out.h, sizeof(int32_t) * nT);
-    if (nk) memcpy(keep_out, f->tgt_out.host<char>() + sizeof(int32_t) * nT, nk);
+    memcpy(area_out, area, sizeof(int32_t) * nT);
+    if (nk) memcpy(keep_out, keep, nk);
     return 0;
 }
 
@@ -1293,35 +1285,21 @@ extern "C" int fm_flow_detect(fm_ctx* ctx, int n, const int32_t* track_idx, cons
     if (n == 0) return 0;
     FM_CHECK_ARG(track_idx && track_tlbr && min_dist && pts_out && counts_out);
     FlowState* f = ctx->flow;
-    hipStream_t s;
-    { int rc_s_ = flow_stream(ctx, &s); if (rc_s_) return rc_s_; }
+    FM_FLOW_STREAM(s);
     FM_HIP(hipStreamSynchronize(s));
-    const int32_t* hrects = reinterpret_cast<const int32_t*>(f->tgt_in.host<char>());
+    const int32_t* hrects = f->tgt_in.host<int32_t>();      // (the integer rects at the head of the staging block)
     std::vector<CropArgs> crops(n);
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         FM_CHECK_ARG(track_idx[i] >= 0 && track_idx[i] < f->nT);
-        const int32_t* r = hrects + 4 * track_idx[i];
-        CropArgs c;
-        c.x0 = r[0]; c.y0 = r[1]; c.w = r[2] - r[0] + 1; c.h = r[3] - r[1] + 1; c.k = track_idx[i];
-        c.eig_off = off;
-        off += (size_t)eig_tiles(c);
-        crops[i] = c;
+        crops[i] = make_crop(hrects + 4 * track_idx[i], track_idx[i], off);
+        off += (size_t)eig_tiles(crops[i]);
     }
-    if (off > f->eig_cap) {     // many small crops (one tile at least each): grow like fm_flow_prepare does (stream idle: synchronised above)
-        f->eig_cap = 0;         // (a failing allocation below must not leave a capacity behind null pointers)
-        FM_HIP(hipFree(f->eig));
-        f->eig = nullptr;
-        FM_HIP(hipFree(f->tile_stat));
-        f->tile_stat = nullptr;
-        FM_HIP(hipMalloc(&f->eig, sizeof(unsigned long long) * EIG_TPX * off * 2));
-        FM_HIP(hipMalloc(&f->tile_stat, sizeof(uint2) * off * 2));
-        f->eig_cap = off * 2;
-    }
-    const size_t o_crop = 0, o_md = sizeof(CropArgs) * n, o_box = (o_md + sizeof(int32_t) * n + 15) & ~size_t(15);
-    const size_t in_bytes = o_box + sizeof(double) * 4 * n;
-    int rc = f->det_in.reserve(in_bytes);
+    int rc = ensure_eig(f, off);            // (many small crops, one tile at least each; stream idle: synchronised above)
     if (rc) return rc;
+    const size_t o_crop = 0, o_md = sizeof(CropArgs) * n, o_box = al16(o_md + sizeof(int32_t) * n);
+    const size_t in_bytes = o_box + sizeof(double) * 4 * n;
+    if ((rc = f->det_in.reserve(in_bytes))) return rc;
     const size_t out_bytes = sizeof(float) * 2 * (size_t)n * cap + sizeof(int32_t) * n;
     if ((rc = f->det_out.reserve(out_bytes))) return rc;
     char* hb = f->det_in.host<char>();
@@ -1331,7 +1309,7 @@ extern "C" int fm_flow_detect(fm_ctx* ctx, int n, const int32_t* track_idx, cons
     FM_HIP(hipMemcpyAsync(f->det_in.d, hb, in_bytes, hipMemcpyHostToDevice, s));
     char* db = f->det_in.dev<char>();
     launch_eig(s, f->gray[f->prev], f->W, reinterpret_cast<const CropArgs*>(db + o_crop), n, eig_max_tiles(crops),
-               f->v_rects, Overlaps{f->v_ov_idx, f->v_ov_off}, f->cfg.block_size, nullptr, f->tile_stat, f->eig);
+               f->rects, Overlaps{f->ov_idx, f->ov_off}, f->cfg.block_size, nullptr, f->tile_stat, f->eig);
     float* d_pts = f->det_out.dev<float>();
     int32_t* d_cnt = reinterpret_cast<int32_t*>(d_pts + 2 * (size_t)n * cap);
     hipLaunchKernelGGL(gftt_select_kernel, dim3(n), dim3(GFTT_BLK), 0, s, reinterpret_cast<const CropArgs*>(db + o_crop),
@@ -1349,21 +1327,11 @@ extern "C" int fm_flow_detect(fm_ctx* ctx, int n, const int32_t* track_idx, cons
 extern "C" int fm_flow_background(fm_ctx* ctx, int cap, float* pts_out, int* n_out) {
     FM_CHECK_ARG(ctx && ctx->flow && cap > 0 && pts_out && n_out);
     FlowState* f = ctx->flow;
-    hipStream_t s;
-    { int rc_s_ = flow_stream(ctx, &s); if (rc_s_) return rc_s_; }
-    const int bw = f->cfg.bg_w, bh = f->cfg.bg_h;
+    FM_FLOW_STREAM(s);
     int rc = f->bg_out.reserve(sizeof(float) * 2 * cap + 16);
     if (rc) return rc;
-    hipLaunchKernelGGL(resize_linear_kernel, dim3((bw + 255) / 256, bh), dim3(256), 0, s, f->gray[f->prev], f->W,
-                       f->H, f->bg_img, bw, bh);
-    hipLaunchKernelGGL(fast_score_kernel, dim3((bw + 63) / 64, bh), dim3(64), 0, s, f->bg_img, bw, bh,
-                       f->cfg.fast_thresh, f->bg_flags);
-    const FastBufs fb = fast_bufs(f->bg_flags, bw, bh);
-    int32_t* d_n = fb.counters;
-    hipLaunchKernelGGL(fast_flag_kernel, dim3(fb.nseg), dim3(FAST_SEG), 0, s, fb.score, bw, bh, f->v_rects, f->nT, f->W,
-                       f->H, fb.flag, fb.seg_cnt);
-    hipLaunchKernelGGL(fast_compact_kernel, dim3(fb.nseg), dim3(FAST_SEG), 0, s, fb.flag, bw, bh, fb.seg_cnt,
-                       f->bg_out.dev<float>(), cap, d_n, nullptr, nullptr);
+    int32_t* d_n = fast_bufs(f->bg_flags, f->cfg.bg_w, f->cfg.bg_h).counters;
+    if ((rc = enqueue_background(f, s, nullptr, f->bg_out.dev<float>(), cap, d_n, nullptr))) return rc;
     FM_HIP(hipGetLastError());
     FM_HIP(hipMemcpyAsync(f->bg_out.host<char>() + sizeof(float) * 2 * cap, d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     FM_HIP(hipMemcpyAsync(f->bg_out.h, f->bg_out.d, sizeof(float) * 2 * cap, hipMemcpyDeviceToHost, s));
@@ -1382,8 +1350,7 @@ extern "C" int fm_flow_lk(fm_ctx* ctx, int n, const float* prev_pts, float* next
                           float* err) {
     FM_CHECK_ARG(ctx && ctx->flow && n >= 0);
     FlowState* f = ctx->flow;
-    hipStream_t s;
-    { int rc_s_ = flow_stream(ctx, &s); if (rc_s_) return rc_s_; }
+    FM_FLOW_STREAM(s);
     if (n > 0) {
         FM_CHECK_ARG(prev_pts && next_pts && status && err);
         int rc = f->lk_in.reserve(sizeof(float) * 2 * n);
@@ -1544,140 +1511,57 @@ extern "C" int fm_flow_prepare(fm_ctx* ctx, int nT, const double* inside_tlbr, c
     f->nT = nT;
     const int nk = nT ? kp_off[nT] : 0;
     double tp0 = fm_now_ms();
-    // ---- host side: integer rects, overlap lists, crop table
-    std::vector<int32_t> irect(4 * (size_t)nT), ov_off(nT + 1, 0), ov_idx;
-    std::vector<CropArgs> crops(nT);
-    size_t eig_total = 0;
-    for (int k = 0; k < nT; ++k) {
-        for (int e = 0; e < 4; ++e) irect[4 * k + e] = (int32_t)inside_tlbr[4 * k + e];
-        const int32_t* a = &irect[4 * k];
-        for (int j = 0; j < k; ++j) {
-            const int32_t* b = &irect[4 * j];
-            if (b[0] <= a[2] && b[2] >= a[0] && b[1] <= a[3] && b[3] >= a[1]) ov_idx.push_back(j);
-        }
-        ov_off[k + 1] = (int32_t)ov_idx.size();
-        CropArgs c;
-        c.x0 = a[0]; c.y0 = a[1]; c.w = a[2] - a[0] + 1; c.h = a[3] - a[1] + 1; c.k = k; c.eig_off = eig_total;
-        eig_total += (size_t)eig_tiles(c);
-        crops[k] = c;
-    }
-    const int n_ov = (int)ov_idx.size();
+    // ---- host side: integer rects, overlap lists, crop table, layout of the upload
+    const Targets t = marshal_targets(nT, inside_tlbr, nk);
     g_flow_sub[0] += fm_now_ms() - tp0; tp0 = fm_now_ms();
     // (no synchronisation here: the staging block was consumed by the previous call, which ended with one, and the
     // kernels of fm_flow_begin that may still be running touch none of the buffers below -- only a reallocation
     // needs an idle stream)
-    if (eig_total > f->eig_cap || nT > f->rect_cap || nT + 1 > f->ov_cap || n_ov > f->ov_cap * 8)
-        FM_HIP(hipStreamSynchronize(s));
+    if (t.eig_tiles > f->eig_cap || t.dev_bytes > f->tgt_in.cap) FM_HIP(hipStreamSynchronize(s));
     g_flow_sub[1] += fm_now_ms() - tp0; tp0 = fm_now_ms();
-    if (eig_total > f->eig_cap) {
-        f->eig_cap = 0;
-        FM_HIP(hipFree(f->eig));
-        f->eig = nullptr;
-        FM_HIP(hipFree(f->tile_stat));
-        f->tile_stat = nullptr;
-        FM_HIP(hipMalloc(&f->eig, sizeof(unsigned long long) * EIG_TPX * eig_total * 2));
-        FM_HIP(hipMalloc(&f->tile_stat, sizeof(uint2) * eig_total * 2));
-        f->eig_cap = eig_total * 2;
-    }
-    if (nT > f->rect_cap) {
-        if (f->rects) FM_HIP(hipFree(f->rects));
-        f->rects = nullptr;
-        int cap = f->rect_cap ? f->rect_cap : 64;
-        while (cap < nT) cap *= 2;
-        FM_HIP(hipMalloc(&f->rects, sizeof(int32_t) * 4 * cap));
-        f->rect_cap = cap;
-    }
-    if (nT + 1 > f->ov_cap || n_ov > f->ov_cap * 8) {
-        if (f->ov_idx) FM_HIP(hipFree(f->ov_idx));
-        if (f->ov_off) FM_HIP(hipFree(f->ov_off));
-        f->ov_idx = f->ov_off = nullptr;
-        int cap = f->ov_cap ? f->ov_cap : 64;
-        while (cap < nT + 1 || cap * 8 < n_ov) cap *= 2;
-        FM_HIP(hipMalloc(&f->ov_off, sizeof(int32_t) * cap));
-        FM_HIP(hipMalloc(&f->ov_idx, sizeof(int32_t) * cap * 8));
-        f->ov_cap = cap;
-    }
-    // ---- packed upload
-    auto al = [](size_t v) { return (v + 15) & ~size_t(15); };
-    const size_t o_rect = 0, o_kpoff = al(o_rect + sizeof(int32_t) * 4 * nT), o_kps = al(o_kpoff + sizeof(int32_t) * (nT + 1));
-    const size_t o_ovoff = al(o_kps + sizeof(float) * 2 * nk), o_ovidx = al(o_ovoff + sizeof(int32_t) * (nT + 1));
-    const size_t o_crop = al(o_ovidx + sizeof(int32_t) * n_ov), o_box = al(o_crop + sizeof(CropArgs) * nT);
-    const size_t o_tot = al(o_box + sizeof(double) * 4 * nT);          // two zeroed counters, uploaded with the rest
-    const size_t in_bytes = o_tot + 16;
-    // device-side scratch behind the upload: needy flags + min distances (read by the eig / select kernels)
-    const size_t o_dneedy = in_bytes, o_dmd = al(o_dneedy + nT);
-    int rc = f->tgt_in.reserve(al(o_dmd + sizeof(int32_t) * nT));
+    int rc = ensure_eig(f, t.eig_tiles);
     if (rc) return rc;
     // outputs (device-visible pinned host memory): area | md | counts | off | total,n_bg | needy | keep | pts | bg
-    const size_t q_area = 0, q_md = al(q_area + 4 * (size_t)nT), q_cnt = al(q_md + 4 * (size_t)nT);
-    const size_t q_off = al(q_cnt + 4 * (size_t)nT), q_tot = al(q_off + 4 * (size_t)nT), q_needy = al(q_tot + 16);
-    const size_t q_keep = al(q_needy + nT), q_pts = al(q_keep + nk), q_bg = al(q_pts + sizeof(float) * 2 * pts_cap);
-    const size_t out_bytes = al(q_bg + sizeof(float) * 2 * bg_cap);
+    const size_t q_area = 0, q_md = al16(q_area + 4 * (size_t)nT), q_cnt = al16(q_md + 4 * (size_t)nT);
+    const size_t q_off = al16(q_cnt + 4 * (size_t)nT), q_tot = al16(q_off + 4 * (size_t)nT), q_needy = al16(q_tot + 16);
+    const size_t q_keep = al16(q_needy + nT), q_pts = al16(q_keep + nk), q_bg = al16(q_pts + sizeof(float) * 2 * pts_cap);
+    const size_t out_bytes = al16(q_bg + sizeof(float) * 2 * bg_cap);
     if ((rc = f->tgt_out.reserve(out_bytes))) return rc;
-    char* hb = f->tgt_in.host<char>();
-    char* db = f->tgt_in.dev<char>();
-    if (nT) {
-        memcpy(hb + o_rect, irect.data(), sizeof(int32_t) * 4 * nT);
-        memcpy(hb + o_kpoff, kp_off, sizeof(int32_t) * (nT + 1));
-        if (nk) memcpy(hb + o_kps, kps, sizeof(float) * 2 * nk);
-        memcpy(hb + o_ovoff, ov_off.data(), sizeof(int32_t) * (nT + 1));
-        if (n_ov) memcpy(hb + o_ovidx, ov_idx.data(), sizeof(int32_t) * n_ov);
-        memcpy(hb + o_crop, crops.data(), sizeof(CropArgs) * nT);
-        memcpy(hb + o_box, full_tlbr, sizeof(double) * 4 * nT);
-    }
-    memset(hb + o_tot, 0, 16);
-    // ONE upload; the kernels read rects / overlap lists / counters straight from it (no device-to-device
-    // copies, no memset)
-    FM_HIP(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, s));
+    if ((rc = upload_targets(f, t, full_tlbr, kps, kp_off, s))) return rc;
     FM_HIP(hipEventRecord(ctx->ev_prep, s));           // the background branch (side stream) needs the rects only
-    f->v_rects = reinterpret_cast<const int32_t*>(db + o_rect);
-    f->v_ov_off = reinterpret_cast<const int32_t*>(db + o_ovoff);
-    f->v_ov_idx = reinterpret_cast<const int32_t*>(db + o_ovidx);
+    char* db = f->tgt_in.dev<char>();
     // results: written by the kernels straight into the pinned, device-mapped block (a device block + one D2H copy
     // measured the same; the consumers of needy / min-distance read device copies either way)
     char* ho = f->tgt_out.host<char>();      // pinned, device accessible
     char* dbo = ho;
     int32_t* tot_host = reinterpret_cast<int32_t*>(ho + q_tot);
-    int32_t* tot = reinterpret_cast<int32_t*>(db + o_tot);             // device counters: [0] new pts, [1] bg pts
+    int32_t* tot = reinterpret_cast<int32_t*>(db + t.o_tot);           // device counters: [0] new pts, [1] bg pts
     if (nT) {
-        const Overlaps ov{f->v_ov_idx, f->v_ov_off};
         // needy flags / min distances are consumed by the eig / select kernels: device copies (behind the upload)
-        uint8_t* d_needy = reinterpret_cast<uint8_t*>(db + o_dneedy);
-        int32_t* d_md = reinterpret_cast<int32_t*>(db + o_dmd);
+        const uint8_t* d_needy = reinterpret_cast<const uint8_t*>(db + t.o_dneedy);
+        const CropArgs* d_crops = reinterpret_cast<const CropArgs*>(db + t.o_crop);
         fm_trace_mark(ctx, s, 44);
-        hipLaunchKernelGGL(prepare_kernel, dim3(nT), dim3(PREP_BLK), 0, s, f->v_rects, ov,
-                           reinterpret_cast<const float*>(db + o_kps), reinterpret_cast<const int32_t*>(db + o_kpoff),
-                           feat_density, feat_dist_factor, reinterpret_cast<int32_t*>(dbo + q_area),
-                           reinterpret_cast<uint8_t*>(dbo + q_keep), d_needy, d_md,
-                           reinterpret_cast<uint8_t*>(dbo + q_needy));
-        launch_eig(s, f->gray[f->prev], f->W, reinterpret_cast<const CropArgs*>(db + o_crop), nT, eig_max_tiles(crops),
-                   f->v_rects, ov, f->cfg.block_size, d_needy, f->tile_stat, f->eig);
-        hipLaunchKernelGGL(gftt_select_kernel, dim3(nT), dim3(GFTT_BLK), 0, s,
-                           reinterpret_cast<const CropArgs*>(db + o_crop), f->tile_stat, f->eig,
-                           (float)f->cfg.quality_level, f->cfg.max_corners, d_md,
-                           reinterpret_cast<const double*>(db + o_box), reinterpret_cast<float*>(ho + q_pts), pts_cap,
-                           reinterpret_cast<int32_t*>(dbo + q_cnt), d_needy, tot, reinterpret_cast<int32_t*>(dbo + q_off));
+        launch_prepare(f, t, s, feat_density, feat_dist_factor, reinterpret_cast<int32_t*>(dbo + q_area),
+                       reinterpret_cast<uint8_t*>(dbo + q_keep), reinterpret_cast<uint8_t*>(dbo + q_needy));
+        launch_eig(s, f->gray[f->prev], f->W, d_crops, nT, eig_max_tiles(t.crops), f->rects,
+                   Overlaps{f->ov_idx, f->ov_off}, f->cfg.block_size, d_needy, f->tile_stat, f->eig);
+        hipLaunchKernelGGL(gftt_select_kernel, dim3(nT), dim3(GFTT_BLK), 0, s, d_crops, f->tile_stat, f->eig,
+                           (float)f->cfg.quality_level, f->cfg.max_corners,
+                           reinterpret_cast<const int32_t*>(db + t.o_dmd), reinterpret_cast<const double*>(db + t.o_box),
+                           reinterpret_cast<float*>(ho + q_pts), pts_cap, reinterpret_cast<int32_t*>(dbo + q_cnt), d_needy,
+                           tot, reinterpret_cast<int32_t*>(dbo + q_off));
         fm_trace_mark(ctx, s, 45);
     }
     // background keypoints under the final mask: four small dependent launches that share nothing with the per-track
     // branch above except the uploaded rects -- they run on the side stream (behind the new frame's pyramid, which is
     // shorter than the per-track branch) and join at the end of the call
     hipStream_t sb = ctx->s_flow2;
-    const int bw = f->cfg.bg_w, bh = f->cfg.bg_h;
     fm_trace_mark(ctx, sb, 46);
-    // (the fork event is recorded behind the upload only: the branch must not wait for the per-track kernels)
-    hipLaunchKernelGGL(resize_linear_kernel, dim3((bw + 255) / 256, bh), dim3(256), 0, sb, f->gray[f->prev], f->W,
-                       f->H, f->bg_img, bw, bh);
-    hipLaunchKernelGGL(fast_score_kernel, dim3((bw + 63) / 64, bh), dim3(64), 0, sb, f->bg_img, bw, bh,
-                       f->cfg.fast_thresh, f->bg_flags);
-    const FastBufs fb = fast_bufs(f->bg_flags, bw, bh);
-    FM_HIP(hipStreamWaitEvent(sb, ctx->ev_prep, 0));
-    hipLaunchKernelGGL(fast_flag_kernel, dim3(fb.nseg), dim3(FAST_SEG), 0, sb, fb.score, bw, bh, f->v_rects, nT, f->W,
-                       f->H, fb.flag, fb.seg_cnt);
-    // the last kernels of the two branches put the totals into the result block
-    hipLaunchKernelGGL(fast_compact_kernel, dim3(fb.nseg), dim3(FAST_SEG), 0, sb, fb.flag, bw, bh, fb.seg_cnt,
-                       reinterpret_cast<float*>(ho + q_bg), bg_cap, tot + 1, nullptr,
-                       reinterpret_cast<int32_t*>(dbo + q_tot));
+    // (the fork event was recorded behind the upload only: the branch must not wait for the per-track kernels; the
+    // last kernels of the two branches put the totals into the result block)
+    if ((rc = enqueue_background(f, sb, ctx->ev_prep, reinterpret_cast<float*>(ho + q_bg), bg_cap, tot + 1,
+                                 reinterpret_cast<int32_t*>(dbo + q_tot))))
+        return rc;
     fm_trace_mark(ctx, sb, 47);
     FM_HIP(hipEventRecord(ctx->ev_bg, sb));
     hipLaunchKernelGGL(copy_total_kernel, dim3(1), dim3(1), 0, s, tot, reinterpret_cast<int32_t*>(dbo + q_tot));
@@ -1743,8 +1627,7 @@ __global__ __launch_bounds__(256) void spin_kernel(int iters, int mode, const ui
 extern "C" int fm_debug_spin(fm_ctx* ctx, int blocks, int iters, int mode, unsigned* out_host) {
     FM_CHECK_ARG(ctx && ctx->flow && blocks > 0 && out_host);
     FlowState* f = ctx->flow;
-    hipStream_t s;
-    { int rc_s_ = flow_stream(ctx, &s); if (rc_s_) return rc_s_; }
+    FM_FLOW_STREAM(s);
     const size_t bytes = sizeof(unsigned) * 256 * (size_t)blocks;
     int rc = f->lk_out.reserve(bytes);
     if (rc) return rc;

@@ -145,16 +145,31 @@ def test_targets_gftt_fast(ctx):
     assert len(kp) > 10
 
 
-def test_gftt_edge_crops(ctx):
-    """Corner detection on the crops the tiled kernel has to get right at its seams: one or two pixels wide, exactly one
-    32 x 32 tile, one pixel more than a tile, a frame corner, a crop with a strong min-distance (few cells), and a track
-    overlapped by 40 earlier ones (more than the 32 rects the kernels keep in LDS: the global overlap list).  Every
-    list must equal the restated goodFeaturesToTrack on the same crop and mask (bit-identical points, same order)."""
-    size = (640, 360)
-    f0 = textured_frame(*size, 11)
-    flow = make_flow(size)
-    flow.init(f0)
-    g0 = cv.bgr2gray(f0)
+def mask_bookkeeping(size, rects, kps, off):
+    """The reference's foreground mask, zeroed rect by rect (flow.py:163-169): -> (area of every track = non-zero mask
+    pixels of its crop, keep flag of every propagated keypoint = _rect_filter, the crops' masks, the final mask)."""
+    mask = np.full((size[1], size[0]), 255, np.uint8)
+    area, keep, masks = [], [], []
+    for k, r in enumerate(np.asarray(rects).astype(int)):
+        crop = mask[r[1]:r[3] + 1, r[0]:r[2] + 1]
+        area.append(int((crop != 0).sum()))
+        for p in kps[off[k]:off[k + 1]]:
+            x, y = int(np.rint(p[0])), int(np.rint(p[1]))
+            inside = r[0] <= x <= r[2] and r[1] <= y <= r[3]
+            keep.append(bool(inside and mask[y, x] == 255))
+        masks.append(crop.copy())
+        crop[:] = 0
+    return np.array(area), np.array(keep, bool), masks, mask
+
+
+def edge_targets():
+    """49 rects for the seams of the mask bookkeeping and the tiled corner kernel -> (rects, kps, kp_off, keep expected
+    of the keypoints).  Rects 0 .. 39 overlap up to ten earlier ones each (prepare_kernel's 64-column words, one ragged
+    word per row); rect 40 is overlapped by all 40 -- more than the OV_LDS = 32 rects the kernels keep in LDS: the
+    per-pixel branch over the global overlap list, 181 x 151 pixels -- and it alone has propagated keypoints.  Then crops
+    one, two and three pixels wide, exactly one 32 x 32 tile, one pixel more, the frame's corners, and 64 x 8.  (Rows of
+    several words under a short list: the 81 and 201 pixel wide rects of test_prepare_matches_staged_calls and
+    test_no_targets_after_targets.)"""
     small = [[300 + 3 * i, 200 + 2 * i, 330 + 3 * i, 240 + 2 * i] for i in range(40)]       # 40 rects crossing the big one
     rects = np.array(small + [
         [280, 180, 460, 330],       # 40: overlapped by all 40 above
@@ -167,13 +182,40 @@ def test_gftt_edge_crops(ctx):
         [560, 300, 639, 359],       # 47: bottom right corner of the frame
         [200, 20, 263, 27],         # 48: 64 x 8
     ], float)
+    kps = np.array([
+        [310.2, 210.7], [400.4, 280.3],     # under rect 0; under rects 24 .. 33
+        [447., 318.], [300., 200.],         # the last pixel of rect 39, the first of rect 0
+        [285., 185.], [455.6, 325.1],       # free: near the two far corners of rect 40
+        [350., 190.], [299.4, 220.],        # free: above the band of small rects, one column left of rect 0
+        [279.4, 250.], [460.6, 200.],       # outside rect 40 by one column on either side (279, 461)
+        [336.5, 205.],                      # rintf -> 336 (even), the last column rect 2 covers in that row; 337 is free
+        [290., 330.5],                      # rintf -> 330 (even), the last row of rect 40; 331 is outside
+    ], np.float32)
     off = np.zeros(len(rects) + 1, np.int32)
-    ctx.flow_targets(rects, np.empty((0, 2), np.float32), off)
-    mask = np.full((size[1], size[0]), 255, np.uint8)
-    masks = []
-    for r in rects.astype(int):
-        masks.append(mask[r[1]:r[3] + 1, r[0]:r[2] + 1].copy())
-        mask[r[1]:r[3] + 1, r[0]:r[2] + 1] = 0
+    off[41:] = len(kps)
+    exp_keep = [False, False, False, False, True, True, True, True, False, False, False, True]
+    return rects, kps, off, exp_keep
+
+
+def test_gftt_edge_crops(ctx):
+    """Mask bookkeeping and corner detection on the crops the kernels have to get right at their seams (edge_targets):
+    one or two pixels wide, exactly one 32 x 32 tile, one pixel more than a tile, a frame corner, a crop with a strong
+    min-distance (few cells), and a track overlapped by 40 earlier ones (more than the 32 rects the kernels keep in
+    LDS: the global overlap list).  Area and keep flags must equal the reference's mask walked in numpy, for all 49
+    rects; every corner list must equal the restated goodFeaturesToTrack on the same crop and mask (bit-identical
+    points, same order)."""
+    size = (640, 360)
+    f0 = textured_frame(*size, 11)
+    flow = make_flow(size)
+    flow.init(f0)
+    g0 = cv.bgr2gray(f0)
+    rects, kps, off, keep_by_hand = edge_targets()
+    area, keep = ctx.flow_targets(rects, kps, off)
+    exp_area, exp_keep, masks, _ = mask_bookkeeping(size, rects, kps, off)
+    assert exp_keep.tolist() == keep_by_hand            # (the numpy statement says what the points were placed for)
+    np.testing.assert_array_equal(area, exp_area)
+    np.testing.assert_array_equal(keep, exp_keep)
+    assert len(area) == 49 and 0 < exp_area[40] < 181 * 151 and (exp_area[41:] == [31, 6, 9, 1024, 1089, 710, 4800, 512]).all()
     idx = list(range(40, len(rects)))
     mds = [7, 1, 1, 1, 3, 4, 2, 25, 2]
     pts, cnt = ctx.flow_detect(idx, rects[idx], mds, cap=1000)
@@ -276,7 +318,9 @@ def test_flow_predict_moving_scene(ctx):
 
 
 def test_prepare_matches_staged_calls(ctx):
-    """fm_flow_prepare (one round trip) == fm_flow_targets + fm_flow_detect + fm_flow_background."""
+    """fm_flow_prepare (one round trip) == fm_flow_targets + fm_flow_detect + fm_flow_background.  Both run the same
+    bookkeeping kernel, so area and keep flags are also held against the reference's mask walked in numpy -- for the
+    four rects here and for the 49 of edge_targets."""
     size = (640, 360)
     f0 = textured_frame(*size, 21)
     flow = make_flow(size)
@@ -305,6 +349,107 @@ def test_prepare_matches_staged_calls(ctx):
     assert needy.tolist() == [True, True, False, True]
     for i, k in enumerate(idx):
         np.testing.assert_array_equal(new_pts[new_off[k]:new_off[k] + new_cnt[k]], pts0[i, :cnt0[i]])
+    exp_area, exp_keep, _, _ = mask_bookkeeping(size, rects, kps, off)
+    np.testing.assert_array_equal(area, exp_area)
+    np.testing.assert_array_equal(keep, exp_keep)
+    assert exp_keep.any() and not exp_keep.all() and exp_area[1] < 81 * 181      # (rect 1: two words per row under rect 0)
+    # the seams: 49 rects, the keypoints of rect 40
+    rects, kps, off, _ = edge_targets()
+    area0, keep0 = ctx.flow_targets(rects, kps, off)
+    area, keep, needy = ctx.flow_prepare(rects, rects, kps, off, 0.005, 0.06)[:3]
+    exp_area, exp_keep, _, _ = mask_bookkeeping(size, rects, kps, off)
+    np.testing.assert_array_equal(area, exp_area)
+    np.testing.assert_array_equal(keep, exp_keep)
+    np.testing.assert_array_equal(area0, exp_area)
+    np.testing.assert_array_equal(keep0, exp_keep)
+    kept = np.array([exp_keep[off[k]:off[k + 1]].sum() for k in range(len(rects))])
+    np.testing.assert_array_equal(needy, kept < 0.005 * exp_area)
+
+
+def test_many_small_targets_grow_the_buffers(ctx):
+    """1000 non-overlapping 3 x 3 rects on an 8-pixel grid: more one-tile crops than the 4 * 640 * 360 / 1024 = 900 tiles
+    the corner arena starts with, and an upload that outgrows the staging block's first size -- once through the staged
+    calls, once through fm_flow_prepare, each on a freshly configured state.  Areas are 9, the two point lists are equal
+    track by track and equal the restated goodFeaturesToTrack on every crop; an ordinary call afterwards shows that
+    the grown state still works."""
+    size = (640, 360)
+    f0 = textured_frame(*size, 11)
+    g0 = cv.bgr2gray(f0)
+    n = 1000
+    x0, y0 = 8 * (np.arange(n) % 80), 8 * (np.arange(n) // 80)
+    rects = np.stack([x0, y0, x0 + 2, y0 + 2], 1).astype(float)
+    assert rects[:, 3].max() < size[1]
+    no_kps, off = np.empty((0, 2), np.float32), np.zeros(n + 1, np.int32)
+    flow = make_flow(size)
+    flow.init(f0)
+    area0, _ = ctx.flow_targets(rects, no_kps, off)
+    pts0, cnt0 = ctx.flow_detect(np.arange(n), rects, np.ones(n, np.int32), cap=4)
+    flow = make_flow(size)                              # (fm_flow_configure: a new state, the arena at its first size)
+    flow.init(f0)
+    area, keep, needy, new_pts, new_off, new_cnt, bg = ctx.flow_prepare(rects, rects, no_kps, off, 1., 0.06)
+    np.testing.assert_array_equal(area0, 9)
+    np.testing.assert_array_equal(area, 9)
+    assert needy.all()
+    np.testing.assert_array_equal(new_cnt, cnt0)
+    seen = 0
+    full = np.full((3, 3), 255, np.uint8)
+    for k in range(n):
+        r = rects[k].astype(int)
+        exp = cv.good_features_to_track(g0[r[1]:r[3] + 1, r[0]:r[2] + 1], full, 1000, 0.06, 1)
+        exp = exp.reshape(-1, 2) + np.array(r[:2], np.float32)       # (a 3 x 3 crop's one candidate is its centre: inside the ellipse)
+        np.testing.assert_array_equal(pts0[k, :cnt0[k]], exp, err_msg=f'staged, crop {k}')
+        np.testing.assert_array_equal(new_pts[new_off[k]:new_off[k] + new_cnt[k]], exp, err_msg=f'prepare, crop {k}')
+        seen += len(exp)
+    assert seen > 0
+    # an ordinary call on the grown state
+    rects = np.array([[100, 200, 180, 359], [150, 120, 230, 300], [400, 50, 460, 200], [0, 0, 50, 90]], float)
+    off = np.zeros(5, np.int32)
+    area, keep, needy, new_pts, new_off, new_cnt, bg2 = ctx.flow_prepare(rects, rects, no_kps, off, 0.005, 0.06)
+    exp_area, _, masks, _ = mask_bookkeeping(size, rects, no_kps, off)
+    np.testing.assert_array_equal(area, exp_area)
+    assert needy.all()
+    for k in range(4):
+        r = rects[k].astype(int)
+        md = max(int(np.rint(np.sqrt(exp_area[k]) * 0.06)), 1)
+        exp = cv.good_features_to_track(g0[r[1]:r[3] + 1, r[0]:r[2] + 1], masks[k], 1000, 0.06, md)
+        exp = exp + np.array(r[:2], np.float32)
+        c = (rects[k][:2] + rects[k][2:]) / 2
+        ax = (rects[k][2:] - rects[k][:2] + 1) * 0.5
+        exp = exp[(((exp - c) / ax) ** 2).sum(1) <= 1.]
+        assert len(exp) > 3
+        np.testing.assert_array_equal(new_pts[new_off[k]:new_off[k] + new_cnt[k]], exp)
+
+
+def test_no_targets_after_targets(ctx):
+    """fm_flow_targets and fm_flow_prepare with no tracks, after a call with tracks: the rects of the earlier call are
+    gone from the mask, the background keypoints are the unmasked FAST keypoints of the restatement.  (The call with
+    tracks has a 201 pixel wide rect under a short overlap list: four 64-column words per row, the last one ragged.)"""
+    size = (640, 360)
+    f0 = textured_frame(*size, 5)
+    flow = make_flow(size)
+    flow.init(f0)
+    kp_all = cv.fast_detect(cv.resize_linear_u8(cv.bgr2gray(f0), (64, 36)), 10)
+    rects = np.array([[100, 100, 300, 200], [50, 150, 250, 250], [240, 90, 400, 160], [420, 20, 620, 340]], float)
+    no_kps, off = np.empty((0, 2), np.float32), np.zeros(5, np.int32)
+    exp_area, _, _, mask = mask_bookkeeping(size, rects, no_kps, off)
+    assert 0 < exp_area[1] < 201 * 101
+    mask_small = cv.resize_nearest(mask, (64, 36))
+    kp_masked = kp_all[[mask_small[int(p[1] + 0.5), int(p[0] + 0.5)] != 0 for p in kp_all]]
+    assert 10 < len(kp_masked) < len(kp_all)
+    none = np.zeros((0, 4)), no_kps, np.zeros(1, np.int32)
+    area, _ = ctx.flow_targets(rects, no_kps, off)
+    np.testing.assert_array_equal(area, exp_area)
+    np.testing.assert_array_equal(ctx.flow_background(), kp_masked)
+    area, _ = ctx.flow_targets(*none)
+    assert len(area) == 0
+    np.testing.assert_array_equal(ctx.flow_background(), kp_all)
+    res = ctx.flow_prepare(rects, rects, no_kps, off, 0.005, 0.06)
+    np.testing.assert_array_equal(res[0], exp_area)
+    np.testing.assert_array_equal(res[6], kp_masked)
+    res = ctx.flow_prepare(none[0], none[0], no_kps, none[2], 0.005, 0.06)
+    assert len(res[0]) == 0
+    np.testing.assert_array_equal(res[6], kp_all)
+    np.testing.assert_array_equal(ctx.flow_background(), kp_all)
 
 
 @pytest.mark.parametrize('hammer', ['liteconv', 'osnet'])

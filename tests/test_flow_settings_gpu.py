@@ -82,7 +82,7 @@ def random_points(w, h, n, seed=3):
 
 def seam_points(w, h, levels):
     """60 points placed where random ones do not fall: the columns around x = 256 at level 0 (the 256-thread block
-    boundary of pyr_level_kernel / scharr_kernel; the image centre when the image is narrower), the first and last two
+    boundary of pyr_level_kernel; the image centre when the image is narrower), the first and last two
     rows and columns, the four corner pixels, and the centre of the coarsest level with its four neighbours there."""
     x0 = 254.5 if w > 260 else w / 2 - 1.5
     pts = [(x0 + 0.5 * i, y) for i in range(7) for y in (1.25, h * 0.3, h / 2 + 0.5, h * 0.8, h - 2.25)]
@@ -251,7 +251,9 @@ def test_lk_window_leaves_the_patch(ctx):
 # ------------------------------------------------------------------------------------------------------------------
 PYR_CASES = {
     # name: (size, scale, win, maxLevel)
-    'plain_0.4':         ((600, 338), (0.4, 0.4), 5, 5),     # gray_kernel, resize_linear_kernel, pyrdown_kernel, scharr_kernel
+    'plain_0.4':         ((600, 338), (0.4, 0.4), 5, 5),     # gray_kernel, resize_linear_kernel; one pyr_level_kernel launch + tail
+    'plain_0.6':         ((802, 452), (0.6, 0.6), 5, 5),     # ... 481 x 271, 241 x 136 above 10 000 px (two launches), then the tail
+    'plain_0.6_2levels': ((802, 452), (0.6, 0.6), 5, 1),     # ... pyr_level_kernel with and without a next level, no tail launch
     'tail_only_win5':    ((96, 56), (0.5, 0.5), 5, 5),       # every level <= 10 000 px: pyr_tail_kernel alone (tail == 0)
     'tail_only_win3':    ((96, 56), (0.5, 0.5), 3, 5),       # ... one level more: the depth depends on the window
     'single_level':      ((640, 360), (0.5, 0.5), 5, 0),     # pyr_level_kernel, has_next == false, no tail launch
@@ -264,8 +266,9 @@ PYR_CASES = {
 def test_pyramid_paths(ctx, case):
     """Gray image, every pyramid level and -- through one LK call, which reads the Scharr derivatives of every level --
     the derivative images, where build_pyramid (flow.hip) takes another way than for 1080p at scale 0.5: the plain path
-    (`gray_kernel`, `resize_linear_kernel`, `pyrdown_kernel`, `scharr_kernel`) at a scale other than 0.5, all levels
-    inside `pyr_tail_kernel` (no level above 10 000 px), a single level (`pyr_level_kernel` without a next level and
+    (`gray_kernel` + `resize_linear_kernel` make gray and level 0, then the level loop every path shares) at a scale
+    other than 0.5 -- with one and with two levels above 10 000 px in front of the tail, and with two levels and no tail --,
+    all levels inside `pyr_tail_kernel` (no level above 10 000 px), a single level (`pyr_level_kernel` without a next level and
     no tail), odd level widths early in the fused path, and the window-dependent depth (96 x 56: winSize 5 gives three
     levels, winSize 3 four)."""
     size, scale, win, max_level = PYR_CASES[case]
