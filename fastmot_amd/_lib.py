@@ -433,7 +433,7 @@ class HipContext:
                       trk_feat_f32=None, after_extractor=False):
         """All pairwise terms of this frame in one launch (fm_assoc_prepare2).  after_extractor: the embeddings are the
         batch extract_async enqueued last and may still be in flight (ordered on the device).  Returns True when the
-        terms also reach page-locked host memory, i.e. `assoc_cascade` can run the whole cascade in one call."""
+        terms also reach page-locked host memory, i.e. `assoc_cascade` solves every stage on the host."""
         s = _as(slots, np.int32)
         nT = len(s)
         tb = _as(trk_tlbr, np.float64).reshape(nT, 4)
@@ -451,13 +451,14 @@ class HipContext:
         return bool(host.value)
 
     def cascade_pack(self, group_sizes, conf_rows, conf_active, unconf_rows, hist_rows, hist_labels, det_conf,
-                     motion_weight, max_assoc_cost, fill_val, max_iou_cost, conf_thresh, max_reid_cost):
-        """Packs the arguments of `assoc_cascade` (fm_cascade_in); everything here is known before the embeddings are."""
+                     motion_weight, max_assoc_cost, fill_val, max_iou_cost, conf_thresh, max_reid_cost, per_stage=False):
+        """Packs the arguments of `assoc_cascade` (fm_cascade_in); everything here is known before the embeddings are.
+        per_stage: every stage the device way (FM_CASCADE_PER_STAGE) even where the terms reached the host."""
         off = np.zeros(len(group_sizes) + 1, np.int32)
         np.cumsum(group_sizes, out=off[1:])
         arrs = (off, _as(conf_rows, np.int32), _as(conf_active, np.uint8), _as(unconf_rows, np.int32),
                 _as(hist_rows, np.int32), _as(hist_labels, np.int64), _as(det_conf, np.float64))
-        cin = CascadeIn(len(group_sizes), len(arrs[3]), len(arrs[4]), 0,
+        cin = CascadeIn(len(group_sizes), len(arrs[3]), len(arrs[4]), CASCADE_PER_STAGE if per_stage else 0,
                         *(a.__array_interface__['data'][0] for a in arrs),
                         motion_weight, max_assoc_cost, fill_val, max_iou_cost, conf_thresh, max_reid_cost)
         n_trk = len(arrs[1]) + len(arrs[3])
@@ -520,10 +521,11 @@ class HipContext:
 
 
 CASCADE_HEADER = 16
+CASCADE_PER_STAGE = 1          # fm_cascade_in.flags
 
 
 class CascadeIn(C.Structure):          # fm_cascade_in
-    _fields_ = [('n_groups', C.c_int32), ('n_unconf', C.c_int32), ('n_hist', C.c_int32), ('reserved', C.c_int32),
+    _fields_ = [('n_groups', C.c_int32), ('n_unconf', C.c_int32), ('n_hist', C.c_int32), ('flags', C.c_int32),
                 ('group_off', C.c_void_p), ('conf_rows', C.c_void_p), ('conf_active', C.c_void_p),
                 ('unconf_rows', C.c_void_p), ('hist_rows', C.c_void_p), ('hist_labels', C.c_void_p),
                 ('det_conf', C.c_void_p),

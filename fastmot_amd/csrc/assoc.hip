@@ -214,19 +214,16 @@ __global__ __launch_bounds__(256) void pairwise_kernel(
 // ---------------------------------------------------------------------------------------
 // stage cost matrix (gather + fuse_motion + gate_cost)
 // ---------------------------------------------------------------------------------------
-__global__ void stage_cost_kernel(int stage, int nr, int nc, int nD, const int32_t* __restrict__ rows,
-                                  const int32_t* __restrict__ cols, const int64_t* __restrict__ rlab,
-                                  const int64_t* __restrict__ dlab, const uint8_t* __restrict__ docc,
-                                  const uint8_t* __restrict__ row_has_feat,
-                                  const double* __restrict__ feat, const double* __restrict__ maha,
-                                  const double* __restrict__ iou, double motion_weight,
-                                  double max_cost, double fill_val, double* __restrict__ cost) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nr * nc) return;
-    const int i = idx / nc, j = idx % nc;
-    const int t = rows[i], d = cols[j];
+// THE cost rule: pairwise row t against detection d under the row label the stage uses for t.  The device kernel and
+// the host fill of the one-call cascade (its re-identification matrix included) both call it, so host and device
+// compare the same doubles (-ffp-contract=off) by construction.
+__host__ __device__ inline double stage_cost(int stage, int t, int d, int nD, const double* __restrict__ feat,
+                                             const double* __restrict__ maha, const double* __restrict__ iou,
+                                             const uint8_t* __restrict__ row_has_feat, const uint8_t* __restrict__ docc,
+                                             int64_t rlab, int64_t dlab, double motion_weight, double max_cost,
+                                             double fill_val) {
     const size_t p = (size_t)t * nD + d;
-    const bool lab_bad = rlab[i] != dlab[d];
+    const bool lab_bad = rlab != dlab;
     double c;
     if (stage == FM_STAGE_MATCHING) {
         // tracker.py:326-340 ; utils/matching.py:101-107
@@ -245,7 +242,22 @@ __global__ void stage_cost_kernel(int stage, int nr, int nc, int nD, const int32
         c = feat[p];
         if (lab_bad) c = INF_COST;                   // tracker.py:363-365 (no threshold)
     }
-    cost[idx] = c;
+    return c;
+}
+
+__global__ void stage_cost_kernel(int stage, int nr, int nc, int nD, const int32_t* __restrict__ rows,
+                                  const int32_t* __restrict__ cols, const int64_t* __restrict__ rlab,
+                                  const int64_t* __restrict__ dlab, const uint8_t* __restrict__ docc,
+                                  const uint8_t* __restrict__ row_has_feat,
+                                  const double* __restrict__ feat, const double* __restrict__ maha,
+                                  const double* __restrict__ iou, double motion_weight,
+                                  double max_cost, double fill_val, double* __restrict__ cost) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nr * nc) return;
+    const int i = idx / nc, j = idx % nc;
+    const int t = rows[i], d = cols[j];
+    cost[idx] = stage_cost(stage, t, d, nD, feat, maha, iou, row_has_feat, docc, rlab[i], dlab[d], motion_weight, max_cost,
+                           fill_val);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -572,41 +584,11 @@ int upload(fm_ctx* ctx, DevBuf& buf, const std::vector<std::pair<const void*, si
     return 0;
 }
 
-// Runs the LAP kernel on a device cost matrix [nr][nc]; outputs SciPy-ordered (rows, cols).
-// Outputs (col4row, cost of every assignment) are written by the kernel directly into the pinned host
-// buffer: one stream synchronise, no D2H blit.  m_cost (optional): cost[m_rows[k]][m_cols[k]].
-// h_cost (optional): the same matrix in pinned host memory, already complete (stream synchronised) --
-// small problems are then solved by fm_lap_host (see lap_host.hip for why).
-int run_lap(fm_ctx* ctx, const double* d_cost, int nr, int nc, int32_t* m_rows, int32_t* m_cols,
-            int* n_match, double* m_cost = nullptr, const double* h_cost = nullptr) {
-    *n_match = 0;
-    if (nr == 0 || nc == 0) return 0;
-    const bool transpose = nc < nr;   // SciPy works on the transposed problem when nc < nr
-    const int R = transpose ? nc : nr, C = transpose ? nr : nc;
-    const long rs = transpose ? 1 : nc, cs = transpose ? nc : 1;
-    if (h_cost) {
-        std::vector<int32_t> c4r(R);
-        if (!fm_lap_host(h_cost, R, C, rs, cs, c4r.data())) {
-            fm_set_error("cost matrix is infeasible");
-            return FM_ERR_STATE;
-        }
-        if (!transpose) {
-            for (int i = 0; i < R; ++i) {
-                m_rows[i] = i; m_cols[i] = c4r[i];
-                if (m_cost) m_cost[i] = h_cost[(size_t)i * nc + c4r[i]];
-            }
-        } else {
-            std::vector<int> order(R);
-            for (int i = 0; i < R; ++i) order[i] = i;
-            std::sort(order.begin(), order.end(), [&](int a, int b) { return c4r[a] < c4r[b]; });
-            for (int k = 0; k < R; ++k) {
-                m_rows[k] = c4r[order[k]]; m_cols[k] = order[k];
-                if (m_cost) m_cost[k] = h_cost[(size_t)m_rows[k] * nc + m_cols[k]];
-            }
-        }
-        *n_match = R;
-        return 0;
-    }
+// The LAP kernels on a device cost matrix, R <= C rows x columns at strides (rs, cs): lap64_kernel in registers for
+// C <= 64, lap_kernel with its LDS modes above.  The kernel writes col4row and the cost of every assignment directly
+// into the pinned host buffer (one stream synchronise, no D2H blit) -- *c4r_out / *mcost_out point there.
+int run_lap_device(fm_ctx* ctx, const double* d_cost, int R, int C, long rs, long cs, const int32_t** c4r_out,
+                   const double** mcost_out) {
     const size_t wd_bytes = sizeof(double) * (R + 2 * (size_t)C);
     const size_t wi_bytes = sizeof(int32_t) * (4 * (size_t)C + 2 * (size_t)R);
     int rc = ctx->as_work.reserve(wd_bytes + wi_bytes + 64);
@@ -643,26 +625,48 @@ int run_lap(fm_ctx* ctx, const double* d_cost, int nr, int nc, int32_t* m_rows, 
         FM_HIP(hipMemcpyAsync(ctx->as_out.h, ctx->as_out.d, mc_off + sizeof(double) * R, hipMemcpyDeviceToHost,
                               ctx->s_main));
     FM_HIP(hipStreamSynchronize(ctx->s_main));
-    const int32_t* c4r = ctx->as_out.host<int32_t>();
-    o_mc = reinterpret_cast<double*>(ctx->as_out.host<char>() + mc_off);
-    if (c4r[0] == -2) {
+    *c4r_out = ctx->as_out.host<int32_t>();
+    *mcost_out = reinterpret_cast<const double*>(ctx->as_out.host<char>() + mc_off);
+    if ((*c4r_out)[0] == -2) {
         fm_set_error("cost matrix is infeasible");
         return FM_ERR_STATE;
     }
-    if (!transpose) {
-        for (int i = 0; i < R; ++i) {
-            m_rows[i] = i; m_cols[i] = c4r[i];
-            if (m_cost) m_cost[i] = o_mc[i];
+    return 0;
+}
+
+// Solves the cost matrix [nr][nc]; outputs SciPy-ordered (rows, cols).  m_cost (optional): cost[m_rows[k]][m_cols[k]].
+// h_cost set: the matrix in host memory, complete (stream synchronised if a kernel wrote it) -- solved by fm_lap_host
+// (see lap_host.hip for why), the context is not touched.  Otherwise d_cost on the device, by the LAP kernels.
+int run_lap(fm_ctx* ctx, const double* d_cost, int nr, int nc, int32_t* m_rows, int32_t* m_cols,
+            int* n_match, double* m_cost = nullptr, const double* h_cost = nullptr) {
+    *n_match = 0;
+    if (nr == 0 || nc == 0) return 0;
+    const bool transpose = nc < nr;   // SciPy works on the transposed problem when nc < nr
+    const int R = transpose ? nc : nr, C = transpose ? nr : nc;
+    const long rs = transpose ? 1 : nc, cs = transpose ? nc : 1;
+    std::vector<int32_t> c4r_host;
+    const int32_t* c4r;            // column of every row of the (possibly transposed) problem
+    const double* o_mc = nullptr;  // device solvers: the cost of every such assignment
+    if (h_cost) {
+        c4r_host.resize(R);
+        if (!fm_lap_host(h_cost, R, C, rs, cs, c4r_host.data())) {
+            fm_set_error("cost matrix is infeasible");
+            return FM_ERR_STATE;
         }
+        c4r = c4r_host.data();
     } else {
-        // rows of the original problem ascending: argsort(col4row)
-        std::vector<int> order(R);
-        for (int i = 0; i < R; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return c4r[a] < c4r[b]; });
-        for (int k = 0; k < R; ++k) {
-            m_rows[k] = c4r[order[k]]; m_cols[k] = order[k];
-            if (m_cost) m_cost[k] = o_mc[order[k]];
-        }
+        int rc = run_lap_device(ctx, d_cost, R, C, rs, cs, &c4r, &o_mc);
+        if (rc) return rc;
+    }
+    // SciPy's output order: rows of the original problem ascending -- argsort(col4row) when it was transposed
+    std::vector<int> order(R);
+    for (int i = 0; i < R; ++i) order[i] = i;
+    if (transpose) std::sort(order.begin(), order.end(), [&](int a, int b) { return c4r[a] < c4r[b]; });
+    for (int k = 0; k < R; ++k) {
+        const int r = order[k];
+        m_rows[k] = transpose ? c4r[r] : r;
+        m_cols[k] = transpose ? r : c4r[r];
+        if (m_cost) m_cost[k] = h_cost ? h_cost[(size_t)m_rows[k] * nc + m_cols[k]] : o_mc[r];
     }
     *n_match = R;
     return 0;
@@ -747,6 +751,15 @@ static int assoc_prepare_impl(fm_ctx* ctx, int metric, int nT, const int32_t* sl
     ctx->as_nD = nD;
     ctx->as_metric = metric;
     ctx->as_mirror = false;
+    if (nT == 0 && nD > 0) {
+        // no terms, but the cascade still splits the detections by their occlusion flags: host copy only
+        FM_CHECK_ARG(det_occluded);
+        int rc = ctx->as_in.reserve(nD);
+        if (rc) return rc;
+        FM_HIP(hipStreamSynchronize(ctx->s_main));   // host mirror reuse
+        memcpy(ctx->as_in.h, det_occluded, nD);
+        ctx->as_off[5] = 0;
+    }
     if (nT == 0 || nD == 0) return 0;
     FM_CHECK_ARG(slots && trk_tlbr && trk_label && det_tlbr && det_label && det_occluded && trk_feat_f32);
     FM_CHECK_ARG(nD <= ctx->emb_n);
@@ -815,37 +828,20 @@ extern "C" int fm_assoc_prepare2(fm_ctx* ctx, int metric, int nT, const int32_t*
 }
 
 // ---------------------------------------------------------------------------------------
-// The association cascade of MultiTracker.update (tracker.py:198-248) in ONE call, on the host, for the problem sizes
-// whose assignment is solved on the host anyway (fm_lap_host: measured ~5x faster than one wavefront at every size,
-// profiles/r02_lap_crossover.txt).  The pairwise terms -- the arithmetic of the stage -- come from pairwise_kernel through
-// as_pair's page-locked mirror; what runs here is what stage_cost_kernel does per stage (a gather, one multiply-add and
-// the gates: the same IEEE doubles, this file is built with -ffp-contract=off for host and device), the solver, and the
-// reference's list bookkeeping between the stages, whose ORDER decides track IDs (utils/matching.py:58-70 with Numba's
-// set iteration order, utils/setorder.py).  Per-stage device launches + host wake-ups + Python round trips cost
-// ~25 us per stage on a GPU the two networks keep busy (profiles/r05_pipeline_trace.txt: 214 us between the embeddings
-// and the end of the step for 46 us of kernels); larger problems keep the per-stage device path (fm_assoc_stage).
+// The association cascade of MultiTracker.update (tracker.py:198-248) in ONE call: the reference's list bookkeeping between
+// the stages, whose ORDER decides track IDs (utils/matching.py:58-70 with Numba's set iteration order), written once around
+// ONE stage solver that has two ways of solving a stage.
+//   host terms:   small problems, whose terms also lie in as_pair's page-locked mirror.  The cost matrix is filled on the host
+//                 by the rule stage_cost_kernel applies and solved there (fm_lap_host is ~5x faster than one wavefront at every
+//                 size, profiles/r02_lap_crossover.txt): no launch, no host wake-up, ~25 us per stage on a GPU the two networks
+//                 keep busy (profiles/r05_pipeline_trace.txt).
+//   device terms: stage_cost_kernel, then the LAP / greedy kernels or -- per stage, by host_lap_elems -- the host solver on a
+//                 cost matrix the kernel wrote into pinned memory.
 // ---------------------------------------------------------------------------------------
 namespace {
 
-// list(set(range(n)) - set(matched)) as Numba's integer set iterates it (fastmot_amd/utils/setorder.py)
-void unmatched_order(int n, const std::vector<uint8_t>& gone, std::vector<int>& out) {
-    out.clear();
-    for (int k = 0; k < n; ++k)
-        if (!gone[k]) out.push_back(k);
-    int size = 16;
-    while (size < 2 * n) size <<= 1;
-    const int min_entries = std::max(2 * (int)out.size(), 16);
-    if (4 * min_entries > size || size <= 16) return;
-    while ((size >> 1) >= min_entries) size >>= 1;
-    const int mask = size - 1;
-    if (out.empty() || out.back() <= mask) return;
-    std::vector<int> table(size, -1);
-    for (int k : out) table[numba_set_slot(table, k)] = k;      // (numba_set.h: shared with tilemerge.hip)
-    out.clear();
-    for (int k : table)
-        if (k >= 0) out.push_back(k);
-}
-
+// The pairwise terms and per-row / per-detection inputs of one frame as the host sees them.  feat == nullptr: the terms
+// lie on the device only (as_pair) and every stage is solved the device way.
 struct Pairwise {
     const double *feat, *maha, *iou;
     const uint8_t* has_feat;
@@ -854,231 +850,36 @@ struct Pairwise {
     int nD;
 };
 
-// one linear-assignment stage (utils/matching.py:10-30,58-70): rows[] = pairwise rows, cols = detection ids.
-// matches: (index into rows[], detection id); u_rows: indices into rows[]; u_cols: detection ids.
-int lap_stage(fm_ctx* ctx, const Pairwise& P, int stage, const int32_t* rows, int nr, const std::vector<int>& cols,
-              double motion_weight, double max_cost, double fill_val, std::vector<double>& cost,
-              std::vector<std::pair<int, int>>& matches, std::vector<int>& u_rows, std::vector<int>& u_cols) {
-    const int nc = (int)cols.size();
-    matches.clear();
-    std::vector<uint8_t> rgone(nr, 0), cgone(nc, 0);
-    std::vector<int32_t> m_rows, m_cols;
-    std::vector<double> m_cost;
-    int n_match = 0;
-    if (nr > 0 && nc > 0) {
-        cost.resize((size_t)nr * nc);
-        const double norm_factor = 1. / CHI_SQ_INV_95, f_weight = 1. - motion_weight;
-        for (int i = 0; i < nr; ++i) {
-            const int t = rows[i];
-            for (int j = 0; j < nc; ++j) {
-                const int d = cols[j];
-                const size_t p = (size_t)t * P.nD + d;
-                const bool lab_bad = P.tlab[t] != P.dlab[d];
-                double c;
-                if (stage == FM_STAGE_MATCHING) {        // tracker.py:326-340 ; utils/matching.py:101-107
-                    const bool empty = (!P.has_feat[t]) || P.docc[d];
-                    const double f = empty ? fill_val : P.feat[p];
-                    const double md = P.maha[p];
-                    c = f_weight * f + (motion_weight * norm_factor) * md;
-                    if (md > CHI_SQ_INV_95) c = INF_COST;
-                    if (lab_bad || c > max_cost) c = INF_COST;
-                } else {                                 // tracker.py:351-352
-                    c = P.iou[p];
-                    if (lab_bad || c > max_cost) c = INF_COST;
-                }
-                cost[(size_t)i * nc + j] = c;
-            }
-        }
-        const int mn = nr < nc ? nr : nc;
-        m_rows.resize(mn); m_cols.resize(mn); m_cost.resize(mn);
-        int rc = run_lap(ctx, nullptr, nr, nc, m_rows.data(), m_cols.data(), &n_match, m_cost.data(), cost.data());
-        if (rc) return rc;
-        for (int k = 0; k < n_match; ++k) { rgone[m_rows[k]] = 1; cgone[m_cols[k]] = 1; }
-    }
-    std::vector<int> uc;
-    unmatched_order(nr, rgone, u_rows);
-    unmatched_order(nc, cgone, uc);
-    u_cols.clear();
-    for (int c : uc) u_cols.push_back(cols[c]);
-    for (int k = 0; k < n_match; ++k) {
-        if (m_cost[k] < INF_COST) matches.emplace_back(m_rows[k], cols[m_cols[k]]);
-        else { u_rows.push_back(m_rows[k]); u_cols.push_back(cols[m_cols[k]]); }
-    }
-    return 0;
+void stage_cost_host(const Pairwise& P, int stage, int nr, const int32_t* rows, int nc, const int32_t* cols,
+                     const int64_t* rlab, double motion_weight, double max_cost, double fill_val, double* cost) {
+    for (int i = 0; i < nr; ++i)
+        for (int j = 0; j < nc; ++j)
+            cost[(size_t)i * nc + j] = stage_cost(stage, rows[i], cols[j], P.nD, P.feat, P.maha, P.iou, P.has_feat, P.docc,
+                                                  rlab[i], P.dlab[cols[j]], motion_weight, max_cost, fill_val);
 }
 
-}  // namespace
-
-static int cascade_run(const Pairwise& P, int nT, int nD, const fm_cascade_in* in, int32_t* out, int out_cap) {
-    fm_ctx* ctx = nullptr;          // (run_lap's host branch does not touch the context)
-    FM_CHECK_ARG(in && out && in->n_groups >= 0 && in->n_unconf >= 0 && in->n_hist >= 0 && nT > 0 && nD > 0);
-    FM_CHECK_ARG(in->group_off && in->det_conf);
-    const int n_conf = in->group_off[in->n_groups];
-    FM_CHECK_ARG(n_conf >= 0 && (n_conf == 0 || (in->conf_rows && in->conf_active)));
-    FM_CHECK_ARG(in->n_unconf == 0 || in->unconf_rows);
-    FM_CHECK_ARG(in->n_hist == 0 || (in->hist_rows && in->hist_labels));
-    for (int i = 0; i < n_conf; ++i) FM_CHECK_ARG(in->conf_rows[i] >= 0 && in->conf_rows[i] < nT);
-    for (int i = 0; i < in->n_unconf; ++i) FM_CHECK_ARG(in->unconf_rows[i] >= 0 && in->unconf_rows[i] < nT);
-    for (int i = 0; i < in->n_hist; ++i) FM_CHECK_ARG(in->hist_rows[i] >= 0 && in->hist_rows[i] < nT);
-    FM_CHECK_ARG(out_cap >= FM_CASCADE_HEADER + 3 * (n_conf + in->n_unconf) + 3 * nD);
-    std::vector<double> cost;
-    std::vector<std::pair<int, int>> m;
-    std::vector<int> u_rows, u_det(nD), nxt;
-    for (int d = 0; d < nD; ++d) u_det[d] = d;
-    int32_t* hdr = out;
-    int32_t* w = out + FM_CASCADE_HEADER;
-    // ---- 1st association: motion + embeddings, depth by depth (tracker.py:205-218)
-    std::vector<int> u1;          // indices into conf_rows
-    int n1 = 0;
-    for (int g = 0; g < in->n_groups; ++g) {
-        const int b = in->group_off[g], e = in->group_off[g + 1];
-        if (u_det.empty()) {
-            for (int i = b; i < n_conf; ++i) u1.push_back(i);
-            break;
-        }
-        if (e == b) continue;
-        int rc = lap_stage(ctx, P, FM_STAGE_MATCHING, in->conf_rows + b, e - b, u_det, in->motion_weight,
-                           in->max_assoc_cost, in->fill_val, cost, m, u_rows, nxt);
-        if (rc) return rc;
-        for (auto& mm : m) { *w++ = in->conf_rows[b + mm.first]; *w++ = mm.second; ++n1; }
-        for (int r : u_rows) u1.push_back(b + r);
-        u_det.swap(nxt);
-    }
-    // ---- 2nd association with IoU: the active ones among the unmatched (tracker.py:220-226)
-    std::vector<int32_t> act_rows;
-    std::vector<int> inact;
-    for (int i : u1) {
-        if (in->conf_active[i]) act_rows.push_back(in->conf_rows[i]);
-        else inact.push_back(in->conf_rows[i]);
-    }
-    int rc = lap_stage(ctx, P, FM_STAGE_IOU, act_rows.data(), (int)act_rows.size(), u_det, 0., in->max_iou_cost, 1., cost,
-                       m, u_rows, nxt);
-    if (rc) return rc;
-    const int n2 = (int)m.size();
-    for (auto& mm : m) { *w++ = act_rows[mm.first]; *w++ = mm.second; }
-    std::vector<int> u2;
-    for (int r : u_rows) u2.push_back(act_rows[r]);
-    u_det.swap(nxt);
-    // ---- 3rd association with unconfirmed tracks (tracker.py:228-231)
-    rc = lap_stage(ctx, P, FM_STAGE_IOU, in->unconf_rows, in->n_unconf, u_det, 0., in->max_iou_cost, 1., cost, m, u_rows, nxt);
-    if (rc) return rc;
-    const int n3 = (int)m.size();
-    for (auto& mm : m) { *w++ = in->unconf_rows[mm.first]; *w++ = mm.second; }
-    std::vector<int> u3;
-    for (int r : u_rows) u3.push_back(in->unconf_rows[r]);
-    u_det.swap(nxt);
-    for (int r : inact) *w++ = r;
-    for (int r : u2) *w++ = r;
-    for (int r : u3) *w++ = r;
-    // ---- reID with the track history (tracker.py:233-240,355-366; greedy: utils/matching.py:74-97)
-    std::vector<int> valid, invalid;
-    for (int d : u_det) {
-        if (!(in->det_conf[d] >= in->conf_thresh)) continue;
-        (P.docc[d] ? invalid : valid).push_back(d);
-    }
-    const int nh = in->n_hist, nv = (int)valid.size();
-    int n_reid = 0;
-    std::vector<uint8_t> taken(nv, 0);
-    if (nh > 0 && nv > 0) {
-        cost.resize((size_t)nh * nv);
-        for (int i = 0; i < nh; ++i)
-            for (int j = 0; j < nv; ++j) {
-                const int d = valid[j];
-                cost[(size_t)i * nv + j] = in->hist_labels[i] != P.dlab[d] ? INF_COST : P.feat[(size_t)in->hist_rows[i] * nD + d];
-            }
-        std::vector<uint8_t> ralive(nh, 1);
-        const int iters = nh < nv ? nh : nv;
-        for (int it = 0; it < iters; ++it) {
-            int bi = -1, bj = -1;
-            double bv = 0.;
-            for (int i = 0; i < nh; ++i) {           // np.argmin of the remaining sub-matrix: first minimum in row-major order
-                if (!ralive[i]) continue;
-                for (int j = 0; j < nv; ++j) {
-                    if (taken[j]) continue;
-                    const double c = cost[(size_t)i * nv + j];
-                    if (bi < 0 || c < bv) { bv = c; bi = i; bj = j; }
-                }
-            }
-            if (bi < 0 || !(bv <= in->max_reid_cost)) break;
-            *w++ = bi; *w++ = valid[bj];
-            ++n_reid;
-            ralive[bi] = 0;
-            taken[bj] = 1;
-        }
-    }
-    for (int d : invalid) *w++ = d;
-    int n_rest = 0;
-    for (int j = 0; j < nv; ++j)
-        if (!taken[j]) { *w++ = valid[j]; ++n_rest; }
-    hdr[0] = n1; hdr[1] = n2; hdr[2] = n3;
-    hdr[3] = (int)inact.size(); hdr[4] = (int)u2.size(); hdr[5] = (int)u3.size();
-    hdr[6] = n_reid; hdr[7] = (int)invalid.size(); hdr[8] = n_rest;
-    hdr[9] = (int)(w - out);
-    return 0;
-}
-
-extern "C" int fm_assoc_cascade(fm_ctx* ctx, const fm_cascade_in* in, int32_t* out, int out_cap) {
-    FM_CHECK_ARG(ctx);
-    const int nT = ctx->as_nT, nD = ctx->as_nD;
-    if (!ctx->as_mirror || nT == 0 || nD == 0) {
-        fm_set_error("fm_assoc_cascade: no host-side pairwise terms (fm_assoc_prepare2 on a small problem first)");
-        return FM_ERR_STATE;
-    }
-    FM_HIP(hipEventSynchronize(ctx->ev_pair));
-    const size_t mat = (size_t)nT * nD;
-    const double* pm = ctx->as_pair.host<double>();
-    const char* hin = ctx->as_in.host<char>();
-    Pairwise P{pm, pm + mat, pm + 2 * mat, reinterpret_cast<const uint8_t*>(pm + 3 * mat),
-               reinterpret_cast<const int64_t*>(hin + ctx->as_off[2]), reinterpret_cast<const int64_t*>(hin + ctx->as_off[4]),
-               reinterpret_cast<const uint8_t*>(hin + ctx->as_off[5]), nD};
-    return cascade_run(P, nT, nD, in, out, out_cap);
-}
-
-extern "C" int fm_cascade_host(int nT, int nD, const double* feat, const double* maha, const double* iou,
-                               const uint8_t* row_has_feat, const int64_t* trk_label, const int64_t* det_label,
-                               const uint8_t* det_occluded, const fm_cascade_in* in, int32_t* out, int out_cap) {
-    FM_CHECK_ARG(feat && maha && iou && row_has_feat && trk_label && det_label && det_occluded);
-    Pairwise P{feat, maha, iou, row_has_feat, trk_label, det_label, det_occluded, nD};
-    return cascade_run(P, nT, nD, in, out, out_cap);
-}
-
-extern "C" int fm_assoc_get_pairwise(fm_ctx* ctx, double* feat, double* maha, double* iou) {
-    FM_CHECK_ARG(ctx);
-    const size_t mat = sizeof(double) * (size_t)ctx->as_nT * ctx->as_nD;
-    if (mat == 0) return 0;
-    FM_HIP(hipStreamSynchronize(ctx->s_main));
-    if (!ctx->as_in_device) FM_HIP(hipStreamSynchronize(ctx->s_ext));   // (an early launch ran there)
-    char* pr = ctx->as_pair.dev<char>();
-    if (feat) FM_HIP(hipMemcpy(feat, pr, mat, hipMemcpyDeviceToHost));
-    if (maha) FM_HIP(hipMemcpy(maha, pr + mat, mat, hipMemcpyDeviceToHost));
-    if (iou) FM_HIP(hipMemcpy(iou, pr + 2 * mat, mat, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int fm_assoc_stage(fm_ctx* ctx, int stage, int solver, int nr, const int32_t* rows, int nc,
-                              const int32_t* cols, double motion_weight, double max_cost,
-                              double fill_val, const int64_t* row_label_override, int32_t* m_rows,
-                              int32_t* m_cols, uint8_t* match_gated, int* n_match, double* cost_out) {
-    FM_CHECK_ARG(ctx && n_match && nr >= 0 && nc >= 0);
-    FM_CHECK_ARG(stage >= FM_STAGE_MATCHING && stage <= FM_STAGE_REID && (solver == 0 || solver == 1));
+// One association stage: the gated cost matrix of rows[] x cols[] (indices into the pairwise terms; rlab: the label the
+// stage uses for each row) and its solver -- 0: rectangular LAP, 1: greedy while cost <= max_cost.  Outputs local
+// (m_rows, m_cols) in the solver's order, n_match, m_cost (LAP only, may be null): the cost of each match.
+// hcost: scratch of the host way.  cost_out (device way only, may be null): the cost matrix.
+int solve_stage(fm_ctx* ctx, const Pairwise& P, int stage, int solver, int nr, const int32_t* rows, int nc,
+                const int32_t* cols, const int64_t* rlab, double motion_weight, double max_cost, double fill_val,
+                int32_t* m_rows, int32_t* m_cols, double* m_cost, int* n_match, std::vector<double>& hcost,
+                double* cost_out = nullptr) {
     *n_match = 0;
     if (nr == 0 || nc == 0) return 0;
-    FM_CHECK_ARG(rows && cols && m_rows && m_cols);
-    const int nT = ctx->as_nT, nD = ctx->as_nD;
-    for (int i = 0; i < nr; ++i) FM_CHECK_ARG(rows[i] >= 0 && rows[i] < nT);
-    for (int j = 0; j < nc; ++j) FM_CHECK_ARG(cols[j] >= 0 && cols[j] < nD);
-    // row labels: override or the labels given at prepare time (gathered on the host: tiny)
-    std::vector<int64_t> rlab(nr);
-    if (row_label_override) memcpy(rlab.data(), row_label_override, sizeof(int64_t) * nr);
-    else {
-        const int64_t* tl = reinterpret_cast<const int64_t*>(ctx->as_in.host<char>() + ctx->as_off[2]);
-        for (int i = 0; i < nr; ++i) rlab[i] = tl[rows[i]];
+    if (P.feat) {
+        hcost.resize((size_t)nr * nc);
+        stage_cost_host(P, stage, nr, rows, nc, cols, rlab, motion_weight, max_cost, fill_val, hcost.data());
+        if (solver == 0) return run_lap(ctx, nullptr, nr, nc, m_rows, m_cols, n_match, m_cost, hcost.data());
+        *n_match = fm_greedy_host(hcost.data(), nr, nc, max_cost, m_rows, m_cols);
+        return 0;
     }
+    const int nT = ctx->as_nT, nD = ctx->as_nD;
     std::vector<size_t> offs;
     char* si = nullptr;
     int rc = upload(ctx, ctx->as_stage_in,
-                    {{rows, sizeof(int32_t) * nr}, {cols, sizeof(int32_t) * nc},
-                     {rlab.data(), sizeof(int64_t) * nr}}, offs, &si,
+                    {{rows, sizeof(int32_t) * nr}, {cols, sizeof(int32_t) * nc}, {rlab, sizeof(int64_t) * nr}}, offs, &si,
                     FM_ZERO_COPY_TRACKS > 0 && (size_t)nr * nc <= 65536);
     if (rc) return rc;
     const size_t cbytes = sizeof(double) * (size_t)nr * nc;
@@ -1108,16 +909,230 @@ extern "C" int fm_assoc_stage(fm_ctx* ctx, int stage, int solver, int nr, const 
     if (host_lap) FM_HIP(hipStreamSynchronize(ctx->s_main));
     else if (cost_out)   // tests / debugging only
         FM_HIP(hipMemcpyAsync(ctx->as_cost.h, ctx->as_cost.d, cbytes, hipMemcpyDeviceToHost, ctx->s_main));
-    std::vector<double> mcost(solver == 0 && match_gated ? (size_t)(nr < nc ? nr : nc) : 0);
     if (solver == 0)
-        rc = run_lap(ctx, ctx->as_cost.dev<double>(), nr, nc, m_rows, m_cols, n_match,
-                     mcost.empty() ? nullptr : mcost.data(), host_lap ? ctx->as_cost.host<double>() : nullptr);
+        rc = run_lap(ctx, ctx->as_cost.dev<double>(), nr, nc, m_rows, m_cols, n_match, m_cost,
+                     host_lap ? ctx->as_cost.host<double>() : nullptr);
     else rc = run_greedy(ctx, ctx->as_cost.dev<double>(), nr, nc, max_cost, m_rows, m_cols, n_match);
     if (rc) return rc;
-    if (solver == 0 && match_gated)
-        for (int k = 0; k < *n_match; ++k)   // utils/matching.py:65
-            match_gated[k] = mcost[k] < INF_COST ? 0 : 1;
     if (cost_out) memcpy(cost_out, ctx->as_cost.host<double>(), cbytes);
+    return 0;
+}
+
+// one linear-assignment stage (utils/matching.py:10-30,58-70): rows[] = pairwise rows, cols = detection ids.
+// matches: (index into rows[], detection id); u_rows: indices into rows[]; u_cols: detection ids.
+int lap_stage(fm_ctx* ctx, const Pairwise& P, int stage, const int32_t* rows, int nr, const std::vector<int>& cols,
+              double motion_weight, double max_cost, double fill_val, std::vector<double>& hcost,
+              std::vector<std::pair<int, int>>& matches, std::vector<int>& u_rows, std::vector<int>& u_cols) {
+    const int nc = (int)cols.size(), mn = nr < nc ? nr : nc;
+    matches.clear();
+    std::vector<uint8_t> rgone(nr, 0), cgone(nc, 0);
+    std::vector<int32_t> m_rows(mn), m_cols(mn);
+    std::vector<double> m_cost(mn);
+    std::vector<int64_t> rlab(nr);
+    if (nc > 0)     // (an empty side has no labels: P.tlab is then not read)
+        for (int i = 0; i < nr; ++i) rlab[i] = P.tlab[rows[i]];
+    int n_match = 0;
+    int rc = solve_stage(ctx, P, stage, 0, nr, rows, nc, cols.data(), rlab.data(), motion_weight, max_cost, fill_val,
+                         m_rows.data(), m_cols.data(), m_cost.data(), &n_match, hcost);
+    if (rc) return rc;
+    for (int k = 0; k < n_match; ++k) { rgone[m_rows[k]] = 1; cgone[m_cols[k]] = 1; }
+    std::vector<int> uc;
+    numba_difference_order(nr, rgone, u_rows);      // (numba_set.h)
+    numba_difference_order(nc, cgone, uc);
+    u_cols.clear();
+    for (int c : uc) u_cols.push_back(cols[c]);
+    for (int k = 0; k < n_match; ++k) {
+        if (m_cost[k] < INF_COST) matches.emplace_back(m_rows[k], cols[m_cols[k]]);
+        else { u_rows.push_back(m_rows[k]); u_cols.push_back(cols[m_cols[k]]); }
+    }
+    return 0;
+}
+
+// ctx: null for fm_cascade_host (the host way does not touch the context).  An empty side needs no terms: without
+// detections every row ends in its stage's unmatched list, without rows the confident detections start new tracks.
+int cascade_run(fm_ctx* ctx, const Pairwise& P, int nT, int nD, const fm_cascade_in* in, int32_t* out, int out_cap) {
+    FM_CHECK_ARG(in && out && in->n_groups >= 0 && in->n_unconf >= 0 && in->n_hist >= 0 && nT >= 0 && nD >= 0);
+    FM_CHECK_ARG(in->group_off && (nD == 0 || in->det_conf));
+    const int n_conf = in->group_off[in->n_groups];
+    FM_CHECK_ARG(n_conf >= 0 && (n_conf == 0 || (in->conf_rows && in->conf_active)));
+    FM_CHECK_ARG(in->n_unconf == 0 || in->unconf_rows);
+    FM_CHECK_ARG(in->n_hist == 0 || (in->hist_rows && in->hist_labels));
+    for (int i = 0; i < n_conf; ++i) FM_CHECK_ARG(in->conf_rows[i] >= 0 && in->conf_rows[i] < nT);
+    for (int i = 0; i < in->n_unconf; ++i) FM_CHECK_ARG(in->unconf_rows[i] >= 0 && in->unconf_rows[i] < nT);
+    for (int i = 0; i < in->n_hist; ++i) FM_CHECK_ARG(in->hist_rows[i] >= 0 && in->hist_rows[i] < nT);
+    FM_CHECK_ARG(out_cap >= FM_CASCADE_HEADER + 3 * (n_conf + in->n_unconf) + 3 * nD);
+    std::vector<double> hcost;
+    std::vector<std::pair<int, int>> m;
+    std::vector<int> u_rows, u_det(nD), nxt;
+    for (int d = 0; d < nD; ++d) u_det[d] = d;
+    int32_t* hdr = out;
+    int32_t* w = out + FM_CASCADE_HEADER;
+    // ---- 1st association: motion + embeddings, depth by depth (tracker.py:205-218)
+    std::vector<int> u1;          // indices into conf_rows
+    int n1 = 0;
+    for (int g = 0; g < in->n_groups; ++g) {
+        const int b = in->group_off[g], e = in->group_off[g + 1];
+        if (u_det.empty()) {
+            for (int i = b; i < n_conf; ++i) u1.push_back(i);
+            break;
+        }
+        if (e == b) continue;
+        int rc = lap_stage(ctx, P, FM_STAGE_MATCHING, in->conf_rows + b, e - b, u_det, in->motion_weight,
+                           in->max_assoc_cost, in->fill_val, hcost, m, u_rows, nxt);
+        if (rc) return rc;
+        for (auto& mm : m) { *w++ = in->conf_rows[b + mm.first]; *w++ = mm.second; ++n1; }
+        for (int r : u_rows) u1.push_back(b + r);
+        u_det.swap(nxt);
+    }
+    // ---- 2nd association with IoU: the active ones among the unmatched (tracker.py:220-226)
+    std::vector<int32_t> act_rows;
+    std::vector<int> inact;
+    for (int i : u1) {
+        if (in->conf_active[i]) act_rows.push_back(in->conf_rows[i]);
+        else inact.push_back(in->conf_rows[i]);
+    }
+    int rc = lap_stage(ctx, P, FM_STAGE_IOU, act_rows.data(), (int)act_rows.size(), u_det, 0., in->max_iou_cost, 1., hcost,
+                       m, u_rows, nxt);
+    if (rc) return rc;
+    const int n2 = (int)m.size();
+    for (auto& mm : m) { *w++ = act_rows[mm.first]; *w++ = mm.second; }
+    std::vector<int> u2;
+    for (int r : u_rows) u2.push_back(act_rows[r]);
+    u_det.swap(nxt);
+    // ---- 3rd association with unconfirmed tracks (tracker.py:228-231)
+    rc = lap_stage(ctx, P, FM_STAGE_IOU, in->unconf_rows, in->n_unconf, u_det, 0., in->max_iou_cost, 1., hcost, m, u_rows, nxt);
+    if (rc) return rc;
+    const int n3 = (int)m.size();
+    for (auto& mm : m) { *w++ = in->unconf_rows[mm.first]; *w++ = mm.second; }
+    std::vector<int> u3;
+    for (int r : u_rows) u3.push_back(in->unconf_rows[r]);
+    u_det.swap(nxt);
+    for (int r : inact) *w++ = r;
+    for (int r : u2) *w++ = r;
+    for (int r : u3) *w++ = r;
+    // ---- reID with the track history (tracker.py:233-240,355-366), greedy (utils/matching.py:74-97)
+    std::vector<int> valid, invalid;
+    for (int d : u_det) {
+        if (!(in->det_conf[d] >= in->conf_thresh)) continue;
+        (P.docc[d] ? invalid : valid).push_back(d);
+    }
+    const int nh = in->n_hist, nv = (int)valid.size(), mn = nh < nv ? nh : nv;
+    std::vector<int32_t> g_rows(mn), g_cols(mn);
+    int n_reid = 0;
+    rc = solve_stage(ctx, P, FM_STAGE_REID, 1, nh, in->hist_rows, nv, valid.data(), in->hist_labels, 0., in->max_reid_cost,
+                     1., g_rows.data(), g_cols.data(), nullptr, &n_reid, hcost);
+    if (rc) return rc;
+    std::vector<uint8_t> taken(nv, 0);
+    for (int k = 0; k < n_reid; ++k) {
+        *w++ = g_rows[k]; *w++ = valid[g_cols[k]];
+        taken[g_cols[k]] = 1;
+    }
+    for (int d : invalid) *w++ = d;
+    int n_rest = 0;
+    for (int j = 0; j < nv; ++j)
+        if (!taken[j]) { *w++ = valid[j]; ++n_rest; }
+    hdr[0] = n1; hdr[1] = n2; hdr[2] = n3;
+    hdr[3] = (int)inact.size(); hdr[4] = (int)u2.size(); hdr[5] = (int)u3.size();
+    hdr[6] = n_reid; hdr[7] = (int)invalid.size(); hdr[8] = n_rest;
+    hdr[9] = (int)(w - out);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int fm_unmatched_order(int n, const int32_t* matched, int n_matched, int32_t* out) {
+    FM_CHECK_ARG(n >= 0 && n_matched >= 0 && (n_matched == 0 || matched) && (n == 0 || out));
+    std::vector<uint8_t> gone(n, 0);
+    for (int k = 0; k < n_matched; ++k)
+        if (matched[k] >= 0 && matched[k] < n) gone[matched[k]] = 1;
+    std::vector<int> order;
+    numba_difference_order(n, gone, order);
+    std::copy(order.begin(), order.end(), out);
+    return (int)order.size();
+}
+
+extern "C" int fm_assoc_cascade(fm_ctx* ctx, const fm_cascade_in* in, int32_t* out, int out_cap) {
+    FM_CHECK_ARG(ctx && in);
+    const int nT = ctx->as_nT, nD = ctx->as_nD;
+    // what the last prepare left in as_in's host copy: everything for a full problem, the occlusion flags alone when there
+    // are no rows, nothing when there are no detections (the labels of an empty side are never read: null)
+    const char* hin = ctx->as_in.host<char>();
+    Pairwise P{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nD};
+    if (nD > 0) P.docc = reinterpret_cast<const uint8_t*>(hin + ctx->as_off[5]);
+    if (nT > 0 && nD > 0) {
+        P.tlab = reinterpret_cast<const int64_t*>(hin + ctx->as_off[2]);
+        P.dlab = reinterpret_cast<const int64_t*>(hin + ctx->as_off[4]);
+    }
+    if (ctx->as_mirror && !(in->flags & FM_CASCADE_PER_STAGE)) {      // the host way
+        FM_HIP(hipEventSynchronize(ctx->ev_pair));
+        const size_t mat = (size_t)nT * nD;
+        const double* pm = ctx->as_pair.host<double>();
+        P.feat = pm; P.maha = pm + mat; P.iou = pm + 2 * mat;
+        P.has_feat = reinterpret_cast<const uint8_t*>(pm + 3 * mat);
+    }
+    return cascade_run(ctx, P, nT, nD, in, out, out_cap);
+}
+
+extern "C" int fm_cascade_host(int nT, int nD, const double* feat, const double* maha, const double* iou,
+                               const uint8_t* row_has_feat, const int64_t* trk_label, const int64_t* det_label,
+                               const uint8_t* det_occluded, const fm_cascade_in* in, int32_t* out, int out_cap) {
+    FM_CHECK_ARG(nT >= 0 && nD >= 0 && (nD == 0 || det_occluded));
+    FM_CHECK_ARG(nT == 0 || nD == 0 || (feat && maha && iou && row_has_feat && trk_label && det_label));
+    Pairwise P{feat, maha, iou, row_has_feat, trk_label, det_label, det_occluded, nD};
+    return cascade_run(nullptr, P, nT, nD, in, out, out_cap);
+}
+
+extern "C" int fm_stage_cost_host(int stage, int nT, int nD, const double* feat, const double* maha, const double* iou,
+                                  const uint8_t* row_has_feat, const int64_t* det_label, const uint8_t* det_occluded,
+                                  int nr, const int32_t* rows, int nc, const int32_t* cols, const int64_t* row_labels,
+                                  double motion_weight, double max_cost, double fill_val, double* cost) {
+    FM_CHECK_ARG(stage >= FM_STAGE_MATCHING && stage <= FM_STAGE_REID && nr >= 0 && nc >= 0);
+    if (nr == 0 || nc == 0) return 0;
+    FM_CHECK_ARG(feat && maha && iou && row_has_feat && det_label && det_occluded && rows && cols && row_labels && cost);
+    for (int i = 0; i < nr; ++i) FM_CHECK_ARG(rows[i] >= 0 && rows[i] < nT);
+    for (int j = 0; j < nc; ++j) FM_CHECK_ARG(cols[j] >= 0 && cols[j] < nD);
+    Pairwise P{feat, maha, iou, row_has_feat, nullptr, det_label, det_occluded, nD};
+    stage_cost_host(P, stage, nr, rows, nc, cols, row_labels, motion_weight, max_cost, fill_val, cost);
+    return 0;
+}
+
+extern "C" int fm_assoc_get_pairwise(fm_ctx* ctx, double* feat, double* maha, double* iou) {
+    FM_CHECK_ARG(ctx);
+    const size_t mat = sizeof(double) * (size_t)ctx->as_nT * ctx->as_nD;
+    if (mat == 0) return 0;
+    FM_HIP(hipStreamSynchronize(ctx->s_main));
+    if (!ctx->as_in_device) FM_HIP(hipStreamSynchronize(ctx->s_ext));   // (an early launch ran there)
+    char* pr = ctx->as_pair.dev<char>();
+    if (feat) FM_HIP(hipMemcpy(feat, pr, mat, hipMemcpyDeviceToHost));
+    if (maha) FM_HIP(hipMemcpy(maha, pr + mat, mat, hipMemcpyDeviceToHost));
+    if (iou) FM_HIP(hipMemcpy(iou, pr + 2 * mat, mat, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int fm_assoc_stage(fm_ctx* ctx, int stage, int solver, int nr, const int32_t* rows, int nc,
+                              const int32_t* cols, double motion_weight, double max_cost,
+                              double fill_val, const int64_t* row_label_override, int32_t* m_rows,
+                              int32_t* m_cols, uint8_t* match_gated, int* n_match, double* cost_out) {
+    FM_CHECK_ARG(ctx && n_match && nr >= 0 && nc >= 0);
+    FM_CHECK_ARG(stage >= FM_STAGE_MATCHING && stage <= FM_STAGE_REID && (solver == 0 || solver == 1));
+    *n_match = 0;
+    if (nr == 0 || nc == 0) return 0;
+    FM_CHECK_ARG(rows && cols && m_rows && m_cols);
+    for (int i = 0; i < nr; ++i) FM_CHECK_ARG(rows[i] >= 0 && rows[i] < ctx->as_nT);
+    for (int j = 0; j < nc; ++j) FM_CHECK_ARG(cols[j] >= 0 && cols[j] < ctx->as_nD);
+    // row labels: override or the labels given at prepare time (gathered on the host: tiny)
+    std::vector<int64_t> rlab(nr);
+    if (row_label_override) memcpy(rlab.data(), row_label_override, sizeof(int64_t) * nr);
+    else {
+        const int64_t* tl = reinterpret_cast<const int64_t*>(ctx->as_in.host<char>() + ctx->as_off[2]);
+        for (int i = 0; i < nr; ++i) rlab[i] = tl[rows[i]];
+    }
+    std::vector<double> mcost(solver == 0 && match_gated ? (size_t)(nr < nc ? nr : nc) : 0), unused;
+    int rc = solve_stage(ctx, Pairwise{}, stage, solver, nr, rows, nc, cols, rlab.data(), motion_weight, max_cost, fill_val,
+                         m_rows, m_cols, mcost.empty() ? nullptr : mcost.data(), n_match, unused, cost_out);
+    if (rc) return rc;
+    for (size_t k = 0; k < mcost.size() && k < (size_t)*n_match; ++k)   // utils/matching.py:65
+        match_gated[k] = mcost[k] < INF_COST ? 0 : 1;
     return 0;
 }
 

@@ -40,6 +40,7 @@ void fm_set_error(const char* fmt, ...);
 // batches up to this many tracks exchange their (tiny) kernel inputs / outputs through pinned,
 // device-mapped host memory instead of blit copies
 bool fm_lap_host(const double* cost, int nr, int nc, long rs, long cs, int32_t* col4row_out);
+int fm_greedy_host(const double* cost, int nr, int nc, double max_cost, int32_t* m_rows, int32_t* m_cols);
 #define FM_ZERO_COPY_TRACKS (ctx->opt_zero_copy_tracks)
 
 struct DevBuf {

@@ -65,3 +65,30 @@ bool fm_lap_host(const double* cost, int nr, int nc, long rs, long cs, int32_t* 
     for (int r = 0; r < nr; ++r) col4row_out[r] = col4row[r];
     return true;
 }
+
+// Greedy matching on a host cost matrix [nr][nc] (utils/matching.py:74-97), the host counterpart of greedy_kernel in
+// assoc.hip: np.argmin of the remaining sub-matrix -- the first minimum in row-major order -- while it is <= max_cost.
+// Returns the number of (m_rows[k], m_cols[k]) pairs, in the order they were picked.
+int fm_greedy_host(const double* cost, int nr, int nc, double max_cost, int32_t* m_rows, int32_t* m_cols) {
+    std::vector<uint8_t> row_alive(nr, 1), col_alive(nc, 1);
+    const int iters = nr < nc ? nr : nc;
+    int n = 0;
+    for (int it = 0; it < iters; ++it) {
+        int bi = -1, bj = -1;
+        double bv = 0.;
+        for (int i = 0; i < nr; ++i) {
+            if (!row_alive[i]) continue;
+            for (int j = 0; j < nc; ++j) {
+                if (!col_alive[j]) continue;
+                const double c = cost[(size_t)i * nc + j];
+                if (bi < 0 || c < bv) { bv = c; bi = i; bj = j; }
+            }
+        }
+        if (bi < 0 || !(bv <= max_cost)) break;
+        m_rows[n] = bi; m_cols[n] = bj;
+        ++n;
+        row_alive[bi] = 0;
+        col_alive[bj] = 0;
+    }
+    return n;
+}

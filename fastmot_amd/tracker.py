@@ -6,7 +6,8 @@ OrderedDict insertion order, CPython set iteration order, list concatenation ord
 
   apply_kalman  -> one fm_trk_step launch for all tracks            (tracker.py:164-183)
   update        -> fm_find_occluded, fm_assoc_prepare (all pairwise terms, one launch),
-                   fm_assoc_stage per cascade stage (cost gather/gate + LAP or greedy kernel),
+                   fm_assoc_cascade (every stage of the cascade and the list bookkeeping between them in one call: on
+                   the host for small problems, cost gather/gate + LAP or greedy kernel per stage otherwise),
                    one fm_trk_update_det launch for all matches, one fm_feat_update launch for
                    all running-mean embeddings, one fm_trk_create launch for all new tracks.
 """
@@ -24,13 +25,12 @@ from .flow import Flow
 from .detector import bind_frame
 from .kalman_filter import KalmanFilter
 from .runtime import get_context
-from .utils.setorder import unmatched_order
 
 LOGGER = logging.getLogger(__name__)
 
 _METRICS = {'EUCLIDEAN': _lib.METRIC_EUCLIDEAN, 'COSINE': _lib.METRIC_COSINE}
-# 0: every association stage through fm_assoc_stage (launch + wait per stage), nothing enqueued ahead of the embeddings --
-# the path of round 5, kept for the A/B and for the tests that compare the two
+# 0: every stage of the cascade solved the device way (FM_CASCADE_PER_STAGE: launch + wait per stage), nothing enqueued
+# ahead of the embeddings -- the path of round 5, kept for the A/B and for the tests that compare the two
 _HOST_CASCADE = os.environ.get('FASTMOT_HOST_CASCADE', '1') != '0'
 
 
@@ -218,36 +218,6 @@ class MultiTracker:
         self._after_kalman(items, next_tlbrs, lost)
 
     # ------------------------------------------------------------------ association
-    def _solve(self, stage, solver, trk_ids, rows, det_ids, cols, **kw):
-        """Runs one association stage on the device; returns local (row, col) matches and the
-        gated mask exactly as scipy.linear_sum_assignment / _greedy_match would order them."""
-        if len(rows) == 0 or len(cols) == 0:
-            return [], [], []
-        m_rows, m_cols, gated, _ = self.ctx.assoc_stage(stage, solver, rows, cols, **kw)
-        return m_rows.tolist(), m_cols.tolist(), gated.tolist()
-
-    @staticmethod
-    def _assignment_matches(nr, nc, row_ids, col_ids, m_rows, m_cols, gated):
-        """utils/matching.py:58-70.  The two set differences run inside @njit in the reference: their iteration order
-        is that of Numba's hash set, not CPython's (utils/setorder.py)."""
-        unmatched_rows = unmatched_order(nr, m_rows)
-        unmatched_cols = unmatched_order(nc, m_cols)
-        unmatched_row_ids = [row_ids[row] for row in unmatched_rows]
-        unmatched_col_ids = [col_ids[col] for col in unmatched_cols]
-        matches = []
-        for row, col, is_gated in zip(m_rows, m_cols, gated):
-            if not is_gated:
-                matches.append((row_ids[row], col_ids[col]))
-            else:
-                unmatched_row_ids.append(row_ids[row])
-                unmatched_col_ids.append(col_ids[col])
-        return matches, unmatched_row_ids, unmatched_col_ids
-
-    def _linear_assignment(self, stage, trk_ids, det_ids, row_of, **kw):
-        rows = [row_of[t] for t in trk_ids]
-        m_rows, m_cols, gated = self._solve(stage, _lib.SOLVER_LAP, trk_ids, rows, det_ids, det_ids, **kw)
-        return self._assignment_matches(len(trk_ids), len(det_ids), trk_ids, det_ids, m_rows, m_cols, gated)
-
     def prepare_detections(self, detections):
         """The part of `update` that depends on the detections only (contiguous copies + find_occluded,
         tracker.py:196).  MOT.step calls it while the ReID network is still running; `update` calls it
@@ -278,22 +248,20 @@ class MultiTracker:
         row_ids = list(self.tracks.keys()) + hist_ids
         row_of = {trk_id: i for i, trk_id in enumerate(row_ids)}
         foreign = self._exchange_gallery(hist_ids) if self.gallery_sync is not None else []
-        assoc_args = trk_feat_f32 = None
-        if len(detections) > 0 and (row_ids or foreign):
-            row_tracks = [self.tracks[t] if t in self.tracks else self.hist_tracks[t] for t in row_ids]
-            # foreign gallery entries (other streams) come after all local rows
-            assoc_args = ([t.slot for t in row_tracks] + self._foreign_slots[:len(foreign)],
-                          np.array([t.tlbr for t in row_tracks] + [np.zeros(4)] * len(foreign)),
-                          [t.label for t in row_tracks] + [e['label'] for e in foreign])
-            trk_feat_f32 = [t not in self.tracks for t in row_ids] + [True] * len(foreign)
+        row_tracks = [self.tracks[t] if t in self.tracks else self.hist_tracks[t] for t in row_ids]
+        # foreign gallery entries (other streams) come after all local rows
+        assoc_args = ([t.slot for t in row_tracks] + self._foreign_slots[:len(foreign)],
+                      np.array([t.tlbr for t in row_tracks] + [np.zeros(4)] * len(foreign)),
+                      [t.label for t in row_tracks] + [e['label'] for e in foreign])
+        trk_feat_f32 = [t not in self.tracks for t in row_ids] + [True] * len(foreign)
         pre = dict(detections=detections, det=(det_tlbr, det_label, det_conf, occluded_det_mask), groups=groups,
                    hist_ids=hist_ids, row_ids=row_ids, row_of=row_of, foreign=foreign, assoc_args=assoc_args,
                    trk_feat_f32=trk_feat_f32, armed=False, cascade=None)
-        if embeddings_in_flight and assoc_args is not None and _HOST_CASCADE:
+        if embeddings_in_flight and len(detections) > 0 and (row_ids or foreign) and _HOST_CASCADE:
             pre['armed'] = True
-            if self.ctx.assoc_prepare(self._metric_id, *assoc_args, det_tlbr, det_label, occluded_det_mask,
-                                      trk_feat_f32=trk_feat_f32, after_extractor=True):
-                pre['cascade'] = self._cascade_pack(pre)
+            self.ctx.assoc_prepare(self._metric_id, *assoc_args, det_tlbr, det_label, occluded_det_mask,
+                                   trk_feat_f32=trk_feat_f32, after_extractor=True)
+            pre['cascade'] = self._cascade_pack(pre)
         return pre
 
     def _cascade_pack(self, pre):
@@ -312,10 +280,12 @@ class MultiTracker:
             [row_of[t] for t in hist_ids] + list(range(n_rows, n_rows + len(foreign))),
             hist_labels + [e['label'] for e in foreign], pre['det'][2],
             self.motion_weight, self.max_assoc_cost, min(self.max_assoc_cost + 0.1, 1.), 1. - self.iou_thresh,
-            self.conf_thresh, self.max_reid_cost)
+            self.conf_thresh, self.max_reid_cost, per_stage=not _HOST_CASCADE)
 
-    def _cascade_host(self, pre):
-        """The cascade of `update` in one library call (fm_assoc_cascade) -> the lists `_cascade_stages` returns."""
+    def _cascade(self, pre):
+        """The cascade of `update` in one library call (fm_assoc_cascade): matches, unmatched track ids, re-identified
+        (history id, detection) pairs, foreign-gallery matches and the detections that start new tracks, in the
+        reference's order."""
         w = self.ctx.assoc_cascade(pre['cascade'])
         n1, n2, n3, nu1, nu2, nu3, n_reid, n_inv, n_rest = w[:9]
         row_ids, hist_ids, foreign = pre['row_ids'], pre['hist_ids'], pre['foreign']
@@ -342,35 +312,25 @@ class MultiTracker:
         n_det = len(detections)
         if pre is None or pre['detections'] is not detections:
             pre = self.update_begin(detections)
-        det_tlbr, det_label, det_conf, occluded_det_mask = pre['det']
-        confirmed_by_depth, unconfirmed = pre['groups']
-        hist_ids, row_ids, row_of, foreign = pre['hist_ids'], pre['row_ids'], pre['row_of'], pre['foreign']
+        det_tlbr, det_label, _, occluded_det_mask = pre['det']
 
-        # ---- device: embeddings + every pairwise term of this frame in one launch
-        host_cascade = False
-        if n_det > 0:
-            on_device = embeddings is ctx.device_emb_host and embeddings is not None
-            if pre['armed'] and on_device:
-                host_cascade = pre['cascade'] is not None          # enqueued by update_begin behind the ReID network
-            else:
-                if pre['armed']:
-                    ctx.synchronize()                              # (the early launch read other embeddings: redo)
+        # ---- device: embeddings + every pairwise term of this frame in one launch, then the cascade in one call
+        on_device = embeddings is ctx.device_emb_host and embeddings is not None
+        if not (pre['armed'] and on_device):                       # (else: enqueued by update_begin behind the ReID network)
+            if pre['armed']:
+                ctx.synchronize()                                  # (the early launch read other embeddings: redo)
+            if n_det > 0:
                 if on_device:
                     ctx.emb_use_device(n_det)
                 else:
                     ctx.emb_upload(embeddings)
                     ctx.device_emb_host = None
-                if row_ids or foreign:
-                    host_cascade = ctx.assoc_prepare(self._metric_id, *pre['assoc_args'], det_tlbr, det_label,
-                                                     occluded_det_mask, trk_feat_f32=pre['trk_feat_f32'])
-                    host_cascade = host_cascade and _HOST_CASCADE
-                    if host_cascade:
-                        pre['cascade'] = self._cascade_pack(pre)
-
-        if host_cascade:
-            matches, u_trk_ids, reid_matches, foreign_matches, new_det_ids = self._cascade_host(pre)
-        else:
-            matches, u_trk_ids, reid_matches, foreign_matches, new_det_ids = self._cascade_stages(pre, n_det)
+            # (on every update, an empty side included: the cascade works on the sizes of the last prepare)
+            ctx.assoc_prepare(self._metric_id, *pre['assoc_args'], det_tlbr, det_label, occluded_det_mask,
+                              trk_feat_f32=pre['trk_feat_f32'])
+        if pre['cascade'] is None:
+            pre['cascade'] = self._cascade_pack(pre)
+        matches, u_trk_ids, reid_matches, foreign_matches, new_det_ids = self._cascade(pre)
 
         # rectify matches that may cause duplicate tracks
         matches, u_trk_ids = self._rectify_matches(matches, u_trk_ids, det_tlbr)
@@ -447,63 +407,6 @@ class MultiTracker:
             ctx.feat_update([trk.slot], [det_id])
             trk.avg_feat.count += 1
             trk.hits = self.confirm_hits
-
-    def _cascade_stages(self, pre, n_det):
-        """The association cascade stage by stage on the device (fm_assoc_stage: cost gather + gate kernel, LAP /
-        greedy kernel or the host solver per stage) -- the path of problems too large for the one-call host cascade,
-        and of `host_lap_elems = 0`.  Returns matches, unmatched track ids, re-identified (history id, detection)
-        pairs, foreign-gallery matches and the detections that start new tracks, in the reference's order."""
-        det_tlbr, det_label, det_conf, occluded_det_mask = pre['det']
-        confirmed_by_depth, unconfirmed = pre['groups']
-        hist_ids, row_ids, row_of, foreign = pre['hist_ids'], pre['row_ids'], pre['row_of'], pre['foreign']
-        # ---- 1st association: motion + embeddings, tracks with small age are prioritized
-        fill_val = min(self.max_assoc_cost + 0.1, 1.)
-        matches1 = []
-        u_trk_ids1 = []
-        u_det_ids = list(range(n_det))
-        for depth, trk_ids in enumerate(confirmed_by_depth):
-            if len(u_det_ids) == 0:
-                u_trk_ids1.extend(itertools.chain.from_iterable(confirmed_by_depth[depth:]))
-                break
-            if len(trk_ids) == 0:
-                continue
-            matches, u_trk_ids, u_det_ids = self._linear_assignment(
-                _lib.STAGE_MATCHING, trk_ids, u_det_ids, row_of, motion_weight=self.motion_weight,
-                max_cost=self.max_assoc_cost, fill_val=fill_val)
-            matches1 += matches
-            u_trk_ids1 += u_trk_ids
-
-        # ---- 2nd association with IoU
-        active = [trk_id for trk_id in u_trk_ids1 if self.tracks[trk_id].active]
-        u_trk_ids1 = [trk_id for trk_id in u_trk_ids1 if not self.tracks[trk_id].active]
-        matches2, u_trk_ids2, u_det_ids = self._linear_assignment(
-            _lib.STAGE_IOU, active, u_det_ids, row_of, max_cost=1. - self.iou_thresh)
-
-        # ---- 3rd association with unconfirmed tracks
-        matches3, u_trk_ids3, u_det_ids = self._linear_assignment(
-            _lib.STAGE_IOU, unconfirmed, u_det_ids, row_of, max_cost=1. - self.iou_thresh)
-
-        # ---- reID with track history
-        u_det_ids = [det_id for det_id in u_det_ids if det_conf[det_id] >= self.conf_thresh]
-        valid_u_det_ids = [det_id for det_id in u_det_ids if not occluded_det_mask[det_id]]
-        invalid_u_det_ids = [det_id for det_id in u_det_ids if occluded_det_mask[det_id]]
-
-        n_hist = len(hist_ids)
-        # quirk Q4 (tracker.py:364): labels come from the first n_hist of ALL history tracks
-        hist_labels = list(itertools.islice((t.label for t in self.hist_tracks.values()), n_hist))
-        n_rows = len(row_ids)
-        m_rows, m_cols, _ = self._solve(_lib.STAGE_REID, _lib.SOLVER_GREEDY, hist_ids,
-                                        [row_of[t] for t in hist_ids] + list(range(n_rows, n_rows + len(foreign))),
-                                        valid_u_det_ids, valid_u_det_ids, max_cost=self.max_reid_cost,
-                                        row_labels=hist_labels + [e['label'] for e in foreign])
-        reid_matches = [(hist_ids[r], valid_u_det_ids[c]) for r, c in zip(m_rows, m_cols) if r < n_hist]
-        foreign_matches = [(foreign[r - n_hist], valid_u_det_ids[c]) for r, c in zip(m_rows, m_cols) if r >= n_hist]
-        taken = set(m_cols)
-        reid_u_det_ids = [det_id for c, det_id in enumerate(valid_u_det_ids) if c not in taken]
-
-        matches = list(itertools.chain(matches1, matches2, matches3))
-        u_trk_ids = list(itertools.chain(u_trk_ids1, u_trk_ids2, u_trk_ids3))
-        return matches, u_trk_ids, reid_matches, foreign_matches, list(itertools.chain(invalid_u_det_ids, reid_u_det_ids))
 
     def _exchange_gallery(self, hist_ids):
         """Hands the local history {id, label, count, avg feature} to the gallery exchange (an asynchronous RCCL

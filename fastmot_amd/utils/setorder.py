@@ -17,36 +17,22 @@ slot k and the survivors of the difference are met in ascending order.  If the t
 minimum for the survivors (max(2 * survivors, 16)) it is halved down to the smallest power of two that still holds
 them, and the survivors are re-inserted in ascending order at `k & mask` with Numba's probe sequence (three linear
 probes, then index = 5 * index + 1 + (perturb >>= 5)); the result is read in slot order."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+
 MINSIZE = 16
 
 
 def unmatched_order(n, matched):
-    gone = set(matched)
-    rest = [k for k in range(n) if k not in gone]
-    size = MINSIZE
-    while size < 2 * n:
-        size <<= 1
-    min_entries = max(2 * len(rest), MINSIZE)
-    if 4 * min_entries > size or size <= MINSIZE:
-        return rest
-    while (size >> 1) >= min_entries:
-        size >>= 1
-    mask = size - 1
-    if not rest or rest[-1] <= mask:
-        return rest                      # nothing wraps: slot k again
-    table = [-1] * size
-    for k in rest:
-        index, perturb = k & mask, k
-        for _ in range(3):
-            if table[index] < 0:
-                break
-            index = (index + 1) & mask
-        else:
-            while table[index] >= 0:
-                perturb >>= 5
-                index = (index * 5 + 1 + perturb) & mask
-        table[index] = k
-    return [k for k in table if k >= 0]
+    """The closed form as the library's cascade executes it (fm_unmatched_order: csrc/numba_set.h)."""
+    m = np.ascontiguousarray(list(matched), np.int32)
+    out = np.empty(n, np.int32)
+    k = _lib.load().fm_unmatched_order(C.c_int(n), _lib._ptr(m), C.c_int(len(m)), _lib._ptr(out))
+    assert k >= 0, _lib.load().fm_last_error()
+    return out[:k].tolist()
 
 
 class IntSet:

@@ -177,13 +177,15 @@ enum {
     FM_STAGE_REID     = 2  /* _reid_cost: feat, label gate only                (tracker.py:355-366) */
 };
 
-/* Builds the gated cost matrix of one association stage from the prepared pairwise terms
- * for the given row / column subsets (indices into the fm_assoc_prepare arrays), then
- * solves it on the device:
+/* One association stage on its own, the device way of fm_assoc_cascade's stage solver (the cascade itself calls that
+ * solver directly; this entry point serves the parity tests and tools): builds the gated cost matrix from the prepared
+ * pairwise terms for the given row / column subsets (indices into the fm_assoc_prepare arrays) with stage_cost_kernel,
+ * then solves it:
  *   solver 0 = rectangular LAP (scipy.optimize.linear_sum_assignment semantics incl.
  *              tie-breaking; utils/matching.py:10-30) followed by the INF_COST un-matching
- *              of utils/matching.py:58-70: match_gated[k]=1 when cost>=1e5.
- *   solver 1 = greedy argmin matching while cost <= max_cost (utils/matching.py:74-97).
+ *              of utils/matching.py:58-70: match_gated[k]=1 when cost>=1e5.  Device kernels, or the host solver on
+ *              the matrix the kernel wrote into pinned memory when nr * nc <= host_lap_elems.
+ *   solver 1 = greedy argmin matching while cost <= max_cost (utils/matching.py:74-97), device kernel.
  * row_label_override: _reid_cost quirk (tracker.py:364) -- labels used for the rows; NULL
  * = labels given to fm_assoc_prepare.
  * Outputs: m_rows/m_cols (local indices into rows[]/cols[], in the solver's output order),
@@ -206,8 +208,10 @@ int fm_assoc_prepare2(fm_ctx* ctx, int metric,
                       int nD, const double* det_tlbr, const int64_t* det_label,
                       const uint8_t* det_occluded, const uint8_t* trk_feat_f32, int after_extractor, int* host_cascade);
 
-/* The association cascade of MultiTracker.update (tracker.py:198-248) in one call, for problems whose assignment is
- * solved on the host anyway (host_lap_elems; after fm_assoc_prepare2 reported host_cascade): the three
+/* The association cascade of MultiTracker.update (tracker.py:198-248) in one call, on the terms of the last
+ * fm_assoc_prepare / fm_assoc_prepare2.  Where those reached page-locked host memory (host_cascade) every stage is
+ * filled and solved on the host; otherwise, or with FM_CASCADE_PER_STAGE in `flags`, each stage runs the device way
+ * (fm_assoc_stage).  Same bookkeeping and same results either way; an empty side (no rows or no detections) is valid.  The three
  * linear-assignment stages -- _matching_cost depth by depth (tracker.py:205-218,314-341), _iou_cost for the remaining
  * active and then for the unconfirmed tracks (:220-231,343-353) -- with the unmatched lists in the order of
  * utils/matching.py:58-70 under Numba's set iteration, the confidence / occlusion split of the remaining detections
@@ -217,10 +221,11 @@ int fm_assoc_prepare2(fm_ctx* ctx, int metric,
  * (row, det) pairs of the three stages, the unmatched rows of the three stages (stage 1: its inactive tracks, :221),
  * (index into hist_rows, det) pairs of the re-identification, the occluded unmatched detections, the others. */
 #define FM_CASCADE_HEADER 16
+#define FM_CASCADE_PER_STAGE 1     /* fm_cascade_in.flags: solve every stage the device way even if the terms reached the host */
 typedef struct fm_cascade_in {
     int32_t n_groups;              /* depth groups of the confirmed tracks (tracker.py:219-233: age // 2) */
     int32_t n_unconf, n_hist;
-    int32_t reserved;
+    int32_t flags;                 /* FM_CASCADE_PER_STAGE or 0 */
     const int32_t* group_off;      /* [n_groups + 1] offsets into conf_rows */
     const int32_t* conf_rows;      /* rows of the confirmed tracks, group by group */
     const uint8_t* conf_active;    /* Track.active of each of them */
@@ -231,13 +236,21 @@ typedef struct fm_cascade_in {
     double motion_weight, max_assoc_cost, fill_val, max_iou_cost, conf_thresh, max_reid_cost;
 } fm_cascade_in;
 int fm_assoc_cascade(fm_ctx* ctx, const fm_cascade_in* in, int32_t* out, int out_cap);
-/* The host half of fm_assoc_cascade on caller-provided pairwise terms ([nT][nD] f64 each; row_has_feat, labels and the
+/* The host way of fm_assoc_cascade on caller-provided pairwise terms ([nT][nD] f64 each; row_has_feat, labels and the
  * occlusion mask as fm_assoc_prepare takes them): no context, no device -- what the CPU test suite checks against the
  * oracle's restatement of utils/matching.py (tests/test_cascade_host.py).  Not a fallback: the terms themselves only
  * ever come from pairwise_kernel. */
 int fm_cascade_host(int nT, int nD, const double* feat, const double* maha, const double* iou,
                     const uint8_t* row_has_feat, const int64_t* trk_label, const int64_t* det_label,
                     const uint8_t* det_occluded, const fm_cascade_in* in, int32_t* out, int out_cap);
+/* Context-free pieces of that cascade, for the CPU tests: the [nr][nc] cost matrix its host fill produces for one stage
+ * (the rule stage_cost_kernel applies; row_labels[nr] as fm_assoc_stage's override), and the order of
+ * list(set(range(n)) - set(matched)) under Numba's set iteration (utils/matching.py:58-60) -- returns the count. */
+int fm_stage_cost_host(int stage, int nT, int nD, const double* feat, const double* maha, const double* iou,
+                       const uint8_t* row_has_feat, const int64_t* det_label, const uint8_t* det_occluded,
+                       int nr, const int32_t* rows, int nc, const int32_t* cols, const int64_t* row_labels,
+                       double motion_weight, double max_cost, double fill_val, double* cost);
+int fm_unmatched_order(int n, const int32_t* matched, int n_matched, int32_t* out);
 
 /* Stand-alone solvers on a host cost matrix [nr][nc] f64 (device kernels; used by
  * _rectify_matches' greedy_match, tracker.py:384, and by the parity tests). */

@@ -1,5 +1,5 @@
 """Cases of the one-call association cascade, shared by test_cascade_host.py (fm_cascade_host on synthetic terms) and
-test_assoc_gpu.py (fm_assoc_cascade on the page-locked mirror pairwise_kernel writes): the oracle's restatement of the
+test_assoc_gpu.py (fm_assoc_cascade in every way it solves its stages): the oracle's restatement of the
 reference's stage logic (np_oracle.matching_cost / gate_cost / lsa / assignment_matches / greedy_match:
 utils/matching.py, tracker.py:198-248), the ctypes call of fm_cascade_host, and a seeded case maker."""
 import ctypes as C
@@ -59,7 +59,9 @@ def reference_cascade(feat, maha, iou, has_feat, tlab, dlab, docc, groups, activ
     return (matches1 + matches2 + matches3, u1 + u2 + u3, [(a, valid[b]) for a, b in gm], invalid + [valid[b] for b in gu])
 
 
-def run_host(feat, maha, iou, has_feat, tlab, dlab, docc, groups, active, unconf, hist_rows, hist_labels, det_conf, p):
+def run_host(feat, maha, iou, has_feat, tlab, dlab, docc, groups, active, unconf, hist_rows, hist_labels, det_conf, p,
+             null_terms=False):
+    """null_terms: NULL for the terms, labels and flags -- what an empty side has no use for and must not read."""
     lib = _lib.load()
     nT, nD = feat.shape
     flat = list(itertools.chain.from_iterable(groups))
@@ -73,7 +75,7 @@ def run_host(feat, maha, iou, has_feat, tlab, dlab, docc, groups, active, unconf
     out = np.full(_lib.CASCADE_HEADER + 3 * (len(flat) + len(unconf)) + 3 * nD, -7, np.int32)
     ins = [np.ascontiguousarray(a, t) for a, t in ((feat, np.float64), (maha, np.float64), (iou, np.float64),
                                                     (has_feat, np.uint8), (tlab, np.int64), (dlab, np.int64), (docc, np.uint8))]
-    rc = lib.fm_cascade_host(C.c_int(nT), C.c_int(nD), *(_lib._ptr(a) for a in ins), C.byref(cin), _lib._ptr(out),
+    rc = lib.fm_cascade_host(C.c_int(nT), C.c_int(nD), *(None if null_terms else _lib._ptr(a) for a in ins), C.byref(cin), _lib._ptr(out),
                              C.c_int(len(out)))
     _lib.check(rc)
     return unpack(out.tolist())

@@ -4,7 +4,7 @@
   * oracle=restated : np_oracle + scipy.optimize.linear_sum_assignment on seeded inputs incl.
     tie-heavy, rectangular, gated (1e5) and degenerate matrices.  Index results must be IDENTICAL.
 Off the defaults: the Mahalanobis term on evolved (non-diagonal) covariances under both parameter sets, the LDS chunk
-loop and the I/O switch of find_occluded, fm_iou_dist, the page-locked mirror fm_assoc_cascade reads, lap_kernel with its
+loop and the I/O switch of find_occluded, fm_iou_dist, every way fm_assoc_cascade solves its stages, lap_kernel with its
 work arrays in global memory and with more than 64 KiB of LDS, infeasible matrices, results returned by blit copy."""
 import numpy as np
 import pytest
@@ -277,12 +277,21 @@ def test_iou_dist_equals_oracle(ctx, shape):
     np.testing.assert_array_equal(ctx.iou_dist(a, b), exp)
 
 
-@pytest.mark.parametrize('nT,nD', [(7, 90), (50, 50)])
-def test_cascade_reads_the_mirror_of_the_device_terms(ctx, nT, nD):
-    """fm_assoc_cascade works on the page-locked mirror pairwise_kernel writes beside its device arrays: its result is
-    fm_cascade_host's on the three matrices read back from the device.  A prepare on other detections goes first, so a
-    term that failed to reach the mirror would be a stale one, not the right one by chance."""
-    rng = np.random.default_rng(70 + nT)
+CASCADE_WAYS = {'mirror': (dict(), False),                                        # host fill, host solvers
+                'device': (dict(host_lap_elems=0), False),                        # cost kernel, device LAP, device greedy
+                'blit': (dict(host_lap_elems=0, zero_copy_tracks=0), False),      # the same through blit copies
+                'per_stage': (dict(), True)}                 # cost kernel into pinned memory, host LAP, device greedy
+
+
+@pytest.mark.parametrize('nT,nD', [(7, 90), (50, 50), (90, 7)])       # lap_kernel (> 64 columns), lap64_kernel, transposed
+@pytest.mark.parametrize('way', list(CASCADE_WAYS))
+def test_cascade_every_way_equals_host_cascade_on_device_terms(ctx, way, nT, nD):
+    """Every way the one cascade (fm_assoc_cascade) can run gives fm_cascade_host's result on the three matrices read
+    back from the device: on the page-locked mirror pairwise_kernel writes beside its device arrays, and stage by stage
+    on the device terms.  A prepare on other detections goes first, so a term that failed to reach the mirror would be
+    a stale one, not the right one by chance."""
+    opts, per_stage = CASCADE_WAYS[way]
+    rng = np.random.default_rng(74 + nT)
     ctx.kf_configure(1 / 30., **KF_DEFAULT)
     ctx.set_frame_rect([0., 0., 1919., 1079.])
     case = cascade_cases.make_case(rng, nT, nD, nT // 4, False)
@@ -303,21 +312,24 @@ def test_cascade_reads_the_mirror_of_the_device_terms(ctx, nT, nD):
     db = np.rint(tb[sel] + rng.normal(0, 6, (nD, 4)))
     XB = (XA[sel] + rng.normal(0, 0.03, (nD, 512))).astype(np.float32)
     XB /= np.linalg.norm(XB, axis=1, keepdims=True)
-    ctx.emb_upload(np.roll(XB, 1, axis=0))
-    assert ctx.assoc_prepare(_lib.METRIC_COSINE, slots, tb, tlab, db[::-1] + 300., dlab, docc)
-    ctx.emb_upload(XB)
-    assert ctx.assoc_prepare(_lib.METRIC_COSINE, slots, tb, tlab, db, dlab, docc)
+    mirror = 'host_lap_elems' not in opts
     flat = [r for g in groups for r in g]
     pack = ctx.cascade_pack([len(g) for g in groups], flat, [active[r] for r in flat], unconf, hist_rows, hist_labels,
                             det_conf, p['motion_weight'], p['max_assoc_cost'], p['fill_val'], p['max_iou_cost'],
-                            p['conf_thresh'], p['max_reid_cost'])
-    got = cascade_cases.unpack(ctx.assoc_cascade(pack))
+                            p['conf_thresh'], p['max_reid_cost'], per_stage=per_stage)
+    with options(ctx, **opts):
+        ctx.emb_upload(np.roll(XB, 1, axis=0))
+        assert ctx.assoc_prepare(_lib.METRIC_COSINE, slots, tb, tlab, db[::-1] + 300., dlab, docc) == mirror
+        ctx.emb_upload(XB)
+        assert ctx.assoc_prepare(_lib.METRIC_COSINE, slots, tb, tlab, db, dlab, docc) == mirror
+        got = cascade_cases.unpack(ctx.assoc_cascade(pack))
     feat, maha, iou = ctx.assoc_get_pairwise(nT, nD)
     has_feat = ctx.feat_read(slots)[1] > 0
     assert not has_feat.all() and has_feat.any()
     ref = cascade_cases.run_host(feat, maha, iou, has_feat, tlab, dlab, docc, groups, active, unconf, hist_rows,
                                  hist_labels, det_conf, p)
     assert len(ref[0]) >= 3 and (maha <= CHI_SQ_INV_95).any() and (maha > CHI_SQ_INV_95).any()
+    assert ref[2] and ref[3], 'the greedy re-identification must have something to match and something to leave'
     assert got[0] == ref[0], 'matches'
     assert got[1] == ref[1], 'unmatched track order'
     assert got[2] == ref[2], 're-identification'
