@@ -3,7 +3,9 @@
 //   channels [0, cn) of the view: per sample and channel over the HW pixels, biased variance,
 //       y = act((x - mean) * (1 / sqrt(var + eps)) * gamma[c] + beta[c]),  rounded to fp16 once, on the store
 //   channels [cn, C): y = act(x)          (the BatchNorm half of IBN-a is folded into the conv in front; its ReLU waits here)
-// to a NEW tensor.  All statistics in fp32; the variance is the sum of CENTRED squares from a second pass over the same
+// to a NEW tensor.  Optionally (template flag RES; the unfused tail of an OSNet-AIN block, relu(IN(conv3(x2)) + identity)) a
+// residual view of C channels is added to every channel behind the affine and in front of the activation; a layer without
+// it runs the instantiation without a single instruction for it.  All statistics in fp32; the variance is the sum of CENTRED squares from a second pass over the same
 // values (E[x^2] - mean^2 in fp32 loses every digit of a channel with mean 100 and std 0.1).
 //
 // Lanes over (pixel, channel group): a workgroup of IN_T threads owns one sample and G consecutive 8-channel groups,
@@ -40,11 +42,11 @@ __device__ __forceinline__ void fold8(float* a, float (*red)[8][8], int wave, in
     }
 }
 
-template <int G, bool REG>
+template <int G, bool REG, bool RES>
 __global__ __launch_bounds__(IN_T) void instnorm_kernel(const f16* __restrict__ in, int in_cs, int in_coff, f16* __restrict__ out,
                                                         int out_cs, int out_coff, int HW, int C, int cn,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        float eps, int act) {
+                                                        float eps, int act, const f16* __restrict__ res, int res_cs, int res_coff) {
     __shared__ float red[2][IN_T / 64][8][8];
     constexpr int PS = IN_T / G;                             // pixel step of a thread
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -127,6 +129,12 @@ __global__ __launch_bounds__(IN_T) void instnorm_kernel(const f16* __restrict__ 
         if (norm)
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = (v[e] - mean[e]) * rstd[e] * g[e] + b[e];
+        if constexpr (RES) {                                 // the residual view: behind the affine, in front of the activation
+            float r[8];
+            unpack8(*reinterpret_cast<const uint4*>(res + ((size_t)blockIdx.y * HW + px) * res_cs + res_coff + c0), r);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += r[e];
+        }
         if (act == ACT_RELU)
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = act_relu(v[e]);
@@ -143,13 +151,16 @@ __global__ __launch_bounds__(IN_T) void instnorm_kernel(const f16* __restrict__ 
 
 template <int G>
 void launch_g(bool reg, dim3 grid, hipStream_t s, const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, int HW,
-              int C, int cn, const float* gamma, const float* beta, float eps, int act) {
-    if (reg)
-        hipLaunchKernelGGL((instnorm_kernel<G, true>), grid, dim3(IN_T), 0, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn,
-                           gamma, beta, eps, act);
-    else
-        hipLaunchKernelGGL((instnorm_kernel<G, false>), grid, dim3(IN_T), 0, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn,
-                           gamma, beta, eps, act);
+              int C, int cn, const float* gamma, const float* beta, float eps, int act, const f16* res, int res_cs, int res_coff) {
+#define FM_IN_LAUNCH(REG, RES)                                                                                                  \
+    hipLaunchKernelGGL((instnorm_kernel<G, REG, RES>), grid, dim3(IN_T), 0, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, \
+                       gamma, beta, eps, act, res, res_cs, res_coff)
+    if (res) {
+        if (reg) FM_IN_LAUNCH(true, true); else FM_IN_LAUNCH(false, true);
+    } else {
+        if (reg) FM_IN_LAUNCH(true, false); else FM_IN_LAUNCH(false, false);
+    }
+#undef FM_IN_LAUNCH
 }
 
 }  // namespace
@@ -171,20 +182,23 @@ int instnorm_groups(int N, int HW, int C) {
     return G;
 }
 
+// res: nullptr, or a view of C channels (res_cs, res_coff) added to every channel behind the affine, in front of the activation
 int launch_instnorm(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, int N, int HW, int C, int cn,
-                    const float* gamma, const float* beta, float eps, int act, hipStream_t s) {
+                    const float* gamma, const float* beta, float eps, int act, hipStream_t s, const f16* res, int res_cs,
+                    int res_coff) {
     FM_CHECK_ARG(in && out && gamma && beta && N >= 1 && N <= 65535 && HW >= 1 && C >= 8 && C % 8 == 0 && cn >= 8 && cn % 8 == 0 && cn <= C);
     FM_CHECK_ARG(in_cs % 8 == 0 && out_cs % 8 == 0 && in_coff >= 0 && out_coff >= 0 && in_coff % 8 == 0 && out_coff % 8 == 0 &&
                  in_coff + C <= in_cs && out_coff + C <= out_cs);
     FM_CHECK_ARG((act == ACT_LINEAR || act == ACT_RELU) && eps >= 0.f && eps < 1.f);
+    FM_CHECK_ARG(!res || (res_cs % 8 == 0 && res_coff >= 0 && res_coff % 8 == 0 && res_coff + C <= res_cs));
     const int G = instnorm_groups(N, HW, C);
     const bool reg = HW <= instnorm_reg_pixels(G);
     const dim3 grid((C / 8 + G - 1) / G, N);
     switch (G) {
-        case 8: launch_g<8>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act); break;
-        case 4: launch_g<4>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act); break;
-        case 2: launch_g<2>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act); break;
-        default: launch_g<1>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act); break;
+        case 8: launch_g<8>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act, res, res_cs, res_coff); break;
+        case 4: launch_g<4>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act, res, res_cs, res_coff); break;
+        case 2: launch_g<2>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act, res, res_cs, res_coff); break;
+        default: launch_g<1>(reg, grid, s, in, in_cs, in_coff, out, out_cs, out_coff, HW, C, cn, gamma, beta, eps, act, res, res_cs, res_coff); break;
     }
     FM_HIP(hipGetLastError());
     return 0;

@@ -62,7 +62,12 @@ int launch_head(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int
 int launch_poolhead(const f16* in, int in_cs, int in_coff, int N, int HW, int C, int D, const float* scale, const float* shift,
                     const f16* w, const float* b, int relu, float* out, float* mirror, hipStream_t s, float gem_p, float gem_eps);
 int launch_instnorm(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, int N, int HW, int C, int cn,
-                    const float* gamma, const float* beta, float eps, int act, hipStream_t s);
+                    const float* gamma, const float* beta, float eps, int act, hipStream_t s, const f16* res = nullptr, int res_cs = 0,
+                    int res_coff = 0);
+bool convin_supported(int K, int cout, int hw);
+int launch_convin(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, const f16* res, int res_cs, int res_coff,
+                  int res_mode, const f16* w, const float* bias, const float* gamma, const float* beta, int N, int HW, int K,
+                  int cout, float eps, int act, hipStream_t s);
 int fm_emb_reserve(fm_ctx* ctx, int n);
 
 
@@ -145,7 +150,7 @@ int fm_net_front_prepare(fm_ctx* ctx, NetState* net, int request, int* k) {
         switch (op) {
             case FM_OP_CONV: case FM_OP_CONVS: case FM_OP_CONVD: case FM_OP_DWCONV3: case FM_OP_DWCONV: case FM_OP_SEPCONV:
             case FM_OP_STEMCONV: case FM_OP_STEM2: case FM_OP_STEMPOOL: case FM_OP_PAIR11: case FM_OP_SPP: case FM_OP_MAXPOOL:
-            case FM_OP_AVGPOOL: case FM_OP_UPSAMPLE2: case FM_OP_RESBLOCK: case FM_OP_ADD: case FM_OP_COPY: case FM_OP_INSTNORM: return true;
+            case FM_OP_AVGPOOL: case FM_OP_UPSAMPLE2: case FM_OP_RESBLOCK: case FM_OP_ADD: case FM_OP_COPY: case FM_OP_INSTNORM: case FM_OP_CONVIN: return true;
             default: return false;
         }
     };
@@ -507,8 +512,47 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
             FM_CHECK_ARG(L.w_off >= 0 && L.b_off >= 0 && L.w_off % 16 == 0 && L.b_off % 16 == 0 &&
                          (size_t)L.w_off + (size_t)L.hid * 4 <= wb && (size_t)L.b_off + (size_t)L.hid * 4 <= wb);
             FM_CHECK_ARG((L.act == FM_ACT_LINEAR || L.act == FM_ACT_RELU) && eps >= 0.f && eps < 1.f);
+            // an optional residual view of cin channels, added behind the affine and in front of the activation (res_mode
+            // FM_RES_BEFORE_ACT; the tail of an OSNet-AIN block unfused): a template flag of the kernel
+            const f16* res = nullptr;
+            int res_cs = 0;
+            if (L.res_mode != FM_RES_NONE) {
+                const fm_tensor& tr = net->tensors[L.res];
+                FM_CHECK_ARG(L.res_mode == FM_RES_BEFORE_ACT && L.res != L.out && !tr.f32 && tr.h == ti.h && tr.w == ti.w &&
+                             L.res_coff >= 0 && L.res_coff % 8 == 0 && L.res_coff + L.cin <= tr.c);
+                res = (const f16*)net->bufs[L.res];
+                res_cs = tr.c;
+            }
             return launch_instnorm(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff, B, ti.h * ti.w, L.cin, L.hid,
-                                   (const float*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off), eps, L.act, s);
+                                   (const float*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off), eps, L.act, s,
+                                   res, res_cs, L.res_coff);
+        }
+        case FM_OP_CONVIN: {    // cin = K, w_off / b_off = the conv (fragment order, f32 bias), w2_off / b2_off = f32 gamma / beta, gate[0] = bits of eps
+            const size_t wb = net->weight_bytes;
+            const size_t cp = (size_t)((L.cout + 31) / 32) * 32;
+            float eps;
+            memcpy(&eps, &L.gate[0], sizeof eps);
+            FM_CHECK_ARG(!ti.f32 && !to.f32 && L.out != L.in[0] && to.h == ti.h && to.w == ti.w && L.k == 1 && L.stride == 1 &&
+                         L.pad == 0 && convin_supported(L.cin, L.cout, ti.h * ti.w));
+            FM_CHECK_ARG(L.in_coff[0] >= 0 && L.out_coff >= 0 && L.in_coff[0] % 8 == 0 && L.out_coff % 8 == 0 &&
+                         L.in_coff[0] + L.cin <= ti.c && L.out_coff + L.cout <= to.c);
+            FM_CHECK_ARG(L.w_off >= 0 && L.b_off >= 0 && L.w2_off >= 0 && L.b2_off >= 0 && L.w2_off % 16 == 0 && L.b2_off % 16 == 0 &&
+                         (size_t)L.w_off + cp * (size_t)((L.cin + 15) / 16) * 32 <= wb && (size_t)L.b_off + cp * 4 <= wb &&
+                         (size_t)L.w2_off + cp * 4 <= wb && (size_t)L.b2_off + cp * 4 <= wb);
+            FM_CHECK_ARG((L.act == FM_ACT_LINEAR || L.act == FM_ACT_RELU) && eps >= 0.f && eps < 1.f);
+            const f16* res = nullptr;
+            int res_cs = 0;
+            if (L.res_mode != FM_RES_NONE) {
+                const fm_tensor& tr = net->tensors[L.res];
+                FM_CHECK_ARG((L.res_mode == FM_RES_BEFORE_ACT || L.res_mode == FM_RES_BEFORE_NORM) && L.res != L.out && !tr.f32 &&
+                             tr.h == ti.h && tr.w == ti.w && L.res_coff >= 0 && L.res_coff % 8 == 0 && L.res_coff + L.cout <= tr.c);
+                res = (const f16*)net->bufs[L.res];
+                res_cs = tr.c;
+            }
+            return launch_convin(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff, res, res_cs, L.res_coff, L.res_mode,
+                                 (const f16*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off),
+                                 (const float*)(net->weights + L.w2_off), (const float*)(net->weights + L.b2_off), B, ti.h * ti.w,
+                                 L.cin, L.cout, eps, L.act, s);
         }
         case FM_OP_POOLHEAD: {  // gate[0] > 0: BN neck (w2_off / b2_off = f32 scale / shift [cin]); gate[1] > 0: FC (w_off fp16 [cout][cin], b_off f32 [cout])
             // gate[2] > 0: GeM pooling, the IEEE bits of p (0.5 .. 16) there and of the clamp eps in gate[3]
@@ -787,7 +831,11 @@ static void layer_cost(const NetState* net, const fm_layer& L, int B, double* fl
         }
         case FM_OP_INSTNORM:    // one read and one write of the view (the register path; the statistics are ~6 flops per element)
             *flops = 6.0 * pin * L.hid;
-            *bytes = (pin + pout) * L.cin * 2;
+            *bytes = (pin + pout) * L.cin * 2 + (L.res_mode != FM_RES_NONE ? pin * L.cin * 2 : 0);
+            break;
+        case FM_OP_CONVIN:      // the conv it contains; input in (once per 32-channel tile, from L2: counted once), output out
+            *flops = 2.0 * L.cin * L.cout * pout + 6.0 * pout * L.cout;
+            *bytes = pin * L.cin * 2 + pout * L.cout * 2 + (double)L.cin * L.cout * 2 + (L.res_mode != FM_RES_NONE ? pout * L.cout * 2 : 0);
             break;
         case FM_OP_POOLHEAD:
             *flops = (double)pin * L.cin + (L.gate[1] > 0 ? 2.0 * L.cin * L.cout * B : 0.);
@@ -808,6 +856,16 @@ extern "C" int fm_net_cost(fm_ctx* ctx, int which, int batch, double* flops, dou
             layer_cost(net, L, batch, &lf, &lb);
             f += lf;
             b += lb;
+        } else if (L.op == FM_OP_CONVIN) {
+            // the conv and the instance normalisation it replaces, as the two stand-alone layers: the conv's FLOPs, and the
+            // write + read of the conv's output on top of the fused op's own bytes (the algorithmic work of a network does not
+            // change with the fusions of its layer table)
+            const fm_tensor& to = net->tensors[L.out];
+            const double pout = (double)batch * to.h * to.w;
+            double lf, lb;
+            layer_cost(net, L, batch, &lf, &lb);
+            f += 2.0 * L.cin * L.cout * pout;
+            b += lb + 2 * pout * L.cout * 2;
         } else if (L.op == FM_OP_STEMPOOL && L.cout > 32) {
             // the stem as the stand-alone FM_OP_CONV it replaces (a stem of <= 32 channels is FM_OP_STEMCONV unfused, which was
             // never part of this sum): the algorithmic work of a network does not change with the fusions of its layer table
@@ -858,7 +916,7 @@ extern "C" int fm_net_profile(fm_ctx* ctx, int which, int batch, int iters, doub
             FM_HIP(hipEventSynchronize(e1));
             float ms = 0;
             FM_HIP(hipEventElapsedTime(&ms, e0, e1));
-            if (L.op == FM_OP_CONV || L.op == FM_OP_CONVS || L.op == FM_OP_CONVD || L.op == FM_OP_RESBLOCK || L.op == FM_OP_STEM2 || L.op == FM_OP_PAIR11) { tc += ms; ++nc; } else { to += ms; ++no; }
+            if (L.op == FM_OP_CONV || L.op == FM_OP_CONVS || L.op == FM_OP_CONVD || L.op == FM_OP_RESBLOCK || L.op == FM_OP_STEM2 || L.op == FM_OP_PAIR11 || L.op == FM_OP_CONVIN) { tc += ms; ++nc; } else { to += ms; ++no; }
         }
     FM_HIP(hipEventDestroy(e0));
     FM_HIP(hipEventDestroy(e1));

@@ -16,11 +16,14 @@ LOGGER = logging.getLogger(__name__)
 
 (OP_CONV, OP_DWCONV3, OP_MAXPOOL, OP_AVGPOOL, OP_UPSAMPLE2, OP_COPY, OP_GATE, OP_GATE_SUM, OP_HEAD,
  OP_LITECONV, OP_SPP, OP_GATED_SUM, OP_STEMCONV, OP_ADD, OP_RESBLOCK, OP_CONVS, OP_LITECHAIN, OP_CONVD, OP_STEM2, OP_PAIR11,
- OP_OSTAIL, OP_DWCONV, OP_SEPCONV, OP_POOLHEAD, OP_STEMPOOL, OP_INSTNORM) = range(26)
+ OP_OSTAIL, OP_DWCONV, OP_SEPCONV, OP_POOLHEAD, OP_STEMPOOL, OP_INSTNORM, OP_CONVIN) = range(27)
 CONV_OPS = (OP_CONV, OP_CONVS, OP_CONVD)      # the three kernels behind Graph.conv (same fields, different weight layouts)
 SPP_MAX_HW = 2048
 ACT = {'linear': 0, 'leaky': 1, 'mish': 2, 'relu': 3, 'logistic': 4, 'swish': 5, 'relu6': 6}
 RES_NONE, RES_AFTER_ACT, RES_BEFORE_ACT = 0, 1, 2
+RES_BEFORE_NORM = 3        # FM_OP_CONVIN only: the residual is part of the value that is normalised
+RES_AFTER_NORM = RES_BEFORE_ACT
+CONVIN_MAX_HW = 2048
 
 
 class fm_tensor(C.Structure):
@@ -107,6 +110,10 @@ class RandomWeights:
         p['w'] = p['w'].reshape(cout, cin)
         return p
 
+    def instnorm(self, name, c):
+        """-> (gamma, beta) of an InstanceNorm2d(c, affine=True): no running statistics."""
+        return self.rng.uniform(0.5, 1.5, c).astype(np.float32), self.rng.normal(0, 0.3, c).astype(np.float32)
+
 
 def fold_bn(p, eps=1e-5):
     """-> (weight fp32, bias fp32) with BatchNorm folded (yolo2onnx.py:419-421 eps)."""
@@ -156,6 +163,10 @@ class Graph:
         self.use_sepconv = os.environ.get('FASTMOT_SEPCONV', '1') != '0'
         # the ResNet stem (7x7 stride-2 conv, ReLU) and its max pool as one launch (stempool.hip, FM_OP_STEMPOOL); 0: conv + pool
         self.use_stempool = os.environ.get('FASTMOT_STEMPOOL', '1') != '0'
+        # the tail of an OSNet-IBN / -AIN block (pointwise conv, instance norm, residual, ReLU): 0 (the default) a linear conv +
+        # FM_OP_INSTNORM; 1: one launch (convin.hip, FM_OP_CONVIN).  The fused form measured SLOWER per pass at x1.0 widths
+        # (profiles/reid_ain.txt), so it stays behind the switch
+        self.use_convin = os.environ.get('FASTMOT_CONVIN', '0') != '0'
         self.conv_params = []  # (layer index, folded fp16-rounded weight fp32, bias) for the test oracle
         h, w = in_hw
         self.input = self.new(h, w, in_c)
@@ -791,7 +802,62 @@ class Graph:
 
     POOLHEAD_MAX = 4096
 
-    def instnorm(self, name, x, gamma, beta, eps=1e-5, act='linear', dst=None):
+    @staticmethod
+    def convin_supported(K, cout, hw):
+        """The shapes FM_OP_CONVIN runs (convin.hip: convin_supported; tests/test_convin_host.py asserts they agree): a
+        workgroup keeps one sample's whole map of 32 output channels in registers, 16 waves x 4 tiles x 32 pixels."""
+        return 8 <= K <= 4096 and K % 8 == 0 and 8 <= cout <= 4096 and cout % 8 == 0 and 1 <= hw <= CONVIN_MAX_HW
+
+    def convin(self, name, x, cout, norm, eps=1e-5, act='relu', res=None, res_mode=RES_NONE, bn=True, bias=True, wb=None, dst=None):
+        """The tail of an OSNet-IBN / -AIN block: pointwise conv x -> cout (BatchNorm folded when bn, else no bias), instance
+        normalisation of the result, residual `res` either inside the normalised value (RES_BEFORE_NORM: relu(IN(conv3(x2) +
+        identity)), osnet_ibn) or behind the affine (RES_AFTER_NORM: relu(IN(conv3(x2)) + identity), osnet_ain), activation.
+        ONE launch (FM_OP_CONVIN, convin.hip: the conv's result stays in fp32 registers) or, with use_convin off / an
+        unsupported shape, a linear conv + FM_OP_INSTNORM.  norm: the parameter name of the InstanceNorm2d, or (gamma,
+        beta); both forms draw the conv's parameters first, then the norm's.  The fused layer keeps convin_ref = (fp16-rounded
+        weight [cout, K, 1, 1] as fp32, bias, gamma, beta, eps as the fp32 value the device uses)."""
+        assert res_mode in (RES_NONE, RES_BEFORE_NORM, RES_AFTER_NORM) and (res is None) == (res_mode == RES_NONE)
+        if act not in ('linear', 'relu'):
+            raise ValueError(f'{name}: activation {act!r} behind an instance normalisation (linear or relu)')
+        w, b = wb if wb is not None else fold_bn(self.wsrc.conv(name, cout, x.c, 1, bn=bn))
+        w, b = np.asarray(w, np.float32), np.asarray(b, np.float32)
+        if not bias:
+            b = np.zeros_like(b)
+        assert w.shape == (cout, x.c, 1, 1) and b.shape == (cout,)
+        gamma, beta = self.wsrc.instnorm(norm, cout) if isinstance(norm, str) else norm
+        gamma, beta = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (gamma, beta))
+        assert gamma.shape == beta.shape == (cout,)
+        assert res is None or ((res.h, res.w, res.c) == (x.h, x.w, cout) and res.coff % 8 == 0)
+        in_name = norm if isinstance(norm, str) else name + '.IN'
+        if not (self.use_convin and x.c % 8 == 0 and x.coff % 8 == 0 and self.convin_supported(x.c, cout, x.h * x.w)):
+            if res_mode == RES_BEFORE_NORM:
+                y = self.conv(name, x, cout, 1, 1, 'linear', wb=(w, b), res=res, res_mode=RES_BEFORE_ACT)
+                return self.instnorm(in_name, y, gamma, beta, eps, act, dst=dst)
+            y = self.conv(name, x, cout, 1, 1, 'linear', wb=(w, b))
+            return self.instnorm(in_name, y, gamma, beta, eps, act, dst=dst, res=res)
+        eps = float(np.float32(eps))
+        if not 0 <= eps < 1:
+            raise ValueError(f'{name}: epsilon {eps}')
+        if dst is None:
+            dst = self.new(x.h, x.w, cout)
+        assert (dst.h, dst.w, dst.c) == (x.h, x.w, cout) and dst.tid != x.tid and dst.coff % 8 == 0 and not self.tensors[dst.tid][3]
+        assert res is None or res.tid != dst.tid
+        w16 = w.astype(np.float16)
+        rows = ceil_to(cout, 32)
+        wp = np.zeros((rows, ceil_to(x.c, 16), 1, 1), np.float16)
+        wp[:cout, :x.c] = w16
+
+        def pad(a):
+            out = np.zeros(rows, np.float32)
+            out[:cout] = a
+            return out
+        self._layer(op=OP_CONVIN, ins=[x], out=dst, cin=x.c, cout=cout, k=1, stride=1, pad=0, act=ACT[act], gates=[f32_bits(eps)],
+                    res=res, res_mode=res_mode, w_off=self._push(self._pack_frag(wp)), b_off=self._push(pad(b)),
+                    w2_off=self._push(pad(gamma)), b2_off=self._push(pad(beta)), name=name,
+                    convin_ref=(w16.astype(np.float32), b, gamma, beta, eps))
+        return dst
+
+    def instnorm(self, name, x, gamma, beta, eps=1e-5, act='linear', dst=None, res=None):
         """Instance normalisation in one launch (FM_OP_INSTNORM, instnorm.hip): the first cn = len(gamma) channels of x are
         normalised per sample and channel over the map (biased variance, eps, gamma / beta in fp32), channels [cn, x.c) pass
         through; `act` ('linear' or 'relu') is applied to all of them.  cn == x.c: a plain InstanceNorm2d(affine=True); cn <
@@ -811,7 +877,11 @@ class Graph:
         if dst is None:
             dst = self.new(x.h, x.w, x.c)
         assert (dst.h, dst.w, dst.c) == (x.h, x.w, x.c) and dst.tid != x.tid and dst.coff % 8 == 0 and not self.tensors[dst.tid][3]
+        # res: a view of x.c channels added to every channel behind the affine, in front of the activation (a template flag
+        # of the kernel: a layer without it runs the code it always ran)
+        assert res is None or ((res.h, res.w, res.c) == (x.h, x.w, x.c) and res.coff % 8 == 0 and res.tid != dst.tid)
         self._layer(op=OP_INSTNORM, ins=[x], out=dst, cin=x.c, cout=x.c, hid=cn, act=ACT[act], gates=[f32_bits(eps)],
+                    res=res, res_mode=RES_BEFORE_ACT if res is not None else RES_NONE,
                     w_off=self._push(gamma), b_off=self._push(beta), name=name, instnorm_ref=(gamma, beta, eps))
         return dst
 
@@ -934,6 +1004,9 @@ class Graph:
             elif d['op'] == OP_RESBLOCK:
                 o = d['out']
                 total += 2 * 10 * d['cin'] * d['hid'] * o.h * o.w * batch
+            elif d['op'] == OP_CONVIN:
+                o = d['out']
+                total += 2 * d['cin'] * d['cout'] * o.h * o.w * batch
             elif d['op'] == OP_SEPCONV:      # (the pointwise stage; depthwise layers are not part of this sum)
                 o = d['out']
                 total += 2 * d['cin'] * d['cout'] * o.h * o.w * batch

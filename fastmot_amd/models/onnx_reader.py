@@ -426,10 +426,18 @@ class _OSNetWalk:
     """Follows the DATA FLOW of an exported torchreid OSNet (torchreid/models/osnet.py) from the graph input and names
     every weight by its place in the structure -- not by its position in the node list (exporters and torchreid
     versions order the four streams and their gates differently) and not by its initialiser name (BatchNorm folding
-    renames them).  Every step checks operator type and weight shape; anything unexpected raises ValueError."""
+    renames them).  Every step checks operator type and weight shape; anything unexpected raises ValueError.
 
-    def __init__(self, model, channels, feature_dim):
+    variant 'ibn' (osnet.py, IN=True) and 'ain' (osnet_ain.py) accept InstanceNormalization nodes at exactly three places --
+    behind conv1 (recorded as conv1.bn.weight / .bias, the name torchreid keeps), behind conv3 in front of the Add (an
+    OSBlockINin of 'ain') and behind the Add in front of the Relu (a block of conv2 / conv3 of 'ibn'), both recorded as
+    <block>.IN.* -- and name streams and transitions as that file does.  A graph of one variant walked as another fails:
+    the node that is expected at one of these places is not there."""
+
+    def __init__(self, model, channels, feature_dim, variant='osnet'):
+        from .reid import _BLOCK_IN
         self.m, self.channels, self.dim = model, channels, feature_dim
+        self.variant, self.block_in = variant, _BLOCK_IN[variant]
         self.cons = {}
         for nd in model.nodes:
             for t in nd.inputs:
@@ -437,8 +445,8 @@ class _OSNetWalk:
         self.sd = {}
 
     def fail(self, where, what):
-        raise ValueError(f'{where}: {what} (the graph does not walk like torchreid OSNet, expected channels '
-                         f'{self.channels})')
+        raise ValueError(f'{where}: {what} (the graph does not walk like torchreid OSNet, variant {self.variant!r}, expected '
+                         f'channels {self.channels})')
 
     def users(self, t, op=None):
         return [nd for nd in self.cons.get(t, []) if op is None or nd.op == op]
@@ -476,6 +484,20 @@ class _OSNetWalk:
             self.fail(name, 'neither a BatchNormalization node behind it nor a folded bias')
         return out
 
+    def instnorm(self, t, name, c):
+        """The InstanceNormalization reading tensor t -> its output; records `<name>.weight` / `.bias`."""
+        nds = self.users(t, 'InstanceNormalization')
+        if not nds:
+            self.fail(name, f'no InstanceNormalization reads {t!r} (readers: {[n.op for n in self.users(t)]})')
+        nd = nds[0]
+        if abs(nd.attrs.get('epsilon', 1e-5) - 1e-5) > 1e-9:
+            self.fail(name, f'InstanceNormalization with epsilon {nd.attrs.get("epsilon")} (torchreid: 1e-5)')
+        g, b = (self.m.tensor(v).astype(np.float32).reshape(-1) for v in nd.inputs[1:3])
+        if g.shape != (c,) or b.shape != (c,):
+            self.fail(name, f'InstanceNormalization scale / bias of shape {g.shape} / {b.shape}, expected ({c},)')
+        self.sd[name + '.weight'], self.sd[name + '.bias'] = g, b
+        return nd.outputs[0]
+
     def through(self, t, op, where):
         nds = self.users(t, op)
         if not nds:
@@ -509,9 +531,10 @@ class _OSNetWalk:
         if [len(c[0]) for c in chains] != [1, 2, 3, 4]:
             self.fail(prefix, f'streams of depth {[len(c[0]) for c in chains]} instead of 1, 2, 3, 4')
         gated = []
-        for (chain, out), sname in zip(chains, ('conv2a', 'conv2b', 'conv2c', 'conv2d')):
+        ain = self.variant == 'ain'
+        for (chain, out), sname in zip(chains, ('conv2.0', 'conv2.1', 'conv2.2', 'conv2.3') if ain else ('conv2a', 'conv2b', 'conv2c', 'conv2d')):
             for i, (pw, dw) in enumerate(chain):
-                lc = f'{prefix}.{sname}' if sname == 'conv2a' else f'{prefix}.{sname}.{i}'
+                lc = f'{prefix}.{sname}.layers.{i}' if ain else f'{prefix}.{sname}' if sname == 'conv2a' else f'{prefix}.{sname}.{i}'
                 self.conv(None, None, lc + '.conv1', node=pw)
                 self.conv(None, None, lc + '.conv2', lc + '.bn', node=dw)
             # ChannelGate: global average pool -> fc1 -> ReLU -> fc2 -> sigmoid -> multiply (one gate, four uses)
@@ -527,23 +550,36 @@ class _OSNetWalk:
             if [n for n in self.users(t, 'Conv') if self.wshape(n) == (cout, mid, 1, 1)]:
                 break
             t = self.through(t, 'Add', prefix + ' (sum of the gated streams)')
-        x3 = self.conv(t, (cout, mid, 1, 1), prefix + '.conv3.conv', prefix + '.conv3.bn')
+        kind = self.block_in.get(prefix)
+        x3 = self.conv(t, (cout, mid, 1, 1), prefix + '.conv3.conv', None if kind == 'ain' else prefix + '.conv3.bn')
         if cin != cout:
             self.conv(x, (cout, cin, 1, 1), prefix + '.downsample.conv', prefix + '.downsample.bn')
-        return self.through(self.through(x3, 'Add', prefix), 'Relu', prefix)
+        if kind == 'ain':           # OSBlockINin: relu(IN(conv3(x2)) + identity), a conv3 without batch norm and bias
+            if prefix + '.conv3.conv.bias' in self.sd:
+                self.fail(prefix + '.conv3', 'a bias on the conv3 of an OSBlockINin')
+            x3 = self.instnorm(x3, prefix + '.IN', cout)
+        x3 = self.through(x3, 'Add', prefix)
+        if kind == 'ibn':           # relu(IN(conv3(x2) + identity))
+            x3 = self.instnorm(x3, prefix + '.IN', cout)
+        return self.through(x3, 'Relu', prefix)
 
     def run(self):
         c0, c1, c2, c3 = self.channels
         if not self.m.data_inputs:
             self.fail('input', 'no data input')
         x = self.m.data_inputs[0][0]
-        x = self.through(self.conv(x, (c0, 3, 7, 7), 'conv1.conv', 'conv1.bn'), 'Relu', 'conv1')
+        if self.variant == 'osnet':
+            x = self.conv(x, (c0, 3, 7, 7), 'conv1.conv', 'conv1.bn')
+        else:                       # ConvLayer(IN=True): the norm module keeps the name `bn`
+            x = self.instnorm(self.conv(x, (c0, 3, 7, 7), 'conv1.conv'), 'conv1.bn', c0)
+        x = self.through(x, 'Relu', 'conv1')
         x = self.through(x, 'MaxPool', 'maxpool')
         for stage, cin, cout, transition in (('conv2', c0, c1, True), ('conv3', c1, c2, True), ('conv4', c2, c3, False)):
             x = self.block(x, cin, cout, stage + '.0')
             x = self.block(x, cout, cout, stage + '.1')
             if transition:
-                x = self.through(self.conv(x, (cout, cout, 1, 1), f'{stage}.2.0.conv', f'{stage}.2.0.bn'), 'Relu', stage)
+                tr = f'pool{stage[4:]}.0' if self.variant == 'ain' else f'{stage}.2.0'
+                x = self.through(self.conv(x, (cout, cout, 1, 1), tr + '.conv', tr + '.bn'), 'Relu', stage)
                 x = self.through(x, 'AveragePool', stage)
         x = self.through(self.conv(x, (c3, c3, 1, 1), 'conv5.conv', 'conv5.bn'), 'Relu', 'conv5')
         x = self.through(x, 'GlobalAveragePool', 'global pool')
@@ -577,9 +613,9 @@ class _OSNetWalk:
         return self.sd
 
 
-def torchreid_state_dict_from_onnx(model, channels, feature_dim=512):
+def torchreid_state_dict_from_onnx(model, channels, feature_dim=512, variant='osnet'):
     """-> dict of torchreid parameter names (`conv1.conv.weight`, `conv1.bn.running_mean`, `fc.0.bias`, ...) from an
     ONNX export of torchreid's OSNet.  A conv whose BatchNorm the exporter folded away carries `<conv>.bias` and no
     `<bn>.*` entries (TorchreidWeights treats that as an already folded layer)."""
     model = model if isinstance(model, OnnxModel) else OnnxModel(model)
-    return _OSNetWalk(model, tuple(channels), feature_dim).run()
+    return _OSNetWalk(model, tuple(channels), feature_dim, variant).run()

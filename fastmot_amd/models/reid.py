@@ -5,7 +5,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .graph import Graph, RES_BEFORE_ACT, fold_bn, missing_weights
+from .graph import Graph, RES_AFTER_NORM, RES_BEFORE_ACT, RES_BEFORE_NORM, fold_bn, missing_weights
 
 
 class ReID:
@@ -23,6 +23,7 @@ class ReID:
     OUTPUT_LAYOUT = None
     METRIC = None
     CHANNELS = None
+    VARIANT = 'osnet'       # which torchreid OSNet a descriptor with CHANNELS is: 'osnet', 'ibn' (osnet_ibn_*), 'ain' (osnet_ain_*)
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)
@@ -73,17 +74,17 @@ class ReID:
         if onnx_src is not None:
             from .onnx_reader import torchreid_state_dict_from_onnx
             from .torchreid_weights import TorchreidWeights
-            weights = ckpt = TorchreidWeights(torchreid_state_dict_from_onnx(onnx_src, cls.CHANNELS, cls.OUTPUT_LAYOUT))
+            weights = ckpt = TorchreidWeights(torchreid_state_dict_from_onnx(onnx_src, cls.CHANNELS, cls.OUTPUT_LAYOUT, cls.VARIANT), cls.VARIANT)
         if weights is None:
             path = cls.weight_file()
             if path is not None:
                 from .torchreid_weights import TorchreidWeights
                 if path.suffix == '.onnx':
                     from .onnx_reader import torchreid_state_dict_from_onnx
-                    weights = ckpt = TorchreidWeights(torchreid_state_dict_from_onnx(path, cls.CHANNELS,
-                                                                                     cls.OUTPUT_LAYOUT))
+                    weights = ckpt = TorchreidWeights(torchreid_state_dict_from_onnx(path, cls.CHANNELS, cls.OUTPUT_LAYOUT,
+                                                                                     cls.VARIANT), cls.VARIANT)
                 else:
-                    weights = ckpt = TorchreidWeights(path)
+                    weights = ckpt = TorchreidWeights(path, cls.VARIANT)
             else:
                 weights = missing_weights(cls, seed=1)
         out = osnet_graph(cls, weights, fuse_lightconv)
@@ -114,9 +115,20 @@ class ReID:
                                        __doc__=f'ReID model read from {path.name}'))
 
 
+# the instance normalisation in the tail of a block, per variant and block (None: OSNet's plain block)
+#   'ibn'  osnet.py, IN=True:   relu(IN(conv3(x2) + identity)) in every block of conv2 and conv3
+#   'ain'  osnet_ain.py:        OSBlockINin, relu(IN(conv3(x2)) + identity) with a conv3 that has neither batch norm nor bias;
+#                               blocks [[INin, INin], [OSBlock, INin], [INin, OSBlock]]
+_BLOCK_IN = {'osnet': {},
+             'ibn': {b: 'ibn' for b in ('conv2.0', 'conv2.1', 'conv3.0', 'conv3.1')},
+             'ain': {b: 'ain' for b in ('conv2.0', 'conv2.1', 'conv3.1', 'conv4.0')}}
+
+
 def osnet_graph(model, weights, fuse_lightconv=True):
     _, H, W = model.INPUT_SHAPE
     c0, c1, c2, c3 = model.CHANNELS
+    variant = getattr(model, 'VARIANT', 'osnet')
+    block_in = _BLOCK_IN[variant]
     g = Graph(weights, (H, W), 3)
 
     def osblock(name, x, cout, cat=None):
@@ -157,25 +169,37 @@ def osnet_graph(model, weights, fuse_lightconv=True):
                 gid, gp = g.gate(name + '.gate', s, hid, gp)
                 gids.append(gid)
             x2 = g.gate_sum(streams, gids)
+        kind = block_in.get(name)
         if cat is not None:
             wd, bd = fold_bn(weights.conv(name + '.down', cout, x.c, 1, bn=True))
             w3, b3 = fold_bn(weights.conv(name + '.conv3', cout, mid, 1, bn=True))
-            return g.conv(name + '.conv3+down', cat, cout, 1, 1, 'relu', wb=(np.concatenate([w3, wd], axis=1), b3 + bd))
+            wb = (np.concatenate([w3, wd], axis=1), b3 + bd)
+            if kind == 'ibn':       # conv3 + downsample is linear: the concat form holds, the norm and the ReLU follow it
+                return g.convin(name + '.conv3+down', cat, cout, name + '.IN', act='relu', wb=wb)
+            return g.conv(name + '.conv3+down', cat, cout, 1, 1, 'relu', wb=wb)
         if x.c != cout:
             ident = g.conv(name + '.down', x, cout, 1, 1, 'linear')
         else:
             ident = x
+        if kind == 'ibn':
+            return g.convin(name + '.conv3', x2, cout, name + '.IN', act='relu', res=ident, res_mode=RES_BEFORE_NORM)
+        if kind == 'ain':           # only the conv3 half is normalised: no concat form; Conv1x1Linear(bn=False)
+            return g.convin(name + '.conv3', x2, cout, name + '.IN', act='relu', res=ident, res_mode=RES_AFTER_NORM, bn=False, bias=False)
         return g.conv(name + '.conv3', x2, cout, 1, 1, 'relu', res=ident, res_mode=RES_BEFORE_ACT)
 
     def down_block(name, make_x, cin, cout, h, w):
         """First block of a stage (cin != cout).  make_x(dst) emits the layer producing the block input."""
         mid = cout // 4
-        if fuse_lightconv and mid % 8 == 0 and mid <= 128:
+        if fuse_lightconv and mid % 8 == 0 and mid <= 128 and block_in.get(name) != 'ain':
             cat = g.new(h, w, mid + cin)
             return osblock(name, make_x(cat.slice(mid, cin)), cout, cat=cat)
         return osblock(name, make_x(None), cout)
 
-    s = g.conv('conv1', g.input, c0, 7, 2, 'relu', pad=3)
+    if variant == 'osnet':
+        s = g.conv('conv1', g.input, c0, 7, 2, 'relu', pad=3)
+    else:       # ConvLayer(IN=True): conv (no bias), InstanceNorm2d(affine), ReLU -- the norm needs the whole map: conv + instnorm
+        s = g.conv('conv1', g.input, c0, 7, 2, 'linear', pad=3, bn=False, bias=False)
+        s = g.instnorm('conv1.IN', s, *weights.instnorm('conv1.IN', c0), 1e-5, 'relu')
     x = down_block('conv2.0', lambda dst: g.pool(s, 3, 2, 1, dst=dst), c0, c1, H // 4, W // 4)
     x = osblock('conv2.1', x, c1)
     t2 = g.conv('conv2.t', x, c1, 1, 1, 'relu')
@@ -188,7 +212,8 @@ def osnet_graph(model, weights, fuse_lightconv=True):
     x = g.conv('conv5', x, c3, 1, 1, 'relu')
     g.head('fc', x, model.OUTPUT_LAYOUT)
     g.outputs = [x]
-    g.fuse_ostail(tail)       # x0.25 widths: everything after the last transition conv as one launch (ostail.hip)
+    fused = g.fuse_ostail(tail)       # x0.25 widths: everything after the last transition conv as one launch (ostail.hip)
+    assert not (fused and variant == 'ain')     # (its conv4.0 is an OSBlockINin: not the sequence that launch computes)
     return g, x
 
 
@@ -209,3 +234,37 @@ class OSNet10(ReID):
     OUTPUT_LAYOUT = 512
     METRIC = 'cosine'
     CHANNELS = (64, 256, 384, 512)
+
+
+class OSNetIBN10(ReID):
+    """torchreid osnet_ibn_x1_0: OSNet with instance normalisation in the stem and behind the residual sum of the blocks
+    of conv2 and conv3.  Not provided."""
+    ENGINE_PATH = Path(__file__).parent / 'osnet_ibn_x1_0.hipnet'
+    MODEL_PATH = Path(__file__).parent / 'osnet_ibn_x1_0.onnx'
+    INPUT_SHAPE = (3, 256, 128)
+    OUTPUT_LAYOUT = 512
+    METRIC = 'cosine'
+    CHANNELS = (64, 256, 384, 512)
+    VARIANT = 'ibn'
+
+
+class OSNetAIN10(ReID):
+    """torchreid osnet_ain_x1_0 (the architecture found by OSNet-AIN's search: OSBlockINin blocks).  Not provided."""
+    ENGINE_PATH = Path(__file__).parent / 'osnet_ain_x1_0.hipnet'
+    MODEL_PATH = Path(__file__).parent / 'osnet_ain_x1_0.onnx'
+    INPUT_SHAPE = (3, 256, 128)
+    OUTPUT_LAYOUT = 512
+    METRIC = 'cosine'
+    CHANNELS = (64, 256, 384, 512)
+    VARIANT = 'ain'
+
+
+class OSNetAIN025(ReID):
+    """torchreid osnet_ain_x0_25.  Not provided."""
+    ENGINE_PATH = Path(__file__).parent / 'osnet_ain_x0_25.hipnet'
+    MODEL_PATH = Path(__file__).parent / 'osnet_ain_x0_25.onnx'
+    INPUT_SHAPE = (3, 256, 128)
+    OUTPUT_LAYOUT = 512
+    METRIC = 'cosine'
+    CHANNELS = (16, 64, 96, 128)
+    VARIANT = 'ain'

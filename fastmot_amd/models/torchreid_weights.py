@@ -14,6 +14,15 @@ checkpoint's state_dict is read directly.  The mapping below follows torchreid/m
     conv5                      Conv1x1
     fc.0 / fc.1                Linear + BatchNorm1d
 
+Two more variants share the loader (VARIANT of the descriptor, models/reid.py):
+
+    'ibn'   osnet_ibn_x1_0 (osnet.py with IN=True): the names above; conv1.bn is an InstanceNorm2d(affine) -- weight and bias,
+            no running statistics -- and every block of conv2 / conv3 has .IN (InstanceNorm2d(affine))
+    'ain'   osnet_ain_x* (osnet_ain.py): streams  .conv2.{0..3}.layers.{i} (LightConvStream; LightConv3x3 as above),
+            transitions  pool2.0 / pool3.0 (Conv1x1 in front of the average pool), conv1.bn an InstanceNorm2d as for 'ibn',
+            OSBlockINin blocks (conv2.0, conv2.1, conv3.1, conv4.0) with .IN and a .conv3 WITHOUT batch norm and bias
+These names are derived from the published torchreid sources, not checked against a checkpoint.
+
 PyTorch is used for unpickling only (`torch.load`); a plain dict of arrays works as well -- that is how the
 reference's ONNX export of the same model arrives (models/onnx_reader.torchreid_state_dict_from_onnx).
 """
@@ -22,9 +31,12 @@ import numpy as np
 _STREAM = {1: 'conv2a', 2: 'conv2b', 3: 'conv2c', 4: 'conv2d'}
 
 
-def _key(name):
+VARIANTS = ('osnet', 'ibn', 'ain')
+
+
+def _key(name, variant='osnet'):
     """Layer-table parameter name (models/reid.py) -> (state_dict prefix of the conv / linear, prefix of the
-    batch norm or None)."""
+    batch norm or None).  variant 'ain': the module names of osnet_ain.py where they differ."""
     parts = name.split('.')
     if name == 'conv1' or name == 'conv5':
         return f'{name}.conv', f'{name}.bn'
@@ -32,6 +44,8 @@ def _key(name):
         return 'fc.0', 'fc.1'
     stage = parts[0]                                   # conv2 / conv3 / conv4
     if parts[1] == 't':
+        if variant == 'ain':
+            return f'pool{stage[4:]}.0.conv', f'pool{stage[4:]}.0.bn'
         return f'{stage}.2.0.conv', f'{stage}.2.0.bn'
     block = f'{stage}.{parts[1]}'
     tail = parts[2:]
@@ -45,13 +59,30 @@ def _key(name):
         return f'{block}.gate.{tail[1]}', None
     if tail[0].startswith('s') and tail[-1] in ('pw', 'dw'):
         t, i = int(tail[0][1:]), int(tail[1])
+        if variant == 'ain':
+            lc = f'{block}.conv2.{t - 1}.layers.{i}'
+            return (f'{lc}.conv1', None) if tail[-1] == 'pw' else (f'{lc}.conv2', f'{lc}.bn')
         lc = f'{block}.{_STREAM[t]}' if t == 1 else f'{block}.{_STREAM[t]}.{i}'
         return (f'{lc}.conv1', None) if tail[-1] == 'pw' else (f'{lc}.conv2', f'{lc}.bn')
     raise KeyError(f'no torchreid parameter for layer {name!r}')
 
 
+def _in_key(name):
+    """Layer-table name of an instance normalisation -> state_dict prefix: the stem's is the module torchreid still calls
+    `bn` (ConvLayer(IN=True)), a block's is `IN`."""
+    if name == 'conv1.IN':
+        return 'conv1.bn'
+    parts = name.split('.')
+    if len(parts) == 3 and parts[2] == 'IN':
+        return name
+    raise KeyError(f'no torchreid instance normalisation for layer {name!r}')
+
+
 class TorchreidWeights:
-    def __init__(self, source):
+    def __init__(self, source, variant='osnet'):
+        if variant not in VARIANTS:
+            raise ValueError(f'variant {variant!r}: expected one of {VARIANTS}')
+        self.variant = variant
         if isinstance(source, dict):
             sd = source
         else:
@@ -77,7 +108,7 @@ class TorchreidWeights:
                     mean=self._get(prefix + '.running_mean', (c,)), var=self._get(prefix + '.running_var', (c,)))
 
     def conv(self, name, cout, cin, k, bn=True, gain=1.0, groups=1):
-        ck, bk = _key(name)
+        ck, bk = _key(name, self.variant)
         p = dict(w=self._get(ck + '.weight', (cout, cin // groups, k, k)))
         if ck + '.bias' in self.sd:
             p['bias'] = self._get(ck + '.bias', (cout,))
@@ -95,13 +126,22 @@ class TorchreidWeights:
         return p
 
     def linear(self, name, cout, cin, bn=False):
-        ck, bk = _key(name)
+        ck, bk = _key(name, self.variant)
         p = dict(w=self._get(ck + '.weight', (cout, cin)))
         if ck + '.bias' in self.sd:
             p['bias'] = self._get(ck + '.bias', (cout,))
         if bn and (bk + '.weight' in self.sd or ck + '.bias' not in self.sd):
             p.update(self._bn(bk, cout))
         return p
+
+    def instnorm(self, name, c):
+        """-> (gamma, beta) of an InstanceNorm2d(c, affine=True).  It has no running statistics: a module that carries
+        them is a BatchNorm2d -- the checkpoint of another variant -- and is refused by name."""
+        prefix = _in_key(name)
+        if prefix + '.running_mean' in self.sd:
+            raise KeyError(f'checkpoint has running statistics {prefix + ".running_mean"!r}: a BatchNorm2d where the '
+                           f'{self.variant!r} variant has an InstanceNorm2d')
+        return self._get(prefix + '.weight', (c,)), self._get(prefix + '.bias', (c,))
 
     def unused(self):
         """Checkpoint entries the layer table did not consume (the classifier is expected)."""

@@ -350,14 +350,26 @@ enum {
                           * w_off / b_off = f32 gamma [cn] / beta [cn], statistics in fp32 (variance from centred squares); channels
                           * [cn, cin) get the activation only; act = linear or ReLU; eps is a per-op extra: gate[0] = the IEEE-754
                           * bits of the fp32 value (0 <= eps < 1; 1e-5 is 0x3727C5AC).  in_coff / out_coff % 8 == 0, any channel
-                          * strides; out is another tensor than in[0] (never in place), fp16 both                              */
+                          * strides; out is another tensor than in[0] (never in place), fp16 both.  Optional residual: res_mode
+                          * FM_RES_BEFORE_ACT adds the view res / res_coff (cin channels, same map) to every channel behind the
+                          * affine and in front of the activation (the unfused tail of an OSNet-AIN block)                      */
+    FM_OP_CONVIN = 26,   /* the tail of an OSNet-IBN / -AIN block in one launch (convin.hip): pointwise conv of in[0]'s view (cin = K
+                          * channels) to cout channels, instance normalisation of the fp32 result per sample and channel over
+                          * h x w (biased variance, centred squares), residual, act (linear or ReLU), one fp16 store:
+                          *   v = W x + b (+ res: FM_RES_BEFORE_NORM);  y = act((v - mean) / sqrt(var + eps) * gamma + beta (+ res:
+                          *   FM_RES_BEFORE_ACT)).  w_off = fp16 weights in MFMA fragment order [ceil32(cout)/32][ceil16(K)/16][lane][8],
+                          * b_off / w2_off / b2_off = f32 bias / gamma / beta [ceil32(cout)], gate[0] = the IEEE-754 bits of eps as
+                          * FM_OP_INSTNORM; k = 1, stride 1, pad 0; K, cout % 8 == 0 and h * w <= 2048 (fm_convin_supported: a
+                          * workgroup keeps one sample's whole map of 32 channels in registers); out is another tensor than
+                          * in[0] and than res                                                                               */
     FM_OP_GATED_SUM = 11 /* OSNet unified aggregation gate in one launch: out = sum_i in[i] *
                           * sigmoid(fc2(relu(fc1(GAP(in[i]))))) with shared fc weights
                           * (w_off, b_off, w2_off, b2_off, hid) -- FM_OP_GATE x n_in + FM_OP_GATE_SUM */
 };
 enum { FM_ACT_LINEAR = 0, FM_ACT_LEAKY = 1, FM_ACT_MISH = 2, FM_ACT_RELU = 3, FM_ACT_LOGISTIC = 4,
        FM_ACT_SWISH = 5, FM_ACT_RELU6 = 6 /* min(max(x, 0), 6) */ };
-enum { FM_RES_NONE = 0, FM_RES_AFTER_ACT = 1, FM_RES_BEFORE_ACT = 2 };
+enum { FM_RES_NONE = 0, FM_RES_AFTER_ACT = 1, FM_RES_BEFORE_ACT = 2,
+       FM_RES_BEFORE_NORM = 3 /* FM_OP_CONVIN only: part of the value that is normalised */ };
 
 typedef struct fm_tensor {
     int32_t h, w, c;     /* per-sample geometry, c = channel stride (multiple of 8) */
@@ -1378,6 +1390,8 @@ size_t fm_litechain_lds_bytes(int c, int w, int h);
 int fm_resblock_supported(int c, int mid);
 /* 1 when FM_OP_SEPCONV supports a separable block cin -> cout with a depthwise stride (no device needed) */
 int fm_sepconv_supported(int cin, int cout, int stride);
+/* 1 when FM_OP_CONVIN runs a pointwise conv K -> cout with instance normalisation over a map of hw pixels (no device needed) */
+int fm_convin_supported(int K, int cout, int hw);
 /* profiling hook: accumulated host wall time (ms) of the stages of fm_flow_predict -- out5 = {begin, prepare,
  * lk, estimate, number of calls}; reset != 0 clears the accumulators */
 int fm_flow_timing(double* out5, int reset);
