@@ -68,6 +68,9 @@ bool convin_supported(int K, int cout, int hw);
 int launch_convin(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, const f16* res, int res_cs, int res_coff,
                   int res_mode, const f16* w, const float* bias, const float* gamma, const float* beta, int N, int HW, int K,
                   int cout, float eps, int act, hipStream_t s);
+bool nonlocal_supported(int C, int hw);
+int launch_nonlocal(const f16* in, int in_cs, int in_coff, f16* out, int out_cs, int out_coff, int N, int HW, int C, const float* w3,
+                    const float* bias3, const float* wa, const float* wb, hipStream_t s);
 int fm_emb_reserve(fm_ctx* ctx, int n);
 
 
@@ -150,7 +153,8 @@ int fm_net_front_prepare(fm_ctx* ctx, NetState* net, int request, int* k) {
         switch (op) {
             case FM_OP_CONV: case FM_OP_CONVS: case FM_OP_CONVD: case FM_OP_DWCONV3: case FM_OP_DWCONV: case FM_OP_SEPCONV:
             case FM_OP_STEMCONV: case FM_OP_STEM2: case FM_OP_STEMPOOL: case FM_OP_PAIR11: case FM_OP_SPP: case FM_OP_MAXPOOL:
-            case FM_OP_AVGPOOL: case FM_OP_UPSAMPLE2: case FM_OP_RESBLOCK: case FM_OP_ADD: case FM_OP_COPY: case FM_OP_INSTNORM: case FM_OP_CONVIN: return true;
+            case FM_OP_AVGPOOL: case FM_OP_UPSAMPLE2: case FM_OP_RESBLOCK: case FM_OP_ADD: case FM_OP_COPY: case FM_OP_INSTNORM: case FM_OP_CONVIN:
+            case FM_OP_NONLOCAL: return true;
             default: return false;
         }
     };
@@ -554,6 +558,19 @@ static int run_layer(fm_ctx* ctx, NetState* net, const fm_layer& L, int B) {
                                  (const float*)(net->weights + L.w2_off), (const float*)(net->weights + L.b2_off), B, ti.h * ti.w,
                                  L.cin, L.cout, eps, L.act, s);
         }
+        case FM_OP_NONLOCAL: {  // w_off = f32 [3][cin] theta / phi / g, b_off = their biases, w2_off / b2_off = f32 a / b [cin]
+            const size_t wb = net->weight_bytes, cb = (size_t)L.cin * 4;
+            FM_CHECK_ARG(!ti.f32 && !to.f32 && L.out != L.in[0] && to.h == ti.h && to.w == ti.w && L.cout == L.cin &&
+                         nonlocal_supported(L.cin, ti.h * ti.w) && L.res_mode == FM_RES_NONE && L.act == FM_ACT_LINEAR);
+            FM_CHECK_ARG(L.in_coff[0] >= 0 && L.out_coff >= 0 && L.in_coff[0] % 8 == 0 && L.out_coff % 8 == 0 &&
+                         L.in_coff[0] + L.cin <= ti.c && L.out_coff + L.cin <= to.c);
+            FM_CHECK_ARG(L.w_off >= 0 && L.b_off >= 0 && L.w2_off >= 0 && L.b2_off >= 0 && L.w_off % 16 == 0 && L.b_off % 16 == 0 &&
+                         L.w2_off % 16 == 0 && L.b2_off % 16 == 0 && (size_t)L.w_off + 3 * cb <= wb && (size_t)L.b_off + 16 <= wb &&
+                         (size_t)L.w2_off + cb <= wb && (size_t)L.b2_off + cb <= wb);
+            return launch_nonlocal(in0, ti.c, L.in_coff[0], out, to.c, L.out_coff, B, ti.h * ti.w, L.cin,
+                                   (const float*)(net->weights + L.w_off), (const float*)(net->weights + L.b_off),
+                                   (const float*)(net->weights + L.w2_off), (const float*)(net->weights + L.b2_off), s);
+        }
         case FM_OP_POOLHEAD: {  // gate[0] > 0: BN neck (w2_off / b2_off = f32 scale / shift [cin]); gate[1] > 0: FC (w_off fp16 [cout][cin], b_off f32 [cout])
             // gate[2] > 0: GeM pooling, the IEEE bits of p (0.5 .. 16) there and of the clamp eps in gate[3]
             const bool neck = L.gate[0] > 0, fc = L.gate[1] > 0;
@@ -837,6 +854,10 @@ static void layer_cost(const NetState* net, const fm_layer& L, int B, double* fl
             *flops = 2.0 * L.cin * L.cout * pout + 6.0 * pout * L.cout;
             *bytes = pin * L.cin * 2 + pout * L.cout * 2 + (double)L.cin * L.cout * 2 + (L.res_mode != FM_RES_NONE ? pout * L.cout * 2 : 0);
             break;
+        case FM_OP_NONLOCAL:    // the view in once (the apply pass re-reads it from L2: counted once), out once, the five fp32 vectors
+            *flops = 2.0 * 3 * L.cin * pin + 2.0 * pin * L.cin;
+            *bytes = (pin + pout) * L.cin * 2 + 5.0 * L.cin * 4;
+            break;
         case FM_OP_POOLHEAD:
             *flops = (double)pin * L.cin + (L.gate[1] > 0 ? 2.0 * L.cin * L.cout * B : 0.);
             *bytes = pin * L.cin * 2 + (L.gate[1] > 0 ? (double)L.cin * L.cout * 2 : 0.) + (double)B * L.cout * 8;
@@ -886,8 +907,8 @@ extern "C" int fm_net_cost(fm_ctx* ctx, int which, int batch, double* flops, dou
                 f += 2.0 * c2 * L.cout * pout;
                 b += pout * c2 * 2 + pout * L.cout * 2 + (double)c2 * L.cout * 2;
             }
-        } else if (L.op == FM_OP_INSTNORM) {
-            // no conv FLOPs, but bytes no fusion removes: the statistics need the whole map before the first output
+        } else if (L.op == FM_OP_INSTNORM || L.op == FM_OP_NONLOCAL) {
+            // no conv FLOPs, but bytes no fusion removes: the statistics (the sample's scalar) need the whole map before the first output
             double lf, lb;
             layer_cost(net, L, batch, &lf, &lb);
             b += lb;

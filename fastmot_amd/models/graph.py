@@ -16,7 +16,7 @@ LOGGER = logging.getLogger(__name__)
 
 (OP_CONV, OP_DWCONV3, OP_MAXPOOL, OP_AVGPOOL, OP_UPSAMPLE2, OP_COPY, OP_GATE, OP_GATE_SUM, OP_HEAD,
  OP_LITECONV, OP_SPP, OP_GATED_SUM, OP_STEMCONV, OP_ADD, OP_RESBLOCK, OP_CONVS, OP_LITECHAIN, OP_CONVD, OP_STEM2, OP_PAIR11,
- OP_OSTAIL, OP_DWCONV, OP_SEPCONV, OP_POOLHEAD, OP_STEMPOOL, OP_INSTNORM, OP_CONVIN) = range(27)
+ OP_OSTAIL, OP_DWCONV, OP_SEPCONV, OP_POOLHEAD, OP_STEMPOOL, OP_INSTNORM, OP_CONVIN, OP_NONLOCAL) = range(28)
 CONV_OPS = (OP_CONV, OP_CONVS, OP_CONVD)      # the three kernels behind Graph.conv (same fields, different weight layouts)
 SPP_MAX_HW = 2048
 ACT = {'linear': 0, 'leaky': 1, 'mish': 2, 'relu': 3, 'logistic': 4, 'swish': 5, 'relu6': 6}
@@ -24,6 +24,7 @@ RES_NONE, RES_AFTER_ACT, RES_BEFORE_ACT = 0, 1, 2
 RES_BEFORE_NORM = 3        # FM_OP_CONVIN only: the residual is part of the value that is normalised
 RES_AFTER_NORM = RES_BEFORE_ACT
 CONVIN_MAX_HW = 2048
+NONLOCAL_MAX_HW, NONLOCAL_MAX_C = 4096, 2048
 
 
 class fm_tensor(C.Structure):
@@ -883,6 +884,34 @@ class Graph:
         self._layer(op=OP_INSTNORM, ins=[x], out=dst, cin=x.c, cout=x.c, hid=cn, act=ACT[act], gates=[f32_bits(eps)],
                     res=res, res_mode=RES_BEFORE_ACT if res is not None else RES_NONE,
                     w_off=self._push(gamma), b_off=self._push(beta), name=name, instnorm_ref=(gamma, beta, eps))
+        return dst
+
+    @staticmethod
+    def nonlocal_supported(c, hw):
+        """The shapes FM_OP_NONLOCAL runs (nonlocal.hip: nonlocal_supported; tests/test_nonlocal_host.py asserts they agree): a
+        workgroup keeps theta of one sample's map, and the parameters of more than 512 channels, in LDS."""
+        return 8 <= c <= NONLOCAL_MAX_C and c % 8 == 0 and 1 <= hw <= NONLOCAL_MAX_HW
+
+    def nonlocal_(self, name, x, wtheta, wphi, wg, biases, a, b, dst=None):
+        """fast-reid's Non_local block in its one-inner-channel, dot-product form in one launch (FM_OP_NONLOCAL, nonlocal.hip):
+        theta_i, phi_i, g_i = wtheta . x_i + biases[0], wphi . x_i + biases[1], wg . x_i + biases[2] per pixel, s =
+        mean_i(phi_i g_i) per sample, out[i, c] = x[i, c] + a[c] theta_i s + b[c] (a, b: the 1 -> C conv W with its BatchNorm
+        folded).  All parameters stay fp32.  The result goes to a new tensor (or the view dst of another one), never in
+        place.  Keeps nl_ref = (wtheta, wphi, wg, biases [3], a, b) as the fp32 arrays the device reads."""
+        wtheta, wphi, wg, a, b = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (wtheta, wphi, wg, a, b))
+        biases = np.ascontiguousarray(biases, np.float32).reshape(-1)
+        c = x.c
+        if x.coff % 8 or not self.nonlocal_supported(c, x.h * x.w):
+            raise ValueError(f'{name}: the non-local block needs 8 <= channels <= {NONLOCAL_MAX_C}, a multiple of 8, and a map of at '
+                             f'most {NONLOCAL_MAX_HW} pixels (got {c} channels at offset {x.coff} on {x.h} x {x.w})')
+        if not (wtheta.shape == wphi.shape == wg.shape == a.shape == b.shape == (c,) and biases.shape == (3,)):
+            raise ValueError(f'{name}: the non-local block over {c} channels takes five vectors of {c} and three biases')
+        if dst is None:
+            dst = self.new(x.h, x.w, c)
+        assert (dst.h, dst.w, dst.c) == (x.h, x.w, c) and dst.tid != x.tid and dst.coff % 8 == 0 and not self.tensors[dst.tid][3]
+        self._layer(op=OP_NONLOCAL, ins=[x], out=dst, cin=c, cout=c, act=ACT['linear'],
+                    w_off=self._push(np.stack([wtheta, wphi, wg])), b_off=self._push(np.append(biases, np.float32(0))),
+                    w2_off=self._push(a), b2_off=self._push(b), name=name, nl_ref=(wtheta, wphi, wg, biases, a, b))
         return dst
 
     def poolhead(self, name, x, neck=None, fc=None, relu=False, gem=None):

@@ -25,6 +25,14 @@ IBN-Net layers (one FM_OP_INSTNORM launch each, Graph.instnorm, csrc/instnorm.hi
                         `res=` for the sum) without activation, then instnorm(cn = c); a Relu behind it becomes the op's
                         activation.  A 7x7 stem followed by InstanceNormalization is conv + instnorm + pool: the normalisation
                         needs the whole conv map before the pool may start, so FM_OP_STEMPOOL is not used there
+fast-reid's non-local blocks (AGW, SBS: `Non_local` with WITH_NL; one FM_OP_NONLOCAL launch each, Graph.nonlocal_, csrc/nonlocal.hip)
+    three Conv (1x1, ONE output channel, with bias) that read the same stored map X -> Reshape [B, 1, -1 | N] each ->
+    Transpose(0, 2, 1) on two of them -> MatMul(theta^T, phi) -> Div by N = H * W (or Mul by 1 / N) -> MatMul(., g^T) ->
+    Transpose(0, 2, 1) -> Reshape [B, 1, H, W] -> Conv 1 -> C (+ BatchNormalization, folded here) -> Add(., X).  Roles come
+    from the wiring: theta is the left operand of the first MatMul, phi its right one (no Transpose), g the right operand of
+    the second.  With one inner channel the N x N matrix never exists on the device: s = mean(phi g) per sample, z = X +
+    a theta s + b.  The shape operands are constants, or the exporter's unfolded Concat(axis 0) of Unsqueeze(axes [0]) of
+    scalar constants: that small integer subgraph is folded here whatever its nodes are called
 Head operators (the suffix of the graph; one FM_OP_POOLHEAD launch, Graph.poolhead)
     GlobalAveragePool | ReduceMean over axes (2, 3) | AveragePool whose kernel is the whole map
     GeM pooling: Clip(min = a positive scalar constant, no max) -> Pow(scalar constant or initialiser p, 0.5 .. 16) -> one of
@@ -37,9 +45,10 @@ The tracker L2-normalises whatever comes out (feature_extractor.py of the refere
 
 Anything else raises NotImplementedError naming the node: an InstanceNormalization of a map that is already stored and
 activated (OSNet-IBN / OSNet-AIN keep theirs inside the fused OSNet operators), a Split whose IN part is no multiple of 8 or
-does not lead, a Pow without its Clip, with a per-channel exponent or without the matching root, Sigmoid / Mul (SE,
-non-local), grouped or dilated convs, asymmetric pads, a second graph output.  Those models need kernels this engine does
-not have; silently approximating them would give embeddings that look plausible and match nothing.
+does not lead, a Pow without its Clip, with a per-channel exponent or without the matching root, Sigmoid / Mul (SE), a
+non-local block with more than one inner channel, a Softmax (the embedded-Gaussian form), a divisor other than H * W or a
+sum with anything but its own input, grouped or dilated convs, asymmetric pads, a second graph output.  Those models need
+kernels this engine does not have; silently approximating them would give embeddings that look plausible and match nothing.
 """
 import numpy as np
 
@@ -52,7 +61,11 @@ SUPPORTED = ('Conv (groups 1, square k in {1, 3, 7}, stride 1 or 2, symmetric pa
              '-> Relu; IBN-b: InstanceNormalization (+ Relu) behind a Conv or a Conv + Add read by it alone; as the head: '
              'GlobalAveragePool / ReduceMean over (2, 3) / whole-map AveragePool, optionally as GeM (Clip(min > 0) -> Pow(scalar '
              'p) -> pool -> Pow(1 / p)), Flatten / Reshape / Squeeze, BatchNormalization on the pooled vector, Gemm or '
-             'MatMul + Add, BatchNormalization, Relu')
+             'MatMul + Add, BatchNormalization, Relu; fast-reid non-local block: three Conv 1x1 -> 1 channel of one stored map X -> '
+             'Reshape [B, 1, N] (+ Transpose(0, 2, 1) on theta and g) -> MatMul(theta, phi) -> Div by H * W (or Mul by its '
+             'reciprocal) -> MatMul(., g) -> Transpose -> Reshape [B, 1, H, W] -> Conv 1x1 1 -> C (+ BatchNormalization) -> '
+             'Add(., X), with 8 <= C <= 2048, C % 8 == 0, H * W <= 4096; shape operands as constants or Concat / Unsqueeze '
+             'of integer constants')
 
 
 class _Conv:
@@ -106,6 +119,35 @@ class _Scalar(_Only):
 
     def __init__(self, value):
         self.value = value
+
+
+class _Ints(_Only):
+    what = 'a folded integer constant: only a shape operand may'
+
+    def __init__(self, values):
+        self.values = values
+
+
+class _NLVec(_Only):
+    """theta, phi or g of a non-local block as [B, 1, N] (t: transposed to [B, N, 1]); conv: the pending 1x1 Conv behind it."""
+    what = 'an intermediate value of a non-local block: only the nodes of that block may'
+
+    def __init__(self, conv, t=False):
+        self.conv, self.t = conv, t
+
+
+class _NLF(_NLVec):
+    """matmul(theta, phi), [B, N, N]; div: already divided by N."""
+
+    def __init__(self, theta, phi, div=False):
+        self.theta, self.phi, self.div = theta, phi, div
+
+
+class _NLY(_NLVec):
+    """matmul(f / N, g): stage 0 as [B, N, 1], 1 transposed, 2 reshaped to the map [B, 1, H, W]; then W (a, b: float64)."""
+
+    def __init__(self, f, g, stage=0, a=None, b=None, bn=False):
+        self.f, self.g, self.stage, self.a, self.b, self.bn = f, g, stage, a, b, bn
 
 
 class _Vec:
@@ -212,6 +254,22 @@ class _Lowering:
                 return float(a.reshape(-1)[0])
         return None
 
+    def ints(self, name):
+        """The integers of a constant of the file or of a folded Unsqueeze / Concat of such; None for anything else."""
+        v = self.env.get(name)
+        if isinstance(v, _Ints):
+            return v.values
+        if name and self.m.has(name):
+            a = np.asarray(self.m.tensor(name))
+            if a.dtype.kind in 'iu' and a.size <= 8:
+                self.use(name)
+                return [int(q) for q in a.reshape(-1)]
+        return None
+
+    def only(self, nd, i):
+        if not self.sole(nd.inputs[i]):
+            self.refuse(nd, f'input {nd.inputs[i]!r} is a value of a non-local block that something else reads as well')
+
     def open_root(self, v, nd):
         if v.gem_node is not None:
             self.refuse(nd, f'follows GeM pooling ({self.name_of(v.gem_node)!r}) whose root Pow(1 / p) has not been applied')
@@ -219,6 +277,8 @@ class _Lowering:
     # ------------------------------------------------------------------------------------------ operators
     def conv(self, nd):
         a = nd.attrs
+        if isinstance(self.env.get(nd.inputs[0]), _NLY):
+            return self.nl_w(nd)
         w = self.const(nd, 1).astype(np.float32)
         if w.ndim != 4:
             self.refuse(nd, f'weights of shape {w.shape}')
@@ -251,6 +311,12 @@ class _Lowering:
             w = (v.w.astype(np.float64) * scale[:, None, None, None]).astype(np.float32)
             b = (v.b.astype(np.float64) * scale + shift).astype(np.float32)
             self.env[nd.outputs[0]] = _Conv(v.node, v.x, w, b, v.k, v.stride, v.pad)
+        elif isinstance(v, _NLY) and v.a is not None and not v.bn:
+            self.only(nd, 0)
+            scale, shift = _bn_affine(self.m, nd, self.use)
+            if scale.shape != v.a.shape:
+                self.refuse(nd, f'{scale.shape[0]} channels behind the W conv of a non-local block over {v.a.shape[0]}')
+            self.env[nd.outputs[0]] = _NLY(v.f, v.g, 2, v.a * scale, v.b * scale + shift, bn=True)
         elif isinstance(v, _Part) and not v.done:
             sp = v.split
             if v.index != 1 or not self.sole(nd.inputs[0]):
@@ -294,6 +360,8 @@ class _Lowering:
 
     def add(self, nd):
         a, b = (self.env.get(t) for t in nd.inputs)
+        if isinstance(a, _NLVec) or isinstance(b, _NLVec):
+            return self.nl_sum(nd, 0 if isinstance(a, _NLVec) else 1)
         if isinstance(a, _Vec) or isinstance(b, _Vec):
             v, other = (a, 1) if isinstance(a, _Vec) else (b, 0)
             if not (v.bias_open and self.m.has(nd.inputs[other])):
@@ -438,6 +506,9 @@ class _Lowering:
             self.refuse(nd, 'Pow that is neither the power of GeM pooling (behind its Clip, scalar exponent) nor its root')
 
     def fold_scalar(self, nd):
+        for i, t in enumerate(nd.inputs[:2]):
+            if nd.op == 'Mul' and len(nd.inputs) == 2 and isinstance(self.env.get(t), _NLF):
+                return self.nl_div(nd, i)
         vals = [self.scalar(t) for t in nd.inputs]
         if not vals or any(v is None for v in vals):
             self.refuse(nd, 'operator not supported')
@@ -478,6 +549,11 @@ class _Lowering:
 
     def reshape(self, nd):
         v = self.env.get(nd.inputs[0])
+        if nd.op == 'Reshape' and len(nd.inputs) > 1 and isinstance(v, (_NLY, _Conv)):
+            shape = self.ints(nd.inputs[1])
+            # (a pending conv flattened to [B, k, N]: theta, phi or g of a non-local block; its product back to a map)
+            if isinstance(v, _NLY) or (shape is not None and len(shape) == 3):
+                return self.nl_reshape(nd, v)
         if not isinstance(v, _Vec):
             self.refuse(nd, f'{nd.op} in front of the global pool')
         for t in nd.inputs[1:]:          # (the target shape / axes: constants of the file)
@@ -488,6 +564,8 @@ class _Lowering:
         self.env[nd.outputs[0]] = v
 
     def fc(self, nd):
+        if nd.op == 'MatMul' and any(isinstance(self.env.get(t), _NLVec) for t in nd.inputs):
+            return self.nl_matmul(nd)
         v = self.env.get(nd.inputs[0])
         if not isinstance(v, _Vec) or v.fc is not None:
             self.refuse(nd, f'{nd.op} that does not read the pooled vector (or a second FC)')
@@ -513,6 +591,112 @@ class _Lowering:
         v.bias_open = nd.op == 'MatMul'
         self.env[nd.outputs[0]] = v
 
+    # ---- fast-reid's non-local block
+    def fold_ints(self, nd):
+        """Unsqueeze(axes [0]) of an integer constant, Concat(axis 0) of such: the exporter's unfolded shape operands."""
+        if nd.op == 'Concat':
+            vals, axes = [self.ints(t) for t in nd.inputs], [nd.attrs.get('axis')]
+            if not vals or any(v is None for v in vals):
+                return self.concat(nd)                # (the Concat of an IBN layer, or one that is refused there)
+        else:
+            vals, axes = [self.ints(nd.inputs[0])], nd.attrs.get('axes')
+            if axes is None and len(nd.inputs) > 1:   # (opset 13: the axes as an input)
+                axes = self.ints(nd.inputs[1])
+            if vals[0] is None or len(vals[0]) != 1:
+                self.refuse(nd, 'operator not supported')
+        if list(axes or []) != [0]:
+            self.refuse(nd, f'{nd.op} of integer constants along axes {axes}')
+        self.env[nd.outputs[0]] = _Ints([q for v in vals for q in v])
+
+    def nl_reshape(self, nd, v):
+        shape = self.ints(nd.inputs[1])
+        if shape is None:
+            self.refuse(nd, f'computed shape input {nd.inputs[1]!r}')
+        self.only(nd, 0)
+        if isinstance(v, _Conv):                      # theta, phi or g: [B, inter, H, W] -> [B, inter, N]
+            k, x = v.w.shape[0], v.x
+            if shape[1] != k or (v.k, v.stride, v.pad) != (1, 1, 0):
+                self.refuse(nd, f'{nd.op} in front of the global pool')
+            if k != 1:
+                self.refuse(nd, f'non-local block with inter channels {k}: only the one-channel form fast-reid\'s Non_local builds')
+            if shape[2] not in (-1, x.h * x.w):
+                self.refuse(nd, f'shape {shape} of a non-local block over a {x.h} x {x.w} map')
+            self.env[nd.outputs[0]] = _NLVec(v)
+            return
+        x = v.g.x
+        if v.stage != 1 or v.a is not None or len(shape) != 4 or shape[1:] != [1, x.h, x.w]:
+            self.refuse(nd, f'shape {shape} behind the products of a non-local block over a {x.h} x {x.w} map ([B, 1, H, W] behind '
+                            'the Transpose)')
+        self.env[nd.outputs[0]] = _NLY(v.f, v.g, 2)
+
+    def transpose(self, nd):
+        v = self.env.get(nd.inputs[0])
+        ok = type(v) is _NLVec and not v.t or (isinstance(v, _NLY) and v.stage == 0)
+        if not ok or list(nd.attrs.get('perm', [])) != [0, 2, 1]:
+            self.refuse(nd, 'Transpose that is not the (0, 2, 1) of a non-local block\'s theta, g or product')
+        self.only(nd, 0)
+        self.env[nd.outputs[0]] = _NLVec(v.conv, t=True) if type(v) is _NLVec else _NLY(v.f, v.g, 1)
+
+    def nl_matmul(self, nd):
+        a, b = (self.env.get(t) for t in nd.inputs[:2])
+        self.only(nd, 0)
+        self.only(nd, 1)
+        if type(a) is _NLVec and a.t and type(b) is _NLVec and not b.t and a.conv.x is b.conv.x:
+            self.env[nd.outputs[0]] = _NLF(a.conv, b.conv)            # theta: the left operand; phi: the right one, no transpose
+        elif isinstance(a, _NLF) and type(b) is _NLVec and b.t and b.conv.x is a.theta.x:
+            if not a.div:
+                self.refuse(nd, 'the second product of a non-local block without the division by N = H * W in front of it')
+            self.env[nd.outputs[0]] = _NLY(a, b.conv)
+        else:
+            self.refuse(nd, 'MatMul of non-local block values that is neither matmul(theta^T, phi) nor matmul(f / N, g^T) over '
+                            'one input map')
+
+    def nl_div(self, nd, i=0):
+        v = self.env.get(nd.inputs[i])
+        if not (isinstance(v, _NLF) and len(nd.inputs) == 2 and (i == 0 or nd.op == 'Mul')):
+            self.refuse(nd, 'operator not supported')
+        c, n = self.scalar(nd.inputs[1 - i]), v.theta.x.h * v.theta.x.w
+        if v.div or c is None:
+            self.refuse(nd, f'{nd.op} of the product of a non-local block that is not its one division by a constant')
+        if (nd.op == 'Div' and c != n) or (nd.op == 'Mul' and abs(c * n - 1) > 1e-6):
+            self.refuse(nd, f'the divisor {c if nd.op == "Div" else 1 / c if c else c:g} of a non-local block does not match N = H * W = '
+                            f'{n} of its map (f / C, the source\'s variable name, is not what it computes)')
+        self.only(nd, i)
+        self.env[nd.outputs[0]] = _NLF(v.theta, v.phi, div=True)
+
+    def softmax(self, nd):
+        if isinstance(self.env.get(nd.inputs[0]), _NLF):
+            self.refuse(nd, 'Softmax between the products of a non-local block (the embedded-Gaussian variant): only the '
+                            'dot-product form, f / N, is supported')
+        self.refuse(nd, 'operator not supported')
+
+    def nl_w(self, nd):
+        v, a = self.env[nd.inputs[0]], nd.attrs
+        x = v.g.x
+        w = self.const(nd, 1).astype(np.float64)
+        if (v.stage != 2 or v.a is not None or w.shape != (x.c, 1, 1, 1) or a.get('group', 1) != 1 or
+                any(q != 1 for q in a.get('strides', [1, 1])) or any(a.get('pads', [0, 0, 0, 0])) or any(q != 1 for q in a.get('dilations', [1, 1]))):
+            self.refuse(nd, f'weights {w.shape} behind the products of a non-local block over {x.c} channels (W: a 1x1 conv 1 -> C '
+                            'behind the Reshape to [B, 1, H, W])')
+        self.only(nd, 0)
+        b = self.const(nd, 2).astype(np.float64).reshape(-1) if len(nd.inputs) > 2 and nd.inputs[2] else np.zeros(x.c)
+        self.env[nd.outputs[0]] = _NLY(v.f, v.g, 2, w.reshape(-1), b)
+
+    def nl_sum(self, nd, i):
+        v, other = self.env[nd.inputs[i]], self.env.get(nd.inputs[1 - i])
+        if not (isinstance(v, _NLY) and v.a is not None):
+            self.refuse(nd, f'reads {v.what}')
+        x = v.g.x
+        if other is not x:
+            self.refuse(nd, f'Add of a non-local block whose other operand {nd.inputs[1 - i]!r} is not the block\'s own input (z = '
+                            'W(y) + x)')
+        self.only(nd, i)
+        if x.coff % 8 or not Graph.nonlocal_supported(x.c, x.h * x.w):
+            self.refuse(nd, f'non-local block over {x.c} channels on a {x.h} x {x.w} map: FM_OP_NONLOCAL runs 8 <= C <= 2048 with '
+                            'C % 8 == 0 on at most 4096 pixels')
+        theta, phi, g = v.f.theta, v.f.phi, v.g
+        self.env[nd.outputs[0]] = self.g.nonlocal_(self.name_of(nd), x, theta.w, phi.w, g.w, [theta.b[0], phi.b[0], g.b[0]], v.a, v.b)
+
     def skip(self, nd):
         if nd.inputs[0] not in self.env:
             self.refuse(nd, f'input {nd.inputs[0]!r} is not produced by a supported node')
@@ -525,7 +709,8 @@ class _Lowering:
     HANDLERS = {'Conv': conv, 'BatchNormalization': batchnorm, 'Relu': relu, 'Add': add, 'MaxPool': maxpool,
                 'GlobalAveragePool': global_pool, 'ReduceMean': global_pool, 'AveragePool': global_pool,
                 'Flatten': reshape, 'Reshape': reshape, 'Squeeze': reshape, 'Gemm': fc, 'MatMul': fc,
-                'Identity': skip, 'Dropout': skip, 'Split': split, 'InstanceNormalization': instnorm, 'Concat': concat,
+                'Identity': skip, 'Dropout': skip, 'Split': split, 'InstanceNormalization': instnorm, 'Concat': fold_ints,
+                'Unsqueeze': fold_ints, 'Transpose': transpose, 'Div': nl_div, 'Softmax': softmax,
                 'Clip': clip, 'Pow': pow, 'Cast': fold_scalar, 'Reciprocal': fold_scalar, 'Mul': fold_scalar}
 
     def run(self):

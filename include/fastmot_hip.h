@@ -362,6 +362,15 @@ enum {
                           * FM_OP_INSTNORM; k = 1, stride 1, pad 0; K, cout % 8 == 0 and h * w <= 2048 (fm_convin_supported: a
                           * workgroup keeps one sample's whole map of 32 channels in registers); out is another tensor than
                           * in[0] and than res                                                                               */
+    FM_OP_NONLOCAL = 27, /* fast-reid's Non_local block (AGW / SBS models; dot-product form, ONE inner channel) over in[0]'s view in one
+                          * launch, a workgroup per sample with up to four sharing its apply pass (nonlocal.hip): theta_i, phi_i, g_i = three dot products over the cin
+                          * channels of pixel i plus their biases, s = mean_i(phi_i g_i) per sample, out[i, c] = in[i, c] +
+                          * a[c] theta_i s + b[c]; all of it fp32 between the fp16 load and the one fp16 store.  w_off = f32 [3][cin]
+                          * (theta, phi, g), b_off = f32 [4]: their biases (the fourth unused), w2_off / b2_off = f32 a [cin] / b [cin]
+                          * (the 1 -> cin conv W with its BatchNorm folded).  cin = cout, cin % 8 == 0, 8 <= cin <= 2048 and
+                          * h * w <= 4096 (fm_nonlocal_supported: theta of one map stays in LDS); in_coff / out_coff % 8 == 0; no
+                          * residual view, no activation; out is another tensor than in[0].  A sample's sum is taken in an order
+                          * that depends on (cin, h * w) alone                                                               */
     FM_OP_GATED_SUM = 11 /* OSNet unified aggregation gate in one launch: out = sum_i in[i] *
                           * sigmoid(fc2(relu(fc1(GAP(in[i]))))) with shared fc weights
                           * (w_off, b_off, w2_off, b2_off, hid) -- FM_OP_GATE x n_in + FM_OP_GATE_SUM */
@@ -1392,6 +1401,8 @@ int fm_resblock_supported(int c, int mid);
 int fm_sepconv_supported(int cin, int cout, int stride);
 /* 1 when FM_OP_CONVIN runs a pointwise conv K -> cout with instance normalisation over a map of hw pixels (no device needed) */
 int fm_convin_supported(int K, int cout, int hw);
+/* 1 when FM_OP_NONLOCAL runs a non-local block over c channels and a map of hw pixels (no device needed) */
+int fm_nonlocal_supported(int c, int hw);
 /* profiling hook: accumulated host wall time (ms) of the stages of fm_flow_predict -- out5 = {begin, prepare,
  * lk, estimate, number of calls}; reset != 0 clears the accumulators */
 int fm_flow_timing(double* out5, int reset);
