@@ -578,6 +578,14 @@ class YoloCfg(C.Structure):
                 ('max_candidates', C.c_int32)]
 
 
+class DflHeads(C.Structure):
+    """fm_dfl_heads: per level the box / class tensor ids with their first channels, and the level's stride."""
+    _fields_ = [('n_levels', C.c_int32),
+                ('box_tensor', C.c_int32 * FM_MAX_HEADS), ('box_coff', C.c_int32 * FM_MAX_HEADS),
+                ('cls_tensor', C.c_int32 * FM_MAX_HEADS), ('cls_coff', C.c_int32 * FM_MAX_HEADS),
+                ('stride', C.c_float * FM_MAX_HEADS)]
+
+
 DET_DTYPE = np.dtype([('tlbr', float, 4), ('label', int), ('conf', float)], align=True)
 assert DET_DTYPE.itemsize == 48
 
@@ -1012,6 +1020,10 @@ def _bind_device_io(cls):
     def detect_configure(self, cfg):
         check(self.lib.fm_detect_configure(self._ctx, C.byref(cfg)))
 
+    def detect_configure_dfl(self, cfg, heads):
+        """fm_detect_configure_dfl: `cfg` as for detect_configure (its anchor fields are ignored), `heads` a DflHeads."""
+        check(self.lib.fm_detect_configure_dfl(self._ctx, C.byref(cfg), C.byref(heads)))
+
     def detect_async(self):
         check(self.lib.fm_detect_async(self._ctx))
 
@@ -1066,6 +1078,12 @@ def _bind_device_io(cls):
         check(self.lib.fm_detect_last_tiles(self._ctx, _ptr(out), C.c_int(cap), _ptr(counts), C.byref(n)))
         ends = np.cumsum(counts[:n.value])
         return [out[e - c:e].copy().view(np.recarray) for c, e in zip(counts[:n.value], ends)]
+
+    def detect_decode_us(self, iters=20):
+        """fm_detect_decode_us: mean HIP-event time of the decode kernel alone over the last pass's head tensors."""
+        us = C.c_float(0)
+        check(self.lib.fm_detect_decode_us(self._ctx, C.c_int(iters), C.byref(us)))
+        return us.value
 
     def detect_raw_candidates(self, cap=65536):
         rows = np.empty((cap, 8), np.float32)
@@ -1152,8 +1170,8 @@ def _bind_device_io(cls):
                frame_render_overlay, overlay_read, overlay_encode_jpeg, overlay_stream_ms, frame_render_redacted, redact_stream_ms,
                frame_ring_select_next, frame_promote_next, detect_async_next, frame_upload_ahead, frame_ring_select_ahead,
                detect_async_ahead,
-               detect_configure, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,
-               detect_raw_candidates, detect_last_counts, detect_configure_tiles, detect_last_tiles,
+               detect_configure, detect_configure_dfl, detect_async, detect_net_ms, detect_preprocess_only, detect_sync, filter_dets,
+               detect_raw_candidates, detect_decode_us, detect_last_counts, detect_configure_tiles, detect_last_tiles,
                ssd_configure, ssd_detect_async, ssd_stage_ms, ssd_preprocess_only, ssd_detect_sync, ssd_postprocess_host_heads,
                extract_configure, extract_async, extract_sync, extract_read_input):
         setattr(cls, fn.__name__, fn)

@@ -103,6 +103,7 @@ struct fm_ctx {
                                        // frame themselves (pixel_source.h); 0 = front-end kernel + input tensor (tests compare the two, A/B)
     int opt_net_timing = 0;            // "net_timing" = N: HIP events around the detector network on every N-th pass (fm_detect_net_ms); 0 = never
     int opt_nms_general = 0;           // "nms_path" = 1: always the three-kernel sort / bit matrix / scan path (tests, A/B)
+    int opt_dfl_decode_form = 0;       // "dfl_decode_form": 0 = 16 lanes per cell (dfl_decode_kernel), 1 = one thread per cell (A/B, dfl_decode.h)
     // front-ahead (detect.hip detect_pass): the leading layers of a single-frame pass run on another stream beside the
     // previous pass's tail
     int opt_det_front_ahead = 1;       // "det_front_ahead": 0 off, 1 when a pass is still in flight on the detector stream, 2 always (tests)

@@ -29,6 +29,10 @@ extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* key, int value) {
     else if (!strcmp(key, "nms_path")) {
         ctx->opt_nms_general = value != 0;
     }
+    else if (!strcmp(key, "dfl_decode_form")) {
+        FM_CHECK_ARG(value <= 1);
+        ctx->opt_dfl_decode_form = value;
+    }
     else if (!strcmp(key, "fused_input")) ctx->opt_fused_input = value != 0;
     else if (!strcmp(key, "net_timing")) ctx->opt_net_timing = value;
     else if (!strcmp(key, "det_front_ahead") || !strcmp(key, "det_front_stream")) {

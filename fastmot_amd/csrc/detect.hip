@@ -81,6 +81,9 @@ struct DetState {
     uint8_t* label_mask = nullptr;
     float* rows_in = nullptr;     // test hook upload
     int rows_cap = 0;
+    // anchor-free heads with a DFL box branch (fm_detect_configure_dfl): detect_pass launches dfl_decode.h's kernel
+    bool dfl = false;
+    fm_dfl_heads dfl_heads{};
 };
 
 void fm_det_free(DetState* d) {
@@ -249,6 +252,8 @@ __global__ void rows_filter_kernel(const float* __restrict__ rows, int n, Filter
     const float* r = rows + (size_t)i * 7;
     emit_candidate(fa, r[0], r[1], r[2], r[3], r[4], (int)r[5], r[6], i);
 }
+
+#include "dfl_decode.h"     // (the decode of anchor-free DFL heads: YOLOv8)
 
 // ------------------------------------------------------------------------------------ sort + NMS + final filter
 #include "nms_core.h"       // (the device code of the candidate sort and of both NMS routes)
@@ -628,6 +633,7 @@ extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
     d->rd = d->wr;            // a new detector: nothing of the previous one is collected any more
     d->pending = 0;
     d->cfg = *cfg;
+    d->dfl = false;           // (fm_detect_configure_dfl sets it behind this call)
     d->general_post = ctx->opt_nms_general != 0;
     d->n_tiles = 0;           // (untiled until fm_detect_configure_tiles says otherwise)
     d->tile_dets.clear();
@@ -635,6 +641,27 @@ extern "C" int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg) {
     if ((rc = alloc_post(d, cfg->max_candidates > 0 ? cfg->max_candidates : 8192, DetState::NSLOT_UNTILED))) return rc;
     FM_HIP(hipMemcpy(d->label_mask, cfg->label_mask, 128, hipMemcpyHostToDevice));
     d->configured = true;
+    return 0;
+}
+
+// Anchor-free heads with a DFL box branch (dfl_decode.h).  Everything but the decode kernel is the detector above: the
+// same DetState, slots, post-processing and tiling.
+extern "C" int fm_detect_configure_dfl(fm_ctx* ctx, const fm_yolo_cfg* cfg, const fm_dfl_heads* heads) {
+    FM_CHECK_ARG(ctx && cfg && heads);
+    FM_CHECK_ARG(cfg->n_heads >= 1 && cfg->n_heads <= FM_MAX_HEADS && heads->n_levels == cfg->n_heads);
+    for (int i = 0; i < heads->n_levels; ++i)
+        FM_CHECK_ARG(heads->box_tensor[i] >= 0 && heads->cls_tensor[i] >= 0 && heads->box_coff[i] >= 0 && heads->cls_coff[i] >= 0 &&
+                     heads->box_coff[i] % 4 == 0 && heads->cls_coff[i] % 4 == 0 && heads->stride[i] > 0.f);
+    fm_yolo_cfg c = *cfg;
+    for (int i = 0; i < FM_MAX_HEADS; ++i) {      // (the anchor fields are not read: one row per cell)
+        c.n_anchors[i] = i < c.n_heads ? 1 : 0;
+        c.head_tensor[i] = -1;
+    }
+    c.new_coords = 0;
+    int rc = fm_detect_configure(ctx, &c);
+    if (rc) return rc;
+    ctx->det->dfl_heads = *heads;
+    ctx->det->dfl = true;
     return 0;
 }
 
@@ -716,6 +743,7 @@ extern "C" int fm_detect_preprocess_only(fm_ctx* ctx) {
 }
 
 static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent_t* uploads, int n, bool look_ahead);
+static int launch_decode(fm_ctx* ctx, DetState* d, NetState* net, int n, hipStream_t s);
 
 extern "C" int fm_detect_async(fm_ctx* ctx) {
     FM_CHECK_ARG(ctx);
@@ -890,7 +918,16 @@ static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent
     d->set_slot[net->set] = d->wr;
     if (timing) FM_HIP(hipEventRecord(d->ev1[d->wr], s));
     fm_trace_mark(ctx, s, 12);
-    FilterArgs fa = filter_args(d, d->wr);      // (counters were zeroed by this pass's preprocess / stem kernel)
+    if ((rc = launch_decode(ctx, d, net, n, s))) return rc;      // (counters were zeroed by this pass's preprocess / stem kernel)
+    fm_trace_mark(ctx, s, 13);
+    return enqueue_post(ctx, d, s, n);
+}
+
+// the decode of the n images of a pass on stream s, into the candidate lists of slots d->wr .. d->wr + n - 1
+static int launch_decode(fm_ctx* ctx, DetState* d, NetState* net, int n, hipStream_t s) {
+    const fm_yolo_cfg& c = d->cfg;
+    const bool tiled = d->n_tiles > 1;
+    FilterArgs fa = filter_args(d, d->wr);
     HeadSet hs{};
     for (int i = 0; i < n; ++i) {
         const int slot = (d->wr + i) % d->nslot;
@@ -903,6 +940,34 @@ static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent
     }
     int base = 0, blocks = 0;
     for (int i = 0; i < FM_MAX_HEADS + 1; ++i) hs.first_block[i] = 0x7fffffff;
+    if (d->dfl) {
+        const fm_dfl_heads& dh = d->dfl_heads;
+        const bool per_cell = ctx->opt_dfl_decode_form == 1;
+        const int cells_per_block = per_cell ? 256 : 16;
+        DflSet ds{};
+        for (int i = 0; i < FM_MAX_HEADS + 1; ++i) ds.first_block[i] = 0x7fffffff;
+        for (int i = 0; i < c.n_heads; ++i) {
+            FM_CHECK_ARG(dh.box_tensor[i] < (int)net->tensors.size() && dh.cls_tensor[i] < (int)net->tensors.size());
+            const fm_tensor& tb = net->tensors[dh.box_tensor[i]];
+            const fm_tensor& tc = net->tensors[dh.cls_tensor[i]];
+            FM_CHECK_ARG(tb.f32 && tc.f32 && tb.h == c.grid_h[i] && tb.w == c.grid_w[i] && tc.h == c.grid_h[i] && tc.w == c.grid_w[i]);
+            FM_CHECK_ARG(tb.c % 4 == 0 && tc.c % 4 == 0 && dh.box_coff[i] + 4 * FM_DFL_BINS <= tb.c && dh.cls_coff[i] + c.num_classes <= tc.c);
+            DflHead& h = ds.h[i];
+            h.box = (const float*)net->bufs[dh.box_tensor[i]];
+            h.cls = (const float*)net->bufs[dh.cls_tensor[i]];
+            h.box_cs = tb.c; h.box_coff = dh.box_coff[i]; h.cls_cs = tc.c; h.cls_coff = dh.cls_coff[i];
+            h.gw = c.grid_w[i]; h.gh = c.grid_h[i]; h.base_index = base;
+            h.stride = dh.stride[i];
+            const int cnt = h.gw * h.gh;
+            ds.first_block[i] = blocks;
+            blocks += (cnt + cells_per_block - 1) / cells_per_block;
+            base += cnt;
+        }
+        if (per_cell) hipLaunchKernelGGL(dfl_decode_cell_kernel, dim3(blocks, n), dim3(256), 0, s, ds, hs, fa, c.in_w, c.in_h);
+        else hipLaunchKernelGGL(dfl_decode_kernel, dim3(blocks, n), dim3(256), 0, s, ds, hs, fa, c.in_w, c.in_h);
+        FM_HIP(hipGetLastError());
+        return 0;
+    }
     for (int i = 0; i < c.n_heads; ++i) {
         FM_CHECK_ARG(c.head_tensor[i] >= 0 && c.head_tensor[i] < (int)net->tensors.size());
         const fm_tensor& t = net->tensors[c.head_tensor[i]];
@@ -920,8 +985,33 @@ static int detect_pass(fm_ctx* ctx, const uint8_t* const* frames, const hipEvent
     }
     if (blocks) hipLaunchKernelGGL(decode_kernel, dim3(blocks, n), dim3(256), 0, s, hs, fa, c.in_w, c.in_h, c.new_coords);
     FM_HIP(hipGetLastError());
-    fm_trace_mark(ctx, s, 13);
-    return enqueue_post(ctx, d, s, n);
+    return 0;
+}
+
+// Measurement hook (scripts/yolov8_timing.py): the decode kernel alone, `iters` times over the head tensors the last pass
+// left, each launch between two HIP events (the candidate counters are zeroed in front of each); -> the mean in us.
+// Nothing may be in flight; the candidate lists it fills are not collected.
+extern "C" int fm_detect_decode_us(fm_ctx* ctx, int iters, float* us) {
+    FM_CHECK_ARG(ctx && ctx->det && ctx->det->configured && ctx->det_net && iters >= 1 && us);
+    DetState* d = ctx->det;
+    FM_CHECK_ARG(d->pending == 0 && d->post_pending < 0);
+    hipStream_t s = ctx->s_det;
+    const int n = d->n_tiles > 1 ? d->n_tiles : 1;
+    FM_HIP(hipStreamSynchronize(s));
+    FM_HIP(hipStreamSynchronize(ctx->s_up));
+    double total = 0;
+    for (int it = 0; it < iters; ++it) {
+        for (int i = 0; i < n; ++i) FM_HIP(hipMemsetAsync(d->counters[(d->wr + i) % d->nslot], 0, sizeof(int32_t) * 4, s));
+        FM_HIP(hipEventRecord(d->ev0[d->wr], s));
+        if (int rc = launch_decode(ctx, d, ctx->det_net, n, s)) return rc;
+        FM_HIP(hipEventRecord(d->ev1[d->wr], s));
+        FM_HIP(hipEventSynchronize(d->ev1[d->wr]));
+        float ms = 0.f;
+        FM_HIP(hipEventElapsedTime(&ms, d->ev0[d->wr], d->ev1[d->wr]));
+        total += ms;
+    }
+    *us = (float)(total * 1e3 / iters);
+    return 0;
 }
 
 extern "C" int fm_detect_sync(fm_ctx* ctx, fm_det48* out, int cap, int* n) {

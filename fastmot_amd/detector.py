@@ -356,7 +356,8 @@ class YOLODetector(Detector):
                  tile_overlap=0.25,
                  merge_thresh=0.6):
         """An object detector for YOLO models; parameters as fastmot/detector.py:221-253
-        (`weights`: optional weight source for the layer table, default seeded random;
+        (`weights`: optional weight source for the layer table, default seeded random; refused for descriptors with
+        HEAD == 'dfl' -- models.YOLO.from_onnx, YOLOv8n .. x -- whose topology and weights both come from their ONNX file;
         `max_candidates`: capacity of the on-device candidate list; `max_batch`: frames one network pass may take,
         detect_batch / prefetch_batch, at most FM_MAX_DET_BATCH).
         `tiling_grid` = (columns, rows) with more than one tile (SSDDetector's tiling, fastmot/detector.py:46-139, not
@@ -432,8 +433,11 @@ class YOLODetector(Detector):
         cfg.in_w, cfg.in_h = m.INPUT_SHAPE[2], m.INPUT_SHAPE[1]
         cfg.roi_x, cfg.roi_y, cfg.roi_w, cfg.roi_h = self.roi
         cfg.input_tensor = self.graph.input.tid
-        cfg.n_heads = len(self.heads)
-        for i, head in enumerate(self.heads):
+        dfl = m.HEAD == 'dfl'        # (self.heads: a DflHeadsInfo -- per level the (box, class) views and the stride)
+        cfg.n_heads = len(self.heads.levels) if dfl else len(self.heads)
+        for i in range(cfg.n_heads if dfl else 0):
+            cfg.grid_w[i], cfg.grid_h[i] = self.heads.levels[i][0].w, self.heads.levels[i][0].h
+        for i, head in enumerate(() if dfl else self.heads):
             cfg.head_tensor[i] = head.tid
             cfg.grid_w[i] = m.INPUT_SHAPE[2] // m.LAYER_FACTORS[i]
             cfg.grid_h[i] = m.INPUT_SHAPE[1] // m.LAYER_FACTORS[i]
@@ -451,7 +455,16 @@ class YOLODetector(Detector):
         cfg.offset[0], cfg.offset[1] = float(self.bbox_offset[0]), float(self.bbox_offset[1])
         cfg.max_candidates = max_candidates
         self._cfg = cfg
-        self.ctx.detect_configure(cfg)
+        if dfl:
+            heads = _lib.DflHeads()
+            heads.n_levels = cfg.n_heads
+            for i, ((box, cls), stride) in enumerate(zip(self.heads.levels, self.heads.strides)):
+                heads.box_tensor[i], heads.box_coff[i] = box.tid, box.coff
+                heads.cls_tensor[i], heads.cls_coff[i] = cls.tid, cls.coff
+                heads.stride[i] = float(stride)
+            self.ctx.detect_configure_dfl(cfg, heads)
+        else:
+            self.ctx.detect_configure(cfg)
         if self.n_tiles > 1:
             self.ctx.detect_configure_tiles(self.tiles[:, :2], self.tiling_region_sz, self.tile_bbox_offsets,
                                             self.merge_thresh)

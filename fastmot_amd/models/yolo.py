@@ -41,6 +41,8 @@ class YOLO:
     TOPOLOGY = 'yolov4'
     BUILTIN_CFG = None          # name of a generator in models/scaled_yolov4.py (used when no .cfg file is present)
     FRONT_LAYERS = -1           # front-ahead cut of the layer table (fm_ctx option 'det_front_layers'): -1 the rule, 0 off, k forced
+    HEAD = 'anchor'             # 'anchor': YoloLayer decode (ANCHORS / SCALES); 'dfl': anchor-free DFL heads read from the
+    #                             model's ONNX file (models/onnx_detector.py; TOPOLOGY 'onnx', no ANCHORS / SCALES)
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)
@@ -79,6 +81,8 @@ class YOLO:
         model file (any YOLOv3/v4/-tiny/Scaled-YOLOv4 cfg, models/darknet.py); the node list of the ONNX file itself
         (rebuilt into cfg sections, onnx_reader.darknet_cfg_from_onnx); the built-in yolov4.cfg table / Scaled-YOLOv4
         generators."""
+        if cls.HEAD == 'dfl':
+            return cls._build_dfl_graph(weights)
         real = None
         onnx_model = None
         if weights is None:
@@ -120,6 +124,46 @@ class YOLO:
             raise ValueError(f'{cls.weight_file()}: {real.remaining()} '
                              f'{"layers" if onnx_model is not None else "bytes"} left after loading {cls.__name__}')
         return g, heads
+
+    @classmethod
+    def _build_dfl_graph(cls, weights=None):
+        """HEAD == 'dfl': topology AND parameters come from the descriptor's ONNX file (models/onnx_detector.py lists what
+        it may contain) -> (Graph, DflHeadsInfo: per level the (box, class) head views, the strides).  There is no
+        built-in topology, so neither another weight source nor seeded random weights are offered."""
+        from .onnx_detector import lower
+        if weights is not None:
+            raise TypeError(f'{cls.__name__} takes topology and weights from its ONNX file {cls.MODEL_PATH}: weights= is not '
+                            'supported for DFL-head models (use models.YOLO.from_onnx(path))')
+        path = Path(cls.MODEL_PATH) if cls.MODEL_PATH is not None else None
+        if path is None or not path.is_file():
+            raise FileNotFoundError(
+                f'{cls.__name__}: ONNX file {cls.MODEL_PATH} not found.  A DFL-head descriptor takes its topology from that '
+                'file (`yolo export format=onnx`): put it there or register another file with models.YOLO.from_onnx(path)')
+        g, info = lower(path, cls.INPUT_SHAPE, cls.NUM_CLASSES, where=f'{cls.__name__} ({path})')
+        if cls.LAYER_FACTORS is not None and list(cls.LAYER_FACTORS) != list(info.strides):
+            raise ValueError(f'{path}: strides {info.strides} != {cls.__name__}.LAYER_FACTORS {list(cls.LAYER_FACTORS)}')
+        return g, info
+
+    @classmethod
+    def from_onnx(cls, path, name=None, letterbox=True):
+        """Creates and registers a descriptor for the ONNX export of an anchor-free detector with DFL heads (Ultralytics
+        YOLOv8; models/onnx_detector.py lists what the file may contain): INPUT_SHAPE, NUM_CLASSES and LAYER_FACTORS are
+        read from the file.  The returned class's name -- `name`, by default the file's stem with every other character
+        than letters, digits and '_' replaced by '_' -- then works as yolo_detector_cfg.model / YOLODetector(model=...)."""
+        import re
+        from .onnx_detector import lower
+        path = Path(path)
+        if not path.is_file():
+            raise FileNotFoundError(f'YOLO.from_onnx: {path} not found')
+        g, info = lower(path)
+        h, w, _, _ = g.tensors[g.input.tid]
+        name = name or re.sub(r'\W', '_', path.stem)
+        if not name.isidentifier():
+            raise ValueError(f'{name!r} is not a usable model name: pass name=')
+        return type(name, (YOLO,), dict(MODEL_PATH=path, ENGINE_PATH=path.with_suffix('.hipnet'), INPUT_SHAPE=(g.input.c, h, w),
+                                        NUM_CLASSES=info.num_classes, LAYER_FACTORS=list(info.strides), LETTERBOX=bool(letterbox),
+                                        HEAD='dfl', TOPOLOGY='onnx', FRONT_LAYERS=0,
+                                        __doc__=f'DFL-head detector read from {path.name}'))
 
 
 def yolov4_graph(model, weights):
@@ -333,3 +377,15 @@ class YOLOv3Tiny(YOLO):
     SCALES = [1., 1.]
     ANCHORS = [[81, 82, 135, 169, 344, 319], [10, 14, 23, 27, 37, 58]]
     TOPOLOGY = 'darknet-cfg'
+
+
+# Ultralytics YOLOv8 (anchor-free, DFL heads): topology and weights come from the ONNX export next to this module
+# (`yolo export model=yolov8n.pt format=onnx imgsz=640`, models/onnx_detector.py); decode in csrc/dfl_decode.h.
+def _v8(name):
+    return type(name, (YOLO,), dict(
+        ENGINE_PATH=Path(__file__).parent / f'{name.lower()}.hipnet', MODEL_PATH=Path(__file__).parent / f'{name.lower()}.onnx',
+        NUM_CLASSES=80, LETTERBOX=True, INPUT_SHAPE=(3, 640, 640), LAYER_FACTORS=[8, 16, 32], HEAD='dfl', TOPOLOGY='onnx',
+        FRONT_LAYERS=0, __module__=__name__))
+
+
+YOLOv8n, YOLOv8s, YOLOv8m, YOLOv8l, YOLOv8x = (_v8(n) for n in ('YOLOv8n', 'YOLOv8s', 'YOLOv8m', 'YOLOv8l', 'YOLOv8x'))

@@ -1183,6 +1183,22 @@ typedef struct fm_yolo_cfg {
 } fm_yolo_cfg;
 
 int fm_detect_configure(fm_ctx* ctx, const fm_yolo_cfg* cfg);
+/* Anchor-free heads with a DFL box branch (Ultralytics YOLOv8 `Detect`, read from its ONNX export by
+ * models/onnx_detector.py): level i ends in 4 * 16 box logits (sides left, top, right, bottom; 16 bins each) and
+ * num_classes class logits per cell, in fp32 NHWC tensors.  Decode (csrc/dfl_decode.h): d_side = sum_k k softmax(b[side])_k,
+ * anchor point (col + 0.5, row + 0.5), corners (anchor -+ d) * stride, class = first maximum, cls_prob = sigmoid(logit),
+ * box_conf = 1, one row per cell, rows numbered level-major. */
+typedef struct fm_dfl_heads {
+    int32_t n_levels;                   /* == cfg->n_heads */
+    int32_t box_tensor[FM_MAX_HEADS], box_coff[FM_MAX_HEADS];   /* tensor id / first channel of the 64 box logits (coff % 4 == 0) */
+    int32_t cls_tensor[FM_MAX_HEADS], cls_coff[FM_MAX_HEADS];   /* ... of the class logits (the same tensor or another) */
+    float stride[FM_MAX_HEADS];         /* input pixels per cell */
+} fm_dfl_heads;
+/* fm_detect_configure for such heads: cfg as there (input, ROI, n_heads, grid_w / grid_h, num_classes <= 128, label mask,
+ * thresholds, size / offset, max_candidates); its head_tensor, n_anchors, anchors, scale_xy and new_coords are ignored.
+ * Everything behind the decode -- fm_detect_async*, fm_detect_sync, fm_detect_raw_candidates, fm_detect_configure_tiles --
+ * works as behind fm_detect_configure; a later fm_detect_configure returns to the anchor-based decode. */
+int fm_detect_configure_dfl(fm_ctx* ctx, const fm_yolo_cfg* cfg, const fm_dfl_heads* heads);
 /* YOLODetector.detect_async (detector.py:270-273): preprocess (bilinear resize in u8, BGR->RGB,
  * /255, detector.py:289-300) -> network -> head decode (plugins/yolo_layer.cu:127-230) ->
  * score/class filter -> per-class DIoU-NMS -> box filter (detector.py:322-365); network and decode on the detector
@@ -1199,6 +1215,9 @@ int fm_detect_last_counts(fm_ctx* ctx, int* n_candidates, int* n_detections);
 int fm_detect_preprocess_only(fm_ctx* ctx);
 int fm_filter_dets(fm_ctx* ctx, const float* rows, int n, fm_det48* out, int cap, int* n_out);
 int fm_detect_raw_candidates(fm_ctx* ctx, float* rows, int cap, int* n);
+/* measurement hook: the decode kernel of the configured detector alone, `iters` launches over the head tensors of the last
+ * pass, each between two HIP events -> the mean time in us.  No pass may be in flight. */
+int fm_detect_decode_us(fm_ctx* ctx, int iters, float* us);
 /* HIP-event duration (ms) of the network launches of the pass fm_detect_sync collected last, recorded on the detector
  * stream (the bench's live roofline measurement); -1 when that pass carried no events (option "net_timing").  A batch
  * pass (fm_detect_async_ahead) reports its duration on the collect of its first frame and -1 on the others.  A pass in
