@@ -223,8 +223,9 @@ void fm_ssd_free(fm_ctx* ctx) {
     ctx->ssd = nullptr;
 }
 
-extern "C" int fm_ssd_configure(fm_ctx* ctx, const fm_ssd_cfg* c) {
-    FM_CHECK_ARG(ctx && c && c->anchors);
+// what the kernels' LDS arrays and the index fields of their keys hold, checked on the host: -> 0 and the anchors per tile
+static int ssd_check_cfg(const fm_ssd_cfg* c, long* total_out) {
+    FM_CHECK_ARG(c && c->anchors);
     FM_CHECK_ARG(c->n_heads >= 1 && c->n_heads <= SSD_MAX_HEADS && c->num_classes >= 2 && c->num_classes <= SSD_MAX_CLASSES);
     FM_CHECK_ARG(c->topk >= 1 && c->topk <= SSD_MAX_TOPK && c->nms_thresh >= 0.f && c->nms_thresh <= 1.f);
     FM_CHECK_ARG(c->n_tiles >= 1 && c->n_tiles <= FM_MAX_SSD_TILES && c->in_w > 0 && c->in_h > 0 && c->region_w > 0 && c->region_h > 0);
@@ -237,6 +238,22 @@ extern "C" int fm_ssd_configure(fm_ctx* ctx, const fm_ssd_cfg* c) {
         total += (long)c->map_w[k] * c->map_h[k] * c->n_anchors[k];
     }
     FM_CHECK_ARG(total == c->n_anchor_rows && total <= SSD_MAX_ANCHORS);
+    *total_out = total;
+    return 0;
+}
+
+// A refused configuration leaves the context without an SSD state, as a failed allocation does: whoever goes on after
+// the error cannot launch with the configuration this call was to replace.
+extern "C" int fm_ssd_configure(fm_ctx* ctx, const fm_ssd_cfg* c) {
+    FM_CHECK_ARG(ctx);
+    long total = 0;
+    if (const int bad = ssd_check_cfg(c, &total)) {
+        if (ctx->ssd) {
+            (void)hipStreamSynchronize(ctx->s_det);
+            fm_ssd_free(ctx);
+        }
+        return bad;
+    }
     FM_HIP(hipStreamSynchronize(ctx->s_det));
     fm_ssd_free(ctx);
     std::unique_ptr<SsdState> s(new SsdState());

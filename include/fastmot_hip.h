@@ -1398,6 +1398,8 @@ typedef struct fm_ssd_cfg {
     int32_t tile_x[FM_MAX_SSD_TILES], tile_y[FM_MAX_SSD_TILES];
     int32_t region_w, region_h;
 } fm_ssd_cfg;
+/* (a configuration beyond these limits is refused with FM_ERR_ARG before anything is launched, and the context is then
+ * left without an SSD state -- as after a failed allocation -- until a call succeeds) */
 int fm_ssd_configure(fm_ctx* ctx, const fm_ssd_cfg* cfg);
 /* preprocess -> fm_net_run at batch n_tiles -> decode / NMS / top-K; nothing synchronises */
 int fm_ssd_detect_async(fm_ctx* ctx);

@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 
 import cv_oracle
+import decode_cases as dc
 import np_oracle as o
+from decode_cases import synthetic_frame
 from fastmot_amd import _lib
 from fastmot_amd.detector import YOLODetector
 from fastmot_amd.feature_extractor import FeatureExtractor
@@ -19,14 +21,6 @@ from fastmot_amd.models import YOLO, ReID
 from fastmot_amd.models.graph import RandomWeights
 
 pytestmark = pytest.mark.gpu
-
-
-def synthetic_frame(w, h, seed=0):
-    rng = np.random.default_rng(seed)
-    base = rng.integers(0, 256, (h // 8 + 1, w // 8 + 1, 3)).astype(np.uint8)
-    frame = np.kron(base, np.ones((8, 8, 1), np.uint8))[:h, :w]
-    noise = rng.integers(-20, 20, frame.shape)
-    return np.clip(frame.astype(int) + noise, 0, 255).astype(np.uint8)
 
 
 class TinyYOLO(YOLO):
@@ -239,6 +233,36 @@ def test_filter_dets_more_candidates_than_the_fused_kernel_holds(ctx):
         np.testing.assert_array_equal(out.tlbr, tl)
         np.testing.assert_array_equal(out.label, lb)
         np.testing.assert_allclose(out.conf, cf, rtol=1e-7)
+
+
+def _sort_detector(cap):
+    return YOLODetector((1920, 1080), (0, 1, 2), model='TinyYOLO', conf_thresh=0.0, nms_thresh=dc.SORT_NMS,
+                        max_area=dc.SORT_MAX_AREA, min_aspect_ratio=dc.SORT_MIN_AR, max_candidates=cap)
+
+
+@pytest.mark.parametrize('cap', [8192, 16448])
+def test_filter_dets_sort_ties_and_signs(ctx, cap, nms_path):
+    """The candidate sort where its key's fields decide (sort_key, nms_core.h): box_conf quantised to 1/16, so the
+    original index orders most neighbours; rows with negative box_conf (and cls_prob: the product passes), -0.0 and +0.0
+    (conf_thresh 0 admits them; they rank as equals).  Capacity 8192 takes rank_sort_lds_kernel, 16448 -- the first
+    multiple of 64 above 16384 -- the chunked rank_sort_kernel (launch_rank_sort, detect.hip), at counts around its
+    256-key chunks and up to its capacity.  The sorted rows equal the host's lexsort bit for bit, the detections the
+    oracle's with the original index as the tie-break.  (Beyond 4096 candidates the greedy kernel hands the pass to the
+    general route whatever nms_path says: those counts run under 'general' alone.)"""
+    counts = dc.SORT_COUNTS + (dc.SORT_COUNTS_LARGE if cap > 16384 and nms_path == 'general' else ())
+    det = _sort_detector(cap)
+    assert det._cfg.max_candidates == cap and (cap > 16384) == (cap == 16448)      # the sort kernel this capacity takes
+    for n in counts:
+        want, want_idx, ref, survivors = dc.sort_reference(n)
+        assert survivors <= dc.SORT_SURVIVOR_CAP
+        det._configure(cap)             # (clears a switch to the general route that the count before may have left)
+        out = ctx.filter_dets(dc.sort_rows(n), cap=cap)
+        assert ctx.detect_last_counts()[0] == n
+        got = ctx.detect_raw_candidates()
+        assert got.shape == (n, 8)
+        np.testing.assert_array_equal(got[:, 7].copy().view(np.int32), want_idx, err_msg=f'n={n}')
+        np.testing.assert_array_equal(np.ascontiguousarray(got[:, :7]).view(np.uint32), want.view(np.uint32), err_msg=f'n={n}')
+        _assert_equals_oracle(out, ref)
 
 
 @pytest.mark.parametrize('model', ['TinyYOLO', 'TinyLetterbox'])
